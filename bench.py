@@ -343,13 +343,64 @@ def build_dlrm(B, sizes, D, precision, world, lr=0.01, overlap=True):
     return m
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: every file of every rank together, at most 64 MB
+DUMP_NPY_HEADER = 256       # bytes allowed per .npy file for its header
+
+
+def dump_rows_per_rank(dense_numel, dense_files, world, dim):
+    """embedding rows each rank writes so that everything --dump-outputs writes stays within
+    DUMP_BYTES: the loss and the dense parameters (rank 0, float32) come off first, the rest is
+    shared by the `world` ranks' row samples (dim x float32 per row + its float64 row id)"""
+    fixed = 8 + dense_numel * 4 + (1 + dense_files + 2 * world) * DUMP_NPY_HEADER
+    if fixed > DUMP_BYTES:
+        raise RuntimeError(f"--dump-outputs: the dense parameters alone take {fixed} bytes "
+                           f"(limit {DUMP_BYTES})")
+    return (DUMP_BYTES - fixed) // (world * (dim * 4 + 8))
+
+
+def dump_outputs(m, emb, out_dir, rank, world):
+    """--dump-outputs: what the timed path left a caller after its last step, as float32 / float64
+    .npy files under `out_dir` -- the loss train() reported, every dense parameter, and a fixed,
+    seeded sample of the embedding table's rows with their row ids, sized by dump_rows_per_rank so
+    that all files of all ranks stay within DUMP_BYTES.  The row ids are drawn from the rows in use;
+    they name the same keys in two builds because the hash index inserts deterministically: a new
+    key's row is the vocabulary counter + the rank of its first occurrence among the batch's new keys
+    (hugectr_amd/csrc/hashtable.hip, header).  N > 1: every rank writes its own table sample, rank 0
+    the rest."""
+    params = list(m._mods.named_parameters())
+    n = emb.get_vocabulary_size()
+    k = min(n, dump_rows_per_rank(sum(q.numel() for _, q in params), len(params), world,
+                                  emb.table().shape[1]))
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    written = []
+
+    def save(name, arr):
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, arr)
+        written.append(path)
+
+    if rank == 0:
+        save("loss", np.array([m.get_current_loss()], dtype=np.float64))
+        for name, q in params:
+            save("dense_" + name.replace(".", "_"), q.detach().float().cpu().numpy())
+    rows = np.sort(np.random.default_rng(20240).choice(n, size=k, replace=False))
+    idx = torch.from_numpy(rows.astype(np.int64)).to(emb.table().device)
+    save(f"embedding_row_ids{sfx}", rows.astype(np.float64))
+    save(f"embedding_rows{sfx}", emb.table()[:n].index_select(0, idx).float().cpu().numpy())
+    if world == 1:
+        total = sum(os.path.getsize(f) for f in written)
+        assert total <= DUMP_BYTES, f"--dump-outputs wrote {total} bytes (limit {DUMP_BYTES})"
+
+
 def dlrm_leg(a, precision, steps, warmup, world, rank, dev, scaling="weak", alpha=None,
-             sizes=None, label=None):
+             sizes=None, label=None, dump_dir=None):
     """one measurement of the DLRM Criteo-1TB step through hugectr.Model.train() -- the product
     surface, on 1 or N GPUs -- at `precision` (see --precision).  scaling = "weak": a.batch
     samples per GPU (global batch N x a.batch); "strong": global batch a.batch (per GPU a.batch/N),
     BASELINE configs[2] read literally.  Every step sees a batch it has not seen before (keys are
-    inserted live).  Builds and releases its own model: the 89.5 GiB table exists once at a time."""
+    inserted live).  Builds and releases its own model: the 89.5 GiB table exists once at a time.
+    dump_dir: the outputs of the last timed step go there (dump_outputs)."""
     from hugectr_amd import _lib
     alpha = a.alpha if alpha is None else alpha
     sizes = sizes or [max(1, int(v * a.table_scale)) for v in CRITEO_1TB]
@@ -421,6 +472,8 @@ def dlrm_leg(a, precision, steps, warmup, world, rank, dev, scaling="weak", alph
             t = t.to(dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir:
+        dump_outputs(m, emb, dump_dir, rank, world)
     prof_timed = emb.profile()
     emb.profiling(False)
     upd_overlapped = bool(getattr(m, "_upd_overlap", False) and getattr(m, "_upd_overlap_on", False)
@@ -1563,7 +1616,16 @@ def main():
                     help="dense-tower GEMM solution selection: auto = hugectr.Model reads the "
                          "committed hugectr_amd/tuning/tunableop_gfx950.csv (solver."
                          "use_algorithm_search); off = library heuristics")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps of the main line, write what its last step left "
+                         "a caller (loss, dense parameters, a seeded sample of embedding rows) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB in all ranks' files "
+                         "together (dump_outputs); --config c3 only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.config != "c3":
+        ap.error("--dump-outputs: the main line of --config c3 only")
     if a.exchange:
         os.environ["HCTR_EXCHANGE"] = a.exchange
     if a.tunable == "off":
@@ -1605,7 +1667,8 @@ def main():
 
     import gc
     first = "strong" if a.scaling == "strong" else "weak"
-    out = dlrm_leg(a, a.precision, a.steps, a.warmup, world, rank, dev, scaling=first)
+    out = dlrm_leg(a, a.precision, a.steps, a.warmup, world, rank, dev, scaling=first,
+                   dump_dir=a.dump_outputs)
     if world > 1 and a.scaling == "both":
         # BASELINE configs[2] read literally: global batch 65536 over N GPUs
         gc.collect()

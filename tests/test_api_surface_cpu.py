@@ -2,18 +2,22 @@
 `hugectr.<name>` the sample / test scripts under R/samples, R/test/embedding_collection_test and
 R/test/pybind_test touch must exist in hugectr_amd.hugectr, and every keyword they pass to
 `hugectr.<callable>(...)` must be accepted.  Layer types of model families outside the hot-path scope
-(attention / sequence models: DIN, BST, MMoE) are listed explicitly.  Runs where the reference
-checkout is mounted (the build container); skipped elsewhere."""
+(attention / sequence models: DIN, BST, MMoE) are listed explicitly.  What the scripts use is
+recorded in tests/golden/reference_script_usage.json (tests/golden/make_ref_fixtures.py); where the
+reference checkout is mounted, the record is checked against the scripts as they stand."""
 import ast
 import collections
 import dataclasses
 import glob
 import inspect
+import json
 import os
 
 import pytest
 
 REF = "/root/reference"
+USAGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                     "reference_script_usage.json")
 # dense layers of model families outside SURVEY 8 (DIN / BST / MMoE attention and sequence blocks)
 OUT_OF_SCOPE_LAYERS = {"FusedReshapeConcat", "LayerNorm", "MatrixMultiply", "MultiHeadAttention",
                        "PReLU_Dice", "ReduceMean", "SequenceMask"}
@@ -30,10 +34,15 @@ def _chain(node):
     return None
 
 
+def _script_files():
+    return sorted(glob.glob(REF + "/samples/**/*.py", recursive=True) +
+                  glob.glob(REF + "/test/embedding_collection_test/*.py") +
+                  glob.glob(REF + "/test/pybind_test/*.py"))
+
+
 def _usage():
-    files = sorted(glob.glob(REF + "/samples/**/*.py", recursive=True) +
-                   glob.glob(REF + "/test/embedding_collection_test/*.py") +
-                   glob.glob(REF + "/test/pybind_test/*.py"))
+    """hugectr.<name> uses, keywords per hugectr.<callable>(...), files that touch hugectr"""
+    files = _script_files()
     names, calls, n_files = collections.Counter(), collections.defaultdict(set), 0
     for f in files:
         try:
@@ -55,10 +64,49 @@ def _usage():
     return names, calls, n_files
 
 
+def _verbs():
+    """`model.<verb>(...)` / `ebc_config.<verb>(...)` calls: counts and keywords per verb"""
+    used, kws = collections.Counter(), collections.defaultdict(set)
+    for f in _script_files():
+        try:
+            tree = ast.parse(open(f).read())
+        except SyntaxError:
+            continue
+        for node in ast.walk(tree):
+            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and
+                    isinstance(node.func.value, ast.Name) and
+                    node.func.value.id in ("model", "ebc_config")):
+                k = (node.func.value.id, node.func.attr)
+                used[k] += 1
+                kws[k].update(a.arg for a in node.keywords if a.arg)
+    return used, kws
+
+
+def record():
+    """the scan of the reference's scripts as stored in USAGE (sorted, JSON)"""
+    names, calls, n_files = _usage()
+    used, kws = _verbs()
+    return {"n_files": n_files, "names": dict(sorted(names.items())),
+            "calls": {k: sorted(v) for k, v in sorted(calls.items())},
+            "verbs": {f"{o}.{v}": {"count": used[(o, v)], "keywords": sorted(kws[(o, v)])}
+                      for (o, v) in sorted(used)}}
+
+
+def _recorded():
+    return json.load(open(USAGE))
+
+
 @pytest.mark.skipif(not os.path.isdir(REF + "/samples"), reason="reference checkout not mounted")
+def test_recorded_usage_is_what_the_reference_scripts_use_today():
+    assert json.loads(json.dumps(record())) == _recorded(), \
+        "re-run tests/golden/make_ref_fixtures.py"
+
+
 def test_every_name_the_reference_scripts_use_exists():
     import hugectr_amd.hugectr as H
-    names, calls, n_files = _usage()
+    rec = _recorded()
+    names, n_files = rec["names"], rec["n_files"]
+    calls = {k: set(v) for k, v in rec["calls"].items()}
     assert n_files >= 20 and len(names) >= 60
     missing = []
     for n in names:
@@ -108,27 +156,15 @@ def test_training_callback_hooks_are_called_in_the_reference_order():
     assert len(s.training_callbacks) == 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/samples"), reason="reference checkout not mounted")
 def test_every_model_method_the_reference_scripts_call_exists():
     """`model.<verb>(...)` / `ebc_config.<verb>(...)` calls of the same scripts: every verb exists and
     accepts the keywords used"""
     import hugectr_amd.hugectr as H
-    files = sorted(glob.glob(REF + "/samples/**/*.py", recursive=True) +
-                   glob.glob(REF + "/test/embedding_collection_test/*.py") +
-                   glob.glob(REF + "/test/pybind_test/*.py"))
     owner = {"model": H.Model, "ebc_config": H.EmbeddingCollectionConfig}
-    used, kws = collections.Counter(), collections.defaultdict(set)
-    for f in files:
-        try:
-            tree = ast.parse(open(f).read())
-        except SyntaxError:
-            continue
-        for node in ast.walk(tree):
-            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and
-                    isinstance(node.func.value, ast.Name) and node.func.value.id in owner):
-                k = (node.func.value.id, node.func.attr)
-                used[k] += 1
-                kws[k].update(a.arg for a in node.keywords if a.arg)
+    used, kws = collections.Counter(), {}
+    for k, v in _recorded()["verbs"].items():
+        o, verb = k.split(".", 1)
+        used[(o, verb)], kws[(o, verb)] = v["count"], set(v["keywords"])
     assert used[("model", "add")] > 500 and used[("model", "fit")] >= 20
     missing, bad = [], {}
     for (obj, verb) in used:

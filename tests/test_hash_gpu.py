@@ -79,8 +79,12 @@ def test_murmur_hash_bit_exact(oracle, key_bytes):
     _lib.check(_lib.lib.hctr_hash_keys(_lib.ptr(kt), ktype, keys.size, _lib.ptr(out), _lib.stream_ptr()))
     got = out.cpu().numpy().view(np.uint32)
     assert (got == oracle.hash_keys(keys, key_bytes)).all()
-    # ... and the reference's own functor, compiled from its header (oracle/_ref, built where the
-    # reference is mounted; it travels with the repository snapshot)
+    # ... and the reference's own functor, compiled from its header: its hashes of these keys are
+    # recorded in tests/golden/ref_murmur3.npz (tests/golden/make_ref_fixtures.py) ...
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_murmur3.npz"))
+    assert (g[f"keys{key_bytes}"] == keys).all()
+    assert (got == g[f"hash{key_bytes}"]).all()
+    # ... and run live where oracle/_ref was built (the reference mounted at build time)
     ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
                        "libref_hash.so")
     if os.path.exists(ref):

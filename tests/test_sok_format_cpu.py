@@ -2,7 +2,9 @@
 (save_meta_file / load_meta_file / write_file_head / read_file_head of
 R/sparse_operation_kit/sparse_operation_kit/dump_load.py), extracted from the source file and run
 in a namespace without TensorFlow.  Both directions: the reference reads what we write, we read what
-the reference writes, and the bytes are identical.  Skipped where the reference is not mounted."""
+the reference writes, and the bytes are identical.  The bytes the reference writes (and what its
+readers return) are recorded in tests/golden/ref_sok_format.npz (tests/golden/make_ref_fixtures.py)
+and checked everywhere; where the reference is mounted, its functions are also run live."""
 import ast
 import os
 from enum import Enum
@@ -11,6 +13,9 @@ import numpy as np
 import pytest
 
 REF = "/root/reference/sparse_operation_kit/sparse_operation_kit/dump_load.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_sok_format.npz")
+HEAD_CASES = [(0, "", np.int64), (1, "", np.float32), (2, "accumulator", np.float32),
+              (0, "", np.uint64)]
 WANTED = {"SOK_var_info", "MetaVarType", "FileType", "get_meta_info_offset", "save_meta_file",
           "convert_bytes_to_int_list", "convert_bytes_to_string_list", "load_meta_file",
           "write_file_head", "read_file_head"}
@@ -32,7 +37,19 @@ def _reference_namespace():
     return ns
 
 
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not mounted")
+live = pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not mounted")
+
+
+def _golden():
+    return np.load(GOLDEN)
+
+
+def _head_array(dtype):
+    return (np.arange(40).reshape(10, 4) * 3).astype(dtype)
+
+
+def _head_key(ftype, var, dtype):
+    return f"head_{ftype}_{var or 'none'}_{np.dtype(dtype).name}"
 
 
 def _infos(fmt):
@@ -41,6 +58,25 @@ def _infos(fmt):
             fmt.VarInfo("t", "", 0, 6, 0, 1)]
 
 
+def test_meta_file_matches_the_recorded_reference_bytes(tmp_path):
+    from hugectr_amd import sok_format as fmt
+    g = _golden()
+    infos = _infos(fmt)
+    for name, sub in (("meta_info", infos), ("meta_info_one", infos[:1])):
+        d = tmp_path / name
+        d.mkdir()
+        fmt.save_meta_file(str(d), sub)
+        assert open(d / "meta_info", "rb").read() == g[name].tobytes(), name
+        # ... and ours reads back what the reference wrote
+        t = tmp_path / (name + "_ref")
+        t.mkdir()
+        (t / "meta_info").write_bytes(g[name].tobytes())
+        got = fmt.load_meta_file(str(t))
+        assert [got[i.emb_name] for i in sub] == sub
+    assert int(g["meta_info_offset_opt_name_3"]) == 4 + (20 + 256) * 3
+
+
+@live
 def test_meta_file_both_directions(tmp_path):
     from hugectr_amd import sok_format as fmt
     ref = _reference_namespace()
@@ -77,13 +113,28 @@ def test_meta_file_both_directions(tmp_path):
     assert ref["get_meta_info_offset"](ref["MetaVarType"].OptName, 3) == 4 + (20 + 256) * 3
 
 
-@pytest.mark.parametrize("ftype,var,dtype", [(0, "", np.int64), (1, "", np.float32),
-                                             (2, "accumulator", np.float32), (0, "", np.uint64)])
+@pytest.mark.parametrize("ftype,var,dtype", HEAD_CASES)
+def test_array_file_heads_match_the_recorded_reference_bytes(tmp_path, ftype, var, dtype):
+    from hugectr_amd import sok_format as fmt
+    g = _golden()
+    assert fmt.FILE_HEAD_LENGTH == int(g["file_head_length"]) == 296
+    arr = _head_array(dtype)
+    theirs = g[_head_key(ftype, var, dtype)].tobytes()  # write_file_head + the rows appended
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    fmt.write_array_file(a, "some/table:0", ftype, var, arr)
+    assert open(a, "rb").read() == theirs
+    open(b, "wb").write(theirs)
+    assert fmt.read_file_head(b) == ("some/table:0", ftype, var, fmt.DTYPE_INDEX[np.dtype(dtype)])
+    assert (fmt.read_array_file(b).reshape(10, 4) == arr).all()
+
+
+@live
+@pytest.mark.parametrize("ftype,var,dtype", HEAD_CASES)
 def test_array_file_heads_both_directions(tmp_path, ftype, var, dtype):
     from hugectr_amd import sok_format as fmt
     ref = _reference_namespace()
     assert fmt.FILE_HEAD_LENGTH == ref["file_head_length"] == 296
-    arr = (np.arange(40).reshape(10, 4) * 3).astype(dtype)
+    arr = _head_array(dtype)
     info = ref["SOK_var_info"]()
     info.emb_name = "some/table:0"
     a, b = str(tmp_path / "a"), str(tmp_path / "b")
