@@ -2,7 +2,7 @@
 // sparse update's (row, bucket) lists: n <= 2^22 .. 2^24 pairs, keys of <= 32 bits.
 //
 // The reference sorts with cub::DeviceRadixSort::SortPairs (R/HugeCTR/src/optimizers/
-// sparse_optimizer.cu:663-668); the library counterpart here (rocprim::radix_sort_pairs) is a
+// sparse_optimizer.cu:663-668); the ROCm library counterpart is a
 // one-sweep sort whose decoupled look-back chain makes every digit pass latency-bound at this size
 // (~46 us per pass at 1.7 M pairs, 3 passes + a histogram launch = 190 us -- profiles/, round 1).
 // This sort has no inter-workgroup dependency inside a launch:
@@ -19,7 +19,7 @@
 // 46-us launch; keys of b bits take ceil(b / 10) digits.
 // The first digit pass can read its keys straight from the index stage's 64-bit rows and make up
 // the payload (position, or its gradient-map image) itself -- the sparse update's pair expansion
-// drops out for one-hot batches -- and can leave out the keys below a bound (RsFirst).  Measured
+// drops out for one-hot batches (RsFirst).  Measured
 // and dropped (round 4, MI355X, 1.7 M pairs): tiles of 2048 / 1024 keys and a 128- / 64-workgroup
 // column scan -- every combination slower than 4096-key tiles with a 32-workgroup scan (sort
 // 104 us -> 107 .. 137 us).
@@ -49,18 +49,9 @@ struct RsSrc {
   const uint64_t* k64;
   const uint32_t* flag;
   uint32_t map_inner, map_outer;
-  // first pass of a one-hot batch: keys below skip_below are left out of the sort altogether (the
-  // sparse update's hot rows, summed by hot_chunk_kernel); the pass that filters posts the number
-  // of keys it kept to *n_kept, and the later passes take their length from *n_live
-  uint32_t skip_below;
-  uint32_t* n_kept;
-  const uint32_t* n_live;
 };
 __device__ __forceinline__ bool rs_first64(const RsSrc& f) {
   return f.k64 != nullptr && *f.flag != 0u;
-}
-__device__ __forceinline__ size_t rs_len(const RsSrc& f, size_t n) {
-  return f.n_live != nullptr ? (size_t)*f.n_live : n;
 }
 __device__ __forceinline__ uint32_t rs_payload(const RsSrc& f, size_t i) {
   const uint32_t u = (uint32_t)i;
@@ -85,10 +76,7 @@ __global__ void __launch_bounds__(kRsBlock)
     rs_hist_kernel(const uint32_t* __restrict__ keys, size_t n, int shift,
                    uint32_t* __restrict__ hist, RsSrc src) {
   constexpr int kRsBins = 1 << BITS;
-  n = rs_len(src, n);
-  if ((size_t)blockIdx.x * kRsTile >= n) return;  // (a tile past the live length: colscan skips it)
   const bool f64 = rs_first64(src);
-  const uint32_t skip = f64 ? src.skip_below : 0u;
   __shared__ uint32_t h[kRsBins];
   for (int b = threadIdx.x; b < kRsBins; b += kRsBlock) h[b] = 0u;
   __syncthreads();
@@ -105,7 +93,7 @@ __global__ void __launch_bounds__(kRsBlock)
   // lane 0 are counted with one ballot and added once; the rest take the plain atomic.
 #pragma unroll
   for (int r = 0; r < kRsRounds; r++) {
-    const bool valid = base + (size_t)r * 64 < n && key[r] >= skip;
+    const bool valid = base + (size_t)r * 64 < n;
     const uint32_t d = (key[r] >> shift) & (kRsBins - 1);
     const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
     const unsigned long long same = __ballot(valid && d == d0);
@@ -121,10 +109,8 @@ __global__ void __launch_bounds__(kRsBlock)
 // hist[t][b] <- sum of hist[t'][b] over t' < t, for the 32 digit values of this workgroup
 template <int BITS>
 __global__ void __launch_bounds__(kRsScanBlock)
-    rs_colscan_kernel(uint32_t* __restrict__ hist, size_t tiles, uint32_t* __restrict__ total,
-                      const uint32_t* __restrict__ n_live, uint32_t tile_keys) {
+    rs_colscan_kernel(uint32_t* __restrict__ hist, size_t tiles, uint32_t* __restrict__ total) {
   constexpr int kRsBins = 1 << BITS;
-  if (n_live != nullptr) tiles = ((size_t)*n_live + tile_keys - 1) / tile_keys;
   constexpr int kChunks = kRsScanBlock / kRsScanBins;
   __shared__ uint32_t part[kChunks][kRsScanBins];
   const int c = threadIdx.x % kRsScanBins, q = threadIdx.x / kRsScanBins;
@@ -158,10 +144,7 @@ __global__ void __launch_bounds__(kRsBlock)
                       int shift, const uint32_t* __restrict__ tile_offs,
                       const uint32_t* __restrict__ total, RsSrc src) {
   constexpr int kRsBins = 1 << BITS;
-  n = rs_len(src, n);
-  if ((size_t)blockIdx.x * kRsTile >= n) return;
   const bool f64 = rs_first64(src);
-  const uint32_t skip = f64 ? src.skip_below : 0u;
   constexpr int kPerThread = kRsBins / kRsBlock;  // digit values per thread in the offset step
   // The tile is first sorted INSIDE LDS (stable, by this digit), then streamed out: consecutive
   // threads write consecutive sorted elements, and elements of one digit value are consecutive
@@ -197,7 +180,7 @@ __global__ void __launch_bounds__(kRsBlock)
   uint32_t info[kRsRounds];  // rank inside the match group | group size << 8
 #pragma unroll
   for (int r = 0; r < kRsRounds; r++) {
-    const bool valid = base + (size_t)r * 64 < n && key[r] >= skip;
+    const bool valid = base + (size_t)r * 64 < n;
     const uint32_t d = (key[r] >> shift) & (kRsBins - 1);
     unsigned long long m = 0ull;
     if (MASK) {
@@ -234,11 +217,10 @@ __global__ void __launch_bounds__(kRsBlock)
     cs += c4[j];
     ts += t4[j];
   }
-  uint32_t all, tile_kept;  // keys of this tile that take part / of all tiles
-  uint32_t lex = block_exclusive_scan<uint32_t, kRsBlock>(cs, scan_smem, &tile_kept);  // local
+  uint32_t all, tile_keys;  // keys of this tile / of all tiles
+  uint32_t lex = block_exclusive_scan<uint32_t, kRsBlock>(cs, scan_smem, &tile_keys);  // local
   uint32_t gex = block_exclusive_scan<uint32_t, kRsBlock>(ts, scan_smem, &all);        // global
-  if (src.n_kept != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *src.n_kept = all;
-  const int tile_n = (int)tile_kept;
+  const int tile_n = (int)tile_keys;
 #pragma unroll
   for (int j = 0; j < kPerThread; j++) {
     const int b = threadIdx.x * kPerThread + j;
@@ -258,7 +240,7 @@ __global__ void __launch_bounds__(kRsBlock)
 #pragma unroll
   for (int r = 0; r < kRsRounds; r++) {
     const size_t i = base + (size_t)r * 64;
-    const bool valid = i < n && key[r] >= skip;
+    const bool valid = i < n;
     const uint32_t d = (key[r] >> shift) & (kRsBins - 1);
     const uint32_t v = valid ? (f64 ? rs_payload(src, i) : vin[i]) : 0u;
     uint32_t first = 0u;
@@ -323,18 +305,11 @@ static int radix_sort_run(uint32_t* ktmp, uint32_t* vtmp, uint32_t* hist, uint32
     src.flag = (p == 0 && first) ? first->flag : nullptr;
     src.map_inner = first ? first->map_inner : 0u;
     src.map_outer = first ? first->map_outer : 0u;
-    // a filtering first pass posts how many keys it kept; the later passes (and the caller's
-    // kernels) work on that many -- their grids are launched for n, tiles past the end exit
-    const bool filtered = first != nullptr && first->skip_below != 0u && first->n_kept != nullptr;
-    src.skip_below = (p == 0 && filtered) ? first->skip_below : 0u;
-    src.n_kept = (p == 0 && filtered) ? first->n_kept : nullptr;
-    src.n_live = (p > 0 && filtered) ? first->n_kept : nullptr;
     hipLaunchKernelGGL((rs_hist_kernel<BITS>), dim3((unsigned)tiles), dim3(kRsBlock), 0, s,
                        sk, n, shift, hist, src);
     HCTR_LAUNCH_CHECK();
     hipLaunchKernelGGL((rs_colscan_kernel<BITS>), dim3(kRsBins / kRsScanBins),
-                       dim3(kRsScanBlock), 0, s, hist, tiles, total, src.n_live,
-                       (uint32_t)kRsTile);
+                       dim3(kRsScanBlock), 0, s, hist, tiles, total);
     HCTR_LAUNCH_CHECK();
     hipLaunchKernelGGL((rs_scatter_kernel<BITS, MASK>), dim3((unsigned)tiles),
                        dim3(kRsBlock), 0, s, sk, sv, dk, dv, n, shift, hist, total, src);

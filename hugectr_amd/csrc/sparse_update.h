@@ -23,13 +23,12 @@ struct SparseUpdater {
   size_t max_nnz = 0;
   size_t max_vocab = 0;
   int D = 0;
-  bool key32 = true;  // sort keys fit 32 bits
   // rows handed out so far are < row_bound (0 = unknown): the sort then covers log2(row_bound)
   // key bits instead of log2(max_vocab) -- one digit pass less while a table is filling up
   size_t row_bound = 0;
   // sort buffers
-  void* sort_keys_in = nullptr;
-  void* sort_keys_out = nullptr;
+  uint32_t* sort_keys_in = nullptr;
+  uint32_t* sort_keys_out = nullptr;
   uint32_t* sort_vals_in = nullptr;
   uint32_t* sort_vals_out = nullptr;
   void* sort_temp = nullptr;
@@ -73,7 +72,6 @@ struct SparseUpdater {
   uint32_t hot_streams = 0;
   uint32_t hot_rows = 0;        // H; 0 = off (HCTR_HOT_ROWS, default 8192, at most 16384)
   hipStream_t hot_side = nullptr;  // the cold pairs' chain (default priority)
-  bool hot_serial = false;         // HCTR_HOT_SERIAL=1: no side stream (measurements)
   size_t hot_min_n = 0;         // batches with fewer positions keep the plain path (HCTR_HOT_MIN)
   uint32_t hot_chunks_max = 0;  // chunks the tables below have room for
   uint16_t* hot_loc = nullptr;        // [hot_rows][hot_chunks_max] partial number of (row, chunk)
@@ -83,14 +81,12 @@ struct SparseUpdater {
   uint32_t* hot_items = nullptr;       // tiles with entries (work list of hot_reduce_kernel)
   uint32_t* hot_loc_blk = nullptr;     // [hot_rows] blocks of 32 chunks that hold a partial of the row
   uint32_t* hot_joins = nullptr;       // [.][3] runs that cross tile borders (hot_join_kernel)
-  uint32_t* hot_counts = nullptr;      // two alternating sets {pool slots, items, joins, -} + [8] pairs the sort kept
+  uint32_t* hot_counts = nullptr;      // two alternating sets {pool slots, items, joins, -}
   uint32_t hot_parity = 0;             // set the next update takes
   float* hot_head = nullptr;           // [hot_chunks_max * 128][D] tile partials of runs that
   float* hot_tail = nullptr;           //   cross tile borders inside a chunk
   // cold rows of the same batches (sparse_update.hip, "cold rows of a one-key-per-position batch"):
-  // counted per row instead of sorted.  HCTR_COLD_COUNT=0 keeps the filtering radix sort + segmented
-  // reduce of round 4 (measurements, the bit-equality tests).
-  bool cold_count = true;
+  // counted per row instead of sorted.
   uint32_t* cold_cnt = nullptr;     // [max_vocab] per-row counter / base word, zero between updates
   uint32_t* cold_rank = nullptr;    // [max_nnz]
   uint32_t* cold_plist = nullptr;   // [max_nnz]

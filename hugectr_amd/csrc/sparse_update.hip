@@ -17,7 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
+#include <type_traits>
 
 #include "block_prims.h"
 
@@ -77,10 +77,10 @@ struct Load4<__hip_bfloat16> {
 };
 
 // ---- step 1: (row index, bucket id) pairs (sample_id_expand_kernel :189-200) ------------------
-template <typename OffT, typename SortK>
+template <typename OffT>
 __global__ void __launch_bounds__(kBlock)
     expand_pairs_kernel(size_t buckets, size_t n_sort, const OffT* __restrict__ row_offset,
-                        const uint64_t* __restrict__ value_index, SortK* __restrict__ keys,
+                        const uint64_t* __restrict__ value_index, uint32_t* __restrict__ keys,
                         uint32_t* __restrict__ vals, uint32_t* __restrict__ span_count,
                         uint32_t map_inner, uint32_t map_outer,
                         const uint32_t* __restrict__ skip_flag) {
@@ -95,28 +95,27 @@ __global__ void __launch_bounds__(kBlock)
   // (SparseUpdater::map_inner)
   for_each_key_wave(buckets, row_offset, [&](size_t u, size_t j) {
     if (j >= n_sort) return;
-    keys[j] = (SortK)value_index[j];
+    keys[j] = (uint32_t)value_index[j];
     vals[j] = map_inner ? ((uint32_t)u % map_inner) * map_outer + (uint32_t)u / map_inner
                         : (uint32_t)u;
   });
   // padding (host upper bound > live nnz): sorts to the end, never forms a counted run
   if (blockIdx.y != 0) return;
   for (size_t j = nnz + tid; j < n_sort; j += nthreads) {
-    keys[j] = (SortK)~(SortK)0;
+    keys[j] = ~0u;
     vals[j] = 0xFFFFFFFFu;
   }
 }
 
 // ---- step 2: run starts ------------------------------------------------------------------------
-template <typename SortK>
-__device__ __forceinline__ bool is_run_start(const SortK* k, size_t i, size_t nnz) {
+__device__ __forceinline__ bool is_run_start(const uint32_t* k, size_t i, size_t nnz) {
   if (i >= nnz) return false;
   return i == 0 || k[i] != k[i - 1];
 }
 
-template <typename OffT, typename SortK>
+template <typename OffT>
 __global__ void __launch_bounds__(kBlock)
-    run_count_kernel(const SortK* __restrict__ keys, const OffT* __restrict__ row_offset,
+    run_count_kernel(const uint32_t* __restrict__ keys, const OffT* __restrict__ row_offset,
                      size_t buckets, size_t n_tiles, uint32_t* __restrict__ tile_sums) {
   __shared__ uint32_t smem[kBlock / 64 + 1];
   const size_t nnz = (size_t)row_offset[buckets];
@@ -152,9 +151,9 @@ __global__ void __launch_bounds__(1024)
   if (threadIdx.x == 0) *d_total = carry;
 }
 
-template <typename OffT, typename SortK>
+template <typename OffT>
 __global__ void __launch_bounds__(kBlock)
-    run_write_kernel(const SortK* __restrict__ keys, const OffT* __restrict__ row_offset,
+    run_write_kernel(const uint32_t* __restrict__ keys, const OffT* __restrict__ row_offset,
                      size_t buckets, size_t n_tiles, const uint32_t* __restrict__ tile_sums,
                      const uint64_t* __restrict__ d_num_runs, uint32_t* __restrict__ run_start) {
   __shared__ uint32_t smem[kBlock / 64 + 1];
@@ -457,17 +456,16 @@ __device__ __forceinline__ uint32_t seg_row_at(const uint32_t (&mrow)[NPL], int 
 
 constexpr int kFuseNone = 0, kFuseSgd = 1, kFuseAdaGrad = 2;
 
-template <int LPR, typename OffT, typename SortK, typename GradT, int kFuse>
+template <int LPR, typename OffT, typename GradT, int kFuse>
 __global__ void __launch_bounds__(kBlock)
     seg_reduce_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                      const SortK* __restrict__ sorted_rows,
+                      const uint32_t* __restrict__ sorted_rows,
                       const uint32_t* __restrict__ sorted_buckets, int combiner,
                       const GradT* __restrict__ grad, float* __restrict__ gsum,
                       float* __restrict__ head, float* __restrict__ tail,
                       uint32_t* __restrict__ span_list, uint32_t* __restrict__ span_count,
                       float* __restrict__ direct_out, const OffT* __restrict__ scale_ro,
-                      OptConst fuse_o, float* __restrict__ fuse_state0,
-                      const uint32_t* __restrict__ n_live) {
+                      OptConst fuse_o, float* __restrict__ fuse_state0) {
   // kFuse (kFuseSgd / kFuseAdaGrad): the optimizer applied where a run's sum is complete --
   // e.g. table[row] += -lr * (sum / scaler) -- right here (direct_out = the table) instead of
   // parking the sum in gsum for seg_apply.  Every row is one run owned by one lane group, so
@@ -496,9 +494,7 @@ __global__ void __launch_bounds__(kBlock)
   const int l = threadIdx.x % LPR;
   const int gshift = ((threadIdx.x & 63) / LPR) * LPR;  // first lane of my group in the wave
   constexpr unsigned long long kGroupMask = ML >= 64 ? ~0ull : ((1ull << ML) - 1ull);
-  // (n_live: the sorted list holds the cold rows' positions only -- the sort's first pass left the
-  //  hot rows to hot_chunk_kernel and posted how many pairs it kept)
-  const size_t nnz = n_live != nullptr ? (size_t)*n_live : (size_t)row_offset[buckets];
+  const size_t nnz = (size_t)row_offset[buckets];
   const size_t n_tiles = (nnz + T - 1) / T;
   // kFuse: the row update of a finished run is completed when the NEXT run finishes -- its row
   // (and accumulator) read travels while the next run's gradients are added, instead of stalling
@@ -726,25 +722,24 @@ __global__ void __launch_bounds__(kBlock)
 // RowRegs (w, two state vectors, four time stamps: 148 VGPRs, 3 waves per SIMD), 8 rows per lane
 // group in flight instead of 4 (93 VGPRs).  Same arithmetic, same bits; seg_apply 98 -> 70 us at
 // the bench shape.
-template <int LPR, typename OffT, typename SortK, bool kSgd>
+template <int LPR, typename OffT, bool kSgd>
 __global__ void __launch_bounds__(kBlock)
     seg_apply_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                     const SortK* __restrict__ sorted_rows, const float* __restrict__ gsum,
+                     const uint32_t* __restrict__ sorted_rows, const float* __restrict__ gsum,
                      OptConst o, float* __restrict__ table, float* __restrict__ state0,
-                     float* __restrict__ state1, unsigned long long* __restrict__ prev_time,
-                     const uint32_t* __restrict__ n_live) {
+                     float* __restrict__ state1, unsigned long long* __restrict__ prev_time) {
   constexpr int D = LPR * 4;
   constexpr int G = 64 / LPR;  // groups per wavefront
   constexpr int T = kSegTile;
   const int lane = threadIdx.x & 63;
   const int g = lane / LPR;
   const int l = lane % LPR;
-  const size_t nnz = n_live != nullptr ? (size_t)*n_live : (size_t)row_offset[buckets];
+  const size_t nnz = (size_t)row_offset[buckets];
   const size_t wave = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
   const size_t nwaves = ((size_t)gridDim.x * kBlock) >> 6;
   for (size_t c0 = wave * 64; c0 < nnz; c0 += nwaves * 64) {
     const size_t p = c0 + lane;
-    SortK row = 0;
+    uint32_t row = 0;
     bool active = false;
     if (p < nnz) {
       row = sorted_rows[p];
@@ -829,16 +824,15 @@ constexpr int kCombBigTiles = 64;
 constexpr int kCombBlock = 1024;
 constexpr int kCombBigChunk = 2048;  // tile partials one workgroup of the big kernel adds
 
-template <int LPR, typename OffT, typename SortK>
+template <int LPR, typename OffT>
 __global__ void __launch_bounds__(kBlock)
     seg_combine_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                       const SortK* __restrict__ sorted_rows, OptConst o,
+                       const uint32_t* __restrict__ sorted_rows, OptConst o,
                        float* __restrict__ table, float* __restrict__ state0,
                        float* __restrict__ state1, unsigned long long* __restrict__ prev_time,
                        const float* __restrict__ head, const float* __restrict__ tail,
                        const uint32_t* __restrict__ span_list, uint32_t* __restrict__ span_count,
-                       uint32_t* __restrict__ big_list, size_t big_stride,
-                       const uint32_t* __restrict__ n_live) {
+                       uint32_t* __restrict__ big_list, size_t big_stride) {
   constexpr int D = LPR * 4;
   constexpr int GPB = kBlock / LPR;
   constexpr int CU = 8;
@@ -846,12 +840,12 @@ __global__ void __launch_bounds__(kBlock)
   const int g = threadIdx.x / LPR;
   const int l = threadIdx.x % LPR;
   const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
-  const size_t nnz = n_live != nullptr ? (size_t)*n_live : (size_t)row_offset[buckets];
+  const size_t nnz = (size_t)row_offset[buckets];
   const size_t n_tiles = (nnz + kSegTile - 1) / kSegTile;
   const uint32_t n_span = span_count[0];
   for (size_t si = (size_t)blockIdx.x * GPB + g; si < n_span; si += (size_t)gridDim.x * GPB) {
     const size_t t0 = span_list[si];
-    const SortK row = sorted_rows[(t0 + 1) * kSegTile - 1];
+    const uint32_t row = sorted_rows[(t0 + 1) * kSegTile - 1];
     float4 acc = *reinterpret_cast<const float4*>(tail + t0 * D + l * 4);
     size_t n_heads = 0;
     bool parked = false;
@@ -921,10 +915,10 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-template <int LPR, typename OffT, typename SortK>
+template <int LPR, typename OffT>
 __global__ void __launch_bounds__(kCombBlock)
     seg_combine_big_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                           const SortK* __restrict__ sorted_rows, OptConst o,
+                           const uint32_t* __restrict__ sorted_rows, OptConst o,
                            float* __restrict__ table, float* __restrict__ state0,
                            float* __restrict__ state1, unsigned long long* __restrict__ prev_time,
                            float* head, const float* __restrict__ tail, uint32_t* big_list,
@@ -962,7 +956,7 @@ __global__ void __launch_bounds__(kCombBlock)
     const size_t n_heads = big_len[slot];
     const uint32_t c = w - big_base[slot];
     const uint32_t nch = (uint32_t)((n_heads + kCombBigChunk - 1) / kCombBigChunk);
-    const SortK row = sorted_rows[(t0 + 1) * kSegTile - 1];
+    const uint32_t row = sorted_rows[(t0 + 1) * kSegTile - 1];
     const size_t h0 = (size_t)c * kCombBigChunk;
     const size_t h1 = h0 + kCombBigChunk < n_heads ? h0 + kCombBigChunk : n_heads;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1049,9 +1043,10 @@ __global__ void __launch_bounds__(kCombBlock)
 //     pairs + hot partials <= nnz) and loc[row][chunk] says where;
 //   * hot_apply_kernel, one lane group per hot row: partials in ascending chunk order, then the
 //     optimizer -- a fixed association, so the result does not depend on scheduling;
-//   * the sort's first pass leaves out keys < H (RsFirst::skip_below); sort and segmented reduce
-//     of the cold pairs (n_live) run on a side stream next to the hot rows' kernels.
-// A batch that is not one-hot (flag 0) makes these kernels exit and the sort keeps every pair.
+//   * the positions of rows >= H go to the cold rows' chain (counted per row, below), which runs
+//     on a side stream next to the hot rows' kernels.
+// A batch that is not one-hot (flag 0) makes these kernels exit and the cold chain takes every
+// position.
 // Measured (MI355X, Criteo-1TB shape, round 4): one workgroup doing sort AND reduce of its chunk
 // (8 tiles per lane group, one after the other) took 132 us for 310 MB -- a latency chain on 3
 // waves per SIMD; hence the flat tile list.
@@ -1708,7 +1703,7 @@ __global__ void __launch_bounds__(kBlock)
                        const uint64_t* __restrict__ value_index, const GradT* __restrict__ grad,
                        OptConst o, float* __restrict__ table, float* __restrict__ state0,
                        float* __restrict__ state1, unsigned long long* __restrict__ prev_time,
-                       float* __restrict__ gsum, ColdBufs cb, uint32_t parts) {
+                       float* __restrict__ gsum, ColdBufs cb) {
   typedef typename Load4<GradT>::raw Raw;
   constexpr int D = LPR * 4;
   constexpr int GPB = kBlock / LPR;
@@ -1763,7 +1758,7 @@ __global__ void __launch_bounds__(kBlock)
   };
 
   // ---- long runs: one workgroup each --------------------------------------------------------------
-  const uint32_t n3 = (parts & 4u) ? cb.counts[kCcPl + 1] : 0u;
+  const uint32_t n3 = cb.counts[kCcPl + 1];
   for (uint32_t ir = blockIdx.x; ir < n3; ir += gridDim.x) {
     const uint4 e = cb.longs[ir];
     const uint32_t row = e.x, base = e.y, c = e.z;
@@ -1870,7 +1865,7 @@ __global__ void __launch_bounds__(kBlock)
   __syncthreads();  // (the long runs' LDS lists are no longer read)
 
   // ---- rows met once ---------------------------------------------------------------------------
-  const uint32_t n1 = (parts & 1u) ? cb.counts[kCcSs + 1] : 0u;
+  const uint32_t n1 = cb.counts[kCcSs + 1];
   for (uint32_t i0 = (blockIdx.x * (uint32_t)GPB + (uint32_t)g) * (uint32_t)NS1; i0 < n1;
        i0 += gridDim.x * (uint32_t)(GPB * NS1)) {
     uint32_t row[NS1], b[NS1];
@@ -1912,7 +1907,7 @@ __global__ void __launch_bounds__(kBlock)
     uint32_t* raw = lds + (size_t)g * (3 * EMAX);
     uint32_t* srt = raw + EMAX;
     uint32_t* erow = srt + EMAX;
-    const uint32_t n2 = (parts & 2u) ? cb.counts[kCcSs] : 0u;
+    const uint32_t n2 = cb.counts[kCcSs];
     for (uint32_t i0 = (blockIdx.x * (uint32_t)GPB + (uint32_t)g) * (uint32_t)NSS; i0 < n2;
          i0 += gridDim.x * (uint32_t)(GPB * NSS)) {
       uint32_t srow[NSS], sbase[NSS], soff[NSS + 1];
@@ -1995,13 +1990,23 @@ __global__ void __launch_bounds__(kBlock)
 
 }
 
-// HCTR_SORT=rocprim selects the library's one-sweep sort (A/B measurements); default: radix_sort.hip
-inline bool use_library_sort() {
-  static const bool v = [] {
-    const char* e = getenv("HCTR_SORT");
-    return e != nullptr && e[0] == 'r';
-  }();
-  return v;
+// D / 4 lanes per row as a compile-time constant: f(std::integral_constant<int, LPR>{}) for
+// LPR = lpr in {1, 2, 4, 8, 16, 32, 64} (lpr_supported; anything else is taken as 64)
+inline bool lpr_supported(int D) {
+  const int lpr = D / 4;
+  return D % 4 == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0;
+}
+template <typename F>
+inline auto with_lpr(int lpr, F&& f) {
+  switch (lpr) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
 }
 
 // What the hot / cold kernels of one batch share: geometry, buffers, counter sets.  Built once per
@@ -2031,11 +2036,9 @@ __global__ void __launch_bounds__(kBlock) cold_clear_kernel(ColdBufs cb) {
 // everything the path asks of a batch except what only the update knows (gradient alignment,
 // store-only mode)
 inline bool plan_possible(const SparseUpdater& u, size_t buckets, size_t nnz) {
-  const int D = u.D, lpr = D / 4;
-  const bool lpr_ok = D % 4 == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0;
   const uint32_t G = u.hot_streams;
   if (!(u.hot_rows > 0 && u.one_hot_flag != nullptr && G > 0 && G <= kHotMaxStreams &&
-        nnz == buckets && nnz >= u.hot_min_n && nnz < 0x7FFFFFF0ull && lpr_ok &&
+        nnz == buckets && nnz >= u.hot_min_n && nnz < 0x7FFFFFF0ull && lpr_supported(u.D) &&
         u.scale_row_offset == nullptr))
     return false;
   // (a gradient map -- the embedding_collection's transposed read -- is applied by the cold chain
@@ -2044,21 +2047,7 @@ inline bool plan_possible(const SparseUpdater& u, size_t buckets, size_t nnz) {
   if (u.map_inner != 0u) return false;
   const size_t per_g = ceil_div<size_t>(nnz, (size_t)G);
   const size_t n_chunks = (size_t)G * ceil_div<size_t>(per_g, (size_t)kHotChunk);
-  const char* ip_env = getenv("HCTR_SORT_IN_PLACE");
-  return n_chunks <= (size_t)u.hot_chunks_max && n_chunks <= (size_t)kHotApplyChunks &&
-         !use_library_sort() && !(ip_env && ip_env[0] == '0');
-}
-
-inline int cold_short_max(int lpr) {
-  switch (lpr) {
-    case 1: return ColdShape<1>::kShortMax;
-    case 2: return ColdShape<2>::kShortMax;
-    case 4: return ColdShape<4>::kShortMax;
-    case 8: return ColdShape<8>::kShortMax;
-    case 16: return ColdShape<16>::kShortMax;
-    case 32: return ColdShape<32>::kShortMax;
-    default: return ColdShape<64>::kShortMax;
-  }
+  return n_chunks <= (size_t)u.hot_chunks_max && n_chunks <= (size_t)kHotApplyChunks;
 }
 
 inline void plan_build(SparseUpdater& u, PrePlan& pp, size_t buckets, size_t nnz, int combiner,
@@ -2084,7 +2073,7 @@ inline void plan_build(SparseUpdater& u, PrePlan& pp, size_t buckets, size_t nnz
   pp.hb.items = u.hot_items;
   pp.hb.loc_blk = u.hot_loc_blk;
   pp.hb.joins = u.hot_joins;
-  // counter sets alternate: [0..3] / [4..7]; [8] = pairs the sort kept
+  // counter sets alternate: [0..3] / [4..7]
   pp.hb.counts = u.hot_counts + 4 * (u.hot_parity & 1u);
   pp.hb.counts_next = u.hot_counts + 4 * ((u.hot_parity + 1u) & 1u);
   pp.hb.loc = u.hot_loc;
@@ -2095,7 +2084,8 @@ inline void plan_build(SparseUpdater& u, PrePlan& pp, size_t buckets, size_t nnz
   pp.cg.max_vocab = (uint32_t)u.max_vocab;
   pp.cg.map_inner = u.map_inner;
   pp.cg.map_outer = u.map_outer;
-  pp.cg.short_max = (uint32_t)cold_short_max(pp.lpr);
+  pp.cg.short_max =
+      (uint32_t)with_lpr(pp.lpr, [](auto L) { return ColdShape<decltype(L)::value>::kShortMax; });
   pp.cg.off_is_u32 = off_is_u32 ? 1 : 0;
   pp.cg.combiner = combiner;
   pp.cg.buckets = buckets;
@@ -2146,11 +2136,11 @@ inline int plan_discard(SparseUpdater& u, PrePlan& pp, hipStream_t s) {
 }
 
 // any D: one wavefront per run, lanes stride over the vector
-template <typename OffT, typename SortK, typename GradT>
+template <typename OffT, typename GradT>
 __global__ void __launch_bounds__(kBlock)
     update_rows_generic_kernel(const uint64_t* __restrict__ d_num_runs,
                                const uint32_t* __restrict__ run_start,
-                               const SortK* __restrict__ sorted_rows,
+                               const uint32_t* __restrict__ sorted_rows,
                                const uint32_t* __restrict__ sorted_buckets,
                                const OffT* __restrict__ scale_ro, int combiner, int D,
                                const GradT* __restrict__ grad, OptConst o,
@@ -2321,62 +2311,22 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 
-template <typename SortK>
-int sort_pairs(void* temp, size_t& temp_bytes, const SortK* kin, SortK* kout, const uint32_t* vin,
-               uint32_t* vout, size_t n, int end_bit, hipStream_t s, const RsFirst* first = nullptr) {
-  static_assert(sizeof(SortK) == 4, "32-bit sort keys");
-  if (temp == nullptr) {  // size query: room for either implementation
-    size_t lib = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, lib, kin, kout, vin, vout, n, 0,
-                                             (unsigned)end_bit, s, false);
-    if (e != hipSuccess) {
-      set_error(std::string("rocprim::radix_sort_pairs: ") + hipGetErrorString(e));
-      return HCTR_ERR_HIP;
-    }
-    const size_t own = radix_sort_temp_bytes(n);
-    temp_bytes = lib > own ? lib : own;
-    return HCTR_OK;
-  }
-  if (!use_library_sort())
-    return radix_sort_pairs_u32(temp, temp_bytes, (const uint32_t*)kin, (uint32_t*)kout, vin, vout,
-                                n, end_bit, s, first);
-  hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, kin, kout, vin, vout, n, 0,
-                                           (unsigned)end_bit, s, false);
-  if (e != hipSuccess) {
-    set_error(std::string("rocprim::radix_sort_pairs: ") + hipGetErrorString(e));
-    return HCTR_ERR_HIP;
-  }
-  return HCTR_OK;
-}
-
-// (row, bucket) pairs -> stable radix sort by row (sparse_optimizer.cu:657-676)
-// skip_below / n_kept: the hot path's filter (RsFirst); `timed`: stage 2 of the profiler brackets
-// the sort here (the hot path brackets the fork .. join on the caller's stream instead)
-template <typename OffT, typename SortK>
+// (row, bucket) pairs -> stable radix sort by row (sparse_optimizer.cu:657-676); stage 2 of the
+// profiler brackets the sort
+template <typename OffT>
 int sort_stage(SparseUpdater& u, size_t buckets, size_t n, const OffT* ro, const uint64_t* vi,
-               hipStream_t s, uint32_t skip_below = 0u, uint32_t* n_kept = nullptr,
-               bool timed = true) {
-  SortK* kin = (SortK*)u.sort_keys_in;
-  SortK* kout = (SortK*)u.sort_keys_out;
+               hipStream_t s) {
   // wavefronts per 64-bucket chunk = the average bucket length (for_each_key_wave): one for
   // one-hot input, 8 for the MLPerf multi-hot shape whose 100-hot table would otherwise be the tail
   const size_t avg = buckets > 0 ? (n + buckets - 1) / buckets : 1;
   const unsigned parts = (unsigned)(avg < 1 ? 1 : (avg > 16 ? 16 : avg));
   // one key per bucket on the host's count AND on the device's word (the index stage checked the
   // offsets): rows and payloads are read in place by the sort's first pass
-  RsFirst first;
-  first.keys64 = vi;
-  first.flag = u.one_hot_flag;
-  first.map_inner = u.map_inner;
-  first.map_outer = u.map_outer;
-  first.skip_below = skip_below;
-  first.n_kept = n_kept;
-  const char* ip_env = getenv("HCTR_SORT_IN_PLACE");
-  const bool in_place = u.one_hot_flag != nullptr && n == buckets && !use_library_sort() &&
-                        !(ip_env && ip_env[0] == '0');
-  hipLaunchKernelGGL((expand_pairs_kernel<OffT, SortK>), dim3(grid_for(buckets, kBlock), parts),
-                     dim3(kBlock), 0, s, buckets, n, ro, vi, kin, u.sort_vals_in, u.span_count,
-                     u.map_inner, u.map_outer, in_place ? u.one_hot_flag : nullptr);
+  const RsFirst first = {vi, u.one_hot_flag, u.map_inner, u.map_outer};
+  const bool in_place = u.one_hot_flag != nullptr && n == buckets;
+  hipLaunchKernelGGL((expand_pairs_kernel<OffT>), dim3(grid_for(buckets, kBlock), parts),
+                     dim3(kBlock), 0, s, buckets, n, ro, vi, u.sort_keys_in, u.sort_vals_in,
+                     u.span_count, u.map_inner, u.map_outer, in_place ? u.one_hot_flag : nullptr);
   HCTR_LAUNCH_CHECK();
   // end_bit = log2(max_vocab)+1 (sparse_optimizer.cu:663).  The padding key and the key of a
   // position without a row are all ones: inside end_bit bits they are 2^end_bit - 1, above every
@@ -2384,21 +2334,16 @@ int sort_stage(SparseUpdater& u, size_t buckets, size_t n, const OffT* ro, const
   int end_bit = 1;
   // (row_bound: the caller may know that only the first row_bound rows of the table exist yet)
   const size_t top = (u.row_bound > 0 && u.row_bound < u.max_vocab) ? u.row_bound : u.max_vocab;
-  while (end_bit < (int)sizeof(SortK) * 8 && ((size_t)1 << end_bit) <= top) end_bit++;
-  size_t tb = u.sort_temp_bytes;
-  if (u.prof && timed) u.prof->begin(2, s);
-  HCTR_TRY(sort_pairs<SortK>(u.sort_temp, tb, kin, kout, u.sort_vals_in, u.sort_vals_out, n,
-                             end_bit, s, in_place ? &first : nullptr));
-  if (u.prof && timed) u.prof->end(2, s);
+  while (end_bit < 32 && ((size_t)1 << end_bit) <= top) end_bit++;
+  if (u.prof) u.prof->begin(2, s);
+  HCTR_TRY(radix_sort_pairs_u32(u.sort_temp, u.sort_temp_bytes, u.sort_keys_in, u.sort_keys_out,
+                                u.sort_vals_in, u.sort_vals_out, n, end_bit, s,
+                                in_place ? &first : nullptr));
+  if (u.prof) u.prof->end(2, s);
   return HCTR_OK;
 }
 
-template <typename OffT, typename SortK, typename GradT>
-int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const OffT* ro,
-                 const uint64_t* vi, const GradT* grad, const OptState& opt, float* table,
-                 float* state0, float* state1, uint64_t* prev_time, hipStream_t s) {
-  const int D = u.D;
-  const OffT* sro = u.scale_row_offset ? (const OffT*)u.scale_row_offset : ro;
+inline OptConst opt_const(const OptState& opt) {
   OptConst o;
   o.optimizer = opt.optimizer;
   o.update_type = opt.update_type;
@@ -2417,15 +2362,238 @@ int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, con
   o.ftrl_l1 = opt.ftrl_lambda1;
   o.ftrl_l2b = opt.ftrl_lambda2 + opt.ftrl_beta / opt.lr;
   o.state_half = opt.state_half;
-  // Global update types sweep the table (sparse_optimizer.cu:269-347 run over all
-  // max_vocabulary_size_per_gpu rows).  A row that was never handed out has zero state,
-  // and zero state is a fixed point of every sweep (m = v = 0 stay 0, w += -alpha * 0 / (0 + eps)
-  // leaves w's bits alone): sweeping the rows handed out so far -- row_bound, the same upper bound
-  // the sort's key width uses -- gives the identical table for a fraction of the traffic while a
-  // table fills up (DeepFM / Criteo-Kaggle, 33.7 M rows x 16: 12.9 GB per step down to the live rows).
-  const size_t live_rows = (u.row_bound > 0 && u.row_bound < u.max_vocab) ? u.row_bound : u.max_vocab;
-  const size_t table_elems = live_rows * (size_t)D;
+  return o;
+}
 
+// Global update types sweep the table (sparse_optimizer.cu:269-347 run over all
+// max_vocabulary_size_per_gpu rows).  A row that was never handed out has zero state,
+// and zero state is a fixed point of every sweep (m = v = 0 stay 0, w += -alpha * 0 / (0 + eps)
+// leaves w's bits alone): sweeping the rows handed out so far -- row_bound, the same upper bound
+// the sort's key width uses -- gives the identical table for a fraction of the traffic while a
+// table fills up (DeepFM / Criteo-Kaggle, 33.7 M rows x 16: 12.9 GB per step down to the live rows).
+inline size_t swept_elems(const SparseUpdater& u) {
+  const size_t live_rows = (u.row_bound > 0 && u.row_bound < u.max_vocab) ? u.row_bound : u.max_vocab;
+  return live_rows * (size_t)u.D;
+}
+
+// the sweep that runs before the rows of the batch are updated (Nesterov)
+inline int global_sweep_before(const SparseUpdater& u, const OptState& opt, float* table,
+                               float* state0, hipStream_t s) {
+  if (!(opt.optimizer == HCTR_OPT_NESTEROV && opt.update_type == HCTR_UPDATE_GLOBAL))
+    return HCTR_OK;
+  const size_t n = swept_elems(u);
+  hipLaunchKernelGGL(nesterov_global_sweep_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
+                     n, opt.momentum_factor, opt.state_half, state0, table);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+// the sweep that runs after them (Adam, momentum SGD)
+inline int global_sweep_after(const SparseUpdater& u, const OptState& opt, const OptConst& o,
+                              float* table, float* state0, float* state1, hipStream_t s) {
+  if (opt.update_type != HCTR_UPDATE_GLOBAL) return HCTR_OK;
+  const size_t n = swept_elems(u);
+  if (opt.optimizer == HCTR_OPT_ADAM) {
+    hipLaunchKernelGGL(adam_global_sweep_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n,
+                       opt.beta1, opt.beta2, opt.epsilon, o.alpha_t, opt.state_half, state0,
+                       state1, table);
+    HCTR_LAUNCH_CHECK();
+  } else if (opt.optimizer == HCTR_OPT_MOMENTUM_SGD) {
+    hipLaunchKernelGGL(momentum_global_sweep_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
+                       n, opt.momentum_factor, opt.state_half, state0, table);
+    HCTR_LAUNCH_CHECK();
+  }
+  return HCTR_OK;
+}
+
+// SGD with atomic_update: every (bucket, key) adds its scaled gradient to its row, nothing sorted
+template <typename OffT, typename GradT>
+int update_sgd_atomic(const SparseUpdater& u, size_t buckets, int combiner, const OffT* ro,
+                      const OffT* sro, const uint64_t* vi, const GradT* grad, const OptState& opt,
+                      float* table, hipStream_t s) {
+  const float lr_scale = opt.lr / opt.scaler;
+  hipLaunchKernelGGL((sgd_atomic_kernel<OffT, GradT>), dim3(grid_for(buckets * 64, kBlock)),
+                     dim3(kBlock), 0, s, buckets, u.D, combiner, ro, vi, grad, lr_scale, table,
+                     sro);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+// the (row, bucket) list the sorted paths walk: ascending rows, n entries (padding behind the live
+// ones); need_sort: it still has to be made, into sort_keys_out / sort_vals_out (sort_stage)
+struct SortedPairs {
+  const uint32_t* rows;
+  const uint32_t* buckets;
+  size_t n;
+  bool need_sort;
+};
+
+inline int pairs_source(SparseUpdater& u, size_t buckets, size_t nnz, const uint64_t* vi,
+                        hipStream_t s, SortedPairs& p) {
+  p = {u.sort_keys_out, u.sort_vals_out, nnz, false};
+  if (u.ext_rows != nullptr) {
+    // presorted by the caller: only the long-run counters need a reset
+    p.rows = u.ext_rows;
+    p.buckets = u.ext_buckets;
+    HCTR_HIP(hipMemsetAsync(u.span_count, 0, 4 * sizeof(uint32_t), s));
+  } else if (u.early_n >= nnz && u.early_vi == vi && u.early_buckets == buckets) {
+    // (row, bucket) pairs of this batch were sorted on the side stream right after the index
+    // stage (SparseUpdater::presort); padding keys sit behind the live ones
+    HCTR_HIP(hipStreamWaitEvent(s, u.ev_sorted, 0));
+    p.n = u.early_n;
+  } else {
+    p.need_sort = true;
+  }
+  u.early_n = 0;
+  return HCTR_OK;
+}
+
+// Hot rows of a one-hot batch (see hot_sort_kernel) on s, the cold rows' chain (see
+// cold_count_kernel) on the side stream; they touch disjoint rows.  pre: prework() enqueued the
+// grouping kernels of this batch already.  Stage 2 of the profiler = fork .. join, all of the
+// update.
+template <typename OffT, typename GradT>
+int update_hot_cold(SparseUpdater& u, PrePlan& pp, bool pre, size_t buckets, size_t nnz,
+                    int combiner, const OffT* ro, const uint64_t* vi, const GradT* grad,
+                    const OptConst& o, float* table, float* state0, float* state1,
+                    uint64_t* prev_time, hipStream_t s) {
+  if (!pre) plan_build(u, pp, buckets, nnz, combiner, sizeof(OffT) == 4, vi);
+  hipStream_t cs = u.hot_side;  // the cold chain's stream
+  if (u.prof) u.prof->begin(2, s);
+  HCTR_HIP(hipEventRecord(u.ev_fork, s));
+  HCTR_HIP(hipStreamWaitEvent(cs, u.ev_fork, 0));
+  if (pre) {  // grouped ahead (prework): the reduces wait for their chain's kernels only
+    HCTR_HIP(hipStreamWaitEvent(s, pp.ev_hot, 0));
+    HCTR_HIP(hipStreamWaitEvent(cs, pp.ev_cold, 0));
+    pp.valid = false;
+  } else {
+    HCTR_TRY(plan_launch_grouping(u, pp, (const void*)ro, s, cs));
+  }
+  float* pool_end = u.gsum + u.max_nnz * (size_t)u.D;
+  const size_t items_max = nnz / kHotTile + pp.n_chunks;
+  // the hot rows' reduce is a grid-stride loop over a bounded number of workgroups: a kernel
+  // that queues one workgroup per tile fills every wave slot of the device and the other
+  // chain only trickles in (measured, round 4: its scatter 21 -> 96 us; 768 workgroups: 60)
+  constexpr int kColdGrid = 2048, kHotGrid = 768;
+  HCTR_TRY(with_lpr(pp.lpr, [&](auto L) -> int {
+    constexpr int LPR = decltype(L)::value;
+    constexpr int GPB = kBlock / LPR;
+    if (o.optimizer == HCTR_OPT_SGD)
+      hipLaunchKernelGGL((cold_reduce_kernel<LPR, GradT, true>), dim3(kColdGrid), dim3(kBlock), 0,
+                         cs, pp.cg, u.one_hot_flag, (const void*)ro, vi, grad, o, table, state0,
+                         state1, (unsigned long long*)prev_time, u.gsum, pp.cb);
+    else
+      hipLaunchKernelGGL((cold_reduce_kernel<LPR, GradT, false>), dim3(kColdGrid), dim3(kBlock),
+                         0, cs, pp.cg, u.one_hot_flag, (const void*)ro, vi, grad, o, table, state0,
+                         state1, (unsigned long long*)prev_time, u.gsum, pp.cb);
+    HCTR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((hot_reduce_kernel<LPR, GradT>), dim3(grid_for(items_max, GPB, kHotGrid)),
+                       dim3(kBlock), 0, s, pp.hg, u.one_hot_flag, grad, pool_end, pp.hb);
+    HCTR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((hot_join_kernel<LPR>), dim3(grid_for(items_max / 8 + 1, GPB, 2048)),
+                       dim3(kBlock), 0, s, pp.hg, u.one_hot_flag, pool_end, pp.hb);
+    HCTR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((hot_apply_kernel<LPR>), dim3(grid_for(u.hot_rows, GPB)), dim3(kBlock), 0,
+                       s, pp.hg, (uint32_t)pp.n_chunks, u.one_hot_flag, o, table, state0, state1,
+                       (unsigned long long*)prev_time, (const float*)pool_end, pp.hb);
+    HCTR_LAUNCH_CHECK();
+    return HCTR_OK;
+  }));
+  // join: the cold chain's end is ordered before whatever follows on s
+  HCTR_HIP(hipEventRecord(u.ev_sorted, cs));
+  HCTR_HIP(hipStreamWaitEvent(s, u.ev_sorted, 0));
+  if (u.prof) u.prof->end(2, s);
+  return HCTR_OK;
+}
+
+// the sorted list, D a supported multiple of 4 (lpr_supported): segmented reduce, the apply pass
+// unless the optimizer folds into the reduce, then the runs that cross tile borders.
+// direct != nullptr: store-only mode, finished runs are written straight to their output row
+template <typename OffT, typename GradT>
+int update_segmented(SparseUpdater& u, const SortedPairs& p, size_t buckets, int combiner,
+                     const OffT* ro, const OffT* sro, const GradT* grad, const OptConst& o,
+                     float* direct, float* table, float* state0, float* state1,
+                     uint64_t* prev_time, hipStream_t s) {
+  // plain SGD: the apply pass folds into the reduce (seg_reduce_kernel<.., kFuseSgd>);
+  // HCTR_SGD_FUSED=0 keeps the two-pass form (measurements, the bit-equality test)
+  const char* fuse_env = getenv("HCTR_SGD_FUSED");  // (read per call: tests flip it in-process)
+  int fuse = kFuseNone;
+  if (!(fuse_env && fuse_env[0] == '0') && direct == nullptr) {
+    if (o.optimizer == HCTR_OPT_SGD) fuse = kFuseSgd;
+    if (o.optimizer == HCTR_OPT_ADAGRAD) fuse = kFuseAdaGrad;
+  }
+  const size_t nnz = p.n;
+  const size_t seg_tiles = ceil_div<size_t>(nnz, (size_t)kSegTile);
+  return with_lpr(u.D / 4, [&](auto L) -> int {
+    constexpr int LPR = decltype(L)::value;
+    constexpr int GPB = kBlock / LPR;
+    auto reduce = [&](auto F, float* out) {
+      hipLaunchKernelGGL((seg_reduce_kernel<LPR, OffT, GradT, decltype(F)::value>),
+                         dim3(grid_for(seg_tiles, GPB, 1 << 20)), dim3(kBlock), 0, s, buckets, ro,
+                         p.rows, p.buckets, combiner, grad, u.gsum, u.seg_head, u.seg_tail,
+                         u.span_list, u.span_count, out, sro, o, state0);
+    };
+    if (fuse == kFuseSgd) reduce(std::integral_constant<int, kFuseSgd>{}, table);
+    else if (fuse == kFuseAdaGrad) reduce(std::integral_constant<int, kFuseAdaGrad>{}, table);
+    else reduce(std::integral_constant<int, kFuseNone>{}, direct);
+    HCTR_LAUNCH_CHECK();
+    if (direct == nullptr && fuse == kFuseNone) {
+      if (o.optimizer == HCTR_OPT_SGD)
+        hipLaunchKernelGGL((seg_apply_kernel<LPR, OffT, true>),
+                           dim3(grid_for(nnz, kBlock, 256 * 8)), dim3(kBlock), 0, s, buckets, ro,
+                           p.rows, u.gsum, o, table, state0, state1,
+                           (unsigned long long*)prev_time);
+      else
+        hipLaunchKernelGGL((seg_apply_kernel<LPR, OffT, false>),
+                           dim3(grid_for(nnz, kBlock, 256 * 8)), dim3(kBlock), 0, s, buckets, ro,
+                           p.rows, u.gsum, o, table, state0, state1,
+                           (unsigned long long*)prev_time);
+      HCTR_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((seg_combine_kernel<LPR, OffT>), dim3(grid_for(seg_tiles, GPB * 4, 1024)),
+                       dim3(kBlock), 0, s, buckets, ro, p.rows, o, table, state0, state1,
+                       (unsigned long long*)prev_time, u.seg_head, u.seg_tail, u.span_list,
+                       u.span_count, u.big_list, u.big_stride);
+    HCTR_LAUNCH_CHECK();
+    hipLaunchKernelGGL((seg_combine_big_kernel<LPR, OffT>), dim3(256), dim3(kCombBlock), 0, s,
+                       buckets, ro, p.rows, o, table, state0, state1,
+                       (unsigned long long*)prev_time, u.seg_head, u.seg_tail, u.big_list,
+                       u.big_stride, u.span_count);
+    HCTR_LAUNCH_CHECK();
+    return HCTR_OK;
+  });
+}
+
+// any other embedding_vec_size: run detection + one wavefront per unique row
+template <typename OffT, typename GradT>
+int update_generic(SparseUpdater& u, const SortedPairs& p, size_t buckets, int combiner,
+                   const OffT* ro, const OffT* sro, const GradT* grad, const OptConst& o,
+                   float* table, float* state0, float* state1, uint64_t* prev_time,
+                   hipStream_t s) {
+  const size_t n_tiles = ceil_div<size_t>(p.n, kTile);
+  const int tgrid = (int)(n_tiles < (size_t)kMaxGrid ? n_tiles : (size_t)kMaxGrid);
+  hipLaunchKernelGGL((run_count_kernel<OffT>), dim3(tgrid), dim3(kBlock), 0, s, p.rows, ro,
+                     buckets, n_tiles, u.tile_sums);
+  HCTR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(scan_tiles_u32_kernel, dim3(1), dim3(1024), 0, s, u.tile_sums, n_tiles,
+                     u.d_num_runs);
+  HCTR_LAUNCH_CHECK();
+  hipLaunchKernelGGL((run_write_kernel<OffT>), dim3(tgrid), dim3(kBlock), 0, s, p.rows, ro,
+                     buckets, n_tiles, u.tile_sums, u.d_num_runs, u.run_start);
+  HCTR_LAUNCH_CHECK();
+  hipLaunchKernelGGL((update_rows_generic_kernel<OffT, GradT>), dim3(grid_for(p.n * 64, kBlock)),
+                     dim3(kBlock), 0, s, u.d_num_runs, u.run_start, p.rows, p.buckets, sro,
+                     combiner, u.D, grad, o, table, state0, state1, (unsigned long long*)prev_time);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+template <typename OffT, typename GradT>
+int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const OffT* ro,
+                 const uint64_t* vi, const GradT* grad, const OptState& opt, float* table,
+                 float* state0, float* state1, uint64_t* prev_time, hipStream_t s) {
+  const OffT* sro = u.scale_row_offset ? (const OffT*)u.scale_row_offset : ro;
+  const OptConst o = opt_const(opt);
   if (u.map_inner != 0u) {
     if (combiner != 0 || u.ext_rows != nullptr || (opt.optimizer == HCTR_OPT_SGD && opt.atomic_update) ||
         (size_t)u.map_inner * u.map_outer != buckets) {
@@ -2433,298 +2601,52 @@ int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, con
       return HCTR_ERR_INVALID_ARG;
     }
   }
-
-  if (opt.optimizer == HCTR_OPT_SGD && opt.atomic_update) {
-    const float lr_scale = opt.lr / opt.scaler;
-    hipLaunchKernelGGL((sgd_atomic_kernel<OffT, GradT>), dim3(grid_for(buckets * 64, kBlock)),
-                       dim3(kBlock), 0, s, buckets, D, combiner, ro, vi, grad, lr_scale, table, sro);
-    HCTR_LAUNCH_CHECK();
-    return HCTR_OK;
-  }
-
-  if (opt.optimizer == HCTR_OPT_NESTEROV && opt.update_type == HCTR_UPDATE_GLOBAL) {
-    hipLaunchKernelGGL(nesterov_global_sweep_kernel, dim3(grid_for(table_elems, kBlock)),
-                       dim3(kBlock), 0, s, table_elems, opt.momentum_factor, opt.state_half, state0,
-                       table);
-    HCTR_LAUNCH_CHECK();
-  }
-
+  if (opt.optimizer == HCTR_OPT_SGD && opt.atomic_update)
+    return update_sgd_atomic(u, buckets, combiner, ro, sro, vi, grad, opt, table, s);
+  HCTR_TRY(global_sweep_before(u, opt, table, state0, s));
   if (nnz > 0) {
-    SortK* kout = (SortK*)u.sort_keys_out;
-    const uint32_t* vout = u.sort_vals_out;
-    bool need_sort = false;
-    if (u.ext_rows != nullptr) {
-      // presorted by the caller: only the long-run counters need a reset
-      static_assert(sizeof(SortK) == 4, "presorted lists carry 32-bit rows");
-      kout = (SortK*)const_cast<uint32_t*>(u.ext_rows);
-      vout = u.ext_buckets;
-      HCTR_HIP(hipMemsetAsync(u.span_count, 0, 4 * sizeof(uint32_t), s));
-    } else if (u.early_n >= nnz && u.early_vi == vi && u.early_buckets == buckets) {
-      // (row, bucket) pairs of this batch were sorted on the side stream right after the index
-      // stage (SparseUpdater::presort); padding keys sit behind the live ones
-      HCTR_HIP(hipStreamWaitEvent(s, u.ev_sorted, 0));
-      nnz = u.early_n;
-    } else {
-      need_sort = true;
-    }
-    u.early_n = 0;
+    SortedPairs p;
+    HCTR_TRY(pairs_source(u, buckets, nnz, vi, s, p));
     const bool a16 = reinterpret_cast<uintptr_t>(grad) % 16 == 0;
-    bool done = false;
-    // store-only mode: finished runs are written straight to their output row
     float* direct = (opt.optimizer == kOptStoreSum && opt.scaler == 1.0f) ? table : nullptr;
-    // ---- hot rows (one key per bucket, device flag): see hot_sort_kernel ------------------------
-    const uint32_t* n_live = nullptr;
-    hipStream_t ss = s;  // stream of the segmented reduce
-    bool hot_taken = false, cold_taken = false;
-    int seg_grid_cap = 1 << 20;
-    {
-      const int lpr = D / 4;
-      PrePlan* pp = (PrePlan*)u.pre_plan;
-      const bool hot = need_sort && a16 && direct == nullptr && plan_possible(u, buckets, nnz);
-      // (prework() only ever runs for an updater whose cold rows are counted)
-      const bool pre = hot && pp != nullptr && pp->valid && pp->vi == vi && pp->n == nnz &&
-                       pp->buckets == buckets;
-      if (pp != nullptr && pp->valid && !pre) HCTR_TRY(plan_discard(u, *pp, s));
-      if (hot) HCTR_TRY(u.hot_buffers(s));
-      if (hot) {
-        pp = (PrePlan*)u.pre_plan;
-        const bool cold = u.cold_count && u.cold_cnt != nullptr;
-        if (!pre) plan_build(u, *pp, buckets, nnz, combiner, sizeof(OffT) == 4, vi);
-        const HotGeom& hg = pp->hg;
-        const HotBufs& hb = pp->hb;
-        const size_t n_chunks = pp->n_chunks;
-        // Two chains side by side: the cold rows (count / base / scatter / reduce -- or, with
-        // HCTR_COLD_COUNT=0, the filtering sort and the segmented reduce over what it kept) on the
-        // side stream, the hot rows on the caller's; they touch disjoint rows.  Stage 2 of the
-        // profiler = fork .. join, all of the update.
-        hipStream_t cs = u.hot_serial ? s : u.hot_side;  // the cold chain's stream
-        if (u.prof) u.prof->begin(2, s);
-        if (cs != s) {
-          HCTR_HIP(hipEventRecord(u.ev_fork, s));
-          HCTR_HIP(hipStreamWaitEvent(cs, u.ev_fork, 0));
-        }
-        if (pre) {  // grouped ahead (prework): the reduces wait for their chain's kernels only
-          HCTR_HIP(hipStreamWaitEvent(s, pp->ev_hot, 0));
-          HCTR_HIP(hipStreamWaitEvent(cs, pp->ev_cold, 0));
-          pp->valid = false;
-        } else if (cold) {
-          HCTR_TRY(plan_launch_grouping(u, *pp, (const void*)ro, s, cs));
-        } else {
-          hipLaunchKernelGGL(hot_sort_kernel, dim3((unsigned)n_chunks), dim3(kHotBlock), 0, s, hg,
-                             u.one_hot_flag, vi, hb);
-          HCTR_LAUNCH_CHECK();
-        }
-        if (cold) {
-          const ColdGeom& cg = pp->cg;
-          const ColdBufs& cb = pp->cb;
-          // HCTR_COLD_SPLIT=1 (measurements): the three parts of the reduce as three launches
-          const char* sp_env = getenv("HCTR_COLD_SPLIT");
-          const bool split = sp_env != nullptr && sp_env[0] == '1';
-          const char* cg_env = getenv("HCTR_COLD_GRID");
-          const int cold_grid = cg_env ? atoi(cg_env) : 2048;
-          const bool sgd = o.optimizer == HCTR_OPT_SGD;
-#define HCTR_COLD_CASE(LPR_)                                                                      \
-  {                                                                                               \
-    for (uint32_t part = split ? 1u : 7u; part <= 7u; part = split && part < 4u ? part << 1 : 8u) { \
-      if (sgd)                                                                                    \
-        hipLaunchKernelGGL((cold_reduce_kernel<LPR_, GradT, true>), dim3(cold_grid), dim3(kBlock), \
-                           0, cs, cg, u.one_hot_flag, (const void*)ro, vi, grad, o, table, state0, \
-                           state1, (unsigned long long*)prev_time, u.gsum, cb, part);             \
-      else                                                                                        \
-        hipLaunchKernelGGL((cold_reduce_kernel<LPR_, GradT, false>), dim3(cold_grid),             \
-                           dim3(kBlock), 0, cs, cg, u.one_hot_flag, (const void*)ro, vi, grad, o, \
-                           table, state0, state1, (unsigned long long*)prev_time, u.gsum, cb,     \
-                           part);                                                                 \
-      HCTR_LAUNCH_CHECK();                                                                        \
-    }                                                                                             \
-  }
-          switch (lpr) {
-            case 1: HCTR_COLD_CASE(1) break;
-            case 2: HCTR_COLD_CASE(2) break;
-            case 4: HCTR_COLD_CASE(4) break;
-            case 8: HCTR_COLD_CASE(8) break;
-            case 16: HCTR_COLD_CASE(16) break;
-            case 32: HCTR_COLD_CASE(32) break;
-            default: HCTR_COLD_CASE(64) break;
-          }
-#undef HCTR_COLD_CASE
-          cold_taken = true;
-        } else {
-          HCTR_TRY((sort_stage<OffT, SortK>(u, buckets, nnz, ro, vi, cs, u.hot_rows,
-                                            u.hot_counts + 8, false)));
-        }
-        float* pool_end = u.gsum + u.max_nnz * (size_t)D;
-        const size_t items_max = nnz / kHotTile + n_chunks;
-        // the hot rows' reduce is a grid-stride loop over a bounded number of workgroups: a kernel
-        // that queues one workgroup per tile fills every wave slot of the device and the other
-        // chain only trickles in (measured, round 4: its scatter 21 -> 96 us; 768 workgroups: 60).
-        // HCTR_SEG_GRID bounds the sorting path's segmented reduce for measurements.
-        const char* hg_env = getenv("HCTR_HOT_GRID");
-        const char* sg_env = getenv("HCTR_SEG_GRID");
-        const int hot_grid = hg_env ? atoi(hg_env) : 768;
-        if (sg_env) seg_grid_cap = atoi(sg_env);
-#define HCTR_HOT_CASE(LPR_)                                                                       \
-  {                                                                                               \
-    constexpr int GPB = kBlock / LPR_;                                                            \
-    hipLaunchKernelGGL((hot_reduce_kernel<LPR_, GradT>), dim3(grid_for(items_max, GPB, hot_grid)), \
-                       dim3(kBlock), 0, s, hg, u.one_hot_flag, grad, pool_end, hb);               \
-    HCTR_LAUNCH_CHECK();                                                                          \
-    hipLaunchKernelGGL((hot_join_kernel<LPR_>), dim3(grid_for(items_max / 8 + 1, GPB, 2048)),     \
-                       dim3(kBlock), 0, s, hg, u.one_hot_flag, pool_end, hb);                     \
-    HCTR_LAUNCH_CHECK();                                                                          \
-    hipLaunchKernelGGL((hot_apply_kernel<LPR_>), dim3(grid_for(u.hot_rows, GPB)), dim3(kBlock),   \
-                       0, s, hg, (uint32_t)n_chunks, u.one_hot_flag, o, table, state0, state1,    \
-                       (unsigned long long*)prev_time, (const float*)pool_end, hb);               \
-    HCTR_LAUNCH_CHECK();                                                                          \
-  }
-        switch (lpr) {
-          case 1: HCTR_HOT_CASE(1) break;
-          case 2: HCTR_HOT_CASE(2) break;
-          case 4: HCTR_HOT_CASE(4) break;
-          case 8: HCTR_HOT_CASE(8) break;
-          case 16: HCTR_HOT_CASE(16) break;
-          case 32: HCTR_HOT_CASE(32) break;
-          default: HCTR_HOT_CASE(64) break;
-        }
-#undef HCTR_HOT_CASE
-        n_live = u.hot_counts + 8;
-        ss = cs;  // the segmented reduce follows the sort on the side stream
-        hot_taken = true;
-      } else if (need_sort) {
-        HCTR_TRY((sort_stage<OffT, SortK>(u, buckets, nnz, ro, vi, s)));
-      }
-    }
-    if (u.prof && !hot_taken) u.prof->begin(3, s);
-    // plain SGD: the apply pass folds into the reduce (seg_reduce_kernel<.., kFuseSgd>);
-    // HCTR_SGD_FUSED=0 keeps the two-pass form (measurements, the bit-equality test)
-    const char* fuse_env = getenv("HCTR_SGD_FUSED");  // (read per call: tests flip it in-process)
-    int fuse = kFuseNone;
-    if (!(fuse_env && fuse_env[0] == '0') && direct == nullptr) {
-      if (o.optimizer == HCTR_OPT_SGD) fuse = kFuseSgd;
-      if (o.optimizer == HCTR_OPT_ADAGRAD) fuse = kFuseAdaGrad;
-    }
-#define HCTR_SEG_REDUCE(LPR_, FUSE_, OUT_)                                                        \
-  hipLaunchKernelGGL((seg_reduce_kernel<LPR_, OffT, SortK, GradT, FUSE_>),                        \
-                     dim3(grid_for(seg_tiles, GPB, seg_grid_cap)), dim3(kBlock), 0, ss, buckets,   \
-                     ro,                                                                          \
-                     kout, vout, combiner, grad, u.gsum, u.seg_head, u.seg_tail, u.span_list,     \
-                     u.span_count, OUT_, sro, o, state0, n_live)
-#define HCTR_SEG_CASE(LPR_)                                                                       \
-  {                                                                                               \
-    constexpr int GPB = kBlock / LPR_;                                                            \
-    const size_t seg_tiles = ceil_div<size_t>(nnz, (size_t)kSegTile);                             \
-    if (fuse == kFuseSgd) HCTR_SEG_REDUCE(LPR_, kFuseSgd, table);                                     \
-    else if (fuse == kFuseAdaGrad) HCTR_SEG_REDUCE(LPR_, kFuseAdaGrad, table);                        \
-    else HCTR_SEG_REDUCE(LPR_, kFuseNone, direct);                                                    \
-    HCTR_LAUNCH_CHECK();                                                                          \
-    if (direct == nullptr && fuse == kFuseNone) {                                                 \
-      if (o.optimizer == HCTR_OPT_SGD)                                                            \
-        hipLaunchKernelGGL((seg_apply_kernel<LPR_, OffT, SortK, true>),                           \
-                           dim3(grid_for(nnz, kBlock, 256 * 8)), dim3(kBlock), 0, ss, buckets, ro, \
-                           kout, u.gsum, o, table, state0, state1,                                \
-                           (unsigned long long*)prev_time, n_live);                               \
-      else                                                                                        \
-        hipLaunchKernelGGL((seg_apply_kernel<LPR_, OffT, SortK, false>),                          \
-                           dim3(grid_for(nnz, kBlock, 256 * 8)), dim3(kBlock), 0, ss, buckets, ro, \
-                           kout, u.gsum, o, table, state0, state1,                                \
-                           (unsigned long long*)prev_time, n_live);                               \
-      HCTR_LAUNCH_CHECK();                                                                        \
-    }                                                                                             \
-    hipLaunchKernelGGL((seg_combine_kernel<LPR_, OffT, SortK>),                                   \
-                       dim3(grid_for(seg_tiles, GPB * 4, 1024)), dim3(kBlock), 0, ss, buckets, ro, \
-                       kout, o, table, state0, state1, (unsigned long long*)prev_time, u.seg_head, \
-                       u.seg_tail, u.span_list, u.span_count, u.big_list, u.big_stride, n_live);  \
-    HCTR_LAUNCH_CHECK();                                                                          \
-    hipLaunchKernelGGL((seg_combine_big_kernel<LPR_, OffT, SortK>), dim3(256), dim3(kCombBlock),  \
-                       0, ss, buckets, ro, kout, o, table, state0, state1,                         \
-                       (unsigned long long*)prev_time, u.seg_head, u.seg_tail, u.big_list,        \
-                       u.big_stride, u.span_count);                                               \
-  }
-    if (cold_taken) {
-      done = true;  // (the cold rows' chain above applied its rows itself)
-    } else if (a16 && D % 4 == 0) {
-      done = true;
-      switch (D / 4) {
-        case 1: HCTR_SEG_CASE(1) break;
-        case 2: HCTR_SEG_CASE(2) break;
-        case 4: HCTR_SEG_CASE(4) break;
-        case 8: HCTR_SEG_CASE(8) break;
-        case 16: HCTR_SEG_CASE(16) break;
-        case 32: HCTR_SEG_CASE(32) break;
-        case 64: HCTR_SEG_CASE(64) break;
-        default: done = false;
-      }
-    }
-#undef HCTR_SEG_CASE
-#undef HCTR_SEG_REDUCE
-    if (!done) {
-      // generic embedding_vec_size: run detection + one wavefront per unique row
-      const size_t n_tiles = ceil_div<size_t>(nnz, kTile);
-      const int tgrid = (int)(n_tiles < (size_t)kMaxGrid ? n_tiles : (size_t)kMaxGrid);
-      hipLaunchKernelGGL((run_count_kernel<OffT, SortK>), dim3(tgrid), dim3(kBlock), 0, s, kout,
-                         ro, buckets, n_tiles, u.tile_sums);
-      HCTR_LAUNCH_CHECK();
-      hipLaunchKernelGGL(scan_tiles_u32_kernel, dim3(1), dim3(1024), 0, s, u.tile_sums, n_tiles,
-                         u.d_num_runs);
-      HCTR_LAUNCH_CHECK();
-      hipLaunchKernelGGL((run_write_kernel<OffT, SortK>), dim3(tgrid), dim3(kBlock), 0, s, kout,
-                         ro, buckets, n_tiles, u.tile_sums, u.d_num_runs, u.run_start);
-      HCTR_LAUNCH_CHECK();
-      hipLaunchKernelGGL((update_rows_generic_kernel<OffT, SortK, GradT>),
-                         dim3(grid_for(nnz * 64, kBlock)), dim3(kBlock), 0, s, u.d_num_runs,
-                         u.run_start, kout, vout, sro, combiner, D, grad, o, table,
-                         state0, state1, (unsigned long long*)prev_time);
-    }
-    HCTR_LAUNCH_CHECK();
-    if (hot_taken) {  // join: the cold chain's end is ordered before whatever follows on s
-      if (ss != s) {
-        HCTR_HIP(hipEventRecord(u.ev_sorted, ss));
-        HCTR_HIP(hipStreamWaitEvent(s, u.ev_sorted, 0));
-      }
-      if (u.prof) u.prof->end(2, s);
-    } else if (u.prof) {
-      u.prof->end(3, s);
+    PrePlan* pp = (PrePlan*)u.pre_plan;
+    const bool hot = p.need_sort && a16 && direct == nullptr && plan_possible(u, buckets, nnz);
+    const bool pre = hot && pp != nullptr && pp->valid && pp->vi == vi && pp->n == nnz &&
+                     pp->buckets == buckets;
+    if (pp != nullptr && pp->valid && !pre) HCTR_TRY(plan_discard(u, *pp, s));
+    if (hot) {
+      HCTR_TRY(u.hot_buffers(s));
+      HCTR_TRY(update_hot_cold(u, *(PrePlan*)u.pre_plan, pre, buckets, nnz, combiner, ro, vi, grad,
+                               o, table, state0, state1, prev_time, s));
+    } else {
+      if (p.need_sort) HCTR_TRY(sort_stage(u, buckets, nnz, ro, vi, s));
+      if (u.prof) u.prof->begin(3, s);
+      if (a16 && lpr_supported(u.D))
+        HCTR_TRY(update_segmented(u, p, buckets, combiner, ro, sro, grad, o, direct, table, state0,
+                                  state1, prev_time, s));
+      else
+        HCTR_TRY(update_generic(u, p, buckets, combiner, ro, sro, grad, o, table, state0, state1,
+                                prev_time, s));
+      if (u.prof) u.prof->end(3, s);
     }
   }
-
-  if (opt.update_type == HCTR_UPDATE_GLOBAL) {
-    if (opt.optimizer == HCTR_OPT_ADAM) {
-      hipLaunchKernelGGL(adam_global_sweep_kernel, dim3(grid_for(table_elems, kBlock)),
-                         dim3(kBlock), 0, s, table_elems, opt.beta1, opt.beta2, opt.epsilon,
-                         o.alpha_t, opt.state_half, state0, state1, table);
-      HCTR_LAUNCH_CHECK();
-    } else if (opt.optimizer == HCTR_OPT_MOMENTUM_SGD) {
-      hipLaunchKernelGGL(momentum_global_sweep_kernel, dim3(grid_for(table_elems, kBlock)),
-                         dim3(kBlock), 0, s, table_elems, opt.momentum_factor, opt.state_half,
-                         state0, table);
-      HCTR_LAUNCH_CHECK();
-    }
-  }
-  return HCTR_OK;
+  return global_sweep_after(u, opt, o, table, state0, state1, s);
 }
 
-template <typename OffT, typename GradT>
-int update_sortk(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const OffT* ro,
-                 const uint64_t* vi, const GradT* grad, const OptState& opt, float* table,
-                 float* s0, float* s1, uint64_t* pt, hipStream_t s) {
-  // row indices are sorted as 32-bit keys; create() rejects tables with >= 2^32 rows per GPU
-  return update_typed<OffT, uint32_t, GradT>(u, buckets, nnz, combiner, ro, vi, grad, opt, table,
-                                             s0, s1, pt, s);
-}
-
+// row indices are sorted as 32-bit keys; create() rejects tables with >= 2^32 rows per GPU
 template <typename OffT>
 int update_grad(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const OffT* ro,
                 const uint64_t* vi, const void* grad, int grad_dtype, const OptState& opt,
                 float* table, float* s0, float* s1, uint64_t* pt, hipStream_t s) {
   switch (grad_dtype) {
     case HCTR_EMB_F32:
-      return update_sortk<OffT, float>(u, buckets, nnz, combiner, ro, vi, (const float*)grad, opt,
+      return update_typed<OffT, float>(u, buckets, nnz, combiner, ro, vi, (const float*)grad, opt,
                                        table, s0, s1, pt, s);
     case HCTR_EMB_F16:
-      return update_sortk<OffT, __half>(u, buckets, nnz, combiner, ro, vi, (const __half*)grad,
+      return update_typed<OffT, __half>(u, buckets, nnz, combiner, ro, vi, (const __half*)grad,
                                         opt, table, s0, s1, pt, s);
     case HCTR_EMB_BF16:
-      return update_sortk<OffT, __hip_bfloat16>(u, buckets, nnz, combiner, ro, vi,
+      return update_typed<OffT, __hip_bfloat16>(u, buckets, nnz, combiner, ro, vi,
                                                 (const __hip_bfloat16*)grad, opt, table, s0, s1,
                                                 pt, s);
   }
@@ -2766,20 +2688,15 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
   max_nnz = max_nnz_ > 0 ? max_nnz_ : 1;
   max_vocab = max_vocab_;
   D = D_;
-  key32 = true;
   if (max_vocab >= 0xFFFFFFF0ull) {
     set_error("more than 2^32 - 16 rows per GPU are not supported by the sparse update");
     return HCTR_ERR_UNSUPPORTED;
   }
-  const size_t ksz = 4;
-  HCTR_HIP(hipMalloc(&sort_keys_in, max_nnz * ksz));
-  HCTR_HIP(hipMalloc(&sort_keys_out, max_nnz * ksz));
+  HCTR_HIP(hipMalloc(&sort_keys_in, max_nnz * sizeof(uint32_t)));
+  HCTR_HIP(hipMalloc(&sort_keys_out, max_nnz * sizeof(uint32_t)));
   HCTR_HIP(hipMalloc(&sort_vals_in, max_nnz * sizeof(uint32_t)));
   HCTR_HIP(hipMalloc(&sort_vals_out, max_nnz * sizeof(uint32_t)));
-  size_t tb = 0;
-  HCTR_TRY(sort_pairs<uint32_t>(nullptr, tb, (const uint32_t*)nullptr, (uint32_t*)nullptr, nullptr,
-                                nullptr, max_nnz, 32, nullptr));
-  sort_temp_bytes = tb > 0 ? tb : 16;
+  sort_temp_bytes = radix_sort_temp_bytes(max_nnz);
   HCTR_HIP(hipMalloc(&sort_temp, sort_temp_bytes));
   HCTR_HIP(hipMalloc(&tile_sums, (ceil_div<size_t>(max_nnz, kTile) + 1) * sizeof(uint32_t)));
   HCTR_HIP(hipMalloc(&run_start, (max_nnz + 2) * sizeof(uint32_t)));
@@ -2788,9 +2705,7 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
   {
     int lo = 0, hi = 0;  // hi = numerically lowest = most urgent
     HCTR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    const char* pr = getenv("HCTR_PRESORT_PRIO");  // "low": fill gaps only (measurements)
-    HCTR_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking,
-                                         (pr && pr[0] == 'l') ? lo : hi));
+    HCTR_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, hi));
     HCTR_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     HCTR_HIP(hipEventCreateWithFlags(&ev_sorted, hipEventDisableTiming));
   }
@@ -2822,8 +2737,6 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
     //  the first update that takes the path -- hot_buffers(); see sparse_update.h)
     if (rows > 0 && max_nnz >= hot_min_n && D % 4 == 0 && D / 4 <= 64 && ((D / 4) & (D / 4 - 1)) == 0) {
       hot_rows = (uint32_t)rows;
-      const char* hs = getenv("HCTR_HOT_SERIAL");  // "1": both chains on the caller's stream (measurements)
-      hot_serial = hs != nullptr && hs[0] == '1';
       hot_chunks_max = (uint32_t)(ceil_div<size_t>(max_nnz, (size_t)kHotChunk) + kHotMaxStreams);
       if (eager_hot) {
         HCTR_TRY(hot_buffers(nullptr));
@@ -2836,13 +2749,7 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
 
 int SparseUpdater::hot_buffers(hipStream_t s) {
   if (hot_loc != nullptr) return HCTR_OK;
-  {
-    int lo = 0, hi = 0;
-    HCTR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    const char* hp = getenv("HCTR_HOT_PRIO");  // "high" / "low": priority of the cold chain
-    const int pr = (hp && hp[0] == 'h') ? hi : ((hp && hp[0] == 'l') ? lo : 0);
-    HCTR_HIP(hipStreamCreateWithPriority(&hot_side, hipStreamNonBlocking, pr));
-  }
+  HCTR_HIP(hipStreamCreateWithPriority(&hot_side, hipStreamNonBlocking, 0));  // default priority
   const size_t C = hot_chunks_max;
   HCTR_HIP(hipMalloc(&hot_S, C * kHotChunk * sizeof(uint32_t)));
   HCTR_HIP(hipMalloc(&hot_loc_blk, (size_t)hot_rows * sizeof(uint32_t)));
@@ -2851,28 +2758,22 @@ int SparseUpdater::hot_buffers(hipStream_t s) {
   HCTR_HIP(hipMalloc(&hot_tpref, C * (kHotTiles + 1) * sizeof(uint32_t)));
   HCTR_HIP(hipMalloc(&hot_items, (max_nnz / kHotTile + C + 1) * sizeof(uint32_t)));
   HCTR_HIP(hipMalloc(&hot_joins, 3 * C * kHotTiles * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&hot_counts, 12 * sizeof(uint32_t)));
-  HCTR_HIP(hipMemsetAsync(hot_counts, 0, 12 * sizeof(uint32_t), s));
+  HCTR_HIP(hipMalloc(&hot_counts, 8 * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(hot_counts, 0, 8 * sizeof(uint32_t), s));
   const size_t part = C * kHotTiles * (size_t)D * sizeof(float);
   HCTR_HIP(hipMalloc(&hot_head, part));
   HCTR_HIP(hipMalloc(&hot_tail, part));
-  {
-    const char* cc = getenv("HCTR_COLD_COUNT");
-    cold_count = !(cc != nullptr && cc[0] == '0');
-  }
-  if (cold_count) {
-    HCTR_HIP(hipMalloc(&cold_cnt, max_vocab * sizeof(uint32_t)));
-    HCTR_HIP(hipMemsetAsync(cold_cnt, 0, max_vocab * sizeof(uint32_t), s));
-    HCTR_HIP(hipMalloc(&cold_rank, max_nnz * sizeof(uint32_t)));
-    HCTR_HIP(hipMalloc(&cold_plist, max_nnz * sizeof(uint32_t)));
-    HCTR_HIP(hipMalloc(&cold_bkt, max_nnz * sizeof(uint32_t)));
-    HCTR_HIP(hipMalloc(&cold_dlist, max_nnz * sizeof(uint2)));
-    HCTR_HIP(hipMalloc(&cold_singles, max_nnz * sizeof(uint2)));
-    HCTR_HIP(hipMalloc(&cold_segs, (max_nnz / 2 + 1) * sizeof(uint4)));
-    HCTR_HIP(hipMalloc(&cold_longs, (max_nnz / 2 + 1) * sizeof(uint4)));
-    HCTR_HIP(hipMalloc(&cold_counts, 2 * kCcWords * sizeof(uint32_t)));
-    HCTR_HIP(hipMemsetAsync(cold_counts, 0, 2 * kCcWords * sizeof(uint32_t), s));
-  }
+  HCTR_HIP(hipMalloc(&cold_cnt, max_vocab * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(cold_cnt, 0, max_vocab * sizeof(uint32_t), s));
+  HCTR_HIP(hipMalloc(&cold_rank, max_nnz * sizeof(uint32_t)));
+  HCTR_HIP(hipMalloc(&cold_plist, max_nnz * sizeof(uint32_t)));
+  HCTR_HIP(hipMalloc(&cold_bkt, max_nnz * sizeof(uint32_t)));
+  HCTR_HIP(hipMalloc(&cold_dlist, max_nnz * sizeof(uint2)));
+  HCTR_HIP(hipMalloc(&cold_singles, max_nnz * sizeof(uint2)));
+  HCTR_HIP(hipMalloc(&cold_segs, (max_nnz / 2 + 1) * sizeof(uint4)));
+  HCTR_HIP(hipMalloc(&cold_longs, (max_nnz / 2 + 1) * sizeof(uint4)));
+  HCTR_HIP(hipMalloc(&cold_counts, 2 * kCcWords * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(cold_counts, 0, 2 * kCcWords * sizeof(uint32_t), s));
   {
     PrePlan* pp = new PrePlan();
     HCTR_HIP(hipEventCreateWithFlags(&pp->ev_hot, hipEventDisableTiming));
@@ -2917,8 +2818,8 @@ int SparseUpdater::destroy() {
     side = nullptr;
   }
   early_n = 0;
-  sort_keys_in = sort_keys_out = sort_temp = nullptr;
-  sort_vals_in = sort_vals_out = tile_sums = run_start = nullptr;
+  sort_temp = nullptr;
+  sort_keys_in = sort_keys_out = sort_vals_in = sort_vals_out = tile_sums = run_start = nullptr;
   d_num_runs = nullptr;
   seg_head = seg_tail = nullptr;
   span_list = span_count = big_list = nullptr;
@@ -2940,11 +2841,9 @@ int SparseUpdater::presort(size_t buckets, size_t n, const void* row_offset, int
   HCTR_HIP(hipStreamWaitEvent(side, ev_fork, 0));
   int rc;
   if (key_type == HCTR_KEY_U32)
-    rc = sort_stage<uint32_t, uint32_t>(*this, buckets, n, (const uint32_t*)row_offset,
-                                        value_index, side);
+    rc = sort_stage<uint32_t>(*this, buckets, n, (const uint32_t*)row_offset, value_index, side);
   else
-    rc = sort_stage<long long, uint32_t>(*this, buckets, n, (const long long*)row_offset,
-                                         value_index, side);
+    rc = sort_stage<long long>(*this, buckets, n, (const long long*)row_offset, value_index, side);
   if (rc != HCTR_OK) return rc;
   HCTR_HIP(hipEventRecord(ev_sorted, side));
   early_n = n;
@@ -2956,8 +2855,7 @@ int SparseUpdater::presort(size_t buckets, size_t n, const void* row_offset, int
 int SparseUpdater::prework(size_t buckets, size_t nnz, int combiner, const void* row_offset,
                             int key_type, const uint64_t* value_index, hipStream_t s) {
   PrePlan* pp = (PrePlan*)pre_plan;
-  if (pp == nullptr || !cold_count || cold_cnt == nullptr || hot_loc == nullptr || !side ||
-      !hot_side || hot_serial)
+  if (pp == nullptr || cold_cnt == nullptr || hot_loc == nullptr || !side || !hot_side)
     return HCTR_OK;
   if (pp->valid) HCTR_TRY(plan_discard(*this, *pp, s));  // (a batch that was never updated)
   if (buckets == 0 || nnz == 0 || nnz > max_nnz || !plan_possible(*this, buckets, nnz))

@@ -792,7 +792,7 @@ def test_update_cold_rows_counted_per_row(oracle, monkeypatch, opt_kw, B, D, dt)
     position comes from a search of the offsets; mean combiner scaling is checked there too).
     Table / state against the oracle: rows with at most 32 positions to 1e-6 (same order of
     additions), the others within the re-association of pieces of 32; the same bits from a second
-    handle; close to the sorting path (HCTR_COLD_COUNT=0)."""
+    handle; close to the sorting path (HCTR_HOT_ROWS=0)."""
     import torch
     import hugectr_amd as ha
     from hugectr_amd import _lib
@@ -806,8 +806,7 @@ def test_update_cold_rows_counted_per_row(oracle, monkeypatch, opt_kw, B, D, dt)
 
     def run(cold_env, combiner):
         monkeypatch.setenv("HCTR_HOT_MIN", "0")
-        monkeypatch.setenv("HCTR_HOT_ROWS", "2")
-        monkeypatch.setenv("HCTR_COLD_COUNT", cold_env)
+        monkeypatch.setenv("HCTR_HOT_ROWS", "2" if cold_env == "1" else "0")
         rng = np.random.default_rng(B + D)
         emb = ha.SparseEmbeddingHash(_lib.EMB_LOCALIZED, B, 0, V, D, 2 * S, S, combiner, opt,
                                      out_dtype=tdt)
