@@ -218,6 +218,16 @@ _SIGNATURES = {
                                _P, _P, c_int, _P]),
     "hctr_cross_v2_bwd_step_workspace_bytes": (c_size_t, [c_size_t, c_int]),
     "hctr_cross_v2_bwd_step": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "hctr_lru_create": (c_int, [c_size_t, c_size_t, c_int, c_int, c_char_p, c_uint64, POINTER(_P)]),
+    "hctr_lru_destroy": (c_int, [_P]),
+    "hctr_lru_lookup_index": (c_int, [_P, _P, c_size_t, c_int, _P, _P, _P, _SZP, _P]),
+    "hctr_lru_find": (c_int, [_P, _P, c_size_t, _P, _P]),
+    "hctr_lru_rows": (c_int, [_P, POINTER(_P), _SZP]),
+    "hctr_lru_state": (c_int, [_P, c_int, POINTER(_P), _P]),
+    "hctr_lru_export": (c_int, [_P, _P, _P, _P, _P, c_size_t, _SZP, _P]),
+    "hctr_lru_size": (c_int, [_P, _SZP, _P]),
+    "hctr_lru_rejected_count": (c_int, [_P, POINTER(c_uint64), _P]),
+    "hctr_lru_capacity": (c_int, [_P, _SZP, _SZP]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

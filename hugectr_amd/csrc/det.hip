@@ -24,6 +24,8 @@
 
 #include "common.h"
 #include "hashtable.h"
+#include "radix_sort.h"  // (hybrid_table.hip, below)
+#include "scan.h"
 
 namespace hctr {
 namespace {
@@ -1332,3 +1334,6 @@ int hctr_det_update(hctr_det* weights, hctr_det* states, const hctr_det_opt_para
 }
 
 }  // extern "C"
+
+// the bounded, LRU-evicting table of SOK's hybrid variables (hctr_lru_*) shares this unit
+#include "hybrid_table.hip"

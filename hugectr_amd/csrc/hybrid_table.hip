@@ -1,0 +1,748 @@
+// hybrid_table.hip -- bounded key -> vector table with LRU eviction (SOK DynamicVariable,
+// var_type="hybrid").
+//
+// Plays the part of the reference's HKV-backed variable
+// (R/sparse_operation_kit/kit_src/variable/impl/hkv_variable.cu:274-493): find_or_insert and
+// lookup_with_evict on a table of fixed capacity whose least recently used entry makes room.  The
+// semantics are this project's own (DESIGN.md "Hybrid table"), chosen so that every call is
+// deterministic and checkable bit for bit against tests/lru_oracle.py:
+//
+//   C = capacity slots in C / S buckets of S slots; bucket = MurmurHash3_32(key) % (C / S).
+//   Slot s holds a key (or kLruEmpty), a uint64 score (the number of the last inserting call that
+//   touched it), a 1-byte digest (hash >> 24) and row s of the [C][D] fp32 store.
+//   An inserting call t: (1) hits get score t; (2) the distinct missing keys of each bucket, in
+//   ascending key order, take the lowest empty slot, else the slot with the smallest (score, slot)
+//   among scores < t (its (key, row) is evicted), else are rejected; (3) new rows get the
+//   initializer's value, a pure function of (seed, key, element), and zero optimizer state.
+//
+// Layout for MI355X: one 128-B digest line per bucket (S = 128) filters the probe to that line plus
+// the matching key; the insert step gives every bucket to one wave, so slots are claimed without
+// CAS and in a fixed order.  Rows after the C slots are scratch: what a key that is not stored
+// (a miss of a read-only lookup, a rejected key) reads in the current call, so the path's gather /
+// pooling kernels run unchanged on the row numbers handed out here.
+//
+// Compiled as part of det.hip's unit (included at its end): the bounded sibling of the dynamic
+// table, built into every library that carries the dynamic table.  Its internal names carry an
+// lru prefix for that reason.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "common.h"
+#include "radix_sort.h"
+#include "scan.h"
+
+namespace hctr {
+namespace {
+
+constexpr int kLruBlock = 256;
+constexpr int kLruWavesPerBlock = kLruBlock / kWave;
+constexpr uint64_t kLruEmpty = ~0ull;
+constexpr int kLruMaxSlotsPerLane = 4;  // S <= 256
+
+__device__ __forceinline__ uint64_t lru_splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// constant, or uniform (0, 1] from 24 bits of a counter-based hash of (seed, key, element)
+__device__ __forceinline__ float lru_init_value(int mode, float val, uint64_t seed, uint64_t key,
+                                                uint32_t e) {
+  if (mode == 0) return val;
+  const uint64_t h = lru_splitmix64(seed ^ lru_splitmix64(key * 0x100000001B3ull + e));
+  return ((float)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);
+}
+
+template <typename K>
+__device__ __forceinline__ uint64_t lru_key_u64(K k);
+template <>
+__device__ __forceinline__ uint64_t lru_key_u64<uint32_t>(uint32_t k) {
+  return (uint64_t)k;
+}
+template <>
+__device__ __forceinline__ uint64_t lru_key_u64<long long>(long long k) {
+  return (uint64_t)k;
+}
+
+struct LruTbl {
+  uint64_t* keys;     // [C]
+  uint64_t* scores;   // [C]
+  uint8_t* digests;   // [C]
+  float* rows;        // [C + scratch][D]
+  float* st0;         // [C][D] or null
+  float* st1;         // [C][D] or null
+  uint64_t nb;        // buckets
+  int S, D;
+  uint64_t C;
+  int init_mode;
+  float init_val;
+  uint64_t seed;
+};
+
+enum { kLruFind = 0, kLruRead = 1, kLruInsert = 2 };
+
+// One thread per key: the bucket's digest line (S bytes, 16 B per load), then the key of every
+// slot whose digest matches.  kLruFind: slot or kInvalidIndex.  kLruRead: slot, or a scratch row
+// holding the initializer's value.  kLruInsert: hits get score t; misses are handed to the sort
+// (bucket = nb marks a hit, which sorts behind every bucket).
+template <typename K>
+__global__ void __launch_bounds__(kLruBlock)
+    lru_find_kernel(LruTbl T, const K* __restrict__ in, size_t n, int mode, uint64_t t,
+                    uint64_t* __restrict__ idx, uint32_t* __restrict__ sbkt,
+                    uint32_t* __restrict__ slo, uint32_t* __restrict__ shi,
+                    uint32_t* __restrict__ sval) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i >= n) return;
+  const K kk = in[i];
+  const uint64_t key = lru_key_u64<K>(kk);
+  const uint32_t h = murmur3_key(kk);
+  const uint64_t b = (uint64_t)h % T.nb;
+  const uint32_t dg = h >> 24;
+  const uint64_t base = b * (uint64_t)T.S;
+  const uint32_t pat = dg * 0x01010101u;
+  const uint4* line = reinterpret_cast<const uint4*>(T.digests + base);
+  uint64_t slot = kInvalidIndex;
+  // (the all-ones key is the empty marker: never stored, never found)
+  for (int w = 0; w < T.S / 16 && slot == kInvalidIndex && key != kLruEmpty; w++) {
+    const uint4 v = line[w];
+    const uint32_t words[4] = {v.x, v.y, v.z, v.w};
+    for (int q = 0; q < 4 && slot == kInvalidIndex; q++) {
+      const uint32_t x = words[q] ^ pat;
+      // every zero byte of x is flagged (bytes above one may be flagged falsely: the key decides)
+      uint32_t m = (x - 0x01010101u) & ~x & 0x80808080u;
+      while (m) {
+        const int byte = __builtin_ctz(m) >> 3;
+        const uint64_t s = base + (uint64_t)(w * 16 + q * 4 + byte);
+        if (T.keys[s] == key) {
+          slot = s;
+          break;
+        }
+        m &= m - 1;
+      }
+    }
+  }
+  if (mode == kLruFind) {
+    idx[i] = slot;
+    return;
+  }
+  if (mode == kLruRead) {
+    if (slot != kInvalidIndex) {
+      idx[i] = slot;
+      return;
+    }
+    const uint64_t r = T.C + (T.init_mode == 0 ? 0 : i);
+    idx[i] = r;
+    if (T.init_mode != 0)
+      for (int e = 0; e < T.D; e++)
+        T.rows[r * T.D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+    return;
+  }
+  if (slot != kInvalidIndex) T.scores[slot] = t;  // every writer writes the same t
+  idx[i] = slot;
+  sbkt[i] = slot != kInvalidIndex ? (uint32_t)T.nb : (uint32_t)b;
+  slo[i] = (uint32_t)key;
+  if (shi) shi[i] = (uint32_t)(key >> 32);
+  sval[i] = (uint32_t)i;
+}
+
+__global__ void __launch_bounds__(kLruBlock)
+    lru_permute_kernel(const uint32_t* __restrict__ src, const uint32_t* __restrict__ perm,
+                       size_t n, uint32_t* __restrict__ out) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i < n) out[i] = src[perm[i]];
+}
+
+__device__ __forceinline__ uint32_t lru_lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t v) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] < v)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// One wave per bucket: its run [lo, hi) in the sorted missing keys, and how many of its distinct
+// keys will evict: min(max(distinct - empty, 0), slots with score < t).
+template <typename K>
+__global__ void __launch_bounds__(kLruBlock)
+    lru_count_kernel(LruTbl T, const K* __restrict__ in, const uint32_t* __restrict__ sbkt,
+                     const uint32_t* __restrict__ perm, uint32_t n, uint64_t t,
+                     uint32_t* __restrict__ rng, uint32_t* __restrict__ evict_cnt) {
+  const uint64_t b = blockIdx.x * (uint64_t)kLruWavesPerBlock + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (b >= T.nb) return;
+  const uint32_t lo = lru_lower_bound_u32(sbkt, n, (uint32_t)b);
+  const uint32_t hi = lru_lower_bound_u32(sbkt, n, (uint32_t)b + 1);
+  if (lane == 0) {
+    rng[2 * b] = lo;
+    rng[2 * b + 1] = hi;
+  }
+  if (lo == hi) {
+    if (lane == 0) evict_cnt[b] = 0;
+    return;
+  }
+  uint32_t distinct = 0;
+  for (uint32_t j0 = lo; j0 < hi; j0 += kWave) {
+    const uint32_t j = j0 + lane;
+    bool first = false;
+    if (j < hi) {
+      const uint64_t k = lru_key_u64<K>(in[perm[j]]);
+      first = k != kLruEmpty && (j == lo || k != lru_key_u64<K>(in[perm[j - 1]]));
+    }
+    distinct += (uint32_t)__popcll(__ballot(first));
+  }
+  uint32_t empty = 0, elig = 0;
+  const uint64_t base = b * (uint64_t)T.S;
+  for (int j = 0; j < T.S / kWave; j++) {
+    const uint64_t s = base + (uint64_t)(j * kWave + lane);
+    const uint64_t k = T.keys[s];
+    empty += (uint32_t)__popcll(__ballot(k == kLruEmpty));
+    elig += (uint32_t)__popcll(__ballot(k != kLruEmpty && T.scores[s] < t));
+  }
+  if (lane == 0) {
+    const uint32_t need = distinct > empty ? distinct - empty : 0;
+    evict_cnt[b] = need < elig ? need : elig;
+  }
+}
+
+__device__ __forceinline__ uint64_t lru_wave_min_u64(uint64_t v) {
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const uint64_t o = __shfl_xor(v, off);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// One wave per bucket inserts the bucket's distinct missing keys in ascending key order.  Lane l
+// keeps slots l, l + 64, ... (key, score) in registers; a victim is the wave-wide minimum of
+// (score << 16 | slot) over slots with score < t.
+template <typename K>
+__global__ void __launch_bounds__(kLruBlock)
+    lru_insert_kernel(LruTbl T, const K* __restrict__ in, const uint32_t* __restrict__ perm,
+                      const uint32_t* __restrict__ rng, const uint32_t* __restrict__ evict_off,
+                      uint64_t t, uint64_t* __restrict__ idx, void* __restrict__ ev_keys,
+                      int key_bytes, float* __restrict__ ev_rows,
+                      unsigned long long* __restrict__ counters) {
+  const uint64_t b = blockIdx.x * (uint64_t)kLruWavesPerBlock + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (b >= T.nb) return;
+  const uint32_t lo = rng[2 * b], hi = rng[2 * b + 1];
+  if (lo == hi) return;
+  const int spl = T.S / kWave;
+  const uint64_t base = b * (uint64_t)T.S;
+  uint64_t k[kLruMaxSlotsPerLane], sc[kLruMaxSlotsPerLane];
+#pragma unroll
+  for (int j = 0; j < kLruMaxSlotsPerLane; j++) {
+    k[j] = j < spl ? T.keys[base + j * kWave + lane] : 0ull;
+    sc[j] = j < spl ? T.scores[base + j * kWave + lane] : t;
+  }
+  uint32_t out_e = evict_off[b];
+  unsigned long long filled = 0, rejected = 0;
+  const int D = T.D;
+  uint32_t j = lo;
+  while (j < hi) {
+    const K kk = in[perm[j]];
+    const uint64_t key = lru_key_u64<K>(kk);
+    uint32_t r = j + 1;
+    while (r < hi && lru_key_u64<K>(in[perm[r]]) == key) r++;
+    // lowest empty slot
+    int sl = -1;
+#pragma unroll
+    for (int q = 0; q < kLruMaxSlotsPerLane; q++) {
+      const uint64_t m = __ballot(q < spl && k[q] == kLruEmpty);
+      if (sl < 0 && m) sl = q * kWave + __ffsll((long long)m) - 1;
+    }
+    if (key == kLruEmpty) sl = -2;  // the empty marker itself is rejected
+    bool evict = false;
+    if (sl == -1) {
+      uint64_t best = ~0ull;
+#pragma unroll
+      for (int q = 0; q < kLruMaxSlotsPerLane; q++)
+        if (q < spl && k[q] != kLruEmpty && sc[q] < t) {
+          const uint64_t c = (sc[q] << 16) | (uint64_t)(q * kWave + lane);
+          best = c < best ? c : best;
+        }
+      best = lru_wave_min_u64(best);
+      if (best != ~0ull) {
+        sl = (int)(best & 0xFFFF);
+        evict = true;
+      }
+    }
+    uint64_t res;
+    if (sl >= 0) {
+      const int q = sl / kWave, owner = sl % kWave;
+      const uint64_t s = base + (uint64_t)sl;
+      uint64_t kq = 0;
+#pragma unroll
+      for (int x = 0; x < kLruMaxSlotsPerLane; x++)
+        if (x == q) kq = k[x];
+      const uint64_t old = __shfl(kq, owner);
+      if (evict && ev_keys) {
+        if (lane == 0) {
+          if (key_bytes == 8)
+            static_cast<uint64_t*>(ev_keys)[out_e] = old;
+          else
+            static_cast<uint32_t*>(ev_keys)[out_e] = (uint32_t)old;
+        }
+        if (ev_rows)
+          for (int e = lane; e < D; e += kWave)
+            ev_rows[(uint64_t)out_e * D + e] = T.rows[s * D + e];  // read before the overwrite
+      }
+      if (evict) out_e++;
+      if (lane == owner) {
+#pragma unroll
+        for (int x = 0; x < kLruMaxSlotsPerLane; x++)
+          if (x == q) {
+            k[x] = key;
+            sc[x] = t;
+          }
+        T.keys[s] = key;
+        T.scores[s] = t;
+        T.digests[s] = (uint8_t)(murmur3_key(kk) >> 24);
+      }
+      for (int e = lane; e < D; e += kWave) {
+        T.rows[s * D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+        if (T.st0) T.st0[s * D + e] = 0.0f;
+        if (T.st1) T.st1[s * D + e] = 0.0f;
+      }
+      if (!evict) filled++;
+      res = s;
+    } else {
+      rejected++;
+      res = kInvalidIndex;
+    }
+    for (uint32_t p = j; p < r; p++) {
+      const uint32_t pos = perm[p];
+      uint64_t row = res;
+      if (res == kInvalidIndex) {
+        row = T.C + (T.init_mode == 0 ? 0 : pos);
+        if (T.init_mode != 0)
+          for (int e = lane; e < D; e += kWave)
+            T.rows[row * D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+      }
+      if (lane == 0) idx[pos] = row;
+    }
+    j = r;
+  }
+  if (lane == 0) {
+    if (filled) atomicAdd(&counters[0], filled);
+    if (rejected) atomicAdd(&counters[1], rejected);
+  }
+}
+
+__global__ void __launch_bounds__(kLruBlock)
+    lru_occupied_kernel(const uint64_t* __restrict__ keys, size_t C, uint32_t* __restrict__ flag) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i < C) flag[i] = keys[i] != kLruEmpty ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(kLruBlock)
+    lru_export_kernel(const uint64_t* __restrict__ keys, size_t C, const uint32_t* __restrict__ off,
+                      const uint64_t* __restrict__ scores, size_t max_out, int key_bytes,
+                      void* __restrict__ out_keys, uint64_t* __restrict__ out_slots,
+                      uint64_t* __restrict__ out_scores) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i >= C || keys[i] == kLruEmpty) return;
+  const uint32_t o = off[i];
+  if (o >= max_out) return;
+  if (out_keys) {
+    if (key_bytes == 8)
+      static_cast<uint64_t*>(out_keys)[o] = keys[i];
+    else
+      static_cast<uint32_t*>(out_keys)[o] = (uint32_t)keys[i];
+  }
+  if (out_slots) out_slots[o] = i;
+  if (out_scores) out_scores[o] = scores[i];
+}
+
+__global__ void __launch_bounds__(kLruBlock)
+    lru_gather_rows_kernel(const uint64_t* __restrict__ slots, size_t n,
+                           const float* __restrict__ rows, int D, float* __restrict__ out) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i < n * (size_t)D) out[i] = rows[slots[i / D] * D + i % D];
+}
+
+__global__ void lru_fill_kernel(float* p, size_t n, float v) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+__global__ void __launch_bounds__(kLruBlock)
+    lru_clear_kernel(uint64_t* keys, uint64_t* scores, size_t C) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i < C) {
+    keys[i] = kLruEmpty;
+    scores[i] = 0;
+  }
+}
+
+inline int lru_blocks(size_t n) { return (int)ceil_div<size_t>(n > 0 ? n : 1, (size_t)kLruBlock); }
+
+}  // namespace
+}  // namespace hctr
+
+using namespace hctr;
+
+struct hctr_lru {
+  size_t C = 0, S = 0, nb = 0;
+  int D = 0, key_type = HCTR_KEY_I64;
+  int init_mode = 1;
+  float init_val = 0.f;
+  uint64_t seed = 0;
+  uint64_t* keys = nullptr;
+  uint64_t* scores = nullptr;
+  uint8_t* digests = nullptr;
+  float* rows = nullptr;
+  size_t scratch = 0;  // rows after the C slots
+  float* st[2] = {nullptr, nullptr};
+  uint64_t t = 0;  // inserting calls so far
+  unsigned long long* counters = nullptr;  // [0] occupied slots, [1] rejected keys
+  unsigned long long* h_word = nullptr;    // pinned host word
+  // per-call workspace (n keys)
+  size_t ws_n = 0;
+  uint32_t* ws = nullptr;  // 8 arrays of ws_n
+  void* sort_temp = nullptr;
+  size_t sort_temp_bytes = 0;
+  // per-bucket workspace
+  uint32_t* rng = nullptr;        // [2 nb]
+  uint32_t* evict_cnt = nullptr;  // [nb]
+  uint32_t* evict_off = nullptr;  // [nb + 1]
+  unsigned long long* tile_sums = nullptr;
+  unsigned long long* d_total = nullptr;
+
+  LruTbl tbl() const {
+    LruTbl T;
+    T.keys = keys;
+    T.scores = scores;
+    T.digests = digests;
+    T.rows = rows;
+    T.st0 = st[0];
+    T.st1 = st[1];
+    T.nb = nb;
+    T.S = (int)S;
+    T.D = D;
+    T.C = C;
+    T.init_mode = init_mode;
+    T.init_val = init_val;
+    T.seed = seed;
+    return T;
+  }
+};
+
+namespace {
+
+void lru_free(hctr_lru* h) {
+  void* ps[] = {h->keys, h->scores, h->digests, h->rows, h->st[0], h->st[1], h->counters, h->ws,
+                h->sort_temp, h->rng, h->evict_cnt, h->evict_off, h->tile_sums, h->d_total};
+  for (void* p : ps)
+    if (p) (void)hipFree(p);
+  if (h->h_word) (void)hipHostFree(h->h_word);
+  delete h;
+}
+
+// per-call workspace and, for a key-dependent initializer, scratch rows for n keys
+int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
+  if (n > h->ws_n) {
+    if (h->ws) HCTR_HIP(hipFree(h->ws));
+    if (h->sort_temp) HCTR_HIP(hipFree(h->sort_temp));
+    h->ws = nullptr;
+    h->sort_temp = nullptr;
+    h->ws_n = 0;
+    const size_t cap = n < 4096 ? 4096 : n;
+    HCTR_HIP(hipMalloc(&h->ws, cap * 8 * sizeof(uint32_t)));
+    h->sort_temp_bytes = radix_sort_temp_bytes(cap);
+    HCTR_HIP(hipMalloc(&h->sort_temp, h->sort_temp_bytes));
+    h->ws_n = cap;
+  }
+  if (h->init_mode != 0 && n > h->scratch) {
+    // the slots' rows move to a larger store once per new largest call (scratch is per call)
+    float* nr = nullptr;
+    HCTR_HIP(hipMalloc(&nr, (h->C + n) * (size_t)h->D * sizeof(float)));
+    HCTR_HIP(hipMemcpyAsync(nr, h->rows, h->C * (size_t)h->D * sizeof(float),
+                            hipMemcpyDeviceToDevice, s));
+    HCTR_HIP(hipStreamSynchronize(s));
+    HCTR_HIP(hipFree(h->rows));
+    h->rows = nr;
+    h->scratch = n;
+  }
+  return HCTR_OK;
+}
+
+template <typename K>
+int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t* row_index,
+               void* ev_keys, float* ev_rows, size_t* n_evicted, hipStream_t s) {
+  HCTR_TRY(lru_reserve(h, n, s));
+  if (!insert) {
+    hipLaunchKernelGGL(lru_find_kernel<K>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->tbl(),
+                       keys, n, (int)kLruRead, h->t, row_index, nullptr, nullptr, nullptr, nullptr);
+    HCTR_LAUNCH_CHECK();
+    if (n_evicted) *n_evicted = 0;
+    return HCTR_OK;
+  }
+  const uint64_t t = ++h->t;
+  const size_t m = h->ws_n;
+  uint32_t *bkt = h->ws, *klo = h->ws + m, *khi = h->ws + 2 * m, *seq = h->ws + 3 * m,
+           *g = h->ws + 4 * m, *tk = h->ws + 5 * m, *pa = h->ws + 6 * m, *pb = h->ws + 7 * m;
+  const bool wide = sizeof(K) == 8;
+  hipLaunchKernelGGL(lru_find_kernel<K>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->tbl(),
+                     keys, n, (int)kLruInsert, t, row_index, bkt, klo, wide ? khi : nullptr, seq);
+  HCTR_LAUNCH_CHECK();
+  // (bucket, key) order by three stable passes: key low word, key high word, bucket
+  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, klo, tk, seq, pa, n, 32, s));
+  if (wide) {
+    hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, khi, pa, n,
+                       g);
+    HCTR_LAUNCH_CHECK();
+    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, 32, s));
+    std::swap(pa, pb);
+  }
+  hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, bkt, pa, n, g);
+  HCTR_LAUNCH_CHECK();
+  int end_bit = 1;
+  while (end_bit < 32 && ((size_t)1 << end_bit) <= h->nb) end_bit++;
+  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, end_bit, s));
+  // tk = buckets in sorted order, pb = positions
+  const int wb = (int)ceil_div<size_t>(h->nb, (size_t)kLruWavesPerBlock);
+  hipLaunchKernelGGL(lru_count_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->tbl(), keys, tk, pb,
+                     (uint32_t)n, t, h->rng, h->evict_cnt);
+  HCTR_LAUNCH_CHECK();
+  HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(h->evict_cnt, h->nb, h->tile_sums, h->d_total,
+                                               h->evict_off, s));
+  hipLaunchKernelGGL(lru_insert_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->tbl(), keys, pb,
+                     h->rng,
+                     h->evict_off, t, row_index, ev_keys, (int)sizeof(K), ev_rows, h->counters);
+  HCTR_LAUNCH_CHECK();
+  if (n_evicted) {
+    HCTR_HIP(hipMemcpyAsync(h->h_word, h->d_total, sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, s));
+    HCTR_HIP(hipStreamSynchronize(s));
+    *n_evicted = (size_t)*h->h_word;
+  }
+  return HCTR_OK;
+}
+
+int lru_read_counter(hctr_lru* h, int which, uint64_t* out, hipStream_t s) {
+  HCTR_HIP(hipMemcpyAsync(h->h_word, h->counters + which, sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, s));
+  HCTR_HIP(hipStreamSynchronize(s));
+  *out = (uint64_t)*h->h_word;
+  return HCTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
+                    const char* initializer, uint64_t seed, hctr_lru** out) {
+  HCTR_REQUIRE(out, "out is null");
+  HCTR_REQUIRE(bucket_size > 0 && bucket_size % kWave == 0 &&
+                   bucket_size <= (size_t)kWave * kLruMaxSlotsPerLane,
+               "bucket_size must be 64, 128, 192 or 256");
+  HCTR_REQUIRE(capacity > 0, "capacity");
+  HCTR_REQUIRE(dim > 0 && dim <= 16384, "dim out of range (1 .. 16384)");
+  HCTR_REQUIRE(key_type == HCTR_KEY_U32 || key_type == HCTR_KEY_I64, "key_type");
+  const size_t C = ceil_div(capacity, bucket_size) * bucket_size;
+  HCTR_REQUIRE(C < 0xFFFFFFFFull, "capacity must stay below 2^32 slots");
+  hctr_lru* h = new hctr_lru();
+  h->C = C;
+  h->S = bucket_size;
+  h->nb = C / bucket_size;
+  h->D = dim;
+  h->key_type = key_type;
+  h->seed = seed;
+  const std::string ini = initializer ? initializer : "";
+  if (ini == "ones") {
+    h->init_mode = 0;
+    h->init_val = 1.f;
+  } else if (ini == "zeros") {
+    h->init_mode = 0;
+    h->init_val = 0.f;
+  } else {
+    char* end = nullptr;
+    const float v = ini.empty() ? 0.f : strtof(ini.c_str(), &end);
+    if (!ini.empty() && end && *end == '\0') {
+      h->init_mode = 0;
+      h->init_val = v;
+    }
+  }
+  h->scratch = 1;  // a constant initializer needs one row; others grow it to the largest call
+  bool ok = hipMalloc(&h->keys, C * 8) == hipSuccess &&
+            hipMalloc(&h->scores, C * 8) == hipSuccess &&
+            hipMalloc(&h->digests, C) == hipSuccess &&
+            hipMalloc(&h->rows, (C + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
+            hipMalloc(&h->counters, 2 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMalloc(&h->rng, 2 * h->nb * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&h->evict_cnt, h->nb * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&h->evict_off, (h->nb + 1) * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&h->tile_sums, (h->nb / 1024 + 2) * 8) == hipSuccess &&
+            hipMalloc(&h->d_total, sizeof(unsigned long long)) == hipSuccess &&
+            hipHostMalloc(&h->h_word, sizeof(unsigned long long)) == hipSuccess;
+  if (ok)
+    ok = hipMemset(h->digests, 0, C) == hipSuccess &&
+         hipMemset(h->rows, 0, (C + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
+         hipMemset(h->counters, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    set_error("hctr_lru_create: out of device memory");
+    lru_free(h);
+    return HCTR_ERR_HIP;
+  }
+  hipLaunchKernelGGL(lru_clear_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, 0, h->keys,
+                     h->scores, C);
+  if (h->init_mode == 0)
+    hipLaunchKernelGGL(lru_fill_kernel, dim3(lru_blocks((size_t)dim)), dim3(kLruBlock), 0, 0,
+                       h->rows + C * (size_t)dim, (size_t)dim, h->init_val);
+  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
+    set_error("hctr_lru_create: initialisation failed");
+    lru_free(h);
+    return HCTR_ERR_HIP;
+  }
+  *out = h;
+  return HCTR_OK;
+}
+
+int hctr_lru_destroy(hctr_lru* h) {
+  if (!h) return HCTR_OK;
+  (void)hipDeviceSynchronize();
+  lru_free(h);
+  return HCTR_OK;
+}
+
+int hctr_lru_lookup_index(hctr_lru* h, const void* keys, size_t n, int insert, uint64_t* row_index,
+                          void* evict_keys, float* evict_rows, size_t* n_evicted,
+                          hctr_stream_t stream) {
+  HCTR_REQUIRE(h, "null handle");
+  HCTR_REQUIRE(n <= ((size_t)1 << 24), "at most 2^24 keys per call");
+  HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
+  HCTR_REQUIRE(!evict_rows || evict_keys, "evict_rows needs evict_keys");
+  if (n == 0) {
+    if (n_evicted) *n_evicted = 0;
+    if (insert) h->t++;
+    return HCTR_OK;
+  }
+  const hipStream_t s = as_stream(stream);
+  if (h->key_type == HCTR_KEY_I64)
+    return lru_lookup<long long>(h, (const long long*)keys, n, insert, row_index, evict_keys,
+                                 evict_rows, n_evicted, s);
+  return lru_lookup<uint32_t>(h, (const uint32_t*)keys, n, insert, row_index, evict_keys,
+                              evict_rows, n_evicted, s);
+}
+
+int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
+                  hctr_stream_t stream) {
+  HCTR_REQUIRE(h, "null handle");
+  HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
+  if (n == 0) return HCTR_OK;
+  const hipStream_t s = as_stream(stream);
+  if (h->key_type == HCTR_KEY_I64)
+    hipLaunchKernelGGL(lru_find_kernel<long long>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
+                       h->tbl(), (const long long*)keys, n, (int)kLruFind, h->t, row_index,
+                       nullptr, nullptr, nullptr, nullptr);
+  else
+    hipLaunchKernelGGL(lru_find_kernel<uint32_t>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
+                       h->tbl(), (const uint32_t*)keys, n, (int)kLruFind, h->t, row_index,
+                       nullptr, nullptr, nullptr, nullptr);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_lru_rows(hctr_lru* h, float** rows, size_t* capacity) {
+  HCTR_REQUIRE(h && rows && capacity, "null argument");
+  *rows = h->rows;
+  *capacity = h->C;
+  return HCTR_OK;
+}
+
+int hctr_lru_state(hctr_lru* h, int i, float** state, hctr_stream_t stream) {
+  HCTR_REQUIRE(h && state, "null argument");
+  HCTR_REQUIRE(i == 0 || i == 1, "state index must be 0 or 1");
+  if (!h->st[i]) {
+    const size_t bytes = h->C * (size_t)h->D * sizeof(float);
+    HCTR_HIP(hipMalloc(&h->st[i], bytes));
+    HCTR_HIP(hipMemsetAsync(h->st[i], 0, bytes, as_stream(stream)));
+  }
+  *state = h->st[i];
+  return HCTR_OK;
+}
+
+int hctr_lru_export(hctr_lru* h, void* keys, uint64_t* slots, uint64_t* scores, float* rows,
+                    size_t max_keys, size_t* exported, hctr_stream_t stream) {
+  HCTR_REQUIRE(h && exported, "null argument");
+  const hipStream_t s = as_stream(stream);
+  uint32_t *flag = nullptr, *off = nullptr;
+  uint64_t* tmp_slots = nullptr;
+  unsigned long long* tiles = nullptr;
+  const size_t C = h->C;
+  int rc = HCTR_OK;
+  if (hipMalloc(&flag, C * 4) != hipSuccess || hipMalloc(&off, (C + 1) * 4) != hipSuccess ||
+      hipMalloc(&tiles, (C / 1024 + 2) * 8) != hipSuccess ||
+      (rows && !slots && hipMalloc(&tmp_slots, (max_keys ? max_keys : 1) * 8) != hipSuccess)) {
+    (void)hipGetLastError();
+    set_error("hctr_lru_export: out of device memory");
+    rc = HCTR_ERR_HIP;
+  }
+  if (rc == HCTR_OK) {
+    uint64_t* sl = slots ? slots : tmp_slots;
+    hipLaunchKernelGGL(lru_occupied_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
+                       C, flag);
+    rc = exclusive_scan_to_offsets<uint32_t>(flag, C, tiles, h->d_total, off, s);
+    if (rc == HCTR_OK) {
+      hipLaunchKernelGGL(lru_export_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
+                         C, off, h->scores, max_keys, h->key_type == HCTR_KEY_I64 ? 8 : 4, keys, sl,
+scores);
+      if (hipMemcpyAsync(h->h_word, h->d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("hctr_lru_export: HIP error");
+        rc = HCTR_ERR_HIP;
+      }
+    }
+    if (rc == HCTR_OK) {
+      const size_t got = (size_t)*h->h_word < max_keys ? (size_t)*h->h_word : max_keys;
+      if (rows && got)
+        hipLaunchKernelGGL(lru_gather_rows_kernel, dim3(lru_blocks(got * (size_t)h->D)),
+                           dim3(kLruBlock), 0, s, sl, got, h->rows, h->D, rows);
+      if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+        set_error("hctr_lru_export: HIP error");
+        rc = HCTR_ERR_HIP;
+      }
+      *exported = got;
+    }
+  }
+  if (flag) (void)hipFree(flag);
+  if (off) (void)hipFree(off);
+  if (tiles) (void)hipFree(tiles);
+  if (tmp_slots) (void)hipFree(tmp_slots);
+  return rc;
+}
+
+int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream) {
+  HCTR_REQUIRE(h && out, "null argument");
+  uint64_t v = 0;
+  HCTR_TRY(lru_read_counter(h, 0, &v, as_stream(stream)));
+  *out = (size_t)v;
+  return HCTR_OK;
+}
+
+int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
+  HCTR_REQUIRE(h && out, "null argument");
+  return lru_read_counter(h, 1, out, as_stream(stream));
+}
+
+int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size) {
+  HCTR_REQUIRE(h && capacity && bucket_size, "null argument");
+  *capacity = h->C;
+  *bucket_size = h->S;
+  return HCTR_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,107 @@
+"""Bounded key -> vector table with LRU eviction: thin ctypes calls into hctr_lru_* (the backend of
+sok.DynamicVariable(var_type="hybrid"); semantics in include/hugectr_amd.h and DESIGN.md "Hybrid
+table").  No compute here."""
+from __future__ import annotations
+
+import ctypes
+import sys
+from typing import Tuple
+
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream_ptr
+
+
+class HybridTable:
+    """capacity slots (rounded up to whole buckets of bucket_size), dim fp32 per row.  close()
+    frees the device memory; __del__ only does so as a fallback outside interpreter shutdown."""
+
+    def __init__(self, capacity: int, dim: int, initializer: str = "", bucket_size: int = 128,
+                 key_dtype=torch.int64, seed: int = 0):
+        self.dim = int(dim)
+        self.key_dtype = key_dtype
+        self._h = ctypes.c_void_p()
+        kt = _lib.KEY_I64 if key_dtype == torch.int64 else _lib.KEY_U32
+        check(lib.hctr_lru_create(int(capacity), int(bucket_size), self.dim, kt,
+                                  str(initializer).encode(), int(seed), ctypes.byref(self._h)))
+        c, s = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib.hctr_lru_capacity(self._h, ctypes.byref(c), ctypes.byref(s)))
+        self.capacity, self.bucket_size = int(c.value), int(s.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.hctr_lru_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _keys(self, keys: torch.Tensor) -> torch.Tensor:
+        return keys.to(self.key_dtype).contiguous()
+
+    def lookup_index(self, keys: torch.Tensor, insert: bool, evict: bool = False):
+        """row numbers int64[n] (rows >= capacity: per-call scratch with the initializer's value);
+        with evict=True also (evicted keys, evicted rows [m, dim]) -- one host synchronisation"""
+        keys = self._keys(keys)
+        n = keys.numel()
+        idx = torch.empty(n, dtype=torch.int64, device=keys.device)
+        if not evict:
+            check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, ptr(idx),
+                                            None, None, None, stream_ptr()))
+            return idx
+        ek = torch.empty(n, dtype=self.key_dtype, device=keys.device)
+        ev = torch.empty((n, self.dim), dtype=torch.float32, device=keys.device)
+        m = ctypes.c_size_t()
+        check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, ptr(idx),
+                                        ptr(ek), ptr(ev), ctypes.byref(m), stream_ptr()))
+        return idx, ek[:m.value], ev[:m.value]
+
+    def find(self, keys: torch.Tensor) -> torch.Tensor:
+        """slot of every stored key, INVALID for the others; no side effects"""
+        keys = self._keys(keys)
+        idx = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
+        check(lib.hctr_lru_find(self._h, ptr(keys), keys.numel(), ptr(idx), stream_ptr()))
+        return idx
+
+    def rows_ptr(self) -> Tuple[int, int]:
+        p, cap = ctypes.c_void_p(), ctypes.c_size_t()
+        check(lib.hctr_lru_rows(self._h, ctypes.byref(p), ctypes.byref(cap)))
+        return p.value, int(cap.value)
+
+    def state_ptr(self, i: int) -> int:
+        p = ctypes.c_void_p()
+        check(lib.hctr_lru_state(self._h, int(i), ctypes.byref(p), stream_ptr()))
+        return p.value
+
+    def export(self, with_slots: bool = False):
+        """(keys, rows [n, dim]) of the occupied slots in slot order; with_slots=True adds their
+        slots and scores (int64)"""
+        n = self.size()
+        keys = torch.empty(n, dtype=self.key_dtype, device="cuda")
+        slots = torch.empty(n, dtype=torch.int64, device="cuda")
+        scores = torch.empty(n, dtype=torch.int64, device="cuda")
+        rows = torch.empty((n, self.dim), dtype=torch.float32, device="cuda")
+        got = ctypes.c_size_t()
+        check(lib.hctr_lru_export(self._h, ptr(keys), ptr(slots), ptr(scores), ptr(rows), n,
+                                  ctypes.byref(got), stream_ptr()))
+        g = got.value
+        if with_slots:
+            return keys[:g], rows[:g], slots[:g], scores[:g]
+        return keys[:g], rows[:g]
+
+    def size(self) -> int:
+        out = ctypes.c_size_t()
+        check(lib.hctr_lru_size(self._h, ctypes.byref(out), stream_ptr()))
+        return int(out.value)
+
+    def rejected_count(self) -> int:
+        out = ctypes.c_uint64()
+        check(lib.hctr_lru_rejected_count(self._h, ctypes.byref(out), stream_ptr()))
+        return int(out.value)
+

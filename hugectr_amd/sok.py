@@ -32,6 +32,7 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .dynamic_table import DynamicEmbeddingTable, DynamicTableOptimizer, _num_state
+from .hybrid_table import HybridTable
 
 _RANK, _WORLD = 0, 1
 INVALID = -1  # 0xFFFFFFFFFFFFFFFF as int64: "row not on this GPU / unknown key"
@@ -168,11 +169,26 @@ def Variable(initial_value, mode: Optional[str] = None, name: Optional[str] = No
 
 
 class DynamicVariable(_VariableBase):
-    """key -> vector map that grows on demand; keys live on GPU key % N"""
+    """key -> vector map; keys live on GPU key % N.
+
+    var_type None / "hbm" (the default here; the reference defaults to "hybrid"): the dynamic
+    table, which grows on demand and keeps every key it has seen.
+    var_type="hybrid": a table of fixed capacity that evicts its least recently used entries
+    (hybrid_table.py, hctr_lru_*).  Keyword options: max_capacity (required; rounded up to whole
+    buckets), max_bucket_size=128, evict_strategy="kLru" (the only strategy).  init_capacity is
+    accepted and ignored: the store is allocated once, at max_capacity.  The reference's other
+    options (max_hbm_for_vectors, max_load_factor, ...) are kept in config_dict.  The table lives in
+    HBM only: evicted pairs go back to the caller (sparse_read_and_evict), not to host memory."""
 
     def __init__(self, dimension: int, initializer: Union[str, float, None] = None,
                  key_type=torch.int64, init_capacity: int = 1 << 20, mode: Optional[str] = None,
-                 seed: int = 0, name: Optional[str] = None):
+                 seed: int = 0, name: Optional[str] = None, *, var_type: Optional[str] = None,
+                 **kwargs):
+        if var_type not in (None, "hbm", "hybrid"):
+            raise ValueError(f'var_type must be "hbm" or "hybrid", not {var_type!r}')
+        if var_type != "hybrid" and kwargs:
+            raise TypeError(f"unexpected keyword arguments {sorted(kwargs)} (they belong to "
+                            'var_type="hybrid")')
         super().__init__(name)
         self.dimension = int(dimension)
         self.key_type = key_type
@@ -180,37 +196,82 @@ class DynamicVariable(_VariableBase):
         if mode is not None and mode.startswith("localized"):
             self.target_gpu = int(mode.split(":")[1]) if ":" in mode else 0
         self.initializer_str = "" if initializer is None else str(initializer)
-        self._det = DynamicEmbeddingTable([self.dimension], self.initializer_str, init_capacity,
-                                          key_type, seed=seed + 1000003 * _RANK)
+        self._var_type = var_type or "hbm"
+        self.config_dict = dict(kwargs, var_type=self._var_type, init_capacity=init_capacity)
+        self._det: Optional[DynamicEmbeddingTable] = None
+        self._lru: Optional[HybridTable] = None
+        if self._var_type == "hybrid":
+            if kwargs.get("max_capacity") is None:
+                raise ValueError('var_type="hybrid" needs max_capacity')
+            strategy = kwargs.get("evict_strategy", "kLru")
+            if strategy != "kLru":
+                raise ValueError(f"evict_strategy {strategy!r} is not supported: only \"kLru\"")
+            # the initial value is a function of (seed, key, element): the same on every rank
+            self._lru = HybridTable(int(kwargs["max_capacity"]), self.dimension,
+                                    self.initializer_str, int(kwargs.get("max_bucket_size", 128)),
+                                    key_type, seed=seed)
+        else:
+            self._det = DynamicEmbeddingTable([self.dimension], self.initializer_str,
+                                              init_capacity, key_type, seed=seed + 1000003 * _RANK)
         self._opt: Optional[DynamicTableOptimizer] = None
         self._updater = None  # (hctr_updater handle, capacity) of the gradient reduce
 
     @property
+    def backend_type(self) -> str:
+        return self._var_type
+
+    @property
     def size(self) -> int:
-        return self._det.size()
+        return self._lru.size() if self._lru is not None else self._det.size()
 
     def _rows(self, keys: torch.Tensor, train: bool) -> torch.Tensor:
+        if self._lru is not None:
+            return self._lru.lookup_index(keys, insert=train)
         idx = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
         check(lib.hctr_det_lookup_index(self._det._h, 0, ptr(keys), keys.numel(), 1 if train else 0,
                                         ptr(idx), stream_ptr()))
         return idx
 
     def _table(self) -> torch.Tensor:
+        if self._lru is not None:
+            # (the scratch rows after the slots are addressed through the pointer only)
+            p, cap = self._lru.rows_ptr()
+            return _view_f32(p, (cap, self.dimension))
         p, cap = ctypes.c_void_p(), ctypes.c_size_t()
         check(lib.hctr_det_rows(self._det._h, 0, ctypes.byref(p), ctypes.byref(cap)))
         return _view_f32(p.value, (cap.value, self.dimension))
 
+    def _hybrid_scatter(self, indices, values, add: bool):
+        """stored keys only, as the dynamic table's scatter does"""
+        idx = self._lru.find(indices.reshape(-1))
+        live = idx >= 0
+        rows = self._table()
+        v = values.reshape(-1, self.dimension).float()[live]
+        if add:
+            rows.index_add_(0, idx[live], v)
+        else:
+            rows[idx[live]] = v
+
     # dynamic_variable.py:294-340
     def sparse_read(self, indices: torch.Tensor) -> torch.Tensor:
+        if self._lru is not None:
+            rows = self._lru.lookup_index(indices.reshape(-1).contiguous(), insert=False)
+            return _gather(self._table(), rows, self.dimension)  # (the store may have moved)
         return self._det.lookup(indices.contiguous()).view(-1, self.dimension)
 
     def scatter_add(self, indices, values):
+        if self._lru is not None:
+            return self._hybrid_scatter(indices, values, True)
         self._det.scatter_add(indices.contiguous(), values)
 
     def scatter_sub(self, indices, values):
+        if self._lru is not None:
+            return self._hybrid_scatter(indices, -values, True)
         self._det.scatter_add(indices.contiguous(), -values)
 
     def scatter_update(self, indices, values):
+        if self._lru is not None:
+            return self._hybrid_scatter(indices, values, False)
         self._det.scatter_update(indices.contiguous(), values)
 
 
@@ -229,15 +290,61 @@ def _view_f32(addr: int, shape) -> torch.Tensor:
     return torch.as_tensor(h, device="cuda").view(*shape)
 
 
+def _gather(table: torch.Tensor, rows: torch.Tensor, D: int) -> torch.Tensor:
+    """out[i] = table[rows[i]]: the path's pooling with one key per bucket"""
+    ro = torch.arange(rows.numel() + 1, dtype=torch.int64, device=rows.device)
+    return _pool(table, ro, rows, None, 0, D)
+
+
 def export(var: DynamicVariable):
-    """(indices, values) of a DynamicVariable (dynamic_variable.py:465-492)"""
+    """(indices, values) of a DynamicVariable (dynamic_variable.py:465-492); a hybrid variable
+    lists its occupied slots in slot order"""
+    if var._lru is not None:
+        return var._lru.export()
     return var._det.export(0)
 
 
 def assign(var: DynamicVariable, indices: torch.Tensor, values: torch.Tensor):
-    """insert-or-overwrite (dynamic_variable.py:494-520)"""
+    """insert-or-overwrite (dynamic_variable.py:494-520).  On a hybrid variable the insert may
+    evict other keys, and a key the table rejects is not stored."""
+    if var._lru is not None:
+        idx = var._lru.lookup_index(indices.reshape(-1).contiguous(), insert=True)
+        cap = var._lru.capacity
+        live = idx < cap
+        var._table()[idx[live]] = values.reshape(-1, var.dimension).float()[live]
+        return
     var._det.lookup(indices.contiguous())       # inserts what is missing
     var._det.scatter_update(indices.contiguous(), values)
+
+
+class _ReadEvictFn(torch.autograd.Function):
+    """values of sparse_read_and_evict; backward leaves the keys' gradients for OptimizerWrapper"""
+
+    @staticmethod
+    def forward(ctx, token, var, keys, rows):
+        ctx.var, ctx.keys, ctx.rows = var, keys, rows
+        return _gather(var._table(), rows, var.dimension)
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.keys.numel()
+        ro = torch.arange(n + 1, dtype=torch.int64, device=g.device)
+        ctx.var._pending.append((ro, ctx.rows, ctx.keys, None, g.contiguous().float(), 0))
+        return torch.zeros(1, device=g.device), None, None, None
+
+
+def sparse_read_and_evict(var: DynamicVariable, indices: torch.Tensor):
+    """(values [n, dimension], evict_keys, evict_values) -- lookup.py:75-80.  An inserting lookup
+    on this GPU's table (as the reference's op); the pairs it evicted come back to the caller, in
+    bucket order.  values carries autograd: OptimizerWrapper.step updates those keys.  Hybrid
+    variables only."""
+    if not isinstance(var, DynamicVariable) or var.backend_type != "hybrid":
+        raise TypeError("sparse_read_and_evict only supports DynamicVariable with "
+                        'var_type="hybrid"')
+    keys = indices.reshape(-1).to(var.key_type).contiguous()
+    rows, ek, ev = var._lru.lookup_index(keys, insert=True, evict=True)
+    values = _ReadEvictFn.apply(var._token, var, keys, rows)
+    return values, ek, ev
 
 
 # ---- collectives (NCCL = RCCL on the GPU boxes; gloo stages through the host, used by tests) ------
@@ -449,7 +556,9 @@ class OptimizerWrapper:
                                                     ptr(w), ptr(g), ptr(kg), stream_ptr()))
                     ks.append(keys)
                     gs.append(kg)
-                if ks:
+                if ks and var._lru is not None:
+                    self._step_hybrid(var, torch.cat(ks), torch.cat(gs))
+                elif ks:
                     self._step_dynamic(var, torch.cat(ks), torch.cat(gs))
             else:
                 for ro, rows, keys, w, g, comb in pend:
@@ -495,6 +604,33 @@ class OptimizerWrapper:
             hp["scaler"], self.times, ptr(var.weight),
             ptr(var._states[0]) if ns >= 1 else None, ptr(var._states[1]) if ns >= 2 else None,
             stream_ptr()))
+
+    # hybrid variable: the keys are found again (find only) -- one evicted since its lookup has no
+    # row any more and its gradient is dropped (kInvalidIndex), never applied to the slot's new
+    # owner -- then the static path's sort + segmented reduce + optimizer on the slot rows
+    def _step_hybrid(self, var: DynamicVariable, keys, kg):
+        if self.name in ("rmsprop", "ftrl"):
+            raise RuntimeError(f"{self.name} is not available for a hybrid DynamicVariable")
+        D = var.dimension
+        n = keys.numel()
+        slots = var._lru.find(keys)
+        rows_p, cap = var._lru.rows_ptr()
+        if var._updater is None or var._updater[1] < n:
+            if var._updater is not None:
+                lib.hctr_updater_destroy(var._updater[0])
+            h = ctypes.c_void_p()
+            ucap = max(2 * n, 1024)
+            check(lib.hctr_updater_create(ucap, cap, D, ctypes.byref(h)))
+            var._updater = (h, ucap)
+        ns = _num_state(self.code)
+        st = [ctypes.c_void_p(var._lru.state_ptr(i)) for i in range(ns)]
+        ro = torch.arange(n + 1, dtype=torch.int64, device=kg.device)
+        hp = self.hp
+        check(lib.hctr_updater_update(
+            var._updater[0], n, n, ptr(ro), ptr(slots), ptr(kg.contiguous()), _lib.F32, self.code,
+            _lib.UPDATE_LOCAL, hp["lr"], hp["beta1"], hp["beta2"], hp["epsilon"], hp["momentum"],
+            hp["scaler"], self.times, ctypes.c_void_p(rows_p), st[0] if ns >= 1 else None,
+            st[1] if ns >= 2 else None, stream_ptr()))
 
     # dynamic variable: per-key gradients -> unique keys + sums (the reference's OptimizerWrapper
     # does this with tf.unique / unsorted_segment_sum, optimizer.py:170-230) -> fused HIP step
@@ -572,6 +708,16 @@ def _var_arrays(var, optimizer):
     """(keys int64 [n], weight [n, D], [state matrices in slot order]) of this rank"""
     D = var.dimension
     slots = _SLOTS[optimizer.name] if optimizer is not None else []
+    if isinstance(var, DynamicVariable) and var._lru is not None:
+        k, w, sl, _ = var._lru.export(with_slots=True)
+        order = torch.argsort(k)
+        k, w, sl = k[order].to(torch.int64), w[order], sl[order]
+        states = []
+        if slots:
+            cap = var._lru.capacity
+            states = [_view_f32(var._lru.state_ptr(j), (cap, D))[sl].clone()
+                      for j in range(len(slots))]
+        return k, w, states
     if isinstance(var, DynamicVariable):
         k, w = var._det.export(0)
         order = torch.argsort(k)
@@ -657,7 +803,16 @@ def load(path: str, load_vars, optimizer: Optional["OptimizerWrapper"] = None):
         dev = torch.device("cuda", torch.cuda.current_device())
         kt = torch.from_numpy(keys).to(dev)
         wt = torch.from_numpy(w).to(dev)
-        if isinstance(var, DynamicVariable):
+        if isinstance(var, DynamicVariable) and var._lru is not None:
+            if kt.numel():
+                assign(var, kt.to(var.key_type), wt)
+            if states and len(states) == len(slots) and kt.numel():
+                idx = var._lru.find(kt.to(var.key_type))
+                live = idx >= 0
+                for j, x in enumerate(states):
+                    sv = _view_f32(var._lru.state_ptr(j), (var._lru.capacity, var.dimension))
+                    sv[idx[live]] = torch.from_numpy(x).to(dev)[live]
+        elif isinstance(var, DynamicVariable):
             if kt.numel():
                 assign(var, kt.to(var.key_type), wt)
             if states and len(states) == len(slots) and kt.numel():

@@ -798,6 +798,53 @@ int hctr_uvm_scatter_rows(hctr_uvm* u, const uint64_t* d_unique_rows, size_t len
 int hctr_uvm_check_overflow(hctr_uvm* u, hctr_stream_t stream);
 int hctr_uvm_size(hctr_uvm* u, hctr_stream_t stream, size_t* out); /* keys held; host sync */
 
+/* ---- bounded table with LRU eviction (SOK DynamicVariable var_type="hybrid") ------------------
+ * The part of the reference's HKV-backed variable (R/sparse_operation_kit/kit_src/variable/impl/
+ * hkv_variable.cu:274-493: find_or_insert, lookup_with_evict) with this project's deterministic
+ * semantics (DESIGN.md "Hybrid table"; restated sequentially in tests/lru_oracle.py):
+ * capacity C = capacity rounded up to a multiple of bucket_size S (64, 128, 192 or 256); key k lives
+ * in bucket MurmurHash3_32(k) % (C / S) (hctr_hash_keys); slot s owns row s of ONE [C][dim] fp32
+ * store allocated at create, so the table never grows.  Every inserting call t (1, 2, ...):
+ *   1. keys already stored get score t;
+ *   2. the distinct missing keys of a bucket, ascending, take the lowest empty slot, else the slot
+ *      with the smallest (score, slot) among scores < t -- its (key, row) is evicted -- else are
+ *      rejected: not stored, read the initializer's value, counted by hctr_lru_rejected_count;
+ *   3. new rows get the initializer's value and zero optimizer state.
+ * initializer: "ones" | "zeros" | a float literal | anything else = uniform (0, 1], a pure function
+ * of (seed, key, element) -- never of the slot.  The all-ones key (-1 as int64) is reserved.
+ * Evicted pairs come out ordered by bucket, then by insertion inside the bucket. */
+typedef struct hctr_lru hctr_lru;
+int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
+                    const char* initializer, uint64_t seed, hctr_lru** out);
+int hctr_lru_destroy(hctr_lru* h);
+/* row_index[n] (device): insert != 0 runs the inserting call above; insert == 0 inserts nothing and
+ * touches no score.  Rows >= C (see hctr_lru_rows) are per-call scratch holding the initializer's
+ * value of a key that is not stored (a miss of a read-only lookup, a rejected key), so gather /
+ * pooling (hctr_forward_pool*) read the right vector for every key.  evict_keys (device, n keys of
+ * key_type) / evict_rows (device, [n][dim]) may be NULL; n_evicted (HOST, may be NULL) receives
+ * the number of evicted pairs -- the call's only host synchronisation.  At most 2^24 keys. */
+int hctr_lru_lookup_index(hctr_lru* h, const void* keys, size_t n, int insert, uint64_t* row_index,
+                          void* evict_keys, float* evict_rows, size_t* n_evicted,
+                          hctr_stream_t stream);
+/* find only: row_index = slot, or SIZE_MAX for a key that is not stored (no side effects; the
+ * optimizer step drops such keys' gradients through it) */
+int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
+                  hctr_stream_t stream);
+/* the row store (*capacity = C slot rows; the scratch rows follow them).  The pointer is stable
+ * unless a call brings more keys than any before it with a key-dependent initializer, which moves
+ * the store once to make room for that many scratch rows. */
+int hctr_lru_rows(hctr_lru* h, float** rows, size_t* capacity);
+/* optimizer state i (0 or 1): [C][dim] fp32 sharing the slot numbers, zero-filled on first request;
+ * a newly inserted key's state rows are zeroed.  Fixed for the table's life. */
+int hctr_lru_state(hctr_lru* h, int i, float** state, hctr_stream_t stream);
+/* occupied slots in slot order: keys (key_type), slots and scores (uint64) and rows
+ * ([max_keys][dim]); any of them may be NULL; *exported = how many (host sync) */
+int hctr_lru_export(hctr_lru* h, void* keys, uint64_t* slots, uint64_t* scores, float* rows,
+                    size_t max_keys, size_t* exported, hctr_stream_t stream);
+int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream);              /* host sync */
+int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream);  /* host sync */
+int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size);
+
 #ifdef __cplusplus
 }
 #endif

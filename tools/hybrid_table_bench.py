@@ -1,0 +1,89 @@
+"""Micro-benchmark of the hybrid (LRU) table, csrc/hybrid_table.hip: capacity 2^24, 1 M keys per
+call, D = 16 and 128.
+
+  find       all keys stored (hctr_lru_find: digest line + key per key)
+  insert10   inserting lookup, 10 % of the keys missing, every bucket full (90 % hits)
+  insert100  inserting lookup, 100 % missing, every bucket full (every key evicts)
+
+Algorithmic bytes per key: a hit reads the 128-B digest line, its 8-B key and its D*4-B row (the
+gather that follows the lookup); an inserted key adds the row write and the evicted row read
+(D*4 each; no optimizer state in this run).  Fraction = bytes / time / 8 TB/s.
+Not part of bench.py's line.  Usage: python tools/hybrid_table_bench.py [--iters 20]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from hugectr_amd.hybrid_table import HybridTable  # noqa: E402
+
+PEAK = 8e12
+
+
+def timed(fn, iters):
+    fn(0)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    tot = 0.0
+    for i in range(iters):
+        a.record()
+        fn(i + 1)
+        b.record()
+        b.synchronize()
+        tot += a.elapsed_time(b)
+    return tot / iters * 1e3  # us
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--capacity", type=int, default=1 << 24)
+    ap.add_argument("--batch", type=int, default=1 << 20)
+    args = ap.parse_args()
+    C, N = args.capacity, args.batch
+    for D in (16, 128):
+        t = HybridTable(C, D, "0.5", 128)
+        nxt = [0]
+
+        def fresh(n):
+            k = torch.arange(nxt[0], nxt[0] + n, dtype=torch.int64, device="cuda")
+            nxt[0] += n
+            return k
+
+        # fill until every bucket is full (evictions start once a bucket is)
+        for _ in range(64):
+            if t.size() == t.capacity:
+                break
+            t.lookup_index(fresh(N), insert=True)
+        assert t.size() == t.capacity, "the table did not fill"
+        stored, _ = t.export()
+        g = torch.Generator(device="cuda").manual_seed(0)
+
+        def hits(n):
+            return stored[torch.randint(0, stored.numel(), (n,), device="cuda", generator=g)]
+
+        hit_sets = [hits(N) for _ in range(args.iters + 1)]
+        res = {}
+        res["find"] = timed(lambda i: t.find(hit_sets[i]), args.iters)
+        # insert10 / insert100 change the table: the hit keys are re-drawn from the live ones
+        stored, _ = t.export()
+        mixes = [torch.cat([hits(N - N // 10), fresh(N // 10)]) for _ in range(args.iters + 1)]
+        res["insert10"] = timed(lambda i: t.lookup_index(mixes[i], insert=True), args.iters)
+        news = [fresh(N) for _ in range(args.iters + 1)]
+        res["insert100"] = timed(lambda i: t.lookup_index(news[i], insert=True), args.iters)
+        hit_b = 128 + 8 + 4 * D
+        ins_b = hit_b + 2 * 4 * D
+        by = {"find": N * hit_b, "insert10": (N - N // 10) * hit_b + (N // 10) * ins_b,
+              "insert100": N * ins_b}
+        for name, us in res.items():
+            print(json.dumps({"case": name, "D": D, "capacity": t.capacity, "batch": N,
+                              "us": round(us, 1), "alg_bytes": by[name],
+                              "frac_of_8TBps": round(by[name] / (us * 1e-6) / PEAK, 4)}))
+        t.close()
+
+
+if __name__ == "__main__":
+    main()
