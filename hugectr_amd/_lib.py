@@ -228,6 +228,11 @@ _SIGNATURES = {
     "hctr_lru_size": (c_int, [_P, _SZP, _P]),
     "hctr_lru_rejected_count": (c_int, [_P, POINTER(c_uint64), _P]),
     "hctr_lru_capacity": (c_int, [_P, _SZP, _SZP]),
+    "hctr_lru_lookup_index_filtered": (c_int, [_P, _P, c_size_t, c_uint64, _P, _P, _P, _SZP, _P]),
+    "hctr_lru_filtered_count": (c_int, [_P, POINTER(c_uint64), _P]),
+    "hctr_lru_compact": (c_int, [_P, c_size_t, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _SZP,
+                                 _P]),
+    "hctr_lru_export_if": (c_int, [_P, c_uint64, _P, _P, _P, _P, c_size_t, _SZP, _SZP, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

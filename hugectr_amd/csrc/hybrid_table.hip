@@ -21,6 +21,11 @@
 // (a miss of a read-only lookup, a rejected key) reads in the current call, so the path's gather /
 // pooling kernels run unchanged on the row numbers handed out here.
 //
+// Low-frequency filter (hctr_lru_lookup_index_filtered): in an inserting call a key that is not
+// stored is admitted only if a hash of (seed, key, t) falls below the admission threshold; the
+// others get the kLruFiltered row, touch nothing, and hctr_lru_compact drops them from the batch.
+// hctr_lru_export_if exports the slots whose score is at least a given call number.
+//
 // Compiled as part of det.hip's unit (included at its end): the bounded sibling of the dynamic
 // table, built into every library that carries the dynamic table.  Its internal names carry an
 // lru prefix for that reason.
@@ -40,6 +45,9 @@ namespace {
 constexpr int kLruBlock = 256;
 constexpr int kLruWavesPerBlock = kLruBlock / kWave;
 constexpr uint64_t kLruEmpty = ~0ull;
+// row index of a key the low-frequency filter did not admit (distinct from kInvalidIndex)
+constexpr uint64_t kLruFiltered = ~0ull - 1;
+constexpr uint64_t kLruAdmitAll = 1ull << 32;
 constexpr int kLruMaxSlotsPerLane = 4;  // S <= 256
 
 __device__ __forceinline__ uint64_t lru_splitmix64(uint64_t x) {
@@ -55,6 +63,12 @@ __device__ __forceinline__ float lru_init_value(int mode, float val, uint64_t se
   if (mode == 0) return val;
   const uint64_t h = lru_splitmix64(seed ^ lru_splitmix64(key * 0x100000001B3ull + e));
   return ((float)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);
+}
+
+// admission draw of a key that is not stored, in inserting call t: 32 bits of a counter-based hash
+// of (seed, key, t); the key is admitted iff the draw < admit_below (= ceil(p * 2^32))
+__device__ __forceinline__ uint32_t lru_admit_draw(uint64_t seed, uint64_t key, uint64_t t) {
+  return (uint32_t)(lru_splitmix64(seed ^ lru_splitmix64(key ^ lru_splitmix64(t))) >> 32);
 }
 
 template <typename K>
@@ -88,16 +102,25 @@ enum { kLruFind = 0, kLruRead = 1, kLruInsert = 2 };
 // One thread per key: the bucket's digest line (S bytes, 16 B per load), then the key of every
 // slot whose digest matches.  kLruFind: slot or kInvalidIndex.  kLruRead: slot, or a scratch row
 // holding the initializer's value.  kLruInsert: hits get score t; misses are handed to the sort
-// (bucket = nb marks a hit, which sorts behind every bucket).
-template <typename K>
+// (bucket = nb marks a hit, which sorts behind every bucket).  Filter (kLruInsert only): a miss
+// whose admission draw is >= admit_below gets kLruFiltered and sorts behind the buckets like a hit;
+// such positions are counted in counters[2], one atomic per wave.
+template <typename K, bool Filter>
 __global__ void __launch_bounds__(kLruBlock)
     lru_find_kernel(LruTbl T, const K* __restrict__ in, size_t n, int mode, uint64_t t,
                     uint64_t* __restrict__ idx, uint32_t* __restrict__ sbkt,
                     uint32_t* __restrict__ slo, uint32_t* __restrict__ shi,
-                    uint32_t* __restrict__ sval) {
+                    uint32_t* __restrict__ sval, uint64_t admit_below,
+                    unsigned long long* __restrict__ counters) {
   const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
-  if (i >= n) return;
-  const K kk = in[i];
+  if (Filter) {
+    // the whole wave reaches the ballot below (lanes past n take part as "not filtered")
+    if (i - (threadIdx.x % kWave) >= n) return;
+  } else if (i >= n) {
+    return;
+  }
+  const bool live = i < n;
+  const K kk = in[live ? i : 0];
   const uint64_t key = lru_key_u64<K>(kk);
   const uint32_t h = murmur3_key(kk);
   const uint64_t b = (uint64_t)h % T.nb;
@@ -141,7 +164,15 @@ __global__ void __launch_bounds__(kLruBlock)
         T.rows[r * T.D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
     return;
   }
-  if (slot != kInvalidIndex) T.scores[slot] = t;  // every writer writes the same t
+  bool filtered = false;
+  if (Filter) {
+    filtered = live && slot == kInvalidIndex && lru_admit_draw(T.seed, key, t) >= admit_below;
+    const uint64_t fm = __ballot(filtered);
+    if (fm && (threadIdx.x % kWave) == 0) atomicAdd(&counters[2], (unsigned long long)__popcll(fm));
+    if (!live) return;
+    if (filtered) slot = kLruFiltered;
+  }
+  if (slot != kInvalidIndex && !filtered) T.scores[slot] = t;  // every writer writes the same t
   idx[i] = slot;
   sbkt[i] = slot != kInvalidIndex ? (uint32_t)T.nb : (uint32_t)b;
   slo[i] = (uint32_t)key;
@@ -338,19 +369,26 @@ __global__ void __launch_bounds__(kLruBlock)
   }
 }
 
+// a slot is exported iff it is occupied and its score >= min_score (0: every occupied slot)
+__device__ __forceinline__ bool lru_exported(const uint64_t* keys, const uint64_t* scores, size_t i,
+                                             uint64_t min_score) {
+  return keys[i] != kLruEmpty && (min_score == 0 || scores[i] >= min_score);
+}
+
 __global__ void __launch_bounds__(kLruBlock)
-    lru_occupied_kernel(const uint64_t* __restrict__ keys, size_t C, uint32_t* __restrict__ flag) {
+    lru_occupied_kernel(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ scores,
+                        size_t C, uint64_t min_score, uint32_t* __restrict__ flag) {
   const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
-  if (i < C) flag[i] = keys[i] != kLruEmpty ? 1u : 0u;
+  if (i < C) flag[i] = lru_exported(keys, scores, i, min_score) ? 1u : 0u;
 }
 
 __global__ void __launch_bounds__(kLruBlock)
     lru_export_kernel(const uint64_t* __restrict__ keys, size_t C, const uint32_t* __restrict__ off,
-                      const uint64_t* __restrict__ scores, size_t max_out, int key_bytes,
-                      void* __restrict__ out_keys, uint64_t* __restrict__ out_slots,
+                      const uint64_t* __restrict__ scores, uint64_t min_score, size_t max_out,
+                      int key_bytes, void* __restrict__ out_keys, uint64_t* __restrict__ out_slots,
                       uint64_t* __restrict__ out_scores) {
   const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
-  if (i >= C || keys[i] == kLruEmpty) return;
+  if (i >= C || !lru_exported(keys, scores, i, min_score)) return;
   const uint32_t o = off[i];
   if (o >= max_out) return;
   if (out_keys) {
@@ -384,6 +422,36 @@ __global__ void __launch_bounds__(kLruBlock)
   }
 }
 
+// CSR compaction of a filtered lookup: keep[i] = 1 unless row i is kLruFiltered; an exclusive scan
+// of keep gives every kept position its output position, so order is kept inside each sample and
+// a sample's new offset is the scan at its old offset.
+__global__ void __launch_bounds__(kLruBlock)
+    lru_keep_kernel(const uint64_t* __restrict__ rows, size_t n, uint32_t* __restrict__ keep) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i < n) keep[i] = rows[i] != kLruFiltered ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(kLruBlock)
+    lru_compact_kernel(size_t B, const long long* __restrict__ off, size_t n,
+                       const uint64_t* __restrict__ rows, const void* __restrict__ keys,
+                       int key_bytes, const float* __restrict__ w,
+                       const uint32_t* __restrict__ pos, long long* __restrict__ out_off,
+                       uint64_t* __restrict__ out_rows, void* __restrict__ out_keys,
+                       float* __restrict__ out_w) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i <= B) out_off[i] = (long long)pos[off[i]];
+  if (i >= n) return;
+  const uint64_t r = rows[i];
+  if (r == kLruFiltered) return;
+  const uint32_t o = pos[i];
+  out_rows[o] = r;
+  if (key_bytes == 8)
+    static_cast<uint64_t*>(out_keys)[o] = static_cast<const uint64_t*>(keys)[i];
+  else
+    static_cast<uint32_t*>(out_keys)[o] = static_cast<const uint32_t*>(keys)[i];
+  if (w) out_w[o] = w[i];
+}
+
 inline int lru_blocks(size_t n) { return (int)ceil_div<size_t>(n > 0 ? n : 1, (size_t)kLruBlock); }
 
 }  // namespace
@@ -404,11 +472,12 @@ struct hctr_lru {
   size_t scratch = 0;  // rows after the C slots
   float* st[2] = {nullptr, nullptr};
   uint64_t t = 0;  // inserting calls so far
-  unsigned long long* counters = nullptr;  // [0] occupied slots, [1] rejected keys
+  unsigned long long* counters = nullptr;  // [0] occupied slots, [1] rejected keys, [2] filtered
   unsigned long long* h_word = nullptr;    // pinned host word
   // per-call workspace (n keys)
   size_t ws_n = 0;
   uint32_t* ws = nullptr;  // 8 arrays of ws_n
+  unsigned long long* ws_tiles = nullptr;  // scan tiles of ws_n + 1 elements (compaction)
   void* sort_temp = nullptr;
   size_t sort_temp_bytes = 0;
   // per-bucket workspace
@@ -441,6 +510,7 @@ namespace {
 
 void lru_free(hctr_lru* h) {
   void* ps[] = {h->keys, h->scores, h->digests, h->rows, h->st[0], h->st[1], h->counters, h->ws,
+                h->ws_tiles,
                 h->sort_temp, h->rng, h->evict_cnt, h->evict_off, h->tile_sums, h->d_total};
   for (void* p : ps)
     if (p) (void)hipFree(p);
@@ -452,12 +522,15 @@ void lru_free(hctr_lru* h) {
 int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
   if (n > h->ws_n) {
     if (h->ws) HCTR_HIP(hipFree(h->ws));
+    if (h->ws_tiles) HCTR_HIP(hipFree(h->ws_tiles));
     if (h->sort_temp) HCTR_HIP(hipFree(h->sort_temp));
     h->ws = nullptr;
+    h->ws_tiles = nullptr;
     h->sort_temp = nullptr;
     h->ws_n = 0;
     const size_t cap = n < 4096 ? 4096 : n;
     HCTR_HIP(hipMalloc(&h->ws, cap * 8 * sizeof(uint32_t)));
+    HCTR_HIP(hipMalloc(&h->ws_tiles, (cap / 1024 + 2) * sizeof(unsigned long long)));
     h->sort_temp_bytes = radix_sort_temp_bytes(cap);
     HCTR_HIP(hipMalloc(&h->sort_temp, h->sort_temp_bytes));
     h->ws_n = cap;
@@ -477,12 +550,14 @@ int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
 }
 
 template <typename K>
-int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t* row_index,
-               void* ev_keys, float* ev_rows, size_t* n_evicted, hipStream_t s) {
+int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t admit_below,
+               uint64_t* row_index, void* ev_keys, float* ev_rows, size_t* n_evicted,
+               hipStream_t s) {
   HCTR_TRY(lru_reserve(h, n, s));
   if (!insert) {
-    hipLaunchKernelGGL(lru_find_kernel<K>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->tbl(),
-                       keys, n, (int)kLruRead, h->t, row_index, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
+                       h->tbl(), keys, n, (int)kLruRead, h->t, row_index, nullptr, nullptr, nullptr,
+                       nullptr, kLruAdmitAll, nullptr);
     HCTR_LAUNCH_CHECK();
     if (n_evicted) *n_evicted = 0;
     return HCTR_OK;
@@ -492,8 +567,14 @@ int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t* row_i
   uint32_t *bkt = h->ws, *klo = h->ws + m, *khi = h->ws + 2 * m, *seq = h->ws + 3 * m,
            *g = h->ws + 4 * m, *tk = h->ws + 5 * m, *pa = h->ws + 6 * m, *pb = h->ws + 7 * m;
   const bool wide = sizeof(K) == 8;
-  hipLaunchKernelGGL(lru_find_kernel<K>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->tbl(),
-                     keys, n, (int)kLruInsert, t, row_index, bkt, klo, wide ? khi : nullptr, seq);
+  if (admit_below < kLruAdmitAll)
+    hipLaunchKernelGGL((lru_find_kernel<K, true>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
+                       h->tbl(), keys, n, (int)kLruInsert, t, row_index, bkt, klo,
+                       wide ? khi : nullptr, seq, admit_below, h->counters);
+  else
+    hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
+                       h->tbl(), keys, n, (int)kLruInsert, t, row_index, bkt, klo,
+                       wide ? khi : nullptr, seq, kLruAdmitAll, nullptr);
   HCTR_LAUNCH_CHECK();
   // (bucket, key) order by three stable passes: key low word, key high word, bucket
   HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, klo, tk, seq, pa, n, 32, s));
@@ -535,6 +616,58 @@ int lru_read_counter(hctr_lru* h, int which, uint64_t* out, hipStream_t s) {
   HCTR_HIP(hipStreamSynchronize(s));
   *out = (uint64_t)*h->h_word;
   return HCTR_OK;
+}
+
+// occupied slots with score >= min_score in slot order; *total = how many there are, the first
+// min(total, max_keys) of them are written
+int lru_export(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots, uint64_t* scores,
+               float* rows, size_t max_keys, size_t* exported, size_t* total, hipStream_t s) {
+  uint32_t *flag = nullptr, *off = nullptr;
+  uint64_t* tmp_slots = nullptr;
+  unsigned long long* tiles = nullptr;
+  const size_t C = h->C;
+  int rc = HCTR_OK;
+  if (hipMalloc(&flag, C * 4) != hipSuccess || hipMalloc(&off, (C + 1) * 4) != hipSuccess ||
+      hipMalloc(&tiles, (C / 1024 + 2) * 8) != hipSuccess ||
+      (rows && !slots && hipMalloc(&tmp_slots, (max_keys ? max_keys : 1) * 8) != hipSuccess)) {
+    (void)hipGetLastError();
+    set_error("hctr_lru_export: out of device memory");
+    rc = HCTR_ERR_HIP;
+  }
+  if (rc == HCTR_OK) {
+    uint64_t* sl = slots ? slots : tmp_slots;
+    hipLaunchKernelGGL(lru_occupied_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
+                       h->scores, C, min_score, flag);
+    rc = exclusive_scan_to_offsets<uint32_t>(flag, C, tiles, h->d_total, off, s);
+    if (rc == HCTR_OK) {
+      hipLaunchKernelGGL(lru_export_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
+                         C, off, h->scores, min_score, max_keys, h->key_type == HCTR_KEY_I64 ? 8 : 4,
+                         keys, sl, scores);
+      if (hipMemcpyAsync(h->h_word, h->d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("hctr_lru_export: HIP error");
+        rc = HCTR_ERR_HIP;
+      }
+    }
+    if (rc == HCTR_OK) {
+      const size_t got = (size_t)*h->h_word < max_keys ? (size_t)*h->h_word : max_keys;
+      if (rows && got)
+        hipLaunchKernelGGL(lru_gather_rows_kernel, dim3(lru_blocks(got * (size_t)h->D)),
+                           dim3(kLruBlock), 0, s, sl, got, h->rows, h->D, rows);
+      if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+        set_error("hctr_lru_export: HIP error");
+        rc = HCTR_ERR_HIP;
+      }
+      *exported = got;
+      if (total) *total = (size_t)*h->h_word;
+    }
+  }
+  if (flag) (void)hipFree(flag);
+  if (off) (void)hipFree(off);
+  if (tiles) (void)hipFree(tiles);
+  if (tmp_slots) (void)hipFree(tmp_slots);
+  return rc;
 }
 
 }  // namespace
@@ -579,7 +712,7 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
             hipMalloc(&h->scores, C * 8) == hipSuccess &&
             hipMalloc(&h->digests, C) == hipSuccess &&
             hipMalloc(&h->rows, (C + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
-            hipMalloc(&h->counters, 2 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMalloc(&h->counters, 3 * sizeof(unsigned long long)) == hipSuccess &&
             hipMalloc(&h->rng, 2 * h->nb * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&h->evict_cnt, h->nb * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&h->evict_off, (h->nb + 1) * sizeof(uint32_t)) == hipSuccess &&
@@ -589,7 +722,7 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
   if (ok)
     ok = hipMemset(h->digests, 0, C) == hipSuccess &&
          hipMemset(h->rows, 0, (C + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
-         hipMemset(h->counters, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
+         hipMemset(h->counters, 0, 3 * sizeof(unsigned long long)) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     set_error("hctr_lru_create: out of device memory");
@@ -631,10 +764,59 @@ int hctr_lru_lookup_index(hctr_lru* h, const void* keys, size_t n, int insert, u
   }
   const hipStream_t s = as_stream(stream);
   if (h->key_type == HCTR_KEY_I64)
-    return lru_lookup<long long>(h, (const long long*)keys, n, insert, row_index, evict_keys,
-                                 evict_rows, n_evicted, s);
-  return lru_lookup<uint32_t>(h, (const uint32_t*)keys, n, insert, row_index, evict_keys,
+    return lru_lookup<long long>(h, (const long long*)keys, n, insert, kLruAdmitAll, row_index,
+                                 evict_keys, evict_rows, n_evicted, s);
+  return lru_lookup<uint32_t>(h, (const uint32_t*)keys, n, insert, kLruAdmitAll, row_index,
+                              evict_keys, evict_rows, n_evicted, s);
+}
+
+int hctr_lru_lookup_index_filtered(hctr_lru* h, const void* keys, size_t n, uint64_t admit_below,
+                                   uint64_t* row_index, void* evict_keys, float* evict_rows,
+                                   size_t* n_evicted, hctr_stream_t stream) {
+  HCTR_REQUIRE(h, "null handle");
+  HCTR_REQUIRE(n <= ((size_t)1 << 24), "at most 2^24 keys per call");
+  HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
+  HCTR_REQUIRE(!evict_rows || evict_keys, "evict_rows needs evict_keys");
+  HCTR_REQUIRE(admit_below <= kLruAdmitAll, "admit_below must be in [0, 2^32]");
+  if (n == 0) {
+    if (n_evicted) *n_evicted = 0;
+    h->t++;
+    return HCTR_OK;
+  }
+  const hipStream_t s = as_stream(stream);
+  if (h->key_type == HCTR_KEY_I64)
+    return lru_lookup<long long>(h, (const long long*)keys, n, 1, admit_below, row_index,
+                                 evict_keys, evict_rows, n_evicted, s);
+  return lru_lookup<uint32_t>(h, (const uint32_t*)keys, n, 1, admit_below, row_index, evict_keys,
                               evict_rows, n_evicted, s);
+}
+
+int hctr_lru_compact(hctr_lru* h, size_t batch, size_t n, const long long* offsets,
+                     const uint64_t* rows, const void* keys, const float* weights,
+                     long long* out_offsets, uint64_t* out_rows, void* out_keys,
+                     float* out_weights, size_t* n_kept, hctr_stream_t stream) {
+  HCTR_REQUIRE(h, "null handle");
+  HCTR_REQUIRE(n_kept, "n_kept is null");
+  HCTR_REQUIRE(n <= ((size_t)1 << 24), "at most 2^24 keys per call");
+  HCTR_REQUIRE(offsets && out_offsets, "offsets / out_offsets are null");
+  HCTR_REQUIRE(n == 0 || (rows && keys && out_rows && out_keys), "rows / keys are null");
+  HCTR_REQUIRE(!weights || out_weights, "weights need out_weights");
+  const hipStream_t s = as_stream(stream);
+  HCTR_TRY(lru_reserve(h, n, s));
+  uint32_t *keep = h->ws, *pos = h->ws + h->ws_n;  // pos: n + 1 entries
+  hipLaunchKernelGGL(lru_keep_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, rows, n, keep);
+  HCTR_LAUNCH_CHECK();
+  HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(keep, n, h->ws_tiles, h->d_total, pos, s));
+  const size_t m = n > batch + 1 ? n : batch + 1;
+  hipLaunchKernelGGL(lru_compact_kernel, dim3(lru_blocks(m)), dim3(kLruBlock), 0, s, batch,
+                     offsets, n, rows, keys, h->key_type == HCTR_KEY_I64 ? 8 : 4, weights, pos,
+                     out_offsets, out_rows, out_keys, out_weights);
+  HCTR_LAUNCH_CHECK();
+  HCTR_HIP(hipMemcpyAsync(h->h_word, h->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          s));
+  HCTR_HIP(hipStreamSynchronize(s));
+  *n_kept = (size_t)*h->h_word;
+  return HCTR_OK;
 }
 
 int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
@@ -644,13 +826,13 @@ int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
   if (n == 0) return HCTR_OK;
   const hipStream_t s = as_stream(stream);
   if (h->key_type == HCTR_KEY_I64)
-    hipLaunchKernelGGL(lru_find_kernel<long long>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), (const long long*)keys, n, (int)kLruFind, h->t, row_index,
-                       nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((lru_find_kernel<long long, false>), dim3(lru_blocks(n)), dim3(kLruBlock),
+                       0, s, h->tbl(), (const long long*)keys, n, (int)kLruFind, h->t, row_index,
+                       nullptr, nullptr, nullptr, nullptr, kLruAdmitAll, nullptr);
   else
-    hipLaunchKernelGGL(lru_find_kernel<uint32_t>, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), (const uint32_t*)keys, n, (int)kLruFind, h->t, row_index,
-                       nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((lru_find_kernel<uint32_t, false>), dim3(lru_blocks(n)), dim3(kLruBlock),
+                       0, s, h->tbl(), (const uint32_t*)keys, n, (int)kLruFind, h->t, row_index,
+                       nullptr, nullptr, nullptr, nullptr, kLruAdmitAll, nullptr);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -677,52 +859,16 @@ int hctr_lru_state(hctr_lru* h, int i, float** state, hctr_stream_t stream) {
 int hctr_lru_export(hctr_lru* h, void* keys, uint64_t* slots, uint64_t* scores, float* rows,
                     size_t max_keys, size_t* exported, hctr_stream_t stream) {
   HCTR_REQUIRE(h && exported, "null argument");
-  const hipStream_t s = as_stream(stream);
-  uint32_t *flag = nullptr, *off = nullptr;
-  uint64_t* tmp_slots = nullptr;
-  unsigned long long* tiles = nullptr;
-  const size_t C = h->C;
-  int rc = HCTR_OK;
-  if (hipMalloc(&flag, C * 4) != hipSuccess || hipMalloc(&off, (C + 1) * 4) != hipSuccess ||
-      hipMalloc(&tiles, (C / 1024 + 2) * 8) != hipSuccess ||
-      (rows && !slots && hipMalloc(&tmp_slots, (max_keys ? max_keys : 1) * 8) != hipSuccess)) {
-    (void)hipGetLastError();
-    set_error("hctr_lru_export: out of device memory");
-    rc = HCTR_ERR_HIP;
-  }
-  if (rc == HCTR_OK) {
-    uint64_t* sl = slots ? slots : tmp_slots;
-    hipLaunchKernelGGL(lru_occupied_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
-                       C, flag);
-    rc = exclusive_scan_to_offsets<uint32_t>(flag, C, tiles, h->d_total, off, s);
-    if (rc == HCTR_OK) {
-      hipLaunchKernelGGL(lru_export_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
-                         C, off, h->scores, max_keys, h->key_type == HCTR_KEY_I64 ? 8 : 4, keys, sl,
-scores);
-      if (hipMemcpyAsync(h->h_word, h->d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-          hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hctr_lru_export: HIP error");
-        rc = HCTR_ERR_HIP;
-      }
-    }
-    if (rc == HCTR_OK) {
-      const size_t got = (size_t)*h->h_word < max_keys ? (size_t)*h->h_word : max_keys;
-      if (rows && got)
-        hipLaunchKernelGGL(lru_gather_rows_kernel, dim3(lru_blocks(got * (size_t)h->D)),
-                           dim3(kLruBlock), 0, s, sl, got, h->rows, h->D, rows);
-      if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-        set_error("hctr_lru_export: HIP error");
-        rc = HCTR_ERR_HIP;
-      }
-      *exported = got;
-    }
-  }
-  if (flag) (void)hipFree(flag);
-  if (off) (void)hipFree(off);
-  if (tiles) (void)hipFree(tiles);
-  if (tmp_slots) (void)hipFree(tmp_slots);
-  return rc;
+  return lru_export(h, 0, keys, slots, scores, rows, max_keys, exported, nullptr,
+                    as_stream(stream));
+}
+
+int hctr_lru_export_if(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots,
+                       uint64_t* scores, float* rows, size_t max_keys, size_t* exported,
+                       size_t* matched, hctr_stream_t stream) {
+  HCTR_REQUIRE(h && exported, "null argument");
+  return lru_export(h, min_score, keys, slots, scores, rows, max_keys, exported, matched,
+                    as_stream(stream));
 }
 
 int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream) {
@@ -736,6 +882,11 @@ int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream) {
 int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
   HCTR_REQUIRE(h && out, "null argument");
   return lru_read_counter(h, 1, out, as_stream(stream));
+}
+
+int hctr_lru_filtered_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
+  HCTR_REQUIRE(h && out, "null argument");
+  return lru_read_counter(h, 2, out, as_stream(stream));
 }
 
 int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size) {

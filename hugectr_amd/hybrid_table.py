@@ -4,22 +4,45 @@ table").  No compute here."""
 from __future__ import annotations
 
 import ctypes
+import math
 import sys
-from typing import Tuple
+import time
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 
+FILTERED = -2  # HCTR_LRU_FILTERED as int64: a key the low-frequency filter did not admit
+
+
+def admit_below(p: float) -> int:
+    """the filter's integer threshold ceil(p * 2^32): a key is admitted iff its 32-bit draw is below it
+    (p = 1 admits every key, p = 0 none)"""
+    return int(math.ceil(float(p) * 4294967296.0))
+
+
+def first_call_since(call_ns: Sequence[int], threshold_ns: int) -> Optional[int]:
+    """t0: the number (1, 2, ...) of the first inserting call issued at or after threshold_ns, None
+    when there is none"""
+    for t, ns in enumerate(call_ns, 1):
+        if ns >= threshold_ns:
+            return t
+    return None
+
+
 
 class HybridTable:
     """capacity slots (rounded up to whole buckets of bucket_size), dim fp32 per row.  close()
-    frees the device memory; __del__ only does so as a fallback outside interpreter shutdown."""
+    frees the device memory; __del__ only does so as a fallback outside interpreter shutdown.
+    call_ns[t - 1] is clock() (time.time_ns unless replaced) when inserting call t was issued."""
 
     def __init__(self, capacity: int, dim: int, initializer: str = "", bucket_size: int = 128,
-                 key_dtype=torch.int64, seed: int = 0):
+                 key_dtype=torch.int64, seed: int = 0, clock: Optional[Callable[[], int]] = None):
         self.dim = int(dim)
+        self.clock = clock or time.time_ns
+        self.call_ns: List[int] = []
         self.key_dtype = key_dtype
         self._h = ctypes.c_void_p()
         kt = _lib.KEY_I64 if key_dtype == torch.int64 else _lib.KEY_U32
@@ -45,12 +68,28 @@ class HybridTable:
     def _keys(self, keys: torch.Tensor) -> torch.Tensor:
         return keys.to(self.key_dtype).contiguous()
 
-    def lookup_index(self, keys: torch.Tensor, insert: bool, evict: bool = False):
+    def lookup_index(self, keys: torch.Tensor, insert: bool, evict: bool = False,
+                     admit: Optional[float] = None):
         """row numbers int64[n] (rows >= capacity: per-call scratch with the initializer's value);
-        with evict=True also (evicted keys, evicted rows [m, dim]) -- one host synchronisation"""
+        with evict=True also (evicted keys, evicted rows [m, dim]) -- one host synchronisation.
+        admit=p (insert only): the low-frequency filter; keys it does not admit get FILTERED."""
         keys = self._keys(keys)
         n = keys.numel()
         idx = torch.empty(n, dtype=torch.int64, device=keys.device)
+        if insert:
+            self.call_ns.append(int(self.clock()))
+        if admit is not None and insert:
+            ab = admit_below(admit)
+            if not evict:
+                check(lib.hctr_lru_lookup_index_filtered(self._h, ptr(keys), n, ab, ptr(idx), None,
+                                                         None, None, stream_ptr()))
+                return idx
+            ek = torch.empty(n, dtype=self.key_dtype, device=keys.device)
+            ev = torch.empty((n, self.dim), dtype=torch.float32, device=keys.device)
+            m = ctypes.c_size_t()
+            check(lib.hctr_lru_lookup_index_filtered(self._h, ptr(keys), n, ab, ptr(idx), ptr(ek),
+                                                     ptr(ev), ctypes.byref(m), stream_ptr()))
+            return idx, ek[:m.value], ev[:m.value]
         if not evict:
             check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, ptr(idx),
                                             None, None, None, stream_ptr()))
@@ -61,6 +100,25 @@ class HybridTable:
         check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, ptr(idx),
                                         ptr(ek), ptr(ev), ctypes.byref(m), stream_ptr()))
         return idx, ek[:m.value], ev[:m.value]
+
+    def compact(self, offsets: torch.Tensor, rows: torch.Tensor, keys: torch.Tensor,
+                weights: Optional[torch.Tensor] = None):
+        """(offsets, rows, keys, weights) of a ragged batch without its FILTERED positions, order
+        kept inside every sample -- one host synchronisation"""
+        keys = self._keys(keys)
+        n, B = rows.numel(), offsets.numel() - 1
+        dev = rows.device
+        o_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        o_rows = torch.empty(n, dtype=torch.int64, device=dev)
+        o_keys = torch.empty(n, dtype=self.key_dtype, device=dev)
+        o_w = torch.empty(n, dtype=torch.float32, device=dev) if weights is not None else None
+        w = weights.float().contiguous() if weights is not None else None
+        kept = ctypes.c_size_t()
+        check(lib.hctr_lru_compact(self._h, B, n, ptr(offsets.contiguous()), ptr(rows), ptr(keys),
+                                   ptr(w), ptr(o_off), ptr(o_rows), ptr(o_keys), ptr(o_w),
+                                   ctypes.byref(kept), stream_ptr()))
+        m = kept.value
+        return o_off, o_rows[:m], o_keys[:m], (o_w[:m] if o_w is not None else None)
 
     def find(self, keys: torch.Tensor) -> torch.Tensor:
         """slot of every stored key, INVALID for the others; no side effects"""
@@ -94,6 +152,29 @@ class HybridTable:
         if with_slots:
             return keys[:g], rows[:g], slots[:g], scores[:g]
         return keys[:g], rows[:g]
+
+    def export_if(self, min_score: int):
+        """(keys, rows [n, dim], slots, scores) of the occupied slots with score >= min_score, in
+        slot order (min_score <= 1: every occupied slot)"""
+        got, matched = ctypes.c_size_t(), ctypes.c_size_t()
+        ms = max(int(min_score), 0)
+        check(lib.hctr_lru_export_if(self._h, ms, None, None, None, None, 0, ctypes.byref(got),
+                                     ctypes.byref(matched), stream_ptr()))
+        n = matched.value
+        keys = torch.empty(n, dtype=self.key_dtype, device="cuda")
+        slots = torch.empty(n, dtype=torch.int64, device="cuda")
+        scores = torch.empty(n, dtype=torch.int64, device="cuda")
+        rows = torch.empty((n, self.dim), dtype=torch.float32, device="cuda")
+        if n:
+            check(lib.hctr_lru_export_if(self._h, ms, ptr(keys), ptr(slots), ptr(scores), ptr(rows),
+                                         n, ctypes.byref(got), None, stream_ptr()))
+        g = got.value if n else 0
+        return keys[:g], rows[:g], slots[:g], scores[:g]
+
+    def filtered_count(self) -> int:
+        out = ctypes.c_uint64()
+        check(lib.hctr_lru_filtered_count(self._h, ctypes.byref(out), stream_ptr()))
+        return int(out.value)
 
     def size(self) -> int:
         out = ctypes.c_size_t()

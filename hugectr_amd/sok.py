@@ -22,6 +22,7 @@ lives on its target GPU.
 from __future__ import annotations
 
 import ctypes
+import datetime as _dt
 import os
 from typing import List, Optional, Sequence, Union
 
@@ -32,7 +33,7 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .dynamic_table import DynamicEmbeddingTable, DynamicTableOptimizer, _num_state
-from .hybrid_table import HybridTable
+from .hybrid_table import HybridTable, first_call_since
 
 _RANK, _WORLD = 0, 1
 INVALID = -1  # 0xFFFFFFFFFFFFFFFF as int64: "row not on this GPU / unknown key"
@@ -175,7 +176,8 @@ class DynamicVariable(_VariableBase):
     table, which grows on demand and keeps every key it has seen.
     var_type="hybrid": a table of fixed capacity that evicts its least recently used entries
     (hybrid_table.py, hctr_lru_*).  Keyword options: max_capacity (required; rounded up to whole
-    buckets), max_bucket_size=128, evict_strategy="kLru" (the only strategy).  init_capacity is
+    buckets), max_bucket_size=128, evict_strategy="kLru" (the only strategy), filter_ratio=1.0 (the
+    admission probability of lookup_sparse(..., use_low_frequency_filter=True)).  init_capacity is
     accepted and ignored: the store is allocated once, at max_capacity.  The reference's other
     options (max_hbm_for_vectors, max_load_factor, ...) are kept in config_dict.  The table lives in
     HBM only: evicted pairs go back to the caller (sparse_read_and_evict), not to host memory."""
@@ -189,6 +191,11 @@ class DynamicVariable(_VariableBase):
         if var_type != "hybrid" and kwargs:
             raise TypeError(f"unexpected keyword arguments {sorted(kwargs)} (they belong to "
                             'var_type="hybrid")')
+        ratio = kwargs.get("filter_ratio", 1.0)
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or \
+                not 0.0 <= float(ratio) <= 1.0:
+            raise ValueError(f"filter_ratio must be a float in [0, 1], not {ratio!r}")
+        self.filter_ratio = float(ratio)
         super().__init__(name)
         self.dimension = int(dimension)
         self.key_type = key_type
@@ -224,9 +231,9 @@ class DynamicVariable(_VariableBase):
     def size(self) -> int:
         return self._lru.size() if self._lru is not None else self._det.size()
 
-    def _rows(self, keys: torch.Tensor, train: bool) -> torch.Tensor:
+    def _rows(self, keys: torch.Tensor, train: bool, admit: Optional[float] = None) -> torch.Tensor:
         if self._lru is not None:
-            return self._lru.lookup_index(keys, insert=train)
+            return self._lru.lookup_index(keys, insert=train, admit=admit if train else None)
         idx = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
         check(lib.hctr_det_lookup_index(self._det._h, 0, ptr(keys), keys.numel(), 1 if train else 0,
                                         ptr(idx), stream_ptr()))
@@ -417,8 +424,10 @@ class _LookupFn(torch.autograd.Function):
     """one (variable, ids[, weights]) lookup; the token input routes backward to the variable"""
 
     @staticmethod
-    def forward(ctx, token, var, ids: Ragged, w: Optional[Ragged], combiner: int, train: bool):
+    def forward(ctx, token, var, ids: Ragged, w: Optional[Ragged], combiner: int, train: bool,
+                filt: bool = False):
         D = var.dimension
+        filt = filt and train
         lens, keys = ids.row_lengths, ids.values
         weights = w.values.float().contiguous() if w is not None else None
         b_local = lens.numel()
@@ -437,11 +446,29 @@ class _LookupFn(torch.autograd.Function):
         else:
             lens_own, keys_own, w_own = lens, keys, weights
         ro = _offsets(lens_own)
-        rows = var._rows(keys_own, train)
+        if filt:
+            # keys the low-frequency filter refused leave their samples before pooling
+            rows = var._rows(keys_own, True, admit=var.filter_ratio)
+            ro, rows, keys_own, w_own = var._lru.compact(ro, rows, keys_own, w_own)
+        else:
+            rows = var._rows(keys_own, train)
         table = var._table()
         # the receiver divides for mean (after all shards are added), so shards always sum
         part = _pool(table, ro, rows, w_own, combiner if _WORLD == 1 else 0, D)
-        if _WORLD > 1:
+        den = None
+        if _WORLD > 1 and filt and combiner == 1:
+            # mean over the admitted keys: their count (weight sum) per sample, added over owners
+            # beside the pooled partials
+            nb = ro.numel() - 1
+            if w_own is not None:
+                seg = torch.repeat_interleave(torch.arange(nb, device=ro.device), ro.diff())
+                den_own = torch.zeros(nb, device=ro.device).index_add_(0, seg, w_own)
+            else:
+                den_own = ro.diff().float()
+            both = _reduce_scatter_rows(torch.cat([part, den_own.unsqueeze(1)], 1), b_local)
+            out, den = both[:, :D], both[:, D].contiguous()
+            out = out / den.clamp_min(1e-30).unsqueeze(1) * (den > 0).unsqueeze(1)
+        elif _WORLD > 1:
             out = _reduce_scatter_rows(part, b_local)
             if combiner == 1:
                 if w is not None:
@@ -457,6 +484,7 @@ class _LookupFn(torch.autograd.Function):
         ctx.var, ctx.combiner, ctx.train = var, combiner, train
         ctx.ro, ctx.rows, ctx.keys, ctx.w = ro, rows, keys_own, w_own
         ctx.local = (ids.row_lengths, w.values.float() if w is not None else None, b_local)
+        ctx.den = den
         return out
 
     @staticmethod
@@ -466,7 +494,9 @@ class _LookupFn(torch.autograd.Function):
         if _WORLD > 1:
             lens_l, w_l, b_local = ctx.local
             if combiner == 1:  # mean was divided on the receiver: its gradient scales here
-                if w_l is not None:
+                if ctx.den is not None:
+                    den = ctx.den
+                elif w_l is not None:
                     seg_l = torch.repeat_interleave(torch.arange(b_local, device=g.device), lens_l)
                     den = torch.zeros(b_local, device=g.device).index_add_(0, seg_l, w_l)
                 else:
@@ -477,12 +507,17 @@ class _LookupFn(torch.autograd.Function):
         else:
             comb_local = combiner
         var._pending.append((ctx.ro, ctx.rows, ctx.keys, ctx.w, g, comb_local))
-        return torch.zeros(1, device=g.device), None, None, None, None, None
+        return torch.zeros(1, device=g.device), None, None, None, None, None, None
 
 
-def lookup_sparse(params, sp_ids, sp_weights=None, combiners=None, training: bool = True):
+def lookup_sparse(params, sp_ids, sp_weights=None, combiners=None, training: bool = True,
+                  use_low_frequency_filter: bool = False):
     """sok.lookup_sparse(params, sp_ids, sp_weights=None, combiners=None): fused lookup of several
-    variables; returns one [batch, dimension] tensor per variable (a list iff sp_ids is one)."""
+    variables; returns one [batch, dimension] tensor per variable (a list iff sp_ids is one).
+    use_low_frequency_filter=True (hybrid DynamicVariables only; lookup.py:543,566): in a training
+    lookup a key the table does not hold enters it with probability filter_ratio (a function of
+    (seed, key, call), DESIGN.md "Hybrid table"); a key that does not is left out of its sample's
+    pooling and gets no gradient."""
     is_list = isinstance(sp_ids, (list, tuple)) and not (
         len(sp_ids) == 2 and isinstance(sp_ids[0], torch.Tensor) and not sp_ids[0].is_sparse
         and sp_ids[0].dim() == 1 and isinstance(params, _VariableBase))
@@ -502,6 +537,11 @@ def lookup_sparse(params, sp_ids, sp_weights=None, combiners=None, training: boo
                 isinstance(p, DistributedVariable) and isinstance(params[0], DistributedVariable)):
             raise RuntimeError("Distributed/Localized/Dynamic Variable cannot be used in the same "
                                "lookup currently")  # lookup.py:436-440
+    if use_low_frequency_filter:
+        for p in params:
+            if not isinstance(p, DynamicVariable) or p.backend_type != "hybrid":
+                raise TypeError("use_low_frequency_filter only supports DynamicVariable with "
+                                'var_type="hybrid"')
     outs = []
     for var, ids, w, c in zip(params, sp_ids, sp_weights, combiners):
         if c not in ("sum", "mean"):
@@ -510,7 +550,8 @@ def lookup_sparse(params, sp_ids, sp_weights=None, combiners=None, training: boo
         w = _as_ragged(w) if w is not None else None
         if w is not None and not torch.equal(w.row_lengths, ids.row_lengths):
             raise RuntimeError("sp_id and sp_weight should be have same shape.")
-        outs.append(_LookupFn.apply(var._token, var, ids, w, 1 if c == "mean" else 0, training))
+        outs.append(_LookupFn.apply(var._token, var, ids, w, 1 if c == "mean" else 0, training,
+                                    bool(use_low_frequency_filter)))
     return outs if is_list else outs[0]
 
 
@@ -833,3 +874,49 @@ def load(path: str, load_vars, optimizer: Optional["OptimizerWrapper"] = None):
                     var._states[j][rows] = torch.from_numpy(x).to(dev)
     if _WORLD > 1:
         dist.barrier()
+
+
+def _threshold_ns(threshold) -> int:
+    """a time threshold in nanoseconds since the epoch, converted as dump_load.py does"""
+    return int(_dt.datetime.timestamp(threshold) * 1e9)
+
+
+def incremental_model_dump(sok_vars, time_threshold, sess=None):
+    """sok.incremental_model_dump(sok_vars, time_threshold, sess=None) -> (keys_list, values_list)
+    (dump_load.py:1343-1500): per variable, the keys and rows of the slots touched by an inserting
+    call issued at or after time_threshold (a datetime, or a list of 1 or len(sok_vars) of them).
+    Every rank exports its shard; the results are all-gathered in rank order.  Hybrid
+    DynamicVariables only; sess is accepted for the signature's sake and must be None."""
+    if not isinstance(sok_vars, (list, tuple)):
+        sok_vars = [sok_vars]
+    thresholds = list(time_threshold) if isinstance(time_threshold, (list, tuple)) \
+        else [time_threshold]
+    if not (len(thresholds) == 1 or len(thresholds) == len(sok_vars)):
+        raise Exception("length of time_threshold should be 1 or same length with sok_vars, if "
+                        "length equals 1 , every sok_var will use same time_threshold!")
+    if sess is not None:
+        raise Exception("sess is a TensorFlow 1.15 session: it must be None here")
+    for i, v in enumerate(sok_vars):
+        if not isinstance(v, DynamicVariable):
+            raise Exception("Now only support sok.DynamicVariable with HKV backend, but the "
+                            f"{i}-th sok variable in the input sok_vars is not a "
+                            "sok.DynamicVariable!")
+        if v.backend_type != "hybrid":
+            raise Exception("Now only support sok.DynamicVariable with HKV backend, but the "
+                            f"{i}-th sok variable in the input sok_vars is not hkv backend!")
+    if len(thresholds) == 1:
+        thresholds = thresholds * len(sok_vars)
+    keys_list, values_list = [], []
+    for var, th in zip(sok_vars, thresholds):
+        t0 = first_call_since(var._lru.call_ns, _threshold_ns(th))
+        if t0 is None:
+            k = torch.empty(0, dtype=var.key_type, device="cuda")
+            w = torch.empty((0, var.dimension), dtype=torch.float32, device="cuda")
+        else:
+            k, w, _, _ = var._lru.export_if(t0)
+        if _WORLD > 1:
+            k = _all_gather_cat(k)
+            w = _all_gather_cat(w.reshape(-1)).view(-1, var.dimension)
+        keys_list.append(k.cpu().numpy())
+        values_list.append(w.cpu().numpy())
+    return keys_list, values_list

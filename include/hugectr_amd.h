@@ -844,6 +844,34 @@ int hctr_lru_export(hctr_lru* h, void* keys, uint64_t* slots, uint64_t* scores, 
 int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream);              /* host sync */
 int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream);  /* host sync */
 int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size);
+/* Low-frequency admission filter (SOK lookup_sparse(..., use_low_frequency_filter=True)).  An
+ * inserting call t as hctr_lru_lookup_index(insert=1), except that a key which is not stored is
+ * admitted only iff u(seed, key, t) < admit_below, where
+ *   u = splitmix64(seed ^ splitmix64(key ^ splitmix64(t))) >> 32   (seed: hctr_lru_create's)
+ * and admit_below = ceil(filter_ratio * 2^32) in [0, 2^32] (2^32 admits every key: the plain call).
+ * A key that is not admitted gets row index HCTR_LRU_FILTERED in every position, is not inserted,
+ * touches no score and is not counted as rejected; its positions are counted by
+ * hctr_lru_filtered_count.  Admitted keys go through the insert path (and may still be rejected). */
+#define HCTR_LRU_FILTERED 0xFFFFFFFFFFFFFFFEull
+int hctr_lru_lookup_index_filtered(hctr_lru* h, const void* keys, size_t n, uint64_t admit_below,
+                                   uint64_t* row_index, void* evict_keys, float* evict_rows,
+                                   size_t* n_evicted, hctr_stream_t stream);
+/* positions dropped by the filter so far (host sync) */
+int hctr_lru_filtered_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream);
+/* drop every position whose row is HCTR_LRU_FILTERED from a ragged batch: offsets [batch + 1]
+ * (int64, offsets[batch] = n), rows [n], keys [n] (key_type), weights [n] (may be NULL) -> out_*
+ * (device, sized for n; out_offsets [batch + 1]), order kept inside every sample.  *n_kept (HOST)
+ * = the kept positions -- the call's one host synchronisation.  Uses the handle's workspace. */
+int hctr_lru_compact(hctr_lru* h, size_t batch, size_t n, const long long* offsets,
+                     const uint64_t* rows, const void* keys, const float* weights,
+                     long long* out_offsets, uint64_t* out_rows, void* out_keys,
+                     float* out_weights, size_t* n_kept, hctr_stream_t stream);
+/* hctr_lru_export restricted to slots with score >= min_score (0: every occupied slot), in slot
+ * order.  *matched (HOST, may be NULL) = how many slots qualify; *exported = min(matched, max_keys)
+ * of them are written (host sync). */
+int hctr_lru_export_if(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots,
+                       uint64_t* scores, float* rows, size_t max_keys, size_t* exported,
+                       size_t* matched, hctr_stream_t stream);
 
 #ifdef __cplusplus
 }

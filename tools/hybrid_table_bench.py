@@ -4,6 +4,10 @@ call, D = 16 and 128.
   find       all keys stored (hctr_lru_find: digest line + key per key)
   insert10   inserting lookup, 10 % of the keys missing, every bucket full (90 % hits)
   insert100  inserting lookup, 100 % missing, every bucket full (every key evicts)
+  insert10_filter  insert10 through the low-frequency filter at p = 0.5 (half the missing keys
+             are admitted; hctr_lru_lookup_index_filtered)
+  export_if  hctr_lru_export_if after one call touched about 10 % of the slots: one pass over keys
+             and scores (16 B per slot) plus the matching keys, slots, scores and rows
 
 Algorithmic bytes per key: a hit reads the 128-B digest line, its 8-B key and its D*4-B row (the
 gather that follows the lookup); an inserted key adds the row write and the evicted row read
@@ -74,14 +78,27 @@ def main():
         res["insert10"] = timed(lambda i: t.lookup_index(mixes[i], insert=True), args.iters)
         news = [fresh(N) for _ in range(args.iters + 1)]
         res["insert100"] = timed(lambda i: t.lookup_index(news[i], insert=True), args.iters)
+        stored, _ = t.export()
+        mixes = [torch.cat([hits(N - N // 10), fresh(N // 10)]) for _ in range(args.iters + 1)]
+        res["insert10_filter"] = timed(
+            lambda i: t.lookup_index(mixes[i], insert=True, admit=0.5), args.iters)
+        stored, _ = t.export()
+        t.lookup_index(hits(t.capacity // 10), insert=True)
+        t0 = len(t.call_ns)
+        matched = t.export_if(t0)[0].numel()
+        res["export_if"] = timed(lambda i: t.export_if(t0), args.iters)
         hit_b = 128 + 8 + 4 * D
         ins_b = hit_b + 2 * 4 * D
+        adm = (N // 10) // 2
         by = {"find": N * hit_b, "insert10": (N - N // 10) * hit_b + (N // 10) * ins_b,
-              "insert100": N * ins_b}
+              "insert100": N * ins_b,
+              "insert10_filter": (N - adm) * hit_b + adm * ins_b,
+              "export_if": t.capacity * 16 + matched * (8 + 8 + 8 + 8 + 4 * D)}
         for name, us in res.items():
             print(json.dumps({"case": name, "D": D, "capacity": t.capacity, "batch": N,
                               "us": round(us, 1), "alg_bytes": by[name],
-                              "frac_of_8TBps": round(by[name] / (us * 1e-6) / PEAK, 4)}))
+                              "frac_of_8TBps": round(by[name] / (us * 1e-6) / PEAK, 4),
+                              **({"matched": matched} if name == "export_if" else {})}))
         t.close()
 
 
