@@ -233,6 +233,15 @@ _SIGNATURES = {
     "hctr_lru_compact": (c_int, [_P, c_size_t, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _SZP,
                                  _P]),
     "hctr_lru_export_if": (c_int, [_P, c_uint64, _P, _P, _P, _P, c_size_t, _SZP, _SZP, _P]),
+    "hctr_lru_create_tiered": (c_int, [c_size_t, c_size_t, c_int, c_int, c_char_p, c_uint64,
+                                       c_size_t, POINTER(_P)]),
+    "hctr_lru_placement": (c_int, [_P, _SZP, _SZP, _SZP]),
+    "hctr_lru_host_part": (c_int, [_P, c_int, POINTER(_P)]),
+    "hctr_lru_gather_slots": (c_int, [_P, c_int, _P, c_size_t, _P, _P]),
+    "hctr_lru_scatter_slots": (c_int, [_P, c_int, _P, c_size_t, _P, c_int, _P]),
+    "hctr_lru_apply_update": (c_int, [_P, _P, c_size_t, c_size_t, _P, _P, _P, c_int, c_int,
+                                      c_float, c_float, c_float, c_float, c_float, c_float,
+                                      c_uint64, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -26,6 +26,15 @@
 // others get the kLruFiltered row, touch nothing, and hctr_lru_compact drops them from the batch.
 // hctr_lru_export_if exports the slots whose score is at least a given call number.
 //
+// Host-memory tier (hctr_lru_create_tiered): slots [0, H) keep their rows (and optimizer states) in
+// HBM, slots [H, C) in pinned, device-mapped host memory, H a whole number of buckets.  Only where
+// the bytes live changes.  The rows handed out are still HBM rows: an HBM-resident key gets its
+// slot, every other position p gets the per-call row H + p, into which lru_stage_kernel copies the
+// host slot's row (or the initializer's value).  hctr_lru_apply_update stages the distinct host
+// slots of a step into rows H + u (u = rank in slot order), runs the sparse optimizer there and
+// writes them back.  The insert kernel reaches host slots through its Tier flag; without it the
+// kernel is the untiered one.
+//
 // Compiled as part of det.hip's unit (included at its end): the bounded sibling of the dynamic
 // table, built into every library that carries the dynamic table.  Its internal names carry an
 // lru prefix for that reason.
@@ -89,6 +98,11 @@ struct LruTbl {
   float* rows;        // [C + scratch][D]
   float* st0;         // [C][D] or null
   float* st1;         // [C][D] or null
+  // tiered (Tier kernels only): slots >= H live in the host arrays, row s at (s - H) * D
+  float* hrows;       // [C - H][D] host-mapped
+  float* hst0;        // [C - H][D] or null
+  float* hst1;        // [C - H][D] or null
+  uint64_t H;
   uint64_t nb;        // buckets
   int S, D;
   uint64_t C;
@@ -252,10 +266,19 @@ __device__ __forceinline__ uint64_t lru_wave_min_u64(uint64_t v) {
   return v;
 }
 
+// a slot's row in one of the table's arrays: HBM below H, host memory from H on (Tier only)
+template <bool Tier>
+__device__ __forceinline__ float* lru_slot_row(float* hbm, float* host, uint64_t H, uint64_t s,
+                                               int D) {
+  if (Tier && s >= H) return host + (s - H) * (uint64_t)D;
+  return hbm + s * (uint64_t)D;
+}
+
 // One wave per bucket inserts the bucket's distinct missing keys in ascending key order.  Lane l
 // keeps slots l, l + 64, ... (key, score) in registers; a victim is the wave-wide minimum of
-// (score << 16 | slot) over slots with score < t.
-template <typename K>
+// (score << 16 | slot) over slots with score < t.  Tier: rows and states of slots >= H are in host
+// memory, and a rejected key gets kInvalidIndex (lru_stage_kernel gives it a per-call row).
+template <typename K, bool Tier>
 __global__ void __launch_bounds__(kLruBlock)
     lru_insert_kernel(LruTbl T, const K* __restrict__ in, const uint32_t* __restrict__ perm,
                       const uint32_t* __restrict__ rng, const uint32_t* __restrict__ evict_off,
@@ -323,9 +346,11 @@ __global__ void __launch_bounds__(kLruBlock)
           else
             static_cast<uint32_t*>(ev_keys)[out_e] = (uint32_t)old;
         }
-        if (ev_rows)
+        if (ev_rows) {
+          const float* src = lru_slot_row<Tier>(T.rows, T.hrows, T.H, s, D);
           for (int e = lane; e < D; e += kWave)
-            ev_rows[(uint64_t)out_e * D + e] = T.rows[s * D + e];  // read before the overwrite
+            ev_rows[(uint64_t)out_e * D + e] = src[e];  // read before the overwrite
+        }
       }
       if (evict) out_e++;
       if (lane == owner) {
@@ -339,10 +364,21 @@ __global__ void __launch_bounds__(kLruBlock)
         T.scores[s] = t;
         T.digests[s] = (uint8_t)(murmur3_key(kk) >> 24);
       }
-      for (int e = lane; e < D; e += kWave) {
-        T.rows[s * D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
-        if (T.st0) T.st0[s * D + e] = 0.0f;
-        if (T.st1) T.st1[s * D + e] = 0.0f;
+      if (Tier) {
+        float* row = lru_slot_row<true>(T.rows, T.hrows, T.H, s, D);
+        float* s0 = T.st0 ? lru_slot_row<true>(T.st0, T.hst0, T.H, s, D) : nullptr;
+        float* s1 = T.st1 ? lru_slot_row<true>(T.st1, T.hst1, T.H, s, D) : nullptr;
+        for (int e = lane; e < D; e += kWave) {
+          row[e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+          if (s0) s0[e] = 0.0f;
+          if (s1) s1[e] = 0.0f;
+        }
+      } else {
+        for (int e = lane; e < D; e += kWave) {
+          T.rows[s * D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+          if (T.st0) T.st0[s * D + e] = 0.0f;
+          if (T.st1) T.st1[s * D + e] = 0.0f;
+        }
       }
       if (!evict) filled++;
       res = s;
@@ -353,7 +389,7 @@ __global__ void __launch_bounds__(kLruBlock)
     for (uint32_t p = j; p < r; p++) {
       const uint32_t pos = perm[p];
       uint64_t row = res;
-      if (res == kInvalidIndex) {
+      if (!Tier && res == kInvalidIndex) {
         row = T.C + (T.init_mode == 0 ? 0 : pos);
         if (T.init_mode != 0)
           for (int e = lane; e < D; e += kWave)
@@ -452,6 +488,119 @@ __global__ void __launch_bounds__(kLruBlock)
   if (w) out_w[o] = w[i];
 }
 
+// ---- host-memory tier ----------------------------------------------------------------------------
+// The row kernels below give each position (key, slot, staged row) a group of gl lanes, gl = the
+// power of two >= D capped at a wave, so rows of D = 16 fill a wave with four of them.  They read
+// the positions' slots from one array and write the rows handed out to another.
+inline int lru_group_lanes(int D) {
+  int g = 1;
+  while (g < D && g < kWave) g <<= 1;
+  return g;
+}
+
+// after a lookup on a tiered table: slot[p] holds a slot, kInvalidIndex (a miss, a rejected key) or
+// kLruFiltered.  A position whose slot is an HBM slot keeps it; every other one (but a filtered
+// one) gets the per-call row H + p, holding the host slot's row or the initializer's value.
+template <typename K>
+__global__ void __launch_bounds__(kLruBlock)
+    lru_stage_kernel(LruTbl T, const K* __restrict__ in, size_t n, int gl,
+                     const uint64_t* __restrict__ slot, uint64_t* __restrict__ idx) {
+  const size_t p = (blockIdx.x * (size_t)kLruBlock + threadIdx.x) / (size_t)gl;
+  const int l = (int)(threadIdx.x % (unsigned)gl);
+  if (p >= n) return;
+  const uint64_t s = slot[p];
+  if (s < T.H || s == kLruFiltered) {
+    if (l == 0) idx[p] = s;
+    return;
+  }
+  const uint64_t r = T.H + p;
+  float* dst = T.rows + r * (uint64_t)T.D;
+  if (s < T.C) {
+    const float* src = T.hrows + (s - T.H) * (uint64_t)T.D;
+    for (int e = l; e < T.D; e += gl) dst[e] = src[e];
+  } else {
+    const uint64_t key = lru_key_u64<K>(in[p]);
+    for (int e = l; e < T.D; e += gl)
+      dst[e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+  }
+  if (l == 0) idx[p] = r;
+}
+
+// optimizer step on a tiered table, 1/3: sort key = the host slot's number above H (all ones for
+// HBM slots and invalid ones: they sort last), value = position; rows[] starts as the slots
+__global__ void __launch_bounds__(kLruBlock)
+    lru_step_keys_kernel(const uint64_t* __restrict__ slots, size_t n, uint64_t H, uint64_t C,
+                         uint32_t* __restrict__ key, uint32_t* __restrict__ val,
+                         uint64_t* __restrict__ rows) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t s = slots[i];
+  key[i] = (s >= H && s < C) ? (uint32_t)(s - H) : 0xFFFFFFFFu;
+  val[i] = (uint32_t)i;
+  rows[i] = s;
+}
+
+// 2/3: first[j] = sorted position j starts a run of one host slot
+__global__ void __launch_bounds__(kLruBlock)
+    lru_step_first_kernel(const uint32_t* __restrict__ key, size_t n, uint32_t host_slots,
+                          uint32_t* __restrict__ first) {
+  const size_t j = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (j < n) first[j] = (key[j] < host_slots && (j == 0 || key[j] != key[j - 1])) ? 1u : 0u;
+}
+
+// 3/3, both directions.  u = the run's rank (off = exclusive scan of first).  in: every position of
+// a host slot gets row H + u, the run's first copies the slot's row and states into that row.
+// out (after the update): the run's first copies them back.
+template <bool In>
+__global__ void __launch_bounds__(kLruBlock)
+    lru_step_stage_kernel(LruTbl T, const uint32_t* __restrict__ key,
+                          const uint32_t* __restrict__ val, const uint32_t* __restrict__ first,
+                          const uint32_t* __restrict__ off, size_t n, int gl,
+                          uint64_t* __restrict__ rows) {
+  const size_t j = (blockIdx.x * (size_t)kLruBlock + threadIdx.x) / (size_t)gl;
+  const int l = (int)(threadIdx.x % (unsigned)gl);
+  if (j >= n) return;
+  const uint32_t k = key[j];
+  if ((uint64_t)k >= T.C - T.H) return;
+  const bool f = first[j] != 0u;
+  const uint64_t r = T.H + (uint64_t)(f ? off[j] : off[j] - 1u);
+  if (In && l == 0) rows[val[j]] = r;
+  if (!f) return;
+  const uint64_t D = (uint64_t)T.D;
+  float* hbm[3] = {T.rows + r * D, T.st0 ? T.st0 + r * D : nullptr,
+                   T.st1 ? T.st1 + r * D : nullptr};
+  float* host[3] = {T.hrows + k * D, T.hst0 ? T.hst0 + k * D : nullptr,
+                    T.hst1 ? T.hst1 + k * D : nullptr};
+  for (int a = 0; a < 3; a++) {
+    if (!hbm[a]) continue;
+    for (int e = l; e < T.D; e += gl) {
+      if (In)
+        hbm[a][e] = host[a][e];
+      else
+        host[a][e] = hbm[a][e];
+    }
+  }
+}
+
+// slot-addressed I/O on one array (rows or a state), either table: a slot below H is in hbm, the
+// others in host; a slot >= C is skipped.  dir 0: out = array[slot]; 1: array[slot] = v; 2: +=.
+__global__ void __launch_bounds__(kLruBlock)
+    lru_slot_io_kernel(float* hbm, float* host, uint64_t H, uint64_t C,
+                       const uint64_t* __restrict__ slots, size_t n, int D, int dir,
+                       float* __restrict__ buf) {
+  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
+  if (i >= n * (size_t)D) return;
+  const uint64_t s = slots[i / D];
+  if (s >= C) return;
+  float* p = (s < H ? hbm + s * (uint64_t)D : host + (s - H) * (uint64_t)D) + i % D;
+  if (dir == 0)
+    buf[i] = *p;
+  else if (dir == 1)
+    *p = buf[i];
+  else
+    *p = *p + buf[i];
+}
+
 inline int lru_blocks(size_t n) { return (int)ceil_div<size_t>(n > 0 ? n : 1, (size_t)kLruBlock); }
 
 }  // namespace
@@ -471,6 +620,13 @@ struct hctr_lru {
   float* rows = nullptr;
   size_t scratch = 0;  // rows after the C slots
   float* st[2] = {nullptr, nullptr};
+  // host-memory tier: slots [H, C) keep rows and states in pinned, device-mapped host memory; the
+  // HBM arrays then hold H slots plus `scratch` per-call rows.  H = C: untiered.
+  size_t H = 0;
+  float* hrows = nullptr;                 // [C - H][D] (device address of the mapping)
+  float* hst[2] = {nullptr, nullptr};     // [C - H][D] each, with the state it belongs to
+  void* host_alloc[3] = {nullptr, nullptr, nullptr};  // the pinned allocations behind them
+  uint64_t* ws_rows = nullptr;            // [ws_n] staged rows of a step (tiered)
   uint64_t t = 0;  // inserting calls so far
   unsigned long long* counters = nullptr;  // [0] occupied slots, [1] rejected keys, [2] filtered
   unsigned long long* h_word = nullptr;    // pinned host word
@@ -495,6 +651,10 @@ struct hctr_lru {
     T.rows = rows;
     T.st0 = st[0];
     T.st1 = st[1];
+    T.hrows = hrows;
+    T.hst0 = hst[0];
+    T.hst1 = hst[1];
+    T.H = H;
     T.nb = nb;
     T.S = (int)S;
     T.D = D;
@@ -504,6 +664,7 @@ struct hctr_lru {
     T.seed = seed;
     return T;
   }
+  bool tiered() const { return H < C; }
 };
 
 namespace {
@@ -514,6 +675,9 @@ void lru_free(hctr_lru* h) {
                 h->sort_temp, h->rng, h->evict_cnt, h->evict_off, h->tile_sums, h->d_total};
   for (void* p : ps)
     if (p) (void)hipFree(p);
+  if (h->ws_rows) (void)hipFree(h->ws_rows);
+  for (void* p : h->host_alloc)
+    if (p) (void)hipHostFree(p);
   if (h->h_word) (void)hipHostFree(h->h_word);
   delete h;
 }
@@ -533,9 +697,29 @@ int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
     HCTR_HIP(hipMalloc(&h->ws_tiles, (cap / 1024 + 2) * sizeof(unsigned long long)));
     h->sort_temp_bytes = radix_sort_temp_bytes(cap);
     HCTR_HIP(hipMalloc(&h->sort_temp, h->sort_temp_bytes));
+    if (h->tiered()) {
+      if (h->ws_rows) HCTR_HIP(hipFree(h->ws_rows));
+      h->ws_rows = nullptr;
+      HCTR_HIP(hipMalloc(&h->ws_rows, cap * sizeof(uint64_t)));
+    }
     h->ws_n = cap;
   }
-  if (h->init_mode != 0 && n > h->scratch) {
+  if (h->tiered() && n > h->scratch) {
+    // every position may need a per-call row: the HBM arrays grow to H + n rows, the H slots move
+    float** arrs[3] = {&h->rows, &h->st[0], &h->st[1]};
+    for (float** a : arrs) {
+      if (!*a) continue;
+      float* nr = nullptr;
+      HCTR_HIP(hipMalloc(&nr, (h->H + n) * (size_t)h->D * sizeof(float)));
+      if (h->H)
+        HCTR_HIP(hipMemcpyAsync(nr, *a, h->H * (size_t)h->D * sizeof(float),
+                                hipMemcpyDeviceToDevice, s));
+      HCTR_HIP(hipStreamSynchronize(s));
+      HCTR_HIP(hipFree(*a));
+      *a = nr;
+    }
+    h->scratch = n;
+  } else if (h->init_mode != 0 && n > h->scratch) {
     // the slots' rows move to a larger store once per new largest call (scratch is per call)
     float* nr = nullptr;
     HCTR_HIP(hipMalloc(&nr, (h->C + n) * (size_t)h->D * sizeof(float)));
@@ -554,6 +738,21 @@ int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t admit_
                uint64_t* row_index, void* ev_keys, float* ev_rows, size_t* n_evicted,
                hipStream_t s) {
   HCTR_TRY(lru_reserve(h, n, s));
+  const int gl = lru_group_lanes(h->D);
+  const int stage_blocks = lru_blocks(n * (size_t)gl);
+  // tiered: the find / insert kernels write slots to ws_rows, lru_stage_kernel the rows
+  uint64_t* const slot_out = h->tiered() ? h->ws_rows : row_index;
+  if (!insert && h->tiered()) {
+    hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
+                       h->tbl(), keys, n, (int)kLruFind, h->t, slot_out, nullptr, nullptr, nullptr,
+                       nullptr, kLruAdmitAll, nullptr);
+    HCTR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lru_stage_kernel<K>, dim3(stage_blocks), dim3(kLruBlock), 0, s, h->tbl(),
+                       keys, n, gl, slot_out, row_index);
+    HCTR_LAUNCH_CHECK();
+    if (n_evicted) *n_evicted = 0;
+    return HCTR_OK;
+  }
   if (!insert) {
     hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
                        h->tbl(), keys, n, (int)kLruRead, h->t, row_index, nullptr, nullptr, nullptr,
@@ -569,11 +768,11 @@ int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t admit_
   const bool wide = sizeof(K) == 8;
   if (admit_below < kLruAdmitAll)
     hipLaunchKernelGGL((lru_find_kernel<K, true>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), keys, n, (int)kLruInsert, t, row_index, bkt, klo,
+                       h->tbl(), keys, n, (int)kLruInsert, t, slot_out, bkt, klo,
                        wide ? khi : nullptr, seq, admit_below, h->counters);
   else
     hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), keys, n, (int)kLruInsert, t, row_index, bkt, klo,
+                       h->tbl(), keys, n, (int)kLruInsert, t, slot_out, bkt, klo,
                        wide ? khi : nullptr, seq, kLruAdmitAll, nullptr);
   HCTR_LAUNCH_CHECK();
   // (bucket, key) order by three stable passes: key low word, key high word, bucket
@@ -597,9 +796,18 @@ int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t admit_
   HCTR_LAUNCH_CHECK();
   HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(h->evict_cnt, h->nb, h->tile_sums, h->d_total,
                                                h->evict_off, s));
-  hipLaunchKernelGGL(lru_insert_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->tbl(), keys, pb,
-                     h->rng,
-                     h->evict_off, t, row_index, ev_keys, (int)sizeof(K), ev_rows, h->counters);
+  if (h->tiered()) {
+    hipLaunchKernelGGL((lru_insert_kernel<K, true>), dim3(wb), dim3(kLruBlock), 0, s, h->tbl(),
+                       keys, pb, h->rng, h->evict_off, t, slot_out, ev_keys, (int)sizeof(K),
+                       ev_rows, h->counters);
+    HCTR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lru_stage_kernel<K>, dim3(stage_blocks), dim3(kLruBlock), 0, s, h->tbl(),
+                       keys, n, gl, slot_out, row_index);
+  } else {
+    hipLaunchKernelGGL((lru_insert_kernel<K, false>), dim3(wb), dim3(kLruBlock), 0, s, h->tbl(),
+                       keys, pb, h->rng,
+                       h->evict_off, t, row_index, ev_keys, (int)sizeof(K), ev_rows, h->counters);
+  }
   HCTR_LAUNCH_CHECK();
   if (n_evicted) {
     HCTR_HIP(hipMemcpyAsync(h->h_word, h->d_total, sizeof(unsigned long long),
@@ -652,7 +860,11 @@ int lru_export(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots, uin
     }
     if (rc == HCTR_OK) {
       const size_t got = (size_t)*h->h_word < max_keys ? (size_t)*h->h_word : max_keys;
-      if (rows && got)
+      if (rows && got && h->tiered())
+        hipLaunchKernelGGL(lru_slot_io_kernel, dim3(lru_blocks(got * (size_t)h->D)),
+                           dim3(kLruBlock), 0, s, h->rows, h->hrows, (uint64_t)h->H,
+                           (uint64_t)h->C, sl, got, h->D, 0, rows);
+      else if (rows && got)
         hipLaunchKernelGGL(lru_gather_rows_kernel, dim3(lru_blocks(got * (size_t)h->D)),
                            dim3(kLruBlock), 0, s, sl, got, h->rows, h->D, rows);
       if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
@@ -670,12 +882,43 @@ int lru_export(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots, uin
   return rc;
 }
 
+// pinned, device-mapped host memory (as hctr_tiered_create's), zeroed; *dev = its device address
+bool lru_host_alloc(hctr_lru* h, int which, size_t bytes, float** dev) {
+  void* p = nullptr;
+  if (hipHostMalloc(&p, bytes ? bytes : 4, hipHostMallocMapped | hipHostMallocPortable) !=
+      hipSuccess)
+    return false;
+  h->host_alloc[which] = p;
+  memset(p, 0, bytes);
+  return hipHostGetDevicePointer((void**)dev, p, 0) == hipSuccess;
+}
+
+// an array's (HBM part, host part): 0 = rows, 1 + i = state i (null while not allocated)
+bool lru_array(hctr_lru* h, int array, float** hbm, float** host) {
+  if (array == 0) {
+    *hbm = h->rows;
+    *host = h->hrows;
+    return true;
+  }
+  if (array < 1 || array > 2 || !h->st[array - 1]) return false;
+  *hbm = h->st[array - 1];
+  *host = h->hst[array - 1];
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
 
 int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
                     const char* initializer, uint64_t seed, hctr_lru** out) {
+  return hctr_lru_create_tiered(capacity, bucket_size, dim, key_type, initializer, seed,
+                                ~(size_t)0, out);
+}
+
+int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key_type,
+                           const char* initializer, uint64_t seed, size_t hbm_slots,
+                           hctr_lru** out) {
   HCTR_REQUIRE(out, "out is null");
   HCTR_REQUIRE(bucket_size > 0 && bucket_size % kWave == 0 &&
                    bucket_size <= (size_t)kWave * kLruMaxSlotsPerLane,
@@ -685,8 +928,11 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
   HCTR_REQUIRE(key_type == HCTR_KEY_U32 || key_type == HCTR_KEY_I64, "key_type");
   const size_t C = ceil_div(capacity, bucket_size) * bucket_size;
   HCTR_REQUIRE(C < 0xFFFFFFFFull, "capacity must stay below 2^32 slots");
+  HCTR_REQUIRE(hbm_slots >= C || hbm_slots % bucket_size == 0,
+               "hbm_slots must be a multiple of bucket_size");
   hctr_lru* h = new hctr_lru();
   h->C = C;
+  h->H = hbm_slots < C ? hbm_slots : C;
   h->S = bucket_size;
   h->nb = C / bucket_size;
   h->D = dim;
@@ -711,7 +957,7 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
   bool ok = hipMalloc(&h->keys, C * 8) == hipSuccess &&
             hipMalloc(&h->scores, C * 8) == hipSuccess &&
             hipMalloc(&h->digests, C) == hipSuccess &&
-            hipMalloc(&h->rows, (C + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
+            hipMalloc(&h->rows, (h->H + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
             hipMalloc(&h->counters, 3 * sizeof(unsigned long long)) == hipSuccess &&
             hipMalloc(&h->rng, 2 * h->nb * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&h->evict_cnt, h->nb * sizeof(uint32_t)) == hipSuccess &&
@@ -719,9 +965,11 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
             hipMalloc(&h->tile_sums, (h->nb / 1024 + 2) * 8) == hipSuccess &&
             hipMalloc(&h->d_total, sizeof(unsigned long long)) == hipSuccess &&
             hipHostMalloc(&h->h_word, sizeof(unsigned long long)) == hipSuccess;
+  if (ok && h->tiered())
+    ok = lru_host_alloc(h, 0, (C - h->H) * (size_t)dim * sizeof(float), &h->hrows);
   if (ok)
     ok = hipMemset(h->digests, 0, C) == hipSuccess &&
-         hipMemset(h->rows, 0, (C + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
+         hipMemset(h->rows, 0, (h->H + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
          hipMemset(h->counters, 0, 3 * sizeof(unsigned long long)) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -731,7 +979,7 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
   }
   hipLaunchKernelGGL(lru_clear_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, 0, h->keys,
                      h->scores, C);
-  if (h->init_mode == 0)
+  if (h->init_mode == 0 && !h->tiered())
     hipLaunchKernelGGL(lru_fill_kernel, dim3(lru_blocks((size_t)dim)), dim3(kLruBlock), 0, 0,
                        h->rows + C * (size_t)dim, (size_t)dim, h->init_val);
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
@@ -840,14 +1088,24 @@ int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
 int hctr_lru_rows(hctr_lru* h, float** rows, size_t* capacity) {
   HCTR_REQUIRE(h && rows && capacity, "null argument");
   *rows = h->rows;
-  *capacity = h->C;
+  *capacity = h->H;  // = C on an untiered table
   return HCTR_OK;
 }
 
 int hctr_lru_state(hctr_lru* h, int i, float** state, hctr_stream_t stream) {
   HCTR_REQUIRE(h && state, "null argument");
   HCTR_REQUIRE(i == 0 || i == 1, "state index must be 0 or 1");
-  if (!h->st[i]) {
+  if (!h->st[i] && h->tiered()) {
+    // the HBM part has the rows' shape (H slots + the per-call rows); the rest is host memory
+    const size_t bytes = (h->H + h->scratch) * (size_t)h->D * sizeof(float);
+    HCTR_HIP(hipMalloc(&h->st[i], bytes));
+    HCTR_HIP(hipMemsetAsync(h->st[i], 0, bytes, as_stream(stream)));
+    if (!lru_host_alloc(h, 1 + i, (h->C - h->H) * (size_t)h->D * sizeof(float), &h->hst[i])) {
+      (void)hipGetLastError();
+      set_error("hctr_lru_state: host allocation failed");
+      return HCTR_ERR_HIP;
+    }
+  } else if (!h->st[i]) {
     const size_t bytes = h->C * (size_t)h->D * sizeof(float);
     HCTR_HIP(hipMalloc(&h->st[i], bytes));
     HCTR_HIP(hipMemsetAsync(h->st[i], 0, bytes, as_stream(stream)));
@@ -887,6 +1145,93 @@ int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
 int hctr_lru_filtered_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
   HCTR_REQUIRE(h && out, "null argument");
   return lru_read_counter(h, 2, out, as_stream(stream));
+}
+
+int hctr_lru_placement(const hctr_lru* h, size_t* hbm_slots, size_t* hbm_rows, size_t* host_rows) {
+  HCTR_REQUIRE(h && hbm_slots && hbm_rows && host_rows, "null argument");
+  *hbm_slots = h->H;
+  *hbm_rows = h->H + h->scratch;
+  *host_rows = h->C - h->H;
+  return HCTR_OK;
+}
+
+int hctr_lru_host_part(const hctr_lru* h, int array, float** host) {
+  HCTR_REQUIRE(h && host, "null argument");
+  HCTR_REQUIRE(array >= 0 && array <= 2, "array must be 0 (rows), 1 or 2 (states)");
+  *host = array == 0 ? h->hrows : h->hst[array - 1];
+  return HCTR_OK;
+}
+
+static int lru_slot_io(hctr_lru* h, int array, const uint64_t* slots, size_t n, int dir,
+                       float* buf, hctr_stream_t stream) {
+  HCTR_REQUIRE(h, "null handle");
+  HCTR_REQUIRE(n == 0 || (slots && buf), "slots / values are null");
+  float *hbm = nullptr, *host = nullptr;
+  HCTR_REQUIRE(lru_array(h, array, &hbm, &host),
+               "array must be 0 (rows) or 1 + i for an allocated state i");
+  if (n == 0) return HCTR_OK;
+  hipLaunchKernelGGL(lru_slot_io_kernel, dim3(lru_blocks(n * (size_t)h->D)), dim3(kLruBlock), 0,
+                     as_stream(stream), hbm, host, (uint64_t)h->H, (uint64_t)h->C, slots, n, h->D,
+                     dir, buf);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_lru_gather_slots(hctr_lru* h, int array, const uint64_t* slots, size_t n, float* out,
+                          hctr_stream_t stream) {
+  return lru_slot_io(h, array, slots, n, 0, out, stream);
+}
+
+int hctr_lru_scatter_slots(hctr_lru* h, int array, const uint64_t* slots, size_t n,
+                           const float* values, int add, hctr_stream_t stream) {
+  return lru_slot_io(h, array, slots, n, add ? 2 : 1, const_cast<float*>(values), stream);
+}
+
+int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t nnz,
+                          const int64_t* bucket_range, const uint64_t* slots, const void* grad,
+                          int grad_dtype, int optimizer, float lr, float beta1, float beta2,
+                          float epsilon, float momentum_factor, float scaler, uint64_t times,
+                          hctr_stream_t stream) {
+  HCTR_REQUIRE(h && u, "null handle");
+  HCTR_REQUIRE(nnz <= ((size_t)1 << 24), "at most 2^24 keys per call");
+  HCTR_REQUIRE(nnz == 0 || slots, "slots are null");
+  const int ns = optimizer == HCTR_OPT_ADAM ? 2 : (optimizer == HCTR_OPT_SGD ? 0 : 1);
+  HCTR_REQUIRE((ns < 1 || h->st[0]) && (ns < 2 || h->st[1]),
+               "the optimizer's states are not allocated (hctr_lru_state)");
+  if (!h->tiered() || nnz == 0)
+    return hctr_updater_update(u, buckets, nnz, bucket_range, slots, grad, grad_dtype, optimizer,
+                               HCTR_UPDATE_LOCAL, lr, beta1, beta2, epsilon, momentum_factor,
+                               scaler, times, h->rows, h->st[0], h->st[1], stream);
+  const hipStream_t s = as_stream(stream);
+  HCTR_TRY(lru_reserve(h, nnz + 1, s));
+  const size_t m = h->ws_n;
+  uint32_t *ka = h->ws, *kb = h->ws + m, *va = h->ws + 2 * m, *vb = h->ws + 3 * m,
+           *first = h->ws + 4 * m, *off = h->ws + 5 * m;
+  const uint64_t host_slots = h->C - h->H;
+  hipLaunchKernelGGL(lru_step_keys_kernel, dim3(lru_blocks(nnz)), dim3(kLruBlock), 0, s, slots,
+                     nnz, (uint64_t)h->H, (uint64_t)h->C, ka, va, h->ws_rows);
+  HCTR_LAUNCH_CHECK();
+  // host slots in ascending order (stable: positions of one slot keep their order)
+  int end_bit = 1;
+  while (end_bit < 32 && ((uint64_t)1 << end_bit) <= host_slots) end_bit++;
+  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, ka, kb, va, vb, nnz, end_bit, s));
+  hipLaunchKernelGGL(lru_step_first_kernel, dim3(lru_blocks(nnz)), dim3(kLruBlock), 0, s, kb, nnz,
+                     (uint32_t)host_slots, first);
+  HCTR_LAUNCH_CHECK();
+  HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(first, nnz, h->ws_tiles, h->d_total, off, s));
+  const int gl = lru_group_lanes(h->D);
+  const int blocks = lru_blocks(nnz * (size_t)gl);
+  hipLaunchKernelGGL(lru_step_stage_kernel<true>, dim3(blocks), dim3(kLruBlock), 0, s, h->tbl(), kb,
+                     vb, first, off, nnz, gl, h->ws_rows);
+  HCTR_LAUNCH_CHECK();
+  HCTR_TRY(hctr_updater_update(u, buckets, nnz, bucket_range, h->ws_rows, grad, grad_dtype,
+                               optimizer, HCTR_UPDATE_LOCAL, lr, beta1, beta2, epsilon,
+                               momentum_factor, scaler, times, h->rows, h->st[0], h->st[1],
+                               stream));
+  hipLaunchKernelGGL(lru_step_stage_kernel<false>, dim3(blocks), dim3(kLruBlock), 0, s, h->tbl(),
+                     kb, vb, first, off, nnz, gl, h->ws_rows);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
 }
 
 int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size) {

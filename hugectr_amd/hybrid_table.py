@@ -32,25 +32,63 @@ def first_call_since(call_ns: Sequence[int], threshold_ns: int) -> Optional[int]
     return None
 
 
+def check_hbm_budget(max_hbm_for_vectors) -> float:
+    """max_hbm_for_vectors (GiB of value rows in HBM) as a float: a non-negative int or float;
+    bool, NaN, negative or non-numeric values raise ValueError"""
+    g = max_hbm_for_vectors
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or math.isnan(g) or g < 0:
+        raise ValueError(f"max_hbm_for_vectors must be a non-negative number of GiB, not {g!r}")
+    return float(g)
+
+
+def hbm_slots_for(max_hbm_for_vectors, dim: int, capacity: int, bucket_size: int) -> int:
+    """H = min(C, floor(G * 2^30 / (dim * 4) / S) * S): the slots whose rows fit in G GiB of HBM,
+    in whole buckets (C = capacity rounded up to whole buckets of S = bucket_size)"""
+    g = check_hbm_budget(max_hbm_for_vectors)
+    S = int(bucket_size)
+    C = -(-int(capacity) // S) * S
+    if math.isinf(g):
+        return C
+    return min(C, math.floor(g * 2**30 / (int(dim) * 4) / S) * S)
+
 
 class HybridTable:
     """capacity slots (rounded up to whole buckets of bucket_size), dim fp32 per row.  close()
     frees the device memory; __del__ only does so as a fallback outside interpreter shutdown.
-    call_ns[t - 1] is clock() (time.time_ns unless replaced) when inserting call t was issued."""
+    call_ns[t - 1] is clock() (time.time_ns unless replaced) when inserting call t was issued.
+    hbm_slots=H < capacity (a multiple of bucket_size): slots >= H keep their rows and optimizer
+    states in host memory (hctr_lru_create_tiered); None or H >= capacity: all in HBM."""
 
     def __init__(self, capacity: int, dim: int, initializer: str = "", bucket_size: int = 128,
-                 key_dtype=torch.int64, seed: int = 0, clock: Optional[Callable[[], int]] = None):
+                 key_dtype=torch.int64, seed: int = 0, clock: Optional[Callable[[], int]] = None,
+                 hbm_slots: Optional[int] = None):
         self.dim = int(dim)
         self.clock = clock or time.time_ns
         self.call_ns: List[int] = []
         self.key_dtype = key_dtype
         self._h = ctypes.c_void_p()
         kt = _lib.KEY_I64 if key_dtype == torch.int64 else _lib.KEY_U32
-        check(lib.hctr_lru_create(int(capacity), int(bucket_size), self.dim, kt,
-                                  str(initializer).encode(), int(seed), ctypes.byref(self._h)))
+        if hbm_slots is None:
+            check(lib.hctr_lru_create(int(capacity), int(bucket_size), self.dim, kt,
+                                      str(initializer).encode(), int(seed), ctypes.byref(self._h)))
+        else:
+            check(lib.hctr_lru_create_tiered(int(capacity), int(bucket_size), self.dim, kt,
+                                             str(initializer).encode(), int(seed), int(hbm_slots),
+                                             ctypes.byref(self._h)))
         c, s = ctypes.c_size_t(), ctypes.c_size_t()
         check(lib.hctr_lru_capacity(self._h, ctypes.byref(c), ctypes.byref(s)))
         self.capacity, self.bucket_size = int(c.value), int(s.value)
+        self.hbm_slots = self.placement()[0]
+
+    @property
+    def tiered(self) -> bool:
+        return self.hbm_slots < self.capacity
+
+    def placement(self) -> Tuple[int, int, int]:
+        """(hbm_slots, rows of the HBM row store (slots + per-call rows), host rows)"""
+        a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib.hctr_lru_placement(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -70,7 +108,8 @@ class HybridTable:
 
     def lookup_index(self, keys: torch.Tensor, insert: bool, evict: bool = False,
                      admit: Optional[float] = None):
-        """row numbers int64[n] (rows >= capacity: per-call scratch with the initializer's value);
+        """row numbers int64[n] (rows >= hbm_slots: per-call rows holding the initializer's value
+        or, on a tiered table, a host-resident key's row);
         with evict=True also (evicted keys, evicted rows [m, dim]) -- one host synchronisation.
         admit=p (insert only): the low-frequency filter; keys it does not admit get FILTERED."""
         keys = self._keys(keys)
@@ -136,6 +175,38 @@ class HybridTable:
         p = ctypes.c_void_p()
         check(lib.hctr_lru_state(self._h, int(i), ctypes.byref(p), stream_ptr()))
         return p.value
+
+    def host_part_ptr(self, array: int = 0) -> int:
+        """device address of the host part of rows (0) or state array - 1; 0 when there is none"""
+        p = ctypes.c_void_p()
+        check(lib.hctr_lru_host_part(self._h, int(array), ctypes.byref(p)))
+        return p.value or 0
+
+    def gather_slots(self, array: int, slots: torch.Tensor) -> torch.Tensor:
+        """[n, dim] rows (array 0) or state array - 1 of the slots, either tier; a row whose slot
+        is not valid (>= capacity) is zero"""
+        slots = slots.to(torch.int64).contiguous()
+        out = torch.zeros((slots.numel(), self.dim), dtype=torch.float32, device=slots.device)
+        check(lib.hctr_lru_gather_slots(self._h, int(array), ptr(slots), slots.numel(), ptr(out),
+                                        stream_ptr()))
+        return out
+
+    def scatter_slots(self, array: int, slots: torch.Tensor, values: torch.Tensor,
+                      add: bool = False):
+        """array[slot] = values (or += with add); distinct slots, invalid ones skipped"""
+        slots = slots.to(torch.int64).contiguous()
+        v = values.reshape(-1, self.dim).float().contiguous()
+        check(lib.hctr_lru_scatter_slots(self._h, int(array), ptr(slots), slots.numel(), ptr(v),
+                                         1 if add else 0, stream_ptr()))
+
+    def apply_update(self, updater, ro: torch.Tensor, slots: torch.Tensor, grads: torch.Tensor,
+                     optimizer: int, hp: dict, times: int):
+        """one sparse optimizer step on the slots' rows and states (hctr_lru_apply_update; the
+        states the optimizer needs must have been allocated through state_ptr)"""
+        check(lib.hctr_lru_apply_update(
+            self._h, updater, ro.numel() - 1, slots.numel(), ptr(ro), ptr(slots),
+            ptr(grads.contiguous()), _lib.F32, optimizer, hp["lr"], hp["beta1"], hp["beta2"],
+            hp["epsilon"], hp["momentum"], hp["scaler"], int(times), stream_ptr()))
 
     def export(self, with_slots: bool = False):
         """(keys, rows [n, dim]) of the occupied slots in slot order; with_slots=True adds their

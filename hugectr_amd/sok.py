@@ -33,7 +33,7 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .dynamic_table import DynamicEmbeddingTable, DynamicTableOptimizer, _num_state
-from .hybrid_table import HybridTable, first_call_since
+from .hybrid_table import HybridTable, check_hbm_budget, first_call_since, hbm_slots_for
 
 _RANK, _WORLD = 0, 1
 INVALID = -1  # 0xFFFFFFFFFFFFFFFF as int64: "row not on this GPU / unknown key"
@@ -178,9 +178,12 @@ class DynamicVariable(_VariableBase):
     (hybrid_table.py, hctr_lru_*).  Keyword options: max_capacity (required; rounded up to whole
     buckets), max_bucket_size=128, evict_strategy="kLru" (the only strategy), filter_ratio=1.0 (the
     admission probability of lookup_sparse(..., use_low_frequency_filter=True)).  init_capacity is
-    accepted and ignored: the store is allocated once, at max_capacity.  The reference's other
-    options (max_hbm_for_vectors, max_load_factor, ...) are kept in config_dict.  The table lives in
-    HBM only: evicted pairs go back to the caller (sparse_read_and_evict), not to host memory."""
+    accepted and ignored: the store is allocated once, at max_capacity.  max_hbm_for_vectors=G
+    (GiB, int or float, >= 0): the rows of H = min(C, floor(G * 2^30 / (dimension * 4) / S) * S)
+    slots, and their optimizer states, stay in HBM and the others live in pinned host memory
+    (DESIGN.md "Hybrid table"); without it everything is in HBM (the reference defaults to 16).
+    The reference's other options (max_load_factor, ...) are kept in config_dict.  Evicted pairs go
+    back to the caller (sparse_read_and_evict), not to host memory."""
 
     def __init__(self, dimension: int, initializer: Union[str, float, None] = None,
                  key_type=torch.int64, init_capacity: int = 1 << 20, mode: Optional[str] = None,
@@ -196,6 +199,8 @@ class DynamicVariable(_VariableBase):
                 not 0.0 <= float(ratio) <= 1.0:
             raise ValueError(f"filter_ratio must be a float in [0, 1], not {ratio!r}")
         self.filter_ratio = float(ratio)
+        if var_type == "hybrid" and "max_hbm_for_vectors" in kwargs:
+            check_hbm_budget(kwargs["max_hbm_for_vectors"])
         super().__init__(name)
         self.dimension = int(dimension)
         self.key_type = key_type
@@ -214,9 +219,15 @@ class DynamicVariable(_VariableBase):
             if strategy != "kLru":
                 raise ValueError(f"evict_strategy {strategy!r} is not supported: only \"kLru\"")
             # the initial value is a function of (seed, key, element): the same on every rank
+            bucket = int(kwargs.get("max_bucket_size", 128))
+            hbm = None
+            if kwargs.get("max_hbm_for_vectors") is not None:
+                # every rank tiers its own shard of max_capacity slots with the same budget
+                hbm = hbm_slots_for(kwargs["max_hbm_for_vectors"], self.dimension,
+                                    int(kwargs["max_capacity"]), bucket)
             self._lru = HybridTable(int(kwargs["max_capacity"]), self.dimension,
-                                    self.initializer_str, int(kwargs.get("max_bucket_size", 128)),
-                                    key_type, seed=seed)
+                                    self.initializer_str, bucket, key_type, seed=seed,
+                                    hbm_slots=hbm)
         else:
             self._det = DynamicEmbeddingTable([self.dimension], self.initializer_str,
                                               init_capacity, key_type, seed=seed + 1000003 * _RANK)
@@ -239,7 +250,16 @@ class DynamicVariable(_VariableBase):
                                         ptr(idx), stream_ptr()))
         return idx
 
+    @property
+    def tiered(self) -> bool:
+        """a hybrid variable whose slots are partly in host memory"""
+        return self._lru is not None and self._lru.tiered
+
     def _table(self) -> torch.Tensor:
+        if self.tiered:
+            # the HBM slots and the per-call rows the last lookup handed out
+            p, _ = self._lru.rows_ptr()
+            return _view_f32(p, (self._lru.placement()[1], self.dimension))
         if self._lru is not None:
             # (the scratch rows after the slots are addressed through the pointer only)
             p, cap = self._lru.rows_ptr()
@@ -252,6 +272,20 @@ class DynamicVariable(_VariableBase):
         """stored keys only, as the dynamic table's scatter does"""
         idx = self._lru.find(indices.reshape(-1))
         live = idx >= 0
+        if self.tiered:
+            # slot-addressed (host slots included): distinct slots, the values summed per slot
+            # for an add as index_add_ does
+            v = values.reshape(-1, self.dimension).float()[live]
+            slots, inv = torch.unique(idx[live], return_inverse=True)
+            if add:
+                u = torch.zeros((slots.numel(), self.dimension), dtype=torch.float32,
+                                device=v.device).index_add_(0, inv, v)
+            else:
+                u = torch.empty((slots.numel(), self.dimension), dtype=torch.float32,
+                                device=v.device)
+                u[inv] = v
+            self._lru.scatter_slots(0, slots, u, add=add)
+            return
         rows = self._table()
         v = values.reshape(-1, self.dimension).float()[live]
         if add:
@@ -316,6 +350,13 @@ def assign(var: DynamicVariable, indices: torch.Tensor, values: torch.Tensor):
     evict other keys, and a key the table rejects is not stored."""
     if var._lru is not None:
         idx = var._lru.lookup_index(indices.reshape(-1).contiguous(), insert=True)
+        if var.tiered:
+            # the rows handed out are per-call copies: write the stored keys' slots
+            slots = var._lru.find(indices.reshape(-1).contiguous())
+            live = slots >= 0
+            var._lru.scatter_slots(0, slots[live],
+                                   values.reshape(-1, var.dimension).float()[live])
+            return
         cap = var._lru.capacity
         live = idx < cap
         var._table()[idx[live]] = values.reshape(-1, var.dimension).float()[live]
@@ -661,11 +702,17 @@ class OptimizerWrapper:
                 lib.hctr_updater_destroy(var._updater[0])
             h = ctypes.c_void_p()
             ucap = max(2 * n, 1024)
-            check(lib.hctr_updater_create(ucap, cap, D, ctypes.byref(h)))
+            # tiered: the update sees the H HBM slots and up to n staged host slots after them
+            check(lib.hctr_updater_create(ucap, cap + ucap if var.tiered else cap, D,
+                                          ctypes.byref(h)))
             var._updater = (h, ucap)
         ns = _num_state(self.code)
         st = [ctypes.c_void_p(var._lru.state_ptr(i)) for i in range(ns)]
         ro = torch.arange(n + 1, dtype=torch.int64, device=kg.device)
+        if var.tiered:
+            # host slots are staged into HBM rows, updated there and written back
+            var._lru.apply_update(var._updater[0], ro, slots, kg, self.code, self.hp, self.times)
+            return
         hp = self.hp
         check(lib.hctr_updater_update(
             var._updater[0], n, n, ptr(ro), ptr(slots), ptr(kg.contiguous()), _lib.F32, self.code,
@@ -754,7 +801,11 @@ def _var_arrays(var, optimizer):
         order = torch.argsort(k)
         k, w, sl = k[order].to(torch.int64), w[order], sl[order]
         states = []
-        if slots:
+        if slots and var.tiered:
+            for j in range(len(slots)):
+                var._lru.state_ptr(j)
+            states = [var._lru.gather_slots(1 + j, sl) for j in range(len(slots))]
+        elif slots:
             cap = var._lru.capacity
             states = [_view_f32(var._lru.state_ptr(j), (cap, D))[sl].clone()
                       for j in range(len(slots))]
@@ -851,6 +902,10 @@ def load(path: str, load_vars, optimizer: Optional["OptimizerWrapper"] = None):
                 idx = var._lru.find(kt.to(var.key_type))
                 live = idx >= 0
                 for j, x in enumerate(states):
+                    if var.tiered:
+                        var._lru.state_ptr(j)
+                        var._lru.scatter_slots(1 + j, idx[live], torch.from_numpy(x).to(dev)[live])
+                        continue
                     sv = _view_f32(var._lru.state_ptr(j), (var._lru.capacity, var.dimension))
                     sv[idx[live]] = torch.from_numpy(x).to(dev)[live]
         elif isinstance(var, DynamicVariable):

@@ -872,6 +872,50 @@ int hctr_lru_compact(hctr_lru* h, size_t batch, size_t n, const long long* offse
 int hctr_lru_export_if(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots,
                        uint64_t* scores, float* rows, size_t max_keys, size_t* exported,
                        size_t* matched, hctr_stream_t stream);
+/* Host-memory value tier (the reference's max_hbm_for_vectors).  A table created with
+ * hbm_slots = H < C (a multiple of bucket_size, else an error naming hbm_slots; 0 allowed) keeps
+ * the rows and optimizer states of slots [0, H) in HBM and those of slots [H, C) in pinned,
+ * device-mapped host memory (hipHostMalloc Mapped | Portable), written with ordinary stores.
+ * hbm_slots >= C gives the table of hctr_lru_create.  Every observable -- row numbers of HBM slots
+ * aside -- is bit for bit that of the untiered table with the same arguments.  On a tiered table:
+ *  - hctr_lru_lookup_index(_filtered) hands out row s for an HBM slot s and the per-call row H + p
+ *    for every other position p (a host-resident key: a copy of its row; a miss / a rejected key:
+ *    the initializer's value), so hctr_forward_pool* read HBM only;
+ *  - hctr_lru_rows / hctr_lru_state cover the HBM part only: *capacity = H, and the H slot rows
+ *    are followed by the per-call rows (hctr_lru_placement's hbm_rows in all).  Host slots are
+ *    reached through hctr_lru_gather_slots / hctr_lru_scatter_slots;
+ *  - a sparse optimizer step goes through hctr_lru_apply_update.
+ * hctr_lru_find and the export calls return slots (< C) as before. */
+int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key_type,
+                           const char* initializer, uint64_t seed, size_t hbm_slots,
+                           hctr_lru** out);
+/* *hbm_slots = H (C untiered), *hbm_rows = rows of the HBM row store (H slots + per-call rows),
+ * *host_rows = C - H */
+int hctr_lru_placement(const hctr_lru* h, size_t* hbm_slots, size_t* hbm_rows, size_t* host_rows);
+/* device address of an array's host part (rows [C - H][dim] for array 0, state array - 1 for 1, 2;
+ * row s - H is slot s), NULL on an untiered table or for a state not allocated yet */
+int hctr_lru_host_part(const hctr_lru* h, int array, float** host);
+/* slot-addressed I/O, either tier, any table.  array: 0 = rows, 1 + i = optimizer state i (must be
+ * allocated: hctr_lru_state).  slots [n] (device, uint64); a slot >= C is skipped (its out row is
+ * left as it was).  gather: out [n][dim] = array[slot].  scatter: array[slot] = values (add == 0)
+ * or += values; the slots of one scatter must be distinct. */
+int hctr_lru_gather_slots(hctr_lru* h, int array, const uint64_t* slots, size_t n, float* out,
+                          hctr_stream_t stream);
+int hctr_lru_scatter_slots(hctr_lru* h, int array, const uint64_t* slots, size_t n,
+                           const float* values, int add, hctr_stream_t stream);
+/* one sparse optimizer step (local update) on the slots' rows and states: hctr_updater_update with
+ * value indices = slots (from hctr_lru_find; SIZE_MAX positions are dropped), the table's row store
+ * and its states, which must be allocated for the optimizer (hctr_lru_state).  On a tiered table the
+ * distinct host slots among `slots`, in ascending order, are staged into the per-call rows H + u
+ * (u = rank), the update runs there, and they are written back; the renumbering is monotone in
+ * the slot, so the update sees the same segments and computes the same bits as on the untiered
+ * table.  u must have been created with max_rows >= H + nnz (capacity C when untiered).  Uses the
+ * handle's workspace; no host synchronisation. */
+int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t nnz,
+                          const int64_t* bucket_range, const uint64_t* slots, const void* grad,
+                          int grad_dtype, int optimizer, float lr, float beta1, float beta2,
+                          float epsilon, float momentum_factor, float scaler, uint64_t times,
+                          hctr_stream_t stream);
 
 #ifdef __cplusplus
 }
