@@ -7,7 +7,10 @@ loss -> backward -> (N > 1: reorder + all-to-all) -> sort + segmented gradient r
 SGD update -> dense SGD step.  Nothing is skipped inside the timed region.
 
 Contract: `python bench.py --gpus N --steps K --warmup W` (N > 1 under torch.distributed.run);
-rank 0 prints ONE JSON line.  See DESIGN.md "Measurement".
+rank 0 prints ONE JSON line.  Such a plain run does only what that line's headline needs: set-up,
+warm-up, the timed steps, --dump-outputs if given, the line.  `--full` adds everything else the
+bench measures (stage times and rooflines, the strong-scaling line, the extra legs, the CPU
+baselines).  See DESIGN.md "Measurement".
 """
 import argparse
 import json
@@ -394,13 +397,16 @@ def dump_outputs(m, emb, out_dir, rank, world):
 
 
 def dlrm_leg(a, precision, steps, warmup, world, rank, dev, scaling="weak", alpha=None,
-             sizes=None, label=None, dump_dir=None):
+             sizes=None, label=None, dump_dir=None, stages=True):
     """one measurement of the DLRM Criteo-1TB step through hugectr.Model.train() -- the product
     surface, on 1 or N GPUs -- at `precision` (see --precision).  scaling = "weak": a.batch
     samples per GPU (global batch N x a.batch); "strong": global batch a.batch (per GPU a.batch/N),
     BASELINE configs[2] read literally.  Every step sees a batch it has not seen before (keys are
     inserted live).  Builds and releases its own model: the 89.5 GiB table exists once at a time.
-    dump_dir: the outputs of the last timed step go there (dump_outputs)."""
+    dump_dir: the outputs of the last timed step go there (dump_outputs).  stages: after the timed
+    steps, the stage times (one GPU: runs of their own, see below) and the rooflines computed from
+    them; without it the record holds the headline, the configuration and the timed region's own
+    stage times."""
     from hugectr_amd import _lib
     alpha = a.alpha if alpha is None else alpha
     sizes = sizes or [max(1, int(v * a.table_scale)) for v in CRITEO_1TB]
@@ -413,7 +419,7 @@ def dlrm_leg(a, precision, steps, warmup, world, rank, dev, scaling="weak", alph
     sel = 0
     if world > 1 and os.environ.get("HCTR_EXCHANGE", "auto") == "auto" and not a.no_overlap:
         sel = m._SEL_WARM + 2 * m._SEL_TIMED + m._SEL_SWITCH + 1  # the exchange selection's steps
-    inline = 8 if world == 1 else 0  # unseen batches for the in-line stage times (see below)
+    inline = 8 if world == 1 and stages else 0  # unseen batches for the in-line stage times (below)
     ov_prev = os.environ.get("HCTR_UPDATE_OVERLAP")
     nb = a.nbatches if a.nbatches > 0 else sel + warmup + steps + inline + 1
     gk = torch.Generator(device=dev)
@@ -480,154 +486,14 @@ def dlrm_leg(a, precision, steps, warmup, world, rank, dev, scaling="weak", alph
                           and (ov_prev or "auto") != "0")
     m.check_overflow()
     new_keys = (emb.get_vocabulary_size() - rows_before) / max(steps, 1)
-    # The timed region runs the product's schedule: on one GPU the sparse update starts from the
-    # gradient hook on a side stream, under the bottom MLP's backward (hugectr.py), so its events
-    # there bracket shared-chip time.  The stage times the rooflines are computed from are taken
-    # right after, on `inline` further unseen batches with the update in line (its own time).
-    prof = prof_timed
-    prof_ahead = None
-    if world == 1 and inline > 0:
-        os.environ["HCTR_UPDATE_OVERLAP"] = "0"
-        # (a) HCTR_PREWORK=1: the update's grouping kernels (hot rows' chunk sort, cold rows'
-        # count / base / scatter) right behind the index stage on side streams, the update stage
-        # itself = the two reduces + join / apply
-        pw_prev = os.environ.get("HCTR_PREWORK")
-        os.environ["HCTR_PREWORK"] = "1"
-        emb.profiling(True)
-        for _ in range(inline // 2):
-            m.train()
-        sync()
-        prof_ahead = emb.profile()
-        # (b) everything of the update inside the update stage (HCTR_PREWORK=0, the default): the
-        # stage time `roofline_update` is computed from
-        os.environ["HCTR_PREWORK"] = "0"
-        emb.profiling(True)
-        for _ in range(inline - inline // 2):
-            m.train()
-        sync()
-        prof = emb.profile()
-        emb.profiling(False)
-        if pw_prev is None:
-            os.environ.pop("HCTR_PREWORK", None)
-        else:
-            os.environ["HCTR_PREWORK"] = pw_prev
-    # the same stages with NO unseen key (batches the tables have met): the index stage's floor
-    steady_us = None
-    if world == 1:
-        m.reader = _CycleReader(batches[-4:])
-        m._lookahead = None
-        for _ in range(4):
-            m.train()
-        sync()
-        emb.profiling(True)
-        for _ in range(8):
-            m.train()
-        sync()
-        steady_us = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in emb.profile().items()}
-        emb.profiling(False)
-        if ov_prev is None:
-            os.environ.pop("HCTR_UPDATE_OVERLAP", None)
-        else:
-            os.environ["HCTR_UPDATE_OVERLAP"] = ov_prev
     xrep = m.exchange_report()["sparse_embedding1"]
-
-    # ---- roofline of the gather+pool kernel (DESIGN.md section 5 / SURVEY 8d) -------------------
-    nnz_g = B * spr  # one-hot: one key per (sample, slot on this rank)
     fused = bool(xrep.get("gather_fused_into_interaction"))
     U = sum(uniq) / max(len(uniq), 1)
-    n_ins = S + 1
-    out_len = D + n_ins * (n_ins - 1) // 2 + 1
-    if fused:
-        # one GPU: the gather rides in the interaction kernel (hctr_emb_forward_interaction).  Per
-        # launch: row index + fp32 row per key, the bottom-MLP row, the pooled vectors written
-        # once, the interaction output -- SURVEY 8(d)'s gather bytes (without the key read, which
-        # is the index stage's) + the interaction's own input / output, minus the pooled re-read
-        io = Bl * D * esz + Bl * out_len * esz
-        alg_bytes = nnz_g * 8 + nnz_g * D * 4 + B * spr * D * esz + io
-        comp_bytes = nnz_g * 8 + U * D * 4 + B * spr * D * esz + io
-    else:
-        alg_bytes = nnz_g * 8 + nnz_g * 8 + nnz_g * D * 4 + B * spr * D * esz
-        # compulsory = what must cross the HBM interface even with a perfect cache: every key and
-        # row index once, every DISTINCT row once, every output element once
-        comp_bytes = nnz_g * 8 + nnz_g * 8 + U * D * 4 + B * spr * D * esz
-    pool_ms, pool_n = prof["gather_pool"]
-    if pool_n == 0:  # unique-row payload kept: the gather kernel only ran during the selection
-        pool_ms, pool_n = pool_prof
-    pool_s = pool_ms / max(pool_n, 1) * 1e-3
-    achieved = alg_bytes / pool_s / 1e9 if pool_ms > 0 else 0.0
-    # HBM bytes per launch from the PMC counters (rocprofv3, separate passes, tools/measure_round.sh
-    # -> profiles/r4_pmc_hbm_traffic_<label>.json, stamped with the kernel sources' hash; a bench
-    # process cannot read the counters of its own kernels)
-    pmc, pmc_src, pmc_upd, pmc_idx, pmc_stale, mfma_busy = None, None, None, None, None, None
-    tag = label or ("fp32" if esz == 4 else "fp16")
-    here = _csrc_hash()
-    if world == 1 and D == 128 and a.batch == 65536 and a.table_scale == 1.0:
-        pmc_path = _counter_file(f"pmc_hbm_traffic_{tag}.json")
-        if not os.path.exists(pmc_path):
-            pmc_path = os.path.join(ROOT, "profiles", f"r4_pmc_hbm_traffic_{tag}.json")
-        try:
-            j = json.load(open(pmc_path))
-            if abs(float(j.get("alpha", 1.1)) - alpha) < 1e-9:
-                pmc_src = os.path.relpath(pmc_path, ROOT) + (
-                    f" @ {j['commit']}" if j.get("commit") else "")
-                # counters are quoted only while the kernel sources are the ones they were taken
-                # on (tools/csrc_hash.py; tools/measure_round.sh regenerates the files)
-                pmc_stale = j.get("csrc_hash") != here
-                if not pmc_stale:
-                    ks = j["kernels"]
-                    pmc = ks["interaction_fwd16_gather_kernel" if fused
-                             else "pool_vec4_kernel"]["hbm_bytes_per_launch"]
-
-                    def per_step(names, once):
-                        # bytes per step of a group of kernels: per-launch average x launches per
-                        # step (= its launch count over that of a kernel launched once a step)
-                        n1 = ks[once]["launches_averaged"][0]
-                        return sum(ks[k]["hbm_bytes_per_launch"] *
-                                   ks[k]["launches_averaged"][0] / n1 for k in names if k in ks)
-                    upd_once = ("cold_reduce_kernel" if "cold_reduce_kernel" in ks
-                                else "seg_reduce_kernel")
-                    if upd_once in ks:
-                        pmc_upd = per_step(("expand_pairs_kernel", "rs_hist_kernel",
-                                            "rs_colscan_kernel", "rs_scatter_kernel",
-                                            "hot_sort_kernel", "hot_reduce_kernel",
-                                            "hot_join_kernel", "hot_apply_kernel",
-                                            "cold_count_kernel", "cold_base_kernel",
-                                            "cold_scatter_kernel", "cold_reduce_kernel",
-                                            "seg_reduce_kernel", "seg_combine_kernel",
-                                            "seg_combine_big_kernel"), upd_once)
-                    if "ht_probe_insert_kernel" in ks:
-                        pmc_idx = per_step(("ht_probe_insert_kernel", "ht_finish_kernel"),
-                                           "ht_probe_insert_kernel")
-        except Exception:
-            pmc = None
-        # matrix-pipe utilisation of the interaction kernels (SQ pass of tools/measure_round.sh)
-        try:
-            sq_path = _counter_file("pmc_sq_counters.json")
-            if not os.path.exists(sq_path):
-                sq_path = os.path.join(ROOT, "profiles", "r4_pmc_sq_counters.json")
-            j = json.load(open(sq_path))
-            if j.get("csrc_hash") == here and tag == "fp16":
-                mfma_busy = {k: {"mfma_util_of_1024_simds": v.get("mfma_util_of_1024_simds"),
-                                 "wave_cycles_split": v.get("wave_cycles_split")}
-                             for k, v in j["kernels"].items() if k.startswith("interaction_")}
-                mfma_busy["source"] = os.path.relpath(sq_path, ROOT) + (
-                    f" @ {j['commit']}" if j.get("commit") else "")
-        except Exception:
-            mfma_busy = None
-    stage_us = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof.items()}
-    # update (a12): SURVEY 8(d) bytes = nnz (8 + K) + B S_g D E (gradients read) + U D 4 x 2 (rows)
-    upd_bytes = nnz_g * 16 + B * spr * D * esz + U * D * 4 * 2
-    upd_s = (stage_us.get("sort", 0.0) + stage_us.get("segmented_update", 0.0)) * 1e-6
-    upd_ahead_s = None
-    if prof_ahead is not None:
-        sa = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof_ahead.items()}
-        upd_ahead_s = (sa.get("sort", 0.0) + sa.get("segmented_update", 0.0)) * 1e-6
-    idx_bytes = nnz_g * (8 + 16 + 8)
-    idx_s = stage_us.get("hash_index", 0.0) * 1e-6
+    stage_us_timed = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof_timed.items()}
     per_rank = None
     if world > 1:
         mine = {"rank": rank, "device": torch.cuda.current_device(), "backend": dist.get_backend(),
-                "slots": spr, "table_rows": my_rows, "stage_us": stage_us,
+                "slots": spr, "table_rows": my_rows, "stage_us": stage_us_timed,
                 "exchange": xrep, "new_keys_per_step": new_keys}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
@@ -663,76 +529,226 @@ def dlrm_leg(a, precision, steps, warmup, world, rank, dev, scaling="weak", alph
                    "gather_fused_into_interaction": fused,
                    "final_loss": m.get_current_loss(),
                    "dense_gemm_selection": getattr(m, "_gemm_selection", "off")},
-        "roofline": {"bound": "hbm",
-                     "kernel": ("interaction_fwd16_gather_kernel (gather + pooling fused into the "
-                                "dot interaction: table rows -> LDS tile -> MFMA, pooled vectors "
-                                "written once)" if fused else
-                                "pool_vec4_kernel (gather + intra-slot pooling)"),
-                     "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc,
-                     "traffic_source": pmc_src, "traffic_stale": pmc_stale,
-                     # SQ_VALU_MFMA_BUSY_CYCLES over the 1024 SIMDs' cycles, and where the waves'
-                     # cycles go, for the interaction kernels (north_star: "MFMA utilisation on the
-                     # interaction"); null when the counter file is not of these sources
-                     "mfma_busy": mfma_busy,
-                     "algorithmic_bytes_per_launch": alg_bytes,
-                     # `achieved` / `avg_launch_us` are of the in-line launches (the update in line,
-                     # the kernel alone on the chip); the timed region's launches share the chip
-                     # with the overlapped update on one GPU -- both averages are given
-                     "launches_inline": pool_n, "avg_launch_us": pool_s * 1e6,
-                     "launches_timed_region": prof_timed.get("gather_pool", (0.0, 0))[1],
-                     "avg_launch_us_timed_region":
-                         (prof_timed["gather_pool"][0] / max(prof_timed["gather_pool"][1], 1) * 1e3)
-                         if prof_timed.get("gather_pool", (0, 0))[1] else None,
-                     "frac_traffic": (pmc / pool_s / 1e9 / HBM_PEAK_GBPS)
-                     if pmc and pool_ms > 0 else None,
-                     # SURVEY 8(d) counts duplicate rows; power-law keys repeat hot rows, which L2
-                     # / Infinity Cache serve, so `frac` can reach 1 without saying much about the
-                     # kernel.  compulsory_bytes counts every DISTINCT row once: the bytes no cache
-                     # can remove; `traffic` is what the counters saw cross the HBM interface
-                     "compulsory_bytes": comp_bytes,
-                     "frac_compulsory": (comp_bytes / pool_s / 1e9 / HBM_PEAK_GBPS)
-                     if pool_ms > 0 else None,
-                     "hbm_traffic_gbps": (pmc / pool_s / 1e9) if pmc and pool_ms > 0 else None},
-        "roofline_update": {"bound": "hbm", "kernels": "hot rows (per-chunk LDS sort, tile reduce, "
-                            "chunk-ordered apply) beside the cold rows' chain (counted per row: "
-                            "count / base / scatter, then singles + sorted short runs + long runs "
-                            "with the optimizer folded in); `us` = fork .. join of the two chains "
-                            "with ALL of it inside the update stage (HCTR_PREWORK=0); "
-                            "`us_grouping_ahead` = the same stage under HCTR_PREWORK=1, the "
-                            "grouping kernels started behind the index stage on side streams "
-                            "(step time within noise of the default, so off by default)",
-                            "us_grouping_ahead": (upd_ahead_s * 1e6) if upd_ahead_s else None,
-                            "frac_grouping_ahead": (upd_bytes / upd_ahead_s / 1e9 / HBM_PEAK_GBPS)
-                            if upd_ahead_s else None,
-                            "achieved": (upd_bytes / upd_s / 1e9) if upd_s > 0 else None,
-                            "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                            "frac": (upd_bytes / upd_s / 1e9 / HBM_PEAK_GBPS) if upd_s > 0 else None,
-                            "algorithmic_bytes": upd_bytes, "us": upd_s * 1e6,
-                            # HBM bytes per step of these kernels (same PMC passes as above)
-                            "traffic": pmc_upd, "traffic_source": pmc_src if pmc_upd else None,
-                            "traffic_ratio": (pmc_upd / upd_bytes) if pmc_upd else None},
-        "roofline_index": {"bound": "hbm", "kernels": "hash index stage (filter + probe / insert)",
-                           "achieved": (idx_bytes / idx_s / 1e9) if idx_s > 0 else None,
-                           "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                           "frac": (idx_bytes / idx_s / 1e9 / HBM_PEAK_GBPS) if idx_s > 0 else None,
-                           "algorithmic_bytes": idx_bytes, "us": idx_s * 1e6,
-                           "traffic": pmc_idx, "traffic_source": pmc_src if pmc_idx else None,
-                           "traffic_ratio": (pmc_idx / idx_bytes) if pmc_idx else None},
-        "stage_us_per_step": stage_us,
-        # the same stages as the timed region saw them (one GPU: the update overlapped with the
-        # bottom MLP's backward -- shared-chip time, not the kernels' own)
-        "stage_us_per_step_timed_region": {k: (v[0] / max(v[1], 1)) * 1e3
-                                           for k, v in prof_timed.items()},
+        # the stages as the timed region saw them (one GPU: the update overlapped with the bottom
+        # MLP's backward -- shared-chip time, not the kernels' own)
+        "stage_us_per_step_timed_region": stage_us_timed,
         # (auto: the product switches it off when the update is a long bandwidth-bound kernel --
         #  hugectr.py _overlap_update_now; this is the mode the timed region ended in)
-        "update_overlapped_with_dense_backward": bool(
-            upd_overlapped and xrep.get("gather_fused_into_interaction")),
-        "stage_us_per_step_no_new_keys": steady_us,
-        "embedding_ms_per_step": sum(stage_us.values()) * 1e-3,
+        "update_overlapped_with_dense_backward": bool(upd_overlapped and fused),
     }
     if per_rank is not None:
         out["per_rank"] = per_rank
+    if stages:
+        # The timed region runs the product's schedule: on one GPU the sparse update starts from
+        # the gradient hook on a side stream, under the bottom MLP's backward (hugectr.py), so its
+        # events there bracket shared-chip time.  The stage times the rooflines are computed from
+        # are taken right after, on `inline` further unseen batches with the update in line (its
+        # own time).
+        prof = prof_timed
+        prof_ahead = None
+        if world == 1 and inline > 0:
+            os.environ["HCTR_UPDATE_OVERLAP"] = "0"
+            # (a) HCTR_PREWORK=1: the update's grouping kernels (hot rows' chunk sort, cold rows'
+            # count / base / scatter) right behind the index stage on side streams, the update
+            # stage itself = the two reduces + join / apply
+            pw_prev = os.environ.get("HCTR_PREWORK")
+            os.environ["HCTR_PREWORK"] = "1"
+            emb.profiling(True)
+            for _ in range(inline // 2):
+                m.train()
+            sync()
+            prof_ahead = emb.profile()
+            # (b) everything of the update inside the update stage (HCTR_PREWORK=0, the default):
+            # the stage time `roofline_update` is computed from
+            os.environ["HCTR_PREWORK"] = "0"
+            emb.profiling(True)
+            for _ in range(inline - inline // 2):
+                m.train()
+            sync()
+            prof = emb.profile()
+            emb.profiling(False)
+            if pw_prev is None:
+                os.environ.pop("HCTR_PREWORK", None)
+            else:
+                os.environ["HCTR_PREWORK"] = pw_prev
+        # the same stages with NO unseen key (batches the tables have met): the index stage's floor
+        steady_us = None
+        if world == 1:
+            m.reader = _CycleReader(batches[-4:])
+            m._lookahead = None
+            for _ in range(4):
+                m.train()
+            sync()
+            emb.profiling(True)
+            for _ in range(8):
+                m.train()
+            sync()
+            steady_us = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in emb.profile().items()}
+            emb.profiling(False)
+            if ov_prev is None:
+                os.environ.pop("HCTR_UPDATE_OVERLAP", None)
+            else:
+                os.environ["HCTR_UPDATE_OVERLAP"] = ov_prev
+
+        # ---- roofline of the gather+pool kernel (DESIGN.md section 5 / SURVEY 8d) ---------------
+        nnz_g = B * spr  # one-hot: one key per (sample, slot on this rank)
+        n_ins = S + 1
+        out_len = D + n_ins * (n_ins - 1) // 2 + 1
+        if fused:
+            # one GPU: the gather rides in the interaction kernel (hctr_emb_forward_interaction).
+            # Per launch: row index + fp32 row per key, the bottom-MLP row, the pooled vectors
+            # written once, the interaction output -- SURVEY 8(d)'s gather bytes (without the key
+            # read, which is the index stage's) + the interaction's own input / output, minus the
+            # pooled re-read
+            io = Bl * D * esz + Bl * out_len * esz
+            alg_bytes = nnz_g * 8 + nnz_g * D * 4 + B * spr * D * esz + io
+            comp_bytes = nnz_g * 8 + U * D * 4 + B * spr * D * esz + io
+        else:
+            alg_bytes = nnz_g * 8 + nnz_g * 8 + nnz_g * D * 4 + B * spr * D * esz
+            # compulsory = what must cross the HBM interface even with a perfect cache: every key
+            # and row index once, every DISTINCT row once, every output element once
+            comp_bytes = nnz_g * 8 + nnz_g * 8 + U * D * 4 + B * spr * D * esz
+        pool_ms, pool_n = prof["gather_pool"]
+        if pool_n == 0:  # unique-row payload kept: the gather kernel only ran during the selection
+            pool_ms, pool_n = pool_prof
+        pool_s = pool_ms / max(pool_n, 1) * 1e-3
+        achieved = alg_bytes / pool_s / 1e9 if pool_ms > 0 else 0.0
+        # HBM bytes per launch from the PMC counters (rocprofv3, separate passes,
+        # tools/measure_round.sh -> profiles/r4_pmc_hbm_traffic_<label>.json, stamped with the
+        # kernel sources' hash; a bench process cannot read the counters of its own kernels)
+        pmc, pmc_src, pmc_upd, pmc_idx, pmc_stale, mfma_busy = None, None, None, None, None, None
+        tag = label or ("fp32" if esz == 4 else "fp16")
+        here = _csrc_hash()
+        if world == 1 and D == 128 and a.batch == 65536 and a.table_scale == 1.0:
+            pmc_path = _counter_file(f"pmc_hbm_traffic_{tag}.json")
+            if not os.path.exists(pmc_path):
+                pmc_path = os.path.join(ROOT, "profiles", f"r4_pmc_hbm_traffic_{tag}.json")
+            try:
+                j = json.load(open(pmc_path))
+                if abs(float(j.get("alpha", 1.1)) - alpha) < 1e-9:
+                    pmc_src = os.path.relpath(pmc_path, ROOT) + (
+                        f" @ {j['commit']}" if j.get("commit") else "")
+                    # counters are quoted only while the kernel sources are the ones they were
+                    # taken on (tools/csrc_hash.py; tools/measure_round.sh regenerates the files)
+                    pmc_stale = j.get("csrc_hash") != here
+                    if not pmc_stale:
+                        ks = j["kernels"]
+                        pmc = ks["interaction_fwd16_gather_kernel" if fused
+                                 else "pool_vec4_kernel"]["hbm_bytes_per_launch"]
+
+                        def per_step(names, once):
+                            # bytes per step of a group of kernels: per-launch average x launches
+                            # per step (= its launch count over that of a kernel launched once a
+                            # step)
+                            n1 = ks[once]["launches_averaged"][0]
+                            return sum(ks[k]["hbm_bytes_per_launch"] *
+                                       ks[k]["launches_averaged"][0] / n1 for k in names if k in ks)
+                        upd_once = ("cold_reduce_kernel" if "cold_reduce_kernel" in ks
+                                    else "seg_reduce_kernel")
+                        if upd_once in ks:
+                            pmc_upd = per_step(("expand_pairs_kernel", "rs_hist_kernel",
+                                                "rs_colscan_kernel", "rs_scatter_kernel",
+                                                "hot_sort_kernel", "hot_reduce_kernel",
+                                                "hot_join_kernel", "hot_apply_kernel",
+                                                "cold_count_kernel", "cold_base_kernel",
+                                                "cold_scatter_kernel", "cold_reduce_kernel",
+                                                "seg_reduce_kernel", "seg_combine_kernel",
+                                                "seg_combine_big_kernel"), upd_once)
+                        if "ht_probe_insert_kernel" in ks:
+                            pmc_idx = per_step(("ht_probe_insert_kernel", "ht_finish_kernel"),
+                                               "ht_probe_insert_kernel")
+            except Exception:
+                pmc = None
+            # matrix-pipe utilisation of the interaction kernels (SQ pass of tools/measure_round.sh)
+            try:
+                sq_path = _counter_file("pmc_sq_counters.json")
+                if not os.path.exists(sq_path):
+                    sq_path = os.path.join(ROOT, "profiles", "r4_pmc_sq_counters.json")
+                j = json.load(open(sq_path))
+                if j.get("csrc_hash") == here and tag == "fp16":
+                    mfma_busy = {k: {"mfma_util_of_1024_simds": v.get("mfma_util_of_1024_simds"),
+                                     "wave_cycles_split": v.get("wave_cycles_split")}
+                                 for k, v in j["kernels"].items() if k.startswith("interaction_")}
+                    mfma_busy["source"] = os.path.relpath(sq_path, ROOT) + (
+                        f" @ {j['commit']}" if j.get("commit") else "")
+            except Exception:
+                mfma_busy = None
+        stage_us = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof.items()}
+        # update (a12): SURVEY 8(d) bytes = nnz (8 + K) + B S_g D E (gradients read)
+        # + U D 4 x 2 (rows)
+        upd_bytes = nnz_g * 16 + B * spr * D * esz + U * D * 4 * 2
+        upd_s = (stage_us.get("sort", 0.0) + stage_us.get("segmented_update", 0.0)) * 1e-6
+        upd_ahead_s = None
+        if prof_ahead is not None:
+            sa = {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in prof_ahead.items()}
+            upd_ahead_s = (sa.get("sort", 0.0) + sa.get("segmented_update", 0.0)) * 1e-6
+        idx_bytes = nnz_g * (8 + 16 + 8)
+        idx_s = stage_us.get("hash_index", 0.0) * 1e-6
+        out.update({
+            "roofline": {"bound": "hbm",
+                         "kernel": ("interaction_fwd16_gather_kernel (gather + pooling fused into "
+                                    "the dot interaction: table rows -> LDS tile -> MFMA, pooled "
+                                    "vectors written once)" if fused else
+                                    "pool_vec4_kernel (gather + intra-slot pooling)"),
+                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc,
+                         "traffic_source": pmc_src, "traffic_stale": pmc_stale,
+                         # SQ_VALU_MFMA_BUSY_CYCLES over the 1024 SIMDs' cycles, and where the
+                         # waves' cycles go, for the interaction kernels (north_star: "MFMA
+                         # utilisation on the interaction"); null when the counter file is not of
+                         # these sources
+                         "mfma_busy": mfma_busy,
+                         "algorithmic_bytes_per_launch": alg_bytes,
+                         # `achieved` / `avg_launch_us` are of the in-line launches (the update in
+                         # line, the kernel alone on the chip); the timed region's launches share
+                         # the chip with the overlapped update on one GPU -- both averages are given
+                         "launches_inline": pool_n, "avg_launch_us": pool_s * 1e6,
+                         "launches_timed_region": prof_timed.get("gather_pool", (0.0, 0))[1],
+                         "avg_launch_us_timed_region":
+                             (prof_timed["gather_pool"][0] / max(prof_timed["gather_pool"][1], 1) * 1e3)
+                             if prof_timed.get("gather_pool", (0, 0))[1] else None,
+                         "frac_traffic": (pmc / pool_s / 1e9 / HBM_PEAK_GBPS)
+                         if pmc and pool_ms > 0 else None,
+                         # SURVEY 8(d) counts duplicate rows; power-law keys repeat hot rows,
+                         # which L2 / Infinity Cache serve, so `frac` can reach 1 without saying
+                         # much about the kernel.  compulsory_bytes counts every DISTINCT row
+                         # once: the bytes no cache can remove; `traffic` is what the counters
+                         # saw cross the HBM interface
+                         "compulsory_bytes": comp_bytes,
+                         "frac_compulsory": (comp_bytes / pool_s / 1e9 / HBM_PEAK_GBPS)
+                         if pool_ms > 0 else None,
+                         "hbm_traffic_gbps": (pmc / pool_s / 1e9) if pmc and pool_ms > 0 else None},
+            "roofline_update": {"bound": "hbm", "kernels": "hot rows (per-chunk LDS sort, tile "
+                                "reduce, chunk-ordered apply) beside the cold rows' chain (counted "
+                                "per row: count / base / scatter, then singles + sorted short runs "
+                                "+ long runs with the optimizer folded in); `us` = fork .. join of "
+                                "the two chains with ALL of it inside the update stage "
+                                "(HCTR_PREWORK=0); "
+                                "`us_grouping_ahead` = the same stage under HCTR_PREWORK=1, the "
+                                "grouping kernels started behind the index stage on side streams "
+                                "(step time within noise of the default, so off by default)",
+                                "us_grouping_ahead": (upd_ahead_s * 1e6) if upd_ahead_s else None,
+                                "frac_grouping_ahead": (upd_bytes / upd_ahead_s / 1e9 / HBM_PEAK_GBPS)
+                                if upd_ahead_s else None,
+                                "achieved": (upd_bytes / upd_s / 1e9) if upd_s > 0 else None,
+                                "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                "frac": (upd_bytes / upd_s / 1e9 / HBM_PEAK_GBPS) if upd_s > 0 else None,
+                                "algorithmic_bytes": upd_bytes, "us": upd_s * 1e6,
+                                # HBM bytes per step of these kernels (same PMC passes as above)
+                                "traffic": pmc_upd, "traffic_source": pmc_src if pmc_upd else None,
+                                "traffic_ratio": (pmc_upd / upd_bytes) if pmc_upd else None},
+            "roofline_index": {"bound": "hbm",
+                               "kernels": "hash index stage (filter + probe / insert)",
+                               "achieved": (idx_bytes / idx_s / 1e9) if idx_s > 0 else None,
+                               "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": (idx_bytes / idx_s / 1e9 / HBM_PEAK_GBPS) if idx_s > 0 else None,
+                               "algorithmic_bytes": idx_bytes, "us": idx_s * 1e6,
+                               "traffic": pmc_idx, "traffic_source": pmc_src if pmc_idx else None,
+                               "traffic_ratio": (pmc_idx / idx_bytes) if pmc_idx else None},
+            "stage_us_per_step": stage_us,
+            "stage_us_per_step_no_new_keys": steady_us,
+            "embedding_ms_per_step": sum(stage_us.values()) * 1e-3,
+        })
     m._drain_prefetch()
     del m, emb, ex, batches
     import gc
@@ -1561,7 +1577,7 @@ def tiered_leg(steps, warmup, dev, alpha=1.1, rows=20_000_000, D=128, n=1 << 20,
     }
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -1569,11 +1585,12 @@ def main():
     ap.add_argument("--batch", type=int, default=65536,
                     help="BASELINE config 3's 65536: per GPU on the main (weak-scaling) line, "
                          "global on the strong-scaling line")
-    ap.add_argument("--scaling", default="both", choices=["both", "weak", "strong"],
+    ap.add_argument("--scaling", default=None, choices=["both", "weak", "strong"],
                     help="N > 1: weak = 65536 samples per GPU (the main line), strong = global "
                          "batch 65536 (the reference's `batchsize` is global, "
                          "solver_wrapper.hpp:127-150); both = the weak line with the strong one "
-                         "under the key `strong` of the same JSON object")
+                         "under the key `strong` of the same JSON object.  Default: both under "
+                         "--full, weak otherwise")
     ap.add_argument("--exchange", default=None, choices=["auto", "rows", "unique", "unique16"],
                     help="multi-GPU payload of the embedding exchange (sets HCTR_EXCHANGE, read by "
                          "hugectr.Model): rows = one pooled vector / gradient per (sample, slot) "
@@ -1589,7 +1606,8 @@ def main():
     ap.add_argument("--nbatches", type=int, default=0,
                     help="batches resident in HBM; 0 = one per step (warm-up included): every "
                          "step then meets keys it has not seen (inserts live), as real data does")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--precision", default="fp16", choices=["fp16", "fp32"],
                     help="precision of the MAIN line.  fp16 = the reference's mixed precision "
                          "(use_mixed_precision=True, scaler=1024: fp16 pooled vectors / top "
@@ -1604,7 +1622,8 @@ def main():
                          "README, DeepFM Criteo-Kaggle, D = 16) through the hugectr surface, the "
                          "embedding_collection legs (one-hot Criteo-1TB, multi-hot MLPerf DCNv2, "
                          "dynamic tables = configs[4]'s embedding half) and the tiered table "
-                         "(configs[3]); auto = all of them when --config c3 runs on one GPU")
+                         "(configs[3]); auto = all of them under --full when --config c3 runs on "
+                         "one GPU, none without --full")
     ap.add_argument("--config", default="c3", choices=["c1", "c2", "c3"],
                     help="c3 = BASELINE configs[2], DLRM Criteo-1TB (the metric's configuration); "
                          "c1 / c2 = configs[0] / [1] as the main line")
@@ -1621,11 +1640,27 @@ def main():
                          "a caller (loss, dense parameters, a seeded sample of embedding rows) "
                          "as DIR/<name>.npy, float32 / float64, at most 64 MB in all ranks' files "
                          "together (dump_outputs); --config c3 only")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the main line's stage times and "
+                         "the rooflines computed from them (runs of their own after the timed "
+                         "steps), the strong-scaling line at N > 1, the extra legs of --extra auto "
+                         "and the CPU baselines.  Without it a run sets up, warms up, times the "
+                         "steps, writes --dump-outputs and prints the line")
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.dump_outputs and a.config != "c3":
         ap.error("--dump-outputs: the main line of --config c3 only")
+    if a.scaling is None:
+        a.scaling = "both" if a.full else "weak"
+    if a.extra == "auto" and not a.full:
+        a.extra = "none"
+    a.cpu_baseline = a.full and not a.no_cpu_baseline
+    return a
+
+
+def main():
+    a = parse_args()
     if a.exchange:
         os.environ["HCTR_EXCHANGE"] = a.exchange
     if a.tunable == "off":
@@ -1668,14 +1703,14 @@ def main():
     import gc
     first = "strong" if a.scaling == "strong" else "weak"
     out = dlrm_leg(a, a.precision, a.steps, a.warmup, world, rank, dev, scaling=first,
-                   dump_dir=a.dump_outputs)
+                   dump_dir=a.dump_outputs, stages=a.full)
     if world > 1 and a.scaling == "both":
         # BASELINE configs[2] read literally: global batch 65536 over N GPUs
         gc.collect()
         torch.cuda.empty_cache()
         try:
             out["strong"] = dlrm_leg(a, a.precision, a.steps, a.warmup, world, rank, dev,
-                                     scaling="strong")
+                                     scaling="strong", stages=a.full)
         except Exception as e:  # (raised on every rank alike)
             out["strong"] = {"error": repr(e)}
     elif world == 1:
@@ -1752,7 +1787,7 @@ def main():
         if isinstance(extra.get("fp32"), dict) and "roofline" in extra["fp32"]:
             out["roofline_fp32"] = extra["fp32"]["roofline"]
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:
+        if a.cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(CRITEO_1TB, a.alpha, a.dim, 4321)
             except Exception as e:  # the oracle is a reported baseline, never the product path

@@ -82,3 +82,34 @@ def test_emit_writes_the_file_and_prints_one_line(tmp_path):
     assert len(lines) == 1
     j = _check(lines[0])
     assert json.load(open(j["extra_file"]))["extra"].keys() == _canned()["extra"].keys()
+
+
+def test_line_of_a_plain_run_record():
+    """a plain run (no --full) records the headline and the configuration only: the line still
+    carries the contract's headline keys and no figure of a run it did not make"""
+    import bench
+    full = _canned()
+    for k in ("roofline", "roofline_update", "roofline_index", "roofline_uniform", "roofline_fp32",
+              "stage_us_per_step", "stage_us_per_step_no_new_keys", "embedding_ms_per_step",
+              "cpu_baseline", "extra"):
+        full.pop(k, None)
+    j = json.loads(bench.compact_line(full, "bench_extra.json"))
+    assert (j["metric"], j["unit"], j["higher_is_better"], j["dtype"]) == (
+        full["metric"], full["unit"], True, "fp16")
+    assert (j["value"], j["ms_per_step"]) == (bench._r(full["value"]), bench._r(full["ms_per_step"]))
+    for k in ("roofline", "roofline_update", "roofline_index", "cpu_baseline", "extra_summary"):
+        assert k not in j, k
+
+
+def test_plain_run_and_full_options():
+    """--full turns on what a plain run leaves out; legs and scaling named explicitly still run"""
+    import bench
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    a = bench.parse_args(plain)
+    assert (a.full, a.extra, a.scaling, a.cpu_baseline) == (False, "none", "weak", False)
+    a = bench.parse_args(plain + ["--full"])
+    assert (a.full, a.extra, a.scaling, a.cpu_baseline) == (True, "auto", "both", True)
+    a = bench.parse_args(plain + ["--full", "--extra", "none", "--no-cpu-baseline"])
+    assert (a.extra, a.cpu_baseline) == ("none", False)
+    a = bench.parse_args(plain + ["--extra", "uniform", "--scaling", "both"])
+    assert (a.full, a.extra, a.scaling, a.cpu_baseline) == (False, "uniform", "both", False)

@@ -9,7 +9,7 @@ export HCTR_BENCH_BACKEND=gloo
 N=${1:-2}
 run() {
   python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port $((29610 + RANDOM % 200)) bench.py --gpus $N --steps 4 --warmup 2 --batch 8192 \
+    --master-port $((29610 + RANDOM % 200)) bench.py --gpus $N --full --steps 4 --warmup 2 --batch 8192 \
     --table-scale 0.02 --tunable off --extra-file /tmp/bench_ranks_extra.json "$@" 2>&1 | grep '^{' | python -c "
 import sys, json
 line = sys.stdin.read().strip()

@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.."
 X=/tmp/emu_bench_extra_$N.json
 HCTR_EMU=1 PYTHONPATH=$PWD/tests/emu/site:$PYTHONPATH HCTR_BENCH_BACKEND=gloo \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29641 \
-  bench.py --gpus $N --steps 3 --warmup $([ "$EX" = auto ] && echo 20 || echo 3) --batch 256 --table-scale 0.001 \
+  bench.py --gpus $N --full --steps 3 --warmup $([ "$EX" = auto ] && echo 20 || echo 3) --batch 256 --table-scale 0.001 \
   --no-cpu-baseline --exchange $EX --extra-file $X 2>&1 | grep "^{" | python -c "
 import json, sys
 line = sys.stdin.read().strip()

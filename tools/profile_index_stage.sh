@@ -2,7 +2,7 @@
 # per-launch medians of the index-stage kernels (steps that insert / steps that do not) from a
 # rocprofv3 kernel trace of the main bench leg
 cd /tmp && export TMPDIR=/tmp
-W="--extra none --no-cpu-baseline --steps 30 --warmup 8"
+W="--full --extra none --no-cpu-baseline --steps 30 --warmup 8"
 rm -rf /tmp/ks
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o k -- python /root/repo/bench.py $W > /tmp/ks.out 2>&1
 cd /root/repo

@@ -5,7 +5,7 @@ TAG=$1; shift
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 OUT=gpurun_out/r5_quick_$TAG.txt; : > $OUT
-W="--extra none --no-cpu-baseline --steps 24 --warmup 6"
+W="--full --extra none --no-cpu-baseline --steps 24 --warmup 6"
 i=0
 for CFG in "$@"; do
   i=$((i+1))
