@@ -188,6 +188,9 @@ _SIGNATURES = {
     "hctr_ebc_scale_average": (c_int, [c_size_t, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, _P]),
     "hctr_interaction_fwd_gather": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
     "hctr_emb_forward_interaction": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "hctr_interaction_bwd_gather": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int,
+                                            _P]),
+    "hctr_emb_backward_interaction": (c_int, [_P, _P, _P, _P, _P, _P]),
     "hctr_interaction_bwd_indexed": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int,
                                              _P]),
     "hctr_interaction_bwd_indexed_scatter": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P,

@@ -296,10 +296,11 @@ __global__ void __launch_bounds__(64, 2)
 // ---- gather fused into the interaction (one GPU, one key per bucket, sum combiner) ---------------
 // The pooled vector of a one-hot bucket IS its table row (rounded to the 16-bit type), and the
 // interaction stages each sample's rows in LDS anyway: this kernel reads the fp32 table rows
-// through value_index straight into the tile, writes the pooled [batch][n_emb][W] vectors once (the
-// backward and the top-gradient layout need them) and runs the same MFMA chain and output stage
-// as interaction_fwd16_kernel -- bit-identical to pool_vec4_kernel + interaction_fwd16_kernel,
-// without the pass that re-reads the pooled vectors (B * n_emb * W * 2 bytes).
+// through value_index straight into the tile and runs the same MFMA chain and output stage as
+// interaction_fwd16_kernel -- bit-identical to pool_vec4_kernel + interaction_fwd16_kernel, without
+// the pass that re-reads the pooled vectors (B * n_emb * W * 2 bytes).  STORE: the pooled
+// [batch][n_emb][W] vectors are written once as well, for a backward that reads them; without it
+// the backward rebuilds the same tile from the table (interaction_bwd16_kernel<.., GATHER>).
 // A missing row (kInvalidIndex: evaluation miss / full table) pools as zeros.
 template <int W, int NPRE>
 __device__ __forceinline__ void load_gather_idx(uint64_t (&idx)[NPRE],
@@ -336,7 +337,50 @@ __device__ __forceinline__ void load_gather_rows(f32x4 (&lo)[NPRE], f32x4 (&hi)[
   }
 }
 
-template <int W, bool BF>
+// load_gather_rows for the backward, whose prefetch registers are scarcer: lane s < n_emb holds
+// the row number of embedding s (my_idx, loaded a sample ahead), each entry takes its own from that
+// lane; returns the entries' live bits (row number != kInvalidIndex), the row numbers die here
+template <int W, int NPRE>
+__device__ __forceinline__ uint32_t load_gather_rows_lane(f32x4 (&lo)[NPRE], f32x4 (&hi)[NPRE],
+                                                          uint64_t my_idx,
+                                                          const unsigned short* __restrict__ mlp,
+                                                          const float* __restrict__ table, size_t b,
+                                                          int n_vec, int lane) {
+  constexpr int W8 = W / 8;
+  uint64_t idx[NPRE];
+#pragma unroll
+  for (int q = 0; q < NPRE; q++) {
+    int i = lane + 64 * q;
+    i = i < n_vec ? i : 0;
+    const int row = i / W8;
+    idx[q] = __shfl(my_idx, row > 0 ? row - 1 : 0);
+  }
+  load_gather_rows<W, NPRE>(lo, hi, idx, mlp, table, b, n_vec, lane);
+  uint32_t live = 0;
+#pragma unroll
+  for (int q = 0; q < NPRE; q++) live |= (idx[q] != kInvalidIndex ? 1u : 0u) << q;
+  return live;
+}
+
+// 8 values of a gathered tile row as the 16-bit vector the tile holds: row 0 (the MLP output) as
+// loaded, an embedding row rounded from fp32 (a missing row -> +0)
+template <typename H>
+__device__ __forceinline__ u32x4 gather_tile_vec(const f32x4& lo, const f32x4& hi, bool live,
+                                                 int row) {
+  if (row == 0) return *reinterpret_cast<const u32x4*>(&lo);
+  float f[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  unsigned short u[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) u[k] = H::from_f32(0.f + (live ? f[k] : 0.f));
+  u32x4 v;
+  v[0] = (uint32_t)u[0] | ((uint32_t)u[1] << 16);
+  v[1] = (uint32_t)u[2] | ((uint32_t)u[3] << 16);
+  v[2] = (uint32_t)u[4] | ((uint32_t)u[5] << 16);
+  v[3] = (uint32_t)u[6] | ((uint32_t)u[7] << 16);
+  return v;
+}
+
+template <int W, bool BF, bool STORE>
 __global__ void __launch_bounds__(64, 2)
     interaction_fwd16_gather_kernel(size_t batch, int n_emb,
                                     const unsigned short* __restrict__ mlp,
@@ -375,21 +419,9 @@ __global__ void __launch_bounds__(64, 2)
       const int i = lane + 64 * q;
       if (i < n_vec) {
         const int row = i / W8, c8 = i % W8;
-        u32x4 v;
-        if (row == 0) {
-          v = *reinterpret_cast<const u32x4*>(&lo[q]);
-        } else {
-          const bool live = idx[q] != kInvalidIndex;
-          float f[8] = {lo[q][0], lo[q][1], lo[q][2], lo[q][3], hi[q][0], hi[q][1], hi[q][2], hi[q][3]};
-          unsigned short u[8];
-#pragma unroll
-          for (int k = 0; k < 8; k++) u[k] = H::from_f32(0.f + (live ? f[k] : 0.f));
-          v[0] = (uint32_t)u[0] | ((uint32_t)u[1] << 16);
-          v[1] = (uint32_t)u[2] | ((uint32_t)u[3] << 16);
-          v[2] = (uint32_t)u[4] | ((uint32_t)u[5] << 16);
-          v[3] = (uint32_t)u[6] | ((uint32_t)u[7] << 16);
+        const u32x4 v = gather_tile_vec<H>(lo[q], hi[q], idx[q] != kInvalidIndex, row);
+        if (STORE && row != 0)
           *reinterpret_cast<u32x4*>(pooled + (b * (size_t)n_emb + (row - 1)) * W + c8 * 8) = v;
-        }
         *reinterpret_cast<u32x4*>(xt + row * C::LD + c8 * 8) = v;
       }
     }
@@ -426,17 +458,22 @@ __global__ void __launch_bounds__(64, 2)
   }
 }
 
-template <int W, bool BF>
+template <int W, bool BF, bool GATHER>
 __global__ void __launch_bounds__(64, 2)
     interaction_bwd16_kernel(size_t batch, int n_emb, const unsigned short* __restrict__ mlp,
                              const unsigned short* __restrict__ emb,
                              const uint32_t* __restrict__ row_of,
+                             const float* __restrict__ table,
+                             const uint64_t* __restrict__ value_index,
                              const unsigned short* __restrict__ top_grad,
                              unsigned short* __restrict__ mlp_grad,
                              unsigned short* __restrict__ emb_grad, int out_len,
                              const uint32_t* __restrict__ grad_map) {
   // grad_map != nullptr: the gradient of embedding s of sample b goes to row
   // grad_map[b * n_emb + s] of emb_grad (the all-to-all send layout: no reorder pass behind it)
+  // GATHER: the tile is rebuilt from the fp32 table through value_index exactly as
+  // interaction_fwd16_gather_kernel built it (emb / row_of unused) -- the pooled vectors are never
+  // stored; row numbers run one sample ahead of the rows, which are rounded when the tile is written
   using C = InterCfg16<W>;
   using H = H16<BF>;
   constexpr int GS = 40;  // G row stride (16-bit elements): 80 B -> 16 distinct 16-B slots
@@ -463,26 +500,40 @@ __global__ void __launch_bounds__(64, 2)
 
   const int r = lane & 31, h = lane >> 5;
   u32x4 pre[NPRE];
+  f32x4 lo[NPRE], hi[NPRE];
+  uint32_t live = 0;
+  uint64_t idx_nxt = 0;
   unsigned short gpre[NG];
   size_t b = blockIdx.x;
-#define HCTR_BWD16_PREFETCH(bb)                                                  \
-  {                                                                              \
-    load_sample_tile16<W, NPRE>(pre, mlp, emb, row_of, (bb), n_emb, n_vec, lane); \
-    const unsigned short* g__ = top_grad + (bb) * (size_t)out_len + W;           \
-    _Pragma("unroll") for (int q = 0; q < NG; q++) {                             \
-      int p__ = lane + 64 * q;                                                   \
-      p__ = p__ < n_pairs ? p__ : 0;                                             \
-      gpre[q] = g__[p__];                                                        \
-    }                                                                            \
+  const size_t last = batch - 1;
+  const int my_s = lane < n_emb ? lane : 0;
+#define HCTR_BWD16_PREFETCH(bb)                                                       \
+  {                                                                                   \
+    if constexpr (GATHER)                                                             \
+      live = load_gather_rows_lane<W, NPRE>(lo, hi, idx_nxt, mlp, table, (bb), n_vec, lane); \
+    else                                                                              \
+      load_sample_tile16<W, NPRE>(pre, mlp, emb, row_of, (bb), n_emb, n_vec, lane);   \
+    const unsigned short* g__ = top_grad + (bb) * (size_t)out_len + W;                \
+    _Pragma("unroll") for (int q = 0; q < NG; q++) {                                  \
+      int p__ = lane + 64 * q;                                                        \
+      p__ = p__ < n_pairs ? p__ : 0;                                                  \
+      gpre[q] = g__[p__];                                                             \
+    }                                                                                 \
   }
+  if constexpr (GATHER) idx_nxt = value_index[(b < batch ? b : last) * (size_t)n_emb + my_s];
   if (b < batch) HCTR_BWD16_PREFETCH(b)
+  if constexpr (GATHER) {
+    const size_t nb = b + gridDim.x;
+    idx_nxt = value_index[(nb < batch ? nb : last) * (size_t)n_emb + my_s];
+  }
   for (; b < batch; b += gridDim.x) {
 #pragma unroll
     for (int q = 0; q < NPRE; q++) {
       const int i = lane + 64 * q;
       if (i < n_vec) {
         const int row = i / W8, c8 = i % W8;
-        *reinterpret_cast<u32x4*>(xt + row * C::LD + c8 * 8) = pre[q];
+        *reinterpret_cast<u32x4*>(xt + row * C::LD + c8 * 8) =
+            GATHER ? gather_tile_vec<H>(lo[q], hi[q], (live >> q) & 1u, row) : pre[q];
       }
     }
 #pragma unroll
@@ -498,6 +549,10 @@ __global__ void __launch_bounds__(64, 2)
     __syncthreads();
     const size_t nb = b + gridDim.x;
     if (nb < batch) HCTR_BWD16_PREFETCH(nb)
+    if constexpr (GATHER) {
+      const size_t nb2 = nb + gridDim.x;
+      idx_nxt = value_index[(nb2 < batch ? nb2 : last) * (size_t)n_emb + my_s];
+    }
 
     constexpr int HP = NT >= 2 ? 2 : 1;
 #pragma unroll
@@ -1870,7 +1925,7 @@ int hctr_interaction_fwd_gather(size_t batch, int n_emb, int width, const void* 
   HCTR_REQUIRE(width == 128 || width == 64 || width == 32 || width == 16,
                "interaction_fwd_gather: width 16 / 32 / 64 / 128");
   if (batch == 0) return HCTR_OK;
-  HCTR_REQUIRE(mlp && table && value_index && pooled && out, "null pointer");
+  HCTR_REQUIRE(mlp && table && value_index && out, "null pointer");
   HCTR_REQUIRE(reinterpret_cast<uintptr_t>(mlp) % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(table) % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(pooled) % 16 == 0 &&
@@ -1891,17 +1946,18 @@ int hctr_interaction_fwd_gather(size_t batch, int n_emb, int width, const void* 
   const size_t gmax = (size_t)256 * (size_t)waves;
   const int grid1 = (int)(batch < gmax ? batch : gmax);
   const bool bf = dtype == HCTR_EMB_BF16;
+#define HCTR_IFG16_L(W_, BF_, ST_)                                                              \
+  hipLaunchKernelGGL((interaction_fwd16_gather_kernel<W_, BF_, ST_>), dim3(grid1), dim3(64),    \
+                     lds, s, batch, n_emb, (const unsigned short*)mlp, table, value_index,      \
+                     (unsigned short*)pooled, (unsigned short*)out, out_len);
 #define HCTR_IFG16(W_)                                                                          \
   {                                                                                             \
     const size_t lds = (size_t)((n_ins + 1) * InterCfg16<W_>::LD + stage_len) * 2;              \
-    if (bf)                                                                                     \
-      hipLaunchKernelGGL((interaction_fwd16_gather_kernel<W_, true>), dim3(grid1), dim3(64),    \
-                         lds, s, batch, n_emb, (const unsigned short*)mlp, table, value_index,  \
-                         (unsigned short*)pooled, (unsigned short*)out, out_len);               \
-    else                                                                                        \
-      hipLaunchKernelGGL((interaction_fwd16_gather_kernel<W_, false>), dim3(grid1), dim3(64),   \
-                         lds, s, batch, n_emb, (const unsigned short*)mlp, table, value_index,  \
-                         (unsigned short*)pooled, (unsigned short*)out, out_len);               \
+    if (bf) {                                                                                   \
+      if (pooled) HCTR_IFG16_L(W_, true, true) else HCTR_IFG16_L(W_, true, false)               \
+    } else {                                                                                    \
+      if (pooled) HCTR_IFG16_L(W_, false, true) else HCTR_IFG16_L(W_, false, false)             \
+    }                                                                                           \
   }
   switch (width) {
     case 128: HCTR_IFG16(128) break;
@@ -1910,6 +1966,55 @@ int hctr_interaction_fwd_gather(size_t batch, int n_emb, int width, const void* 
     default: HCTR_IFG16(16) break;
   }
 #undef HCTR_IFG16
+#undef HCTR_IFG16_L
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_interaction_bwd_gather(size_t batch, int n_emb, int width, const void* mlp,
+                                const float* table, const uint64_t* value_index,
+                                const void* top_grad, void* mlp_grad, void* emb_grad, int dtype,
+                                hctr_stream_t stream) {
+  const int n_ins = n_emb + 1;
+  const int out_len = width + n_ins * (n_ins - 1) / 2 + 1;
+  HCTR_REQUIRE(n_emb >= 1 && n_emb <= 31, "interaction_bwd_gather: 1 .. 31 embeddings");
+  HCTR_REQUIRE(dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16,
+               "interaction_bwd_gather: 16-bit vectors (fp16 / bf16)");
+  HCTR_REQUIRE((width == 128 || width == 64 || width == 32) && out_len % 8 == 0,
+               "interaction_bwd_gather: width 32 / 64 / 128, output length % 8 == 0");
+  if (batch == 0) return HCTR_OK;
+  HCTR_REQUIRE(mlp && table && value_index && top_grad && mlp_grad && emb_grad, "null pointer");
+  HCTR_REQUIRE(reinterpret_cast<uintptr_t>(mlp) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(table) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(top_grad) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(mlp_grad) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(emb_grad) % 16 == 0,
+               "interaction_bwd_gather: 16-byte aligned buffers");
+  hipStream_t s = as_stream(stream);
+  const size_t gmax = (size_t)256 * (size_t)inter_waves_per_cu(1);
+  const int grid1 = (int)(batch < gmax ? batch : gmax);
+  const int n_pairs = n_ins * (n_ins - 1) / 2;
+  const bool bf = dtype == HCTR_EMB_BF16;
+#define HCTR_IBWDG16(W_)                                                                         \
+  {                                                                                              \
+    const size_t lds = (size_t)(InterCfg16<W_>::XT + 32 * 40 + ((n_pairs + 7) & ~7)) * 2;        \
+    if (bf)                                                                                      \
+      hipLaunchKernelGGL((interaction_bwd16_kernel<W_, true, true>), dim3(grid1), dim3(64), lds, \
+                         s, batch, n_emb, (const unsigned short*)mlp, nullptr, nullptr, table,   \
+                         value_index, (const unsigned short*)top_grad,                           \
+                         (unsigned short*)mlp_grad, (unsigned short*)emb_grad, out_len, nullptr); \
+    else                                                                                         \
+      hipLaunchKernelGGL((interaction_bwd16_kernel<W_, false, true>), dim3(grid1), dim3(64),     \
+                         lds, s, batch, n_emb, (const unsigned short*)mlp, nullptr, nullptr,     \
+                         table, value_index, (const unsigned short*)top_grad,                    \
+                         (unsigned short*)mlp_grad, (unsigned short*)emb_grad, out_len, nullptr); \
+  }
+  switch (width) {
+    case 128: HCTR_IBWDG16(128) break;
+    case 64: HCTR_IBWDG16(64) break;
+    default: HCTR_IBWDG16(32) break;
+  }
+#undef HCTR_IBWDG16
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -1974,14 +2079,15 @@ static int interaction_bwd_impl(size_t batch, int n_emb, int width, const void* 
   {                                                                                              \
     const size_t lds = (size_t)(InterCfg16<W_>::XT + 32 * 40 + ((n_pairs + 7) & ~7)) * 2;        \
     if (bf)                                                                                      \
-      hipLaunchKernelGGL((interaction_bwd16_kernel<W_, true>), dim3(grid1), dim3(64), lds, s,    \
-                         batch, n_emb, (const unsigned short*)mlp, (const unsigned short*)emb,   \
-                         row_of, (const unsigned short*)top_grad, (unsigned short*)mlp_grad,     \
-                         (unsigned short*)emb_grad, out_len, grad_map);                          \
+      hipLaunchKernelGGL((interaction_bwd16_kernel<W_, true, false>), dim3(grid1), dim3(64), lds, \
+                         s, batch, n_emb, (const unsigned short*)mlp, (const unsigned short*)emb, \
+                         row_of, nullptr, nullptr, (const unsigned short*)top_grad,              \
+                         (unsigned short*)mlp_grad, (unsigned short*)emb_grad, out_len, grad_map); \
     else                                                                                         \
-      hipLaunchKernelGGL((interaction_bwd16_kernel<W_, false>), dim3(grid1), dim3(64), lds, s,   \
-                         batch, n_emb, (const unsigned short*)mlp, (const unsigned short*)emb,   \
-                         row_of, (const unsigned short*)top_grad, (unsigned short*)mlp_grad,     \
+      hipLaunchKernelGGL((interaction_bwd16_kernel<W_, false, false>), dim3(grid1), dim3(64),    \
+                         lds, s, batch, n_emb, (const unsigned short*)mlp,                       \
+                         (const unsigned short*)emb, row_of, nullptr, nullptr,                   \
+                         (const unsigned short*)top_grad, (unsigned short*)mlp_grad,             \
                          (unsigned short*)emb_grad, out_len, grad_map);                          \
   }
     switch (width) {

@@ -922,7 +922,7 @@ int hctr_emb_backward(hctr_embedding* e, const void* top_grad, hctr_stream_t str
 
 int hctr_emb_forward_interaction(hctr_embedding* e, int is_train, const void* mlp, void* pooled,
                                  void* out, hctr_stream_t stream) {
-  HCTR_REQUIRE(e && mlp && pooled && out, "null pointer");
+  HCTR_REQUIRE(e && mlp && out, "null pointer");
   HCTR_REQUIRE(e->p.world == 1, "forward_interaction: one GPU (the pooled vectors are exchanged "
                                 "before the interaction otherwise)");
   HCTR_REQUIRE(!is_train || e->has_train_batch, "forward_interaction before the index stage");
@@ -939,6 +939,35 @@ int hctr_emb_forward_interaction(hctr_embedding* e, int is_train, const void* ml
                                              bb.value_index, pooled, out, e->p.out_dtype, stream);
   e->prof.end(0, s);
   return rc;
+}
+
+// The backward reads the table rows of the current training batch again, after the forward read
+// them and after the dense layers above the interaction ran.  No row of this batch is written in
+// between, so the tile it rebuilds is the forward's, bit for bit:
+//  - the previous step's update_params is ordered before this step's index stage (in line, or its
+//    side stream joined by the caller before the forward; Model.train() does, HCTR_INDEX_AHEAD=tail
+//    included, whose index stage on that stream is adopted only behind its event);
+//  - this step's update starts from the embedding gradient, which exists only once this kernel is
+//    enqueued: in line behind the backward, or on a side stream ordered behind it;
+//  - an index stage in the window (hctr_emb_index_ahead for the next batch, HCTR_INDEX_AHEAD=mlp,
+//    on a side stream) inserts keys: it writes hash-table slots, slot ids of NEW rows and
+//    tb_spare -- never a table value (rows are initialised at init_params) and never this batch's
+//    value_index (tb), which this entry reads; tb_spare is not read here.  The update's work started
+//    ahead (presort / prework) groups positions and writes no row.
+//  - e->table never moves (allocated once at create).
+int hctr_emb_backward_interaction(hctr_embedding* e, const void* mlp, const void* top_grad,
+                                  void* mlp_grad, void* emb_grad, hctr_stream_t stream) {
+  HCTR_REQUIRE(e && mlp && top_grad && mlp_grad && emb_grad, "null pointer");
+  HCTR_REQUIRE(e->p.world == 1, "backward_interaction: one GPU (the pooled vectors are exchanged "
+                                "before the interaction otherwise)");
+  HCTR_REQUIRE(e->has_train_batch, "backward_interaction before the index stage");
+  const size_t batch = e->p.train_batch_size;
+  HCTR_REQUIRE(e->cur_nnz_bound == batch * e->p.slot_num,
+               "backward_interaction: the indexed batch does not hold one key per bucket");
+  HCTR_REQUIRE(e->tb.value_index != nullptr, "batch size 0 configured for training");
+  return hctr_interaction_bwd_gather(batch, (int)e->p.slot_num, (int)e->p.embedding_vec_size, mlp,
+                                     e->table, e->tb.value_index, top_grad, mlp_grad, emb_grad,
+                                     e->p.out_dtype, stream);
 }
 
 int hctr_emb_get_wgrad(hctr_embedding* e, void* wgrad, hctr_stream_t stream) {

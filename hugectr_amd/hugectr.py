@@ -30,7 +30,8 @@ from .dense import FusedMLP, bce_with_logits
 from .embedding import OptParams, SparseEmbeddingHash, backward_reorder, forward_reorder
 from .embedding_collection import (DataParallelCollection, EmbeddingCollection,  # noqa: F401
                                    EmbeddingCollectionConfig, EmbeddingTableConfig)
-from .layers import MultiCrossLayer, interaction, interaction_gather, interaction_indexed
+from .layers import (MultiCrossLayer, interaction, interaction_gather, interaction_indexed,
+                     regather_supported)
 from .parallel import DistributedExchange, LocalizedExchange, reorder_row_map
 from .parallel import all_reduce as _all_reduce
 from . import data as _data
@@ -530,7 +531,8 @@ class _IndexedEmb:
 class _GatherEmb:
     """embedding output that is not materialised before the Interaction layer: on one GPU with one
     key per bucket the interaction kernel reads the table rows through the index stage's result
-    itself (hctr_emb_forward_interaction) and writes the pooled vectors once, for the backward"""
+    itself (hctr_emb_forward_interaction); the pooled vectors are written once for the backward,
+    or, where the shape allows (regather_supported), not at all: the backward reads the rows again"""
 
     def __init__(self, emb, train, on_grad, after_forward=None):
         self.emb, self.train, self.on_grad = emb, train, on_grad
@@ -1249,7 +1251,8 @@ class Model:
                 if isinstance(x[1], _GatherEmb):
                     e = x[1]
                     y = interaction_gather(x[0].to(e.emb.out_dtype).contiguous(), e.emb, e.train,
-                                           on_emb_grad=e.on_grad)
+                                           on_emb_grad=e.on_grad, store_pooled=not regather_supported(
+                                               e.emb.embedding_vec_size, e.emb.slot_num))
                     if e.after_forward is not None:
                         e.after_forward()
                 elif isinstance(x[1], _IndexedEmb):

@@ -113,12 +113,57 @@ class _InteractionGatherFn(torch.autograd.Function):
         return mlp_grad, None, None, None
 
 
-def interaction_gather(mlp: torch.Tensor, emb, is_train: bool = True, on_emb_grad=None):
+class _InteractionRegatherFn(torch.autograd.Function):
+    """_InteractionGatherFn without the pooled vectors: the forward does not write them, the
+    backward reads the training batch's table rows again (hctr_emb_backward_interaction).  The
+    rows must not change in between: the embedding's update comes after on_emb_grad."""
+
+    @staticmethod
+    def forward(ctx, mlp, emb, is_train, on_emb_grad):
+        mlp = mlp.contiguous()
+        B, W = mlp.shape
+        n_ins = emb.slot_num + 1
+        out = torch.empty((B, W + n_ins * (n_ins - 1) // 2 + 1), dtype=mlp.dtype, device=mlp.device)
+        check(lib.hctr_emb_forward_interaction(emb._h, 1 if is_train else 0, ptr(mlp), None,
+                                               ptr(out), stream_ptr()))
+        ctx.save_for_backward(mlp)
+        ctx.emb, ctx.is_train, ctx.on_emb_grad = emb, is_train, on_emb_grad
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        (mlp,) = ctx.saved_tensors
+        if not ctx.is_train:
+            raise RuntimeError("interaction_gather: backward of an evaluation batch")
+        grad = grad.contiguous()
+        B, W = mlp.shape
+        mlp_grad = torch.empty_like(mlp)
+        emb_grad = torch.empty((B, ctx.emb.slot_num, W), dtype=mlp.dtype, device=mlp.device)
+        check(lib.hctr_emb_backward_interaction(ctx.emb._h, ptr(mlp), ptr(grad), ptr(mlp_grad),
+                                                ptr(emb_grad), stream_ptr()))
+        if ctx.on_emb_grad is not None:
+            ctx.on_emb_grad(emb_grad)
+        return mlp_grad, None, None, None
+
+
+def regather_supported(width: int, n_emb: int) -> bool:
+    """shapes whose backward can read the rows again (hctr_interaction_bwd_gather)"""
+    n_ins = n_emb + 1
+    return width in (32, 64, 128) and n_emb <= 31 and (width + n_ins * (n_ins - 1) // 2 + 1) % 8 == 0
+
+
+def interaction_gather(mlp: torch.Tensor, emb, is_train: bool = True, on_emb_grad=None,
+                       store_pooled: bool = True):
     """mlp [B, W] 16-bit; emb: a SparseEmbeddingHash (world 1, one key per bucket, vector size W,
     output type = mlp's) whose index stage has run (emb.index) -> interaction output; the pooled
-    vectors never make a second trip through HBM."""
+    vectors never make a second trip through HBM.  store_pooled=False (regather_supported shapes):
+    they are not written at all, the backward reads the current training batch's rows again -- no
+    row of it may be updated before that backward has run."""
     assert mlp.dtype == emb.out_dtype and mlp.shape[1] == emb.embedding_vec_size
-    return _InteractionGatherFn.apply(mlp, emb, is_train, on_emb_grad)
+    if store_pooled:
+        return _InteractionGatherFn.apply(mlp, emb, is_train, on_emb_grad)
+    assert regather_supported(mlp.shape[1], emb.slot_num)
+    return _InteractionRegatherFn.apply(mlp, emb, is_train, on_emb_grad)
 
 
 def interaction_indexed(mlp: torch.Tensor, rows: torch.Tensor, row_of: torch.Tensor,
