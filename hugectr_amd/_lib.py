@@ -55,6 +55,23 @@ class DetOptParams(Structure):
     ]
 
 
+class RowCopyTask(Structure):
+    """hctr_row_copy_task"""
+    _fields_ = [
+        ("src", c_void_p), ("src_rows", c_size_t), ("dim", c_int), ("index_type", c_int),
+        ("index", c_void_p), ("index_div", c_uint64), ("n", c_size_t), ("dst", c_void_p),
+        ("dst_rows", c_size_t), ("dst_pos", c_void_p),
+    ]
+
+
+ROW_COPY_MAX_TASKS = 32
+
+
+def dist_select_ws_bytes(num_splits: int) -> int:
+    """HCTR_DIST_SELECT_WS_BYTES"""
+    return 8 * (num_splits * 1024 + 1)
+
+
 _P = c_void_p
 _SZP = POINTER(c_size_t)
 _SIGNATURES = {
@@ -245,6 +262,8 @@ _SIGNATURES = {
     "hctr_lru_apply_update": (c_int, [_P, _P, c_size_t, c_size_t, _P, _P, _P, c_int, c_int,
                                       c_float, c_float, c_float, c_float, c_float, c_float,
                                       c_uint64, _P]),
+    "hctr_dist_select": (c_int, [_P, c_int, c_size_t, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "hctr_indexed_row_copy": (c_int, [POINTER(RowCopyTask), c_int, c_int, c_int, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

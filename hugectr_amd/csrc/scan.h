@@ -77,16 +77,17 @@ __global__ void __launch_bounds__(kBlock)
 template <typename OffT>
 int exclusive_scan_to_offsets(const OffT* lens, size_t n, unsigned long long* tile_sums,
                               unsigned long long* d_total, OffT* offsets, hipStream_t s) {
+  // (kBlock is qualified: a unit that includes this header may have one of its own)
   using namespace scan_detail;
   const size_t n_tiles = ceil_div<size_t>(n, kTile);
   const int tgrid = (int)(n_tiles < (size_t)kMaxGrid ? (n_tiles ? n_tiles : 1) : (size_t)kMaxGrid);
-  hipLaunchKernelGGL(tile_sum_kernel<OffT>, dim3(tgrid), dim3(kBlock), 0, s, lens, n, n_tiles,
-                     tile_sums);
+  hipLaunchKernelGGL(tile_sum_kernel<OffT>, dim3(tgrid), dim3(scan_detail::kBlock), 0, s, lens, n,
+                     n_tiles, tile_sums);
   HCTR_LAUNCH_CHECK();
   hipLaunchKernelGGL(scan_tiles_u64_kernel, dim3(1), dim3(1024), 0, s, tile_sums, n_tiles, d_total);
   HCTR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tile_downsweep_kernel<OffT>, dim3(tgrid), dim3(kBlock), 0, s, lens, n, n_tiles,
-                     tile_sums, d_total, offsets);
+  hipLaunchKernelGGL(tile_downsweep_kernel<OffT>, dim3(tgrid), dim3(scan_detail::kBlock), 0, s,
+                     lens, n, n_tiles, tile_sums, d_total, offsets);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }

@@ -2,22 +2,25 @@
 
 Mirrors `sparse_operation_kit` (R/sparse_operation_kit/sparse_operation_kit/): `init`,
 `Variable` (Distributed / Localized, distributed_variable.py:26-331), `DynamicVariable`
-(dynamic_variable.py:34-300), `lookup_sparse` (lookup.py:425-700), `OptimizerWrapper`
+(dynamic_variable.py:34-300), `lookup_sparse` (lookup.py:425-700), the dense lookups
+`all2all_dense_embedding` / `group_lookup` (lookup.py:83-139), `OptimizerWrapper`
 (optimizer.py:25-250), `export` / `assign` (dynamic_variable.py:465-520).  TensorFlow's
 RaggedTensor / IndexedSlices have no PyTorch equivalent, so ids are `Ragged(values, row_lengths)`
 (2-D sparse COO tensors are accepted too) and the sparse gradient of a variable is kept on the
 variable between `backward()` and `OptimizerWrapper.step()`.
 
 Compute is the C ABI's: hash / index (`hctr_det_lookup_index`), gather + pooling
-(`hctr_forward_pool*`), per-key gradients (`hctr_expand_key_grads`), sparse update
+(`hctr_forward_pool*`), owner partition and row copies of the dense lookups (`hctr_dist_select`,
+`hctr_indexed_row_copy`), per-key gradients (`hctr_expand_key_grads`), sparse update
 (`hctr_updater_update` for static variables, `hctr_det_update` for dynamic ones).  Torch is used
 for buffers, for the key-ownership masks of the multi-GPU route and for `torch.distributed`.
 
 Multi-GPU (one process per GPU): the reference's schedule -- all-gather keys, every GPU pools the
 rows it owns for the global batch, partial sums return to the sample's GPU (reduce-scatter), mean
-is divided on the receiver.  Distributed variables own row r on GPU r % N at local row r // N
-(distributed_variable.py:231-233); dynamic variables own key k on GPU k % N; a localized variable
-lives on its target GPU.
+is divided on the receiver.  The dense lookup sends each key to its owner and each row back to its
+asker instead (two all-to-alls, lookup.py:122-139).  Distributed variables own row r on GPU r % N
+at local row r // N (distributed_variable.py:231-233); dynamic variables own key k on GPU k % N; a
+localized variable lives on its target GPU.
 """
 from __future__ import annotations
 
@@ -594,6 +597,237 @@ def lookup_sparse(params, sp_ids, sp_weights=None, combiners=None, training: boo
         outs.append(_LookupFn.apply(var._token, var, ids, w, 1 if c == "mean" else 0, training,
                                     bool(use_low_frequency_filter)))
     return outs if is_list else outs[0]
+
+
+# ---- dense lookups (lookup.py:83-139) -----------------------------------------------------------
+def _row_copy(tasks, src_dtype=_lib.F32, dst_dtype=_lib.F32):
+    """hctr_indexed_row_copy over (src, src_rows, dim, index, index_div, n, dst, dst_pos) tuples:
+    one launch per HCTR_ROW_COPY_MAX_TASKS tasks.  index is int32 (read as U32: keys and rows are
+    non-negative) / int64 or None, dst_pos int32 or None."""
+    for a in range(0, len(tasks), _lib.ROW_COPY_MAX_TASKS):
+        part = tasks[a:a + _lib.ROW_COPY_MAX_TASKS]
+        arr = (_lib.RowCopyTask * len(part))()
+        for t, (src, src_rows, dim, index, div, n, dst, dst_pos) in zip(arr, part):
+            t.src, t.src_rows, t.dim = src.data_ptr(), src_rows, dim
+            if index is not None:
+                t.index = index.data_ptr()
+                t.index_type = _lib.KEY_I64 if index.dtype == torch.int64 else _lib.KEY_U32
+            t.index_div, t.n = div, n
+            t.dst, t.dst_rows = dst.data_ptr(), dst.numel() // dim
+            if dst_pos is not None:
+                t.dst_pos = dst_pos.data_ptr()
+        check(lib.hctr_indexed_row_copy(arr, len(part), src_dtype, dst_dtype, stream_ptr()))
+
+
+def _dist_select(keys: torch.Tensor, n_splits: int):
+    """(keys grouped by key % n_splits, order, splits) -- hctr_dist_select; stable inside a group"""
+    n = keys.numel()
+    out = torch.empty_like(keys)
+    order = torch.empty(n, dtype=torch.int32, device=keys.device)
+    splits = torch.empty(n_splits, dtype=torch.int32, device=keys.device)
+    nbytes = _lib.dist_select_ws_bytes(n_splits)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=keys.device)
+    kt = _lib.KEY_I64 if keys.dtype == torch.int64 else _lib.KEY_U32
+    check(lib.hctr_dist_select(ptr(keys), kt, n, n_splits, ptr(out), ptr(order), ptr(splits),
+                               ptr(ws), nbytes, stream_ptr()))
+    return out, order, splits
+
+
+def _check_indices(indices):
+    if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.int32, torch.int64) \
+            or not indices.is_cuda:
+        raise TypeError("indices must be an int32 or int64 CUDA tensor")
+
+
+def _static_rows(var: DistributedVariable, keys: torch.Tensor) -> torch.Tensor:
+    """local rows (int64) of a static variable for the sparse update; a key without a row here
+    carries INVALID, which the update drops as the lookup read it as zero"""
+    rows = var.key_map(keys.to(torch.int64))
+    ok = (keys >= 0) & (rows < var.weight.shape[0])
+    return torch.where(ok, rows, torch.full_like(rows, INVALID))
+
+
+def _local_rows_into(var, keys: torch.Tensor, train: bool, dst: torch.Tensor, dst_pos=None):
+    """dst[dst_pos[i] or i] = the variable's vector of keys[i] (keys this rank owns); returns the
+    rows a DynamicVariable handed out (None for a static variable)"""
+    n, D = keys.numel(), var.dimension
+    if isinstance(var, DynamicVariable):
+        rows = var._rows(keys, train)
+        if not train and var._lru is not None:
+            # a hybrid table gives a read-only miss a per-call row holding the initializer's
+            # value; here an evaluation lookup reads an unknown key as zero, whatever the backend
+            rows = torch.where(var._lru.find(keys) < 0, torch.full_like(rows, INVALID), rows)
+        table = var._table()
+        # (rows are per-call rows behind the slots for a tiered variable: no upper bound)
+        task = (table, 0, D, rows, 1, n, dst, dst_pos)
+    else:
+        rows = None
+        table = var.weight
+        div = _WORLD if var.target_gpu < 0 else 1
+        task = (table, table.shape[0], D, keys, div, n, dst, dst_pos)
+    if n and table.numel() == 0:
+        dst.zero_()  # nothing is stored here: every key reads as zero
+    elif n:
+        _row_copy([task])
+    return rows
+
+
+class _DenseFn(torch.autograd.Function):
+    """all2all_dense_embedding of one variable; the token input routes backward to the variable"""
+
+    @staticmethod
+    def forward(ctx, token, var, keys, train: bool):
+        n, D = keys.numel(), var.dimension
+        out = torch.empty((n, D), dtype=torch.float32, device=keys.device)
+        if _WORLD == 1:
+            rows = _local_rows_into(var, keys, train, out)
+            ctx.route = None
+            ctx.var, ctx.keys, ctx.rows = var, keys, rows
+            return out
+        from .parallel import all_to_all_single
+        # keys grouped by owner (dist_select), counts then keys to the owners (lookup.py:125-129)
+        sel, order, splits = _dist_select(keys, _WORLD)
+        send = splits.cpu().to(torch.int64)
+        recv = torch.empty(_WORLD, dtype=torch.int64)
+        if _backend_is_gloo():
+            dist.all_to_all_single(recv, send)
+        else:
+            r = torch.empty(_WORLD, dtype=torch.int64, device=keys.device)
+            dist.all_to_all_single(r, send.to(keys.device))
+            recv = r.cpu()
+        send, recv = send.tolist(), recv.tolist()
+        m = sum(recv)
+        mine = torch.empty(m, dtype=keys.dtype, device=keys.device)
+        all_to_all_single(mine, sel, recv, send)
+        # the owners' rows (lookup.py:131-134), back to the askers, into input order (:136-138)
+        vecs = torch.empty((m, D), dtype=torch.float32, device=keys.device)
+        rows = _local_rows_into(var, mine, train, vecs)
+        got = torch.empty((n, D), dtype=torch.float32, device=keys.device)
+        all_to_all_single(got, vecs, send, recv)
+        if n:
+            _row_copy([(got, n, D, None, 1, n, out, order)])
+        ctx.route = (order, send, recv)
+        ctx.var, ctx.keys, ctx.rows = var, mine, rows
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        var, keys, rows = ctx.var, ctx.keys, ctx.rows
+        g = g.contiguous().float()
+        if ctx.route is not None:
+            from .parallel import all_to_all_single
+            order, send, recv = ctx.route
+            n, D = order.numel(), var.dimension
+            sel = torch.empty((n, D), dtype=torch.float32, device=g.device)
+            if n:  # gradient rows in the order the keys were sent (gatherEx)
+                _row_copy([(g, n, D, order, 1, n, sel, None)])
+            g = torch.empty((keys.numel(), D), dtype=torch.float32, device=g.device)
+            all_to_all_single(g, sel, recv, send)
+        if rows is None:
+            rows = _static_rows(var, keys)
+        ro = torch.arange(keys.numel() + 1, dtype=torch.int64, device=g.device)
+        var._pending.append((ro, rows, keys, None, g, 0))
+        return torch.zeros(1, device=g.device), None, None, None
+
+
+def all2all_dense_embedding(param, indices, *, training: bool = True):
+    """sok.all2all_dense_embedding(param, indices) (lookup.py:122-139): a dense lookup -- one key
+    per position, no pooling -- returning fp32 indices.shape + (dimension,).  param: a distributed
+    sok.Variable or a DynamicVariable (keys live on GPU key % N).  With several GPUs every key goes
+    to its owner and every vector back to its asker (two all-to-alls; B_local * D floats per rank
+    and direction, where lookup_sparse's all-gather / reduce-scatter moves B_global * D).  A
+    training lookup inserts unknown keys into a DynamicVariable, an evaluation lookup reads them
+    as zero.  OptimizerWrapper.step applies the gradients."""
+    if isinstance(param, LocalizedVariable) or not isinstance(
+            param, (DistributedVariable, DynamicVariable)) or param.target_gpu >= 0:
+        raise TypeError("all2all_dense_embedding takes a distributed sok.Variable or a "
+                        "sok.DynamicVariable (keys are sharded by key % num_gpus)")
+    _check_indices(indices)
+    keys = indices.reshape(-1).contiguous()
+    if isinstance(param, DynamicVariable):
+        keys = keys.to(param.key_type)
+    out = _DenseFn.apply(param._token, param, keys, bool(training))
+    return out.view(*indices.shape, param.dimension)
+
+
+class _GroupFn(torch.autograd.Function):
+    """group_lookup: every table through one hctr_indexed_row_copy call"""
+
+    @staticmethod
+    def forward(ctx, params, indices, out_dtype, *handles):
+        outs, tasks = [], []
+        for p, idx in zip(params, indices):
+            w = p.weight if isinstance(p, _VariableBase) else p.detach()
+            rows, D = w.shape
+            out = torch.empty((idx.numel(), D), dtype=out_dtype, device=idx.device)
+            if idx.numel() and rows == 0:
+                out.zero_()
+            elif idx.numel():
+                tasks.append((w, rows, D, idx, 1, idx.numel(), out, None))
+            outs.append(out)
+        if tasks:
+            _row_copy(tasks, _lib.F32, _lib.F16 if out_dtype == torch.float16 else _lib.F32)
+        ctx.params, ctx.indices = params, indices
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        grads = []
+        for p, idx, g in zip(ctx.params, ctx.indices, gs):
+            if g is None:
+                grads.append(None)
+                continue
+            g = g.contiguous().float()
+            if isinstance(p, _VariableBase):
+                ro = torch.arange(idx.numel() + 1, dtype=torch.int64, device=g.device)
+                p._pending.append((ro, _static_rows(p, idx), idx, None, g, 0))
+                grads.append(torch.zeros(1, device=g.device))
+            elif p.requires_grad:
+                # sparse COO, uncoalesced, as nn.Embedding(sparse=True) gives; a row out of range
+                # was read as zero and gets a zero gradient on row 0
+                i64 = idx.to(torch.int64)
+                ok = (i64 >= 0) & (i64 < p.shape[0])
+                grads.append(torch.sparse_coo_tensor(
+                    torch.where(ok, i64, torch.zeros_like(i64)).unsqueeze(0),
+                    g * ok.unsqueeze(1), size=tuple(p.shape)))
+            else:
+                grads.append(None)
+        return (None, None, None, *grads)
+
+
+def group_lookup(params, indices, dtype=None, name=None):
+    """sok.group_lookup(params, indices, dtype=None, name=None) (lookup.py:83-96): the fused
+    tf.nn.embedding_lookup of several tables on one GPU -- one kernel launch for all of them.
+    params / indices: one item or equally long lists; a param is a static sok.Variable wholly held
+    by this GPU or a 2-D float32 CUDA tensor / nn.Parameter.  dtype: torch.float32 (default) or
+    torch.float16.  Always returns a list of indices.shape + (dimension,) tensors.  Gradients: a
+    sok.Variable's wait for OptimizerWrapper.step, a plain tensor's is a sparse COO tensor."""
+    params = list(params) if isinstance(params, (list, tuple)) else [params]
+    indices = list(indices) if isinstance(indices, (list, tuple)) else [indices]
+    if len(params) != len(indices):
+        raise RuntimeError("params and indices must have the same length")
+    if dtype is None:
+        dtype = torch.float32
+    if dtype not in (torch.float32, torch.float16):
+        raise TypeError("dtype must be torch.float32 or torch.float16")
+    for p in params:
+        if isinstance(p, DistributedVariable):
+            if (p.target_gpu < 0 and _WORLD > 1) or (p.target_gpu >= 0 and p.target_gpu != _RANK):
+                raise TypeError("group_lookup is a single-GPU lookup: the variable must be held "
+                                "wholly by this GPU (all2all_dense_embedding looks up a "
+                                "distributed one)")
+        elif not (isinstance(p, torch.Tensor) and p.dim() == 2 and p.dtype == torch.float32
+                  and p.is_cuda and p.is_contiguous()):
+            raise TypeError("params must be static sok.Variables or contiguous 2-D float32 CUDA "
+                            "tensors")
+    flat = []
+    for idx in indices:
+        _check_indices(idx)
+        flat.append(idx.reshape(-1).contiguous())
+    handles = [p._token if isinstance(p, _VariableBase) else p for p in params]
+    outs = _GroupFn.apply(params, flat, dtype, *handles)
+    dims = [p.dimension if isinstance(p, _VariableBase) else p.shape[1] for p in params]
+    return [o.view(*idx.shape, d) for o, idx, d in zip(outs, indices, dims)]
 
 
 # ---- optimizer ----------------------------------------------------------------------------------

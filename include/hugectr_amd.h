@@ -932,6 +932,63 @@ int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t n
                           float epsilon, float momentum_factor, float scaler, uint64_t times,
                           hctr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* SOK dense lookups (sok.all2all_dense_embedding, sok.group_lookup)                           */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Groups keys by the GPU that owns them; replaces the DistSelect op
+ * (R/sparse_operation_kit/kit_src/lookup/impl/select_kernel.cu:22-170, kernels/select.cc:41-70).
+ * keys [n] of key_type (non-negative); owner of a key = key mod num_splits (the non-negative
+ * remainder), num_splits in [1, 256].  out_keys [n]: the keys of owner 0, then of owner 1, ...;
+ * order [n] (int32): order[j] = the position in `keys` of out_keys[j]; splits [num_splits] (int32):
+ * keys per owner.  DIFFERENCE from the reference: inside an owner the keys keep ascending input
+ * position (a stable partition).  The reference fills a split through shared-memory atomics, so
+ * its order inside a split changes from run to run; every order gives the same embeddings, a
+ * stable one makes the result reproducible bit for bit (and with it the summation order of the
+ * sparse update that follows).  n == 0 is legal (splits = 0); n >= 2^31 is refused.
+ * workspace: device scratch of at least HCTR_DIST_SELECT_WS_BYTES(num_splits) bytes, 8-byte
+ * aligned, the caller's.  Three launches, no allocation, no host synchronisation: the caller reads
+ * splits back itself, as the reference does (select_kernel.cu:159-161). */
+#define HCTR_DIST_SELECT_WS_BYTES(num_splits) ((size_t)8 * ((size_t)(num_splits) * 1024 + 1))
+int hctr_dist_select(const void* keys, int key_type, size_t n, int num_splits, void* out_keys,
+                     int32_t* order, int32_t* splits, void* workspace, size_t workspace_bytes,
+                     hctr_stream_t stream);
+
+/* Batched indexed row copy: ONE launch for all tasks.  Replaces FusedLookupKernel
+ * (R/sparse_operation_kit/kit_src/lookup/impl/group_lookup.cu:24-42: several tables, one launch),
+ * reorderKernel and gatherExKernel (impl/reorder_kernel.cu:24-48: dst_pos / index on one task).
+ * A task means, for i < n:
+ *   r = index ? floor(index[i] / index_div) : i
+ *   dst[dst_pos ? dst_pos[i] : i][0:dim] = (0 <= r and (src_rows == 0 or r < src_rows))
+ *                                          ? src[r][0:dim] : 0
+ * index: device [n] of index_type (HCTR_KEY_U32 / HCTR_KEY_I64) or NULL; index_div >= 1 folds a
+ * distributed variable's key -> local row map (row = key / N) into the copy.  A row out of range,
+ * SIZE_MAX / -1 ("no row") included, gives a zero row -- what an evaluation lookup of an unknown key
+ * returns everywhere in this library.  src_rows == 0: no upper bound (negative rows still give
+ * zeros); src must hold at least one row when n > 0 (row 0 is read in place of a row out of
+ * range).  dst_pos: device int32 [n] or NULL; a position outside [0, dst_rows) is skipped, and
+ * without dst_pos dst_rows >= n is required.  The dst_pos of a task should be distinct (rows that
+ * share a position race).  src is src_dtype and dst is dst_dtype for every task of the call
+ * (HCTR_EMB_F32 / HCTR_EMB_F16; fp32 -> fp16 rounds to nearest even); dim may differ between
+ * tasks.  16-byte accesses when dim % 4 == 0 and src and dst are 16-byte aligned, element-wise
+ * otherwise.  The descriptors travel as kernel arguments: at most HCTR_ROW_COPY_MAX_TASKS tasks per
+ * call, no allocation, no copy, no synchronisation. */
+#define HCTR_ROW_COPY_MAX_TASKS 32
+typedef struct {
+  const void* src;
+  size_t src_rows;
+  int dim;
+  int index_type;
+  const void* index;
+  uint64_t index_div;
+  size_t n;
+  void* dst;
+  size_t dst_rows;
+  const int32_t* dst_pos;
+} hctr_row_copy_task;
+int hctr_indexed_row_copy(const hctr_row_copy_task* tasks, int num_tasks, int src_dtype,
+                          int dst_dtype, hctr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
