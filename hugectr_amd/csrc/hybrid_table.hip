@@ -17,7 +17,7 @@
 //
 // Layout for MI355X: one 128-B digest line per bucket (S = 128) filters the probe to that line plus
 // the matching key; the insert step gives every bucket to one wave, so slots are claimed without
-// CAS and in a fixed order.  Rows after the C slots are scratch: what a key that is not stored
+// CAS and in a fixed order.  Rows after the slots are per-call rows: what a key that is not stored
 // (a miss of a read-only lookup, a rejected key) reads in the current call, so the path's gather /
 // pooling kernels run unchanged on the row numbers handed out here.
 //
@@ -32,8 +32,20 @@
 // slot, every other position p gets the per-call row H + p, into which lru_stage_kernel copies the
 // host slot's row (or the initializer's value).  hctr_lru_apply_update stages the distinct host
 // slots of a step into rows H + u (u = rank in slot order), runs the sparse optimizer there and
-// writes them back.  The insert kernel reaches host slots through its Tier flag; without it the
-// kernel is the untiered one.
+// writes them back.
+//
+// One table, one code path: hctr_lru holds the LruTbl the kernels take, and an untiered table is the
+// case H = C of it (no host arrays, every slot an HBM slot).  Every host function serves both
+// kinds; where they differ it is in which kernels a lookup launches:
+//   untiered  a position that is not stored gets its per-call row, and the initializer's value in
+//             it, from the find kernel (kLruRead) or from lru_insert_kernel<K, false> (a rejected
+//             key): no launch beyond the find / insert ones;
+//   tiered    the find / insert kernels hand out slots (kLruFind, lru_insert_kernel<K, true>, whose
+//             Tier flag also makes lru_slot_row look at H), and lru_stage_kernel turns them into
+//             rows.
+// The Filter flag of lru_find_kernel is set by an inserting call whose threshold admits less than
+// every key.  lru_slot_io_kernel (slot-addressed reads and writes, the export's rows) tests
+// slot < H at run time and so needs no flag.
 //
 // Compiled as part of det.hip's unit (included at its end): the bounded sibling of the dynamic
 // table, built into every library that carries the dynamic table.  Its internal names carry an
@@ -95,13 +107,11 @@ struct LruTbl {
   uint64_t* keys;     // [C]
   uint64_t* scores;   // [C]
   uint8_t* digests;   // [C]
-  float* rows;        // [C + scratch][D]
-  float* st0;         // [C][D] or null
-  float* st1;         // [C][D] or null
-  // tiered (Tier kernels only): slots >= H live in the host arrays, row s at (s - H) * D
+  float* rows;        // [H + scratch][D]: the slots in HBM, then the per-call rows
+  float* st[2];       // optimizer states: [C][D] (tiered: the rows' shape) or null
+  // slots >= H live in the host arrays, row s at (s - H) * D.  H = C: untiered, no host arrays
   float* hrows;       // [C - H][D] host-mapped
-  float* hst0;        // [C - H][D] or null
-  float* hst1;        // [C - H][D] or null
+  float* hst[2];      // [C - H][D] or null, with the state it belongs to
   uint64_t H;
   uint64_t nb;        // buckets
   int S, D;
@@ -364,21 +374,13 @@ __global__ void __launch_bounds__(kLruBlock)
         T.scores[s] = t;
         T.digests[s] = (uint8_t)(murmur3_key(kk) >> 24);
       }
-      if (Tier) {
-        float* row = lru_slot_row<true>(T.rows, T.hrows, T.H, s, D);
-        float* s0 = T.st0 ? lru_slot_row<true>(T.st0, T.hst0, T.H, s, D) : nullptr;
-        float* s1 = T.st1 ? lru_slot_row<true>(T.st1, T.hst1, T.H, s, D) : nullptr;
-        for (int e = lane; e < D; e += kWave) {
-          row[e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
-          if (s0) s0[e] = 0.0f;
-          if (s1) s1[e] = 0.0f;
-        }
-      } else {
-        for (int e = lane; e < D; e += kWave) {
-          T.rows[s * D + e] = lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
-          if (T.st0) T.st0[s * D + e] = 0.0f;
-          if (T.st1) T.st1[s * D + e] = 0.0f;
-        }
+      // (the addresses stay inside the loop: three row pointers kept across it cost the untiered
+      // instantiation two more spilled SGPRs)
+      for (int e = lane; e < D; e += kWave) {
+        lru_slot_row<Tier>(T.rows, T.hrows, T.H, s, D)[e] =
+            lru_init_value(T.init_mode, T.init_val, T.seed, key, e);
+        if (T.st[0]) lru_slot_row<Tier>(T.st[0], T.hst[0], T.H, s, D)[e] = 0.0f;
+        if (T.st[1]) lru_slot_row<Tier>(T.st[1], T.hst[1], T.H, s, D)[e] = 0.0f;
       }
       if (!evict) filled++;
       res = s;
@@ -435,13 +437,6 @@ __global__ void __launch_bounds__(kLruBlock)
   }
   if (out_slots) out_slots[o] = i;
   if (out_scores) out_scores[o] = scores[i];
-}
-
-__global__ void __launch_bounds__(kLruBlock)
-    lru_gather_rows_kernel(const uint64_t* __restrict__ slots, size_t n,
-                           const float* __restrict__ rows, int D, float* __restrict__ out) {
-  const size_t i = blockIdx.x * (size_t)kLruBlock + threadIdx.x;
-  if (i < n * (size_t)D) out[i] = rows[slots[i / D] * D + i % D];
 }
 
 __global__ void lru_fill_kernel(float* p, size_t n, float v) {
@@ -567,10 +562,10 @@ __global__ void __launch_bounds__(kLruBlock)
   if (In && l == 0) rows[val[j]] = r;
   if (!f) return;
   const uint64_t D = (uint64_t)T.D;
-  float* hbm[3] = {T.rows + r * D, T.st0 ? T.st0 + r * D : nullptr,
-                   T.st1 ? T.st1 + r * D : nullptr};
-  float* host[3] = {T.hrows + k * D, T.hst0 ? T.hst0 + k * D : nullptr,
-                    T.hst1 ? T.hst1 + k * D : nullptr};
+  float* hbm[3] = {T.rows + r * D, T.st[0] ? T.st[0] + r * D : nullptr,
+                   T.st[1] ? T.st[1] + r * D : nullptr};
+  float* host[3] = {T.hrows + k * D, T.hst[0] ? T.hst[0] + k * D : nullptr,
+                    T.hst[1] ? T.hst[1] + k * D : nullptr};
   for (int a = 0; a < 3; a++) {
     if (!hbm[a]) continue;
     for (int e = l; e < T.D; e += gl) {
@@ -609,23 +604,13 @@ inline int lru_blocks(size_t n) { return (int)ceil_div<size_t>(n > 0 ? n : 1, (s
 using namespace hctr;
 
 struct hctr_lru {
-  size_t C = 0, S = 0, nb = 0;
-  int D = 0, key_type = HCTR_KEY_I64;
-  int init_mode = 1;
-  float init_val = 0.f;
-  uint64_t seed = 0;
-  uint64_t* keys = nullptr;
-  uint64_t* scores = nullptr;
-  uint8_t* digests = nullptr;
-  float* rows = nullptr;
-  size_t scratch = 0;  // rows after the C slots
-  float* st[2] = {nullptr, nullptr};
-  // host-memory tier: slots [H, C) keep rows and states in pinned, device-mapped host memory; the
-  // HBM arrays then hold H slots plus `scratch` per-call rows.  H = C: untiered.
-  size_t H = 0;
-  float* hrows = nullptr;                 // [C - H][D] (device address of the mapping)
-  float* hst[2] = {nullptr, nullptr};     // [C - H][D] each, with the state it belongs to
-  void* host_alloc[3] = {nullptr, nullptr, nullptr};  // the pinned allocations behind them
+  // what the kernels see, passed to them as it stands.  Slots [H, C) keep rows and states in
+  // pinned, device-mapped host memory; the HBM arrays of rows (and, tiered, of states) hold H slots
+  // plus `scratch` per-call rows.  H = C: untiered.
+  LruTbl T{};
+  int key_type = HCTR_KEY_I64;
+  size_t scratch = 0;  // rows after the H slots
+  void* host_alloc[3] = {nullptr, nullptr, nullptr};  // the pinned allocations behind hrows / hst
   uint64_t* ws_rows = nullptr;            // [ws_n] staged rows of a step (tiered)
   uint64_t t = 0;  // inserting calls so far
   unsigned long long* counters = nullptr;  // [0] occupied slots, [1] rejected keys, [2] filtered
@@ -643,46 +628,54 @@ struct hctr_lru {
   unsigned long long* tile_sums = nullptr;
   unsigned long long* d_total = nullptr;
 
-  LruTbl tbl() const {
-    LruTbl T;
-    T.keys = keys;
-    T.scores = scores;
-    T.digests = digests;
-    T.rows = rows;
-    T.st0 = st[0];
-    T.st1 = st[1];
-    T.hrows = hrows;
-    T.hst0 = hst[0];
-    T.hst1 = hst[1];
-    T.H = H;
-    T.nb = nb;
-    T.S = (int)S;
-    T.D = D;
-    T.C = C;
-    T.init_mode = init_mode;
-    T.init_val = init_val;
-    T.seed = seed;
-    return T;
-  }
-  bool tiered() const { return H < C; }
+  bool tiered() const { return T.H < T.C; }
+  int key_bytes() const { return key_type == HCTR_KEY_I64 ? 8 : 4; }
+  size_t row_bytes() const { return (size_t)T.D * sizeof(float); }
 };
 
 namespace {
 
 void lru_free(hctr_lru* h) {
-  void* ps[] = {h->keys, h->scores, h->digests, h->rows, h->st[0], h->st[1], h->counters, h->ws,
-                h->ws_tiles,
-                h->sort_temp, h->rng, h->evict_cnt, h->evict_off, h->tile_sums, h->d_total};
-  for (void* p : ps)
+  void* dev[] = {h->T.keys, h->T.scores, h->T.digests, h->T.rows, h->T.st[0], h->T.st[1],
+                 h->counters, h->ws, h->ws_tiles, h->ws_rows, h->sort_temp, h->rng, h->evict_cnt,
+                 h->evict_off, h->tile_sums, h->d_total};
+  for (void* p : dev)
     if (p) (void)hipFree(p);
-  if (h->ws_rows) (void)hipFree(h->ws_rows);
-  for (void* p : h->host_alloc)
+  void* host[] = {h->host_alloc[0], h->host_alloc[1], h->host_alloc[2], h->h_word};
+  for (void* p : host)
     if (p) (void)hipHostFree(p);
-  if (h->h_word) (void)hipHostFree(h->h_word);
   delete h;
 }
 
-// per-call workspace and, for a key-dependent initializer, scratch rows for n keys
+// f(const K* keys), K the table's key type: the key-type dispatch of every entry point
+template <typename F>
+int lru_with_keys(const hctr_lru* h, const void* keys, F f) {
+  if (h->key_type == HCTR_KEY_I64) return f(static_cast<const long long*>(keys));
+  return f(static_cast<const uint32_t*>(keys));
+}
+
+// one device word through the pinned host word: one host synchronisation
+template <typename W>
+int lru_read_word(hctr_lru* h, const unsigned long long* d, hipStream_t s, W* out) {
+  HCTR_HIP(hipMemcpyAsync(h->h_word, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HCTR_HIP(hipStreamSynchronize(s));
+  *out = (W)*h->h_word;
+  return HCTR_OK;
+}
+
+// the HBM array *a moves to a store of `rows` rows; its H slots are kept
+int lru_grow(hctr_lru* h, float** a, size_t rows, hipStream_t s) {
+  float* nr = nullptr;
+  HCTR_HIP(hipMalloc(&nr, rows * h->row_bytes()));
+  if (h->T.H)
+    HCTR_HIP(hipMemcpyAsync(nr, *a, h->T.H * h->row_bytes(), hipMemcpyDeviceToDevice, s));
+  HCTR_HIP(hipStreamSynchronize(s));
+  HCTR_HIP(hipFree(*a));
+  *a = nr;
+  return HCTR_OK;
+}
+
+// per-call workspace and per-call rows for n keys
 int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
   if (n > h->ws_n) {
     if (h->ws) HCTR_HIP(hipFree(h->ws));
@@ -704,32 +697,34 @@ int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
     }
     h->ws_n = cap;
   }
-  if (h->tiered() && n > h->scratch) {
-    // every position may need a per-call row: the HBM arrays grow to H + n rows, the H slots move
-    float** arrs[3] = {&h->rows, &h->st[0], &h->st[1]};
-    for (float** a : arrs) {
-      if (!*a) continue;
-      float* nr = nullptr;
-      HCTR_HIP(hipMalloc(&nr, (h->H + n) * (size_t)h->D * sizeof(float)));
-      if (h->H)
-        HCTR_HIP(hipMemcpyAsync(nr, *a, h->H * (size_t)h->D * sizeof(float),
-                                hipMemcpyDeviceToDevice, s));
-      HCTR_HIP(hipStreamSynchronize(s));
-      HCTR_HIP(hipFree(*a));
-      *a = nr;
-    }
-    h->scratch = n;
-  } else if (h->init_mode != 0 && n > h->scratch) {
-    // the slots' rows move to a larger store once per new largest call (scratch is per call)
-    float* nr = nullptr;
-    HCTR_HIP(hipMalloc(&nr, (h->C + n) * (size_t)h->D * sizeof(float)));
-    HCTR_HIP(hipMemcpyAsync(nr, h->rows, h->C * (size_t)h->D * sizeof(float),
-                            hipMemcpyDeviceToDevice, s));
-    HCTR_HIP(hipStreamSynchronize(s));
-    HCTR_HIP(hipFree(h->rows));
-    h->rows = nr;
+  // Per-call rows, grown once per new largest call (the slots move with their array).  Tiered:
+  // every position may need one, in the rows and in the states.  Untiered: only the rows, and only
+  // a key-dependent initializer needs more than the one row a constant takes.
+  if (n > h->scratch && (h->tiered() || h->T.init_mode != 0)) {
+    HCTR_TRY(lru_grow(h, &h->T.rows, h->T.H + n, s));
+    for (float*& st : h->T.st)
+      if (st && h->tiered()) HCTR_TRY(lru_grow(h, &st, h->T.H + n, s));
     h->scratch = n;
   }
+  return HCTR_OK;
+}
+
+// lru_find_kernel over n keys, idx[i] = kLruFind: slot or kInvalidIndex; kLruRead: row; kLruInsert
+// (call h->t, through the filter when admit_below < kLruAdmitAll): slot, kInvalidIndex for the
+// insert step or kLruFiltered, and the sort's inputs (bucket, key low / high word, position) in
+// the first four arrays of ws
+template <typename K>
+int lru_launch_find(hctr_lru* h, const K* keys, size_t n, int mode, uint64_t admit_below,
+                    uint64_t* idx, hipStream_t s) {
+  uint32_t* w[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (mode == kLruInsert)
+    for (int a = 0; a < 4; a++) w[a] = h->ws + a * h->ws_n;
+  if (sizeof(K) != 8) w[2] = nullptr;
+  auto kernel = mode == kLruInsert && admit_below < kLruAdmitAll ? lru_find_kernel<K, true>
+                                                                  : lru_find_kernel<K, false>;
+  hipLaunchKernelGGL(kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->T, keys, n, mode, h->t,
+                     idx, w[0], w[1], w[2], w[3], admit_below, h->counters);
+  HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
 
@@ -738,148 +733,122 @@ int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t admit_
                uint64_t* row_index, void* ev_keys, float* ev_rows, size_t* n_evicted,
                hipStream_t s) {
   HCTR_TRY(lru_reserve(h, n, s));
-  const int gl = lru_group_lanes(h->D);
-  const int stage_blocks = lru_blocks(n * (size_t)gl);
   // tiered: the find / insert kernels write slots to ws_rows, lru_stage_kernel the rows
   uint64_t* const slot_out = h->tiered() ? h->ws_rows : row_index;
-  if (!insert && h->tiered()) {
-    hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), keys, n, (int)kLruFind, h->t, slot_out, nullptr, nullptr, nullptr,
-                       nullptr, kLruAdmitAll, nullptr);
-    HCTR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lru_stage_kernel<K>, dim3(stage_blocks), dim3(kLruBlock), 0, s, h->tbl(),
-                       keys, n, gl, slot_out, row_index);
-    HCTR_LAUNCH_CHECK();
-    if (n_evicted) *n_evicted = 0;
-    return HCTR_OK;
-  }
+  if (n_evicted) *n_evicted = 0;
   if (!insert) {
-    hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), keys, n, (int)kLruRead, h->t, row_index, nullptr, nullptr, nullptr,
-                       nullptr, kLruAdmitAll, nullptr);
-    HCTR_LAUNCH_CHECK();
-    if (n_evicted) *n_evicted = 0;
-    return HCTR_OK;
-  }
-  const uint64_t t = ++h->t;
-  const size_t m = h->ws_n;
-  uint32_t *bkt = h->ws, *klo = h->ws + m, *khi = h->ws + 2 * m, *seq = h->ws + 3 * m,
-           *g = h->ws + 4 * m, *tk = h->ws + 5 * m, *pa = h->ws + 6 * m, *pb = h->ws + 7 * m;
-  const bool wide = sizeof(K) == 8;
-  if (admit_below < kLruAdmitAll)
-    hipLaunchKernelGGL((lru_find_kernel<K, true>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), keys, n, (int)kLruInsert, t, slot_out, bkt, klo,
-                       wide ? khi : nullptr, seq, admit_below, h->counters);
-  else
-    hipLaunchKernelGGL((lru_find_kernel<K, false>), dim3(lru_blocks(n)), dim3(kLruBlock), 0, s,
-                       h->tbl(), keys, n, (int)kLruInsert, t, slot_out, bkt, klo,
-                       wide ? khi : nullptr, seq, kLruAdmitAll, nullptr);
-  HCTR_LAUNCH_CHECK();
-  // (bucket, key) order by three stable passes: key low word, key high word, bucket
-  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, klo, tk, seq, pa, n, 32, s));
-  if (wide) {
-    hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, khi, pa, n,
+    HCTR_TRY(lru_launch_find(h, keys, n, h->tiered() ? kLruFind : kLruRead, kLruAdmitAll, slot_out,
+                             s));
+  } else {
+    const uint64_t t = ++h->t;
+    HCTR_TRY(lru_launch_find(h, keys, n, kLruInsert, admit_below, slot_out, s));
+    const size_t m = h->ws_n;
+    uint32_t *bkt = h->ws, *klo = h->ws + m, *khi = h->ws + 2 * m, *seq = h->ws + 3 * m,
+             *g = h->ws + 4 * m, *tk = h->ws + 5 * m, *pa = h->ws + 6 * m, *pb = h->ws + 7 * m;
+    // (bucket, key) order by three stable passes: key low word, key high word, bucket
+    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, klo, tk, seq, pa, n, 32, s));
+    if (sizeof(K) == 8) {
+      hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, khi, pa,
+                         n, g);
+      HCTR_LAUNCH_CHECK();
+      HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, 32, s));
+      std::swap(pa, pb);
+    }
+    hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, bkt, pa, n,
                        g);
     HCTR_LAUNCH_CHECK();
-    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, 32, s));
-    std::swap(pa, pb);
-  }
-  hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, bkt, pa, n, g);
-  HCTR_LAUNCH_CHECK();
-  int end_bit = 1;
-  while (end_bit < 32 && ((size_t)1 << end_bit) <= h->nb) end_bit++;
-  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, end_bit, s));
-  // tk = buckets in sorted order, pb = positions
-  const int wb = (int)ceil_div<size_t>(h->nb, (size_t)kLruWavesPerBlock);
-  hipLaunchKernelGGL(lru_count_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->tbl(), keys, tk, pb,
-                     (uint32_t)n, t, h->rng, h->evict_cnt);
-  HCTR_LAUNCH_CHECK();
-  HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(h->evict_cnt, h->nb, h->tile_sums, h->d_total,
-                                               h->evict_off, s));
-  if (h->tiered()) {
-    hipLaunchKernelGGL((lru_insert_kernel<K, true>), dim3(wb), dim3(kLruBlock), 0, s, h->tbl(),
-                       keys, pb, h->rng, h->evict_off, t, slot_out, ev_keys, (int)sizeof(K),
-                       ev_rows, h->counters);
+    int end_bit = 1;
+    while (end_bit < 32 && ((uint64_t)1 << end_bit) <= h->T.nb) end_bit++;
+    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, end_bit, s));
+    // tk = buckets in sorted order, pb = positions
+    const int wb = (int)ceil_div<size_t>(h->T.nb, (size_t)kLruWavesPerBlock);
+    hipLaunchKernelGGL(lru_count_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->T, keys, tk, pb,
+                       (uint32_t)n, t, h->rng, h->evict_cnt);
     HCTR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lru_stage_kernel<K>, dim3(stage_blocks), dim3(kLruBlock), 0, s, h->tbl(),
-                       keys, n, gl, slot_out, row_index);
-  } else {
-    hipLaunchKernelGGL((lru_insert_kernel<K, false>), dim3(wb), dim3(kLruBlock), 0, s, h->tbl(),
-                       keys, pb, h->rng,
-                       h->evict_off, t, row_index, ev_keys, (int)sizeof(K), ev_rows, h->counters);
+    HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(h->evict_cnt, h->T.nb, h->tile_sums, h->d_total,
+                                                 h->evict_off, s));
+    auto kernel = h->tiered() ? lru_insert_kernel<K, true> : lru_insert_kernel<K, false>;
+    hipLaunchKernelGGL(kernel, dim3(wb), dim3(kLruBlock), 0, s, h->T, keys, pb, h->rng,
+                       h->evict_off, t, slot_out, ev_keys, (int)sizeof(K), ev_rows, h->counters);
+    HCTR_LAUNCH_CHECK();
   }
-  HCTR_LAUNCH_CHECK();
-  if (n_evicted) {
-    HCTR_HIP(hipMemcpyAsync(h->h_word, h->d_total, sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, s));
-    HCTR_HIP(hipStreamSynchronize(s));
-    *n_evicted = (size_t)*h->h_word;
+  if (h->tiered()) {
+    const int gl = lru_group_lanes(h->T.D);
+    hipLaunchKernelGGL(lru_stage_kernel<K>, dim3(lru_blocks(n * (size_t)gl)), dim3(kLruBlock), 0, s,
+                       h->T, keys, n, gl, slot_out, row_index);
+    HCTR_LAUNCH_CHECK();
   }
+  if (insert && n_evicted) HCTR_TRY(lru_read_word(h, h->d_total, s, n_evicted));
   return HCTR_OK;
 }
 
-int lru_read_counter(hctr_lru* h, int which, uint64_t* out, hipStream_t s) {
-  HCTR_HIP(hipMemcpyAsync(h->h_word, h->counters + which, sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, s));
-  HCTR_HIP(hipStreamSynchronize(s));
-  *out = (uint64_t)*h->h_word;
-  return HCTR_OK;
+// the checks and the empty call shared by hctr_lru_lookup_index and _filtered
+int lru_lookup_checked(hctr_lru* h, const void* keys, size_t n, int insert, uint64_t admit_below,
+                       uint64_t* row_index, void* evict_keys, float* evict_rows, size_t* n_evicted,
+                       hctr_stream_t stream) {
+  HCTR_REQUIRE(h, "null handle");
+  HCTR_REQUIRE(n <= ((size_t)1 << 24), "at most 2^24 keys per call");
+  HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
+  HCTR_REQUIRE(!evict_rows || evict_keys, "evict_rows needs evict_keys");
+  HCTR_REQUIRE(admit_below <= kLruAdmitAll, "admit_below must be in [0, 2^32]");
+  if (n == 0) {
+    if (n_evicted) *n_evicted = 0;
+    if (insert) h->t++;
+    return HCTR_OK;
+  }
+  return lru_with_keys(h, keys, [&](auto* k) {
+    return lru_lookup(h, k, n, insert, admit_below, row_index, evict_keys, evict_rows, n_evicted,
+                      as_stream(stream));
+  });
 }
+
+// device buffers of one call, freed on every return path
+struct LruTemps {
+  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+  int n = 0;
+  ~LruTemps() {
+    for (int i = 0; i < n; i++) (void)hipFree(p[i]);
+  }
+  template <typename T>
+  int alloc(T** out, size_t bytes) {
+    HCTR_HIP(hipMalloc(out, bytes));
+    p[n++] = *out;
+    return HCTR_OK;
+  }
+};
 
 // occupied slots with score >= min_score in slot order; *total = how many there are, the first
 // min(total, max_keys) of them are written
 int lru_export(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* slots, uint64_t* scores,
                float* rows, size_t max_keys, size_t* exported, size_t* total, hipStream_t s) {
+  const LruTbl& T = h->T;
+  const size_t C = T.C;
+  LruTemps tmp;
   uint32_t *flag = nullptr, *off = nullptr;
-  uint64_t* tmp_slots = nullptr;
   unsigned long long* tiles = nullptr;
-  const size_t C = h->C;
-  int rc = HCTR_OK;
-  if (hipMalloc(&flag, C * 4) != hipSuccess || hipMalloc(&off, (C + 1) * 4) != hipSuccess ||
-      hipMalloc(&tiles, (C / 1024 + 2) * 8) != hipSuccess ||
-      (rows && !slots && hipMalloc(&tmp_slots, (max_keys ? max_keys : 1) * 8) != hipSuccess)) {
-    (void)hipGetLastError();
-    set_error("hctr_lru_export: out of device memory");
-    rc = HCTR_ERR_HIP;
+  HCTR_TRY(tmp.alloc(&flag, C * 4));
+  HCTR_TRY(tmp.alloc(&off, (C + 1) * 4));
+  HCTR_TRY(tmp.alloc(&tiles, (C / 1024 + 2) * 8));
+  if (rows && !slots) HCTR_TRY(tmp.alloc(&slots, (max_keys ? max_keys : 1) * 8));
+  hipLaunchKernelGGL(lru_occupied_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, T.keys,
+                     T.scores, C, min_score, flag);
+  HCTR_LAUNCH_CHECK();
+  HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(flag, C, tiles, h->d_total, off, s));
+  hipLaunchKernelGGL(lru_export_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, T.keys, C, off,
+                     T.scores, min_score, max_keys, h->key_bytes(), keys, slots, scores);
+  HCTR_LAUNCH_CHECK();
+  size_t matched = 0;
+  HCTR_TRY(lru_read_word(h, h->d_total, s, &matched));
+  const size_t got = matched < max_keys ? matched : max_keys;
+  if (rows && got) {
+    hipLaunchKernelGGL(lru_slot_io_kernel, dim3(lru_blocks(got * (size_t)T.D)), dim3(kLruBlock), 0,
+                       s, T.rows, T.hrows, T.H, T.C, slots, got, T.D, 0, rows);
+    HCTR_LAUNCH_CHECK();
   }
-  if (rc == HCTR_OK) {
-    uint64_t* sl = slots ? slots : tmp_slots;
-    hipLaunchKernelGGL(lru_occupied_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
-                       h->scores, C, min_score, flag);
-    rc = exclusive_scan_to_offsets<uint32_t>(flag, C, tiles, h->d_total, off, s);
-    if (rc == HCTR_OK) {
-      hipLaunchKernelGGL(lru_export_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, s, h->keys,
-                         C, off, h->scores, min_score, max_keys, h->key_type == HCTR_KEY_I64 ? 8 : 4,
-                         keys, sl, scores);
-      if (hipMemcpyAsync(h->h_word, h->d_total, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-          hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hctr_lru_export: HIP error");
-        rc = HCTR_ERR_HIP;
-      }
-    }
-    if (rc == HCTR_OK) {
-      const size_t got = (size_t)*h->h_word < max_keys ? (size_t)*h->h_word : max_keys;
-      if (rows && got && h->tiered())
-        hipLaunchKernelGGL(lru_slot_io_kernel, dim3(lru_blocks(got * (size_t)h->D)),
-                           dim3(kLruBlock), 0, s, h->rows, h->hrows, (uint64_t)h->H,
-                           (uint64_t)h->C, sl, got, h->D, 0, rows);
-      else if (rows && got)
-        hipLaunchKernelGGL(lru_gather_rows_kernel, dim3(lru_blocks(got * (size_t)h->D)),
-                           dim3(kLruBlock), 0, s, sl, got, h->rows, h->D, rows);
-      if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-        set_error("hctr_lru_export: HIP error");
-        rc = HCTR_ERR_HIP;
-      }
-      *exported = got;
-      if (total) *total = (size_t)*h->h_word;
-    }
-  }
-  if (flag) (void)hipFree(flag);
-  if (off) (void)hipFree(off);
-  if (tiles) (void)hipFree(tiles);
-  if (tmp_slots) (void)hipFree(tmp_slots);
-  return rc;
+  HCTR_HIP(hipStreamSynchronize(s));  // before the temporaries go
+  *exported = got;
+  if (total) *total = matched;
+  return HCTR_OK;
 }
 
 // pinned, device-mapped host memory (as hctr_tiered_create's), zeroed; *dev = its device address
@@ -896,13 +865,13 @@ bool lru_host_alloc(hctr_lru* h, int which, size_t bytes, float** dev) {
 // an array's (HBM part, host part): 0 = rows, 1 + i = state i (null while not allocated)
 bool lru_array(hctr_lru* h, int array, float** hbm, float** host) {
   if (array == 0) {
-    *hbm = h->rows;
-    *host = h->hrows;
+    *hbm = h->T.rows;
+    *host = h->T.hrows;
     return true;
   }
-  if (array < 1 || array > 2 || !h->st[array - 1]) return false;
-  *hbm = h->st[array - 1];
-  *host = h->hst[array - 1];
+  if (array < 1 || array > 2 || !h->T.st[array - 1]) return false;
+  *hbm = h->T.st[array - 1];
+  *host = h->T.hst[array - 1];
   return true;
 }
 
@@ -931,45 +900,47 @@ int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key
   HCTR_REQUIRE(hbm_slots >= C || hbm_slots % bucket_size == 0,
                "hbm_slots must be a multiple of bucket_size");
   hctr_lru* h = new hctr_lru();
-  h->C = C;
-  h->H = hbm_slots < C ? hbm_slots : C;
-  h->S = bucket_size;
-  h->nb = C / bucket_size;
-  h->D = dim;
+  LruTbl& T = h->T;
+  T.C = C;
+  T.H = hbm_slots < C ? hbm_slots : C;
+  T.S = (int)bucket_size;
+  T.nb = C / bucket_size;
+  T.D = dim;
   h->key_type = key_type;
-  h->seed = seed;
+  T.seed = seed;
+  T.init_mode = 1;
   const std::string ini = initializer ? initializer : "";
   if (ini == "ones") {
-    h->init_mode = 0;
-    h->init_val = 1.f;
+    T.init_mode = 0;
+    T.init_val = 1.f;
   } else if (ini == "zeros") {
-    h->init_mode = 0;
-    h->init_val = 0.f;
+    T.init_mode = 0;
+    T.init_val = 0.f;
   } else {
     char* end = nullptr;
     const float v = ini.empty() ? 0.f : strtof(ini.c_str(), &end);
     if (!ini.empty() && end && *end == '\0') {
-      h->init_mode = 0;
-      h->init_val = v;
+      T.init_mode = 0;
+      T.init_val = v;
     }
   }
   h->scratch = 1;  // a constant initializer needs one row; others grow it to the largest call
-  bool ok = hipMalloc(&h->keys, C * 8) == hipSuccess &&
-            hipMalloc(&h->scores, C * 8) == hipSuccess &&
-            hipMalloc(&h->digests, C) == hipSuccess &&
-            hipMalloc(&h->rows, (h->H + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
+  const size_t hbm_bytes = (T.H + h->scratch) * h->row_bytes();
+  bool ok = hipMalloc(&T.keys, C * 8) == hipSuccess &&
+            hipMalloc(&T.scores, C * 8) == hipSuccess &&
+            hipMalloc(&T.digests, C) == hipSuccess &&
+            hipMalloc(&T.rows, hbm_bytes) == hipSuccess &&
             hipMalloc(&h->counters, 3 * sizeof(unsigned long long)) == hipSuccess &&
-            hipMalloc(&h->rng, 2 * h->nb * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&h->evict_cnt, h->nb * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&h->evict_off, (h->nb + 1) * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&h->tile_sums, (h->nb / 1024 + 2) * 8) == hipSuccess &&
+            hipMalloc(&h->rng, 2 * T.nb * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&h->evict_cnt, T.nb * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&h->evict_off, (T.nb + 1) * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&h->tile_sums, (T.nb / 1024 + 2) * 8) == hipSuccess &&
             hipMalloc(&h->d_total, sizeof(unsigned long long)) == hipSuccess &&
             hipHostMalloc(&h->h_word, sizeof(unsigned long long)) == hipSuccess;
-  if (ok && h->tiered())
-    ok = lru_host_alloc(h, 0, (C - h->H) * (size_t)dim * sizeof(float), &h->hrows);
+  if (ok && h->tiered()) ok = lru_host_alloc(h, 0, (C - T.H) * h->row_bytes(), &T.hrows);
   if (ok)
-    ok = hipMemset(h->digests, 0, C) == hipSuccess &&
-         hipMemset(h->rows, 0, (h->H + h->scratch) * (size_t)dim * sizeof(float)) == hipSuccess &&
+    ok = hipMemset(T.digests, 0, C) == hipSuccess &&
+         hipMemset(T.rows, 0, hbm_bytes) == hipSuccess &&
          hipMemset(h->counters, 0, 3 * sizeof(unsigned long long)) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -977,11 +948,11 @@ int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key
     lru_free(h);
     return HCTR_ERR_HIP;
   }
-  hipLaunchKernelGGL(lru_clear_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, 0, h->keys,
-                     h->scores, C);
-  if (h->init_mode == 0 && !h->tiered())
+  hipLaunchKernelGGL(lru_clear_kernel, dim3(lru_blocks(C)), dim3(kLruBlock), 0, 0, T.keys,
+                     T.scores, C);
+  if (T.init_mode == 0 && !h->tiered())
     hipLaunchKernelGGL(lru_fill_kernel, dim3(lru_blocks((size_t)dim)), dim3(kLruBlock), 0, 0,
-                       h->rows + C * (size_t)dim, (size_t)dim, h->init_val);
+                       T.rows + C * (size_t)dim, (size_t)dim, T.init_val);
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
     set_error("hctr_lru_create: initialisation failed");
     lru_free(h);
@@ -1001,42 +972,15 @@ int hctr_lru_destroy(hctr_lru* h) {
 int hctr_lru_lookup_index(hctr_lru* h, const void* keys, size_t n, int insert, uint64_t* row_index,
                           void* evict_keys, float* evict_rows, size_t* n_evicted,
                           hctr_stream_t stream) {
-  HCTR_REQUIRE(h, "null handle");
-  HCTR_REQUIRE(n <= ((size_t)1 << 24), "at most 2^24 keys per call");
-  HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
-  HCTR_REQUIRE(!evict_rows || evict_keys, "evict_rows needs evict_keys");
-  if (n == 0) {
-    if (n_evicted) *n_evicted = 0;
-    if (insert) h->t++;
-    return HCTR_OK;
-  }
-  const hipStream_t s = as_stream(stream);
-  if (h->key_type == HCTR_KEY_I64)
-    return lru_lookup<long long>(h, (const long long*)keys, n, insert, kLruAdmitAll, row_index,
-                                 evict_keys, evict_rows, n_evicted, s);
-  return lru_lookup<uint32_t>(h, (const uint32_t*)keys, n, insert, kLruAdmitAll, row_index,
-                              evict_keys, evict_rows, n_evicted, s);
+  return lru_lookup_checked(h, keys, n, insert, kLruAdmitAll, row_index, evict_keys, evict_rows,
+                            n_evicted, stream);
 }
 
 int hctr_lru_lookup_index_filtered(hctr_lru* h, const void* keys, size_t n, uint64_t admit_below,
                                    uint64_t* row_index, void* evict_keys, float* evict_rows,
                                    size_t* n_evicted, hctr_stream_t stream) {
-  HCTR_REQUIRE(h, "null handle");
-  HCTR_REQUIRE(n <= ((size_t)1 << 24), "at most 2^24 keys per call");
-  HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
-  HCTR_REQUIRE(!evict_rows || evict_keys, "evict_rows needs evict_keys");
-  HCTR_REQUIRE(admit_below <= kLruAdmitAll, "admit_below must be in [0, 2^32]");
-  if (n == 0) {
-    if (n_evicted) *n_evicted = 0;
-    h->t++;
-    return HCTR_OK;
-  }
-  const hipStream_t s = as_stream(stream);
-  if (h->key_type == HCTR_KEY_I64)
-    return lru_lookup<long long>(h, (const long long*)keys, n, 1, admit_below, row_index,
-                                 evict_keys, evict_rows, n_evicted, s);
-  return lru_lookup<uint32_t>(h, (const uint32_t*)keys, n, 1, admit_below, row_index, evict_keys,
-                              evict_rows, n_evicted, s);
+  return lru_lookup_checked(h, keys, n, 1, admit_below, row_index, evict_keys, evict_rows,
+                            n_evicted, stream);
 }
 
 int hctr_lru_compact(hctr_lru* h, size_t batch, size_t n, const long long* offsets,
@@ -1057,14 +1001,10 @@ int hctr_lru_compact(hctr_lru* h, size_t batch, size_t n, const long long* offse
   HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(keep, n, h->ws_tiles, h->d_total, pos, s));
   const size_t m = n > batch + 1 ? n : batch + 1;
   hipLaunchKernelGGL(lru_compact_kernel, dim3(lru_blocks(m)), dim3(kLruBlock), 0, s, batch,
-                     offsets, n, rows, keys, h->key_type == HCTR_KEY_I64 ? 8 : 4, weights, pos,
-                     out_offsets, out_rows, out_keys, out_weights);
+                     offsets, n, rows, keys, h->key_bytes(), weights, pos, out_offsets, out_rows,
+                     out_keys, out_weights);
   HCTR_LAUNCH_CHECK();
-  HCTR_HIP(hipMemcpyAsync(h->h_word, h->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                          s));
-  HCTR_HIP(hipStreamSynchronize(s));
-  *n_kept = (size_t)*h->h_word;
-  return HCTR_OK;
+  return lru_read_word(h, h->d_total, s, n_kept);
 }
 
 int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
@@ -1072,45 +1012,35 @@ int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
   HCTR_REQUIRE(h, "null handle");
   HCTR_REQUIRE(n == 0 || (keys && row_index), "keys / row_index are null");
   if (n == 0) return HCTR_OK;
-  const hipStream_t s = as_stream(stream);
-  if (h->key_type == HCTR_KEY_I64)
-    hipLaunchKernelGGL((lru_find_kernel<long long, false>), dim3(lru_blocks(n)), dim3(kLruBlock),
-                       0, s, h->tbl(), (const long long*)keys, n, (int)kLruFind, h->t, row_index,
-                       nullptr, nullptr, nullptr, nullptr, kLruAdmitAll, nullptr);
-  else
-    hipLaunchKernelGGL((lru_find_kernel<uint32_t, false>), dim3(lru_blocks(n)), dim3(kLruBlock),
-                       0, s, h->tbl(), (const uint32_t*)keys, n, (int)kLruFind, h->t, row_index,
-                       nullptr, nullptr, nullptr, nullptr, kLruAdmitAll, nullptr);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
+  return lru_with_keys(h, keys, [&](auto* k) {
+    return lru_launch_find(h, k, n, kLruFind, kLruAdmitAll, row_index, as_stream(stream));
+  });
 }
 
 int hctr_lru_rows(hctr_lru* h, float** rows, size_t* capacity) {
   HCTR_REQUIRE(h && rows && capacity, "null argument");
-  *rows = h->rows;
-  *capacity = h->H;  // = C on an untiered table
+  *rows = h->T.rows;
+  *capacity = h->T.H;  // = C on an untiered table
   return HCTR_OK;
 }
 
 int hctr_lru_state(hctr_lru* h, int i, float** state, hctr_stream_t stream) {
   HCTR_REQUIRE(h && state, "null argument");
   HCTR_REQUIRE(i == 0 || i == 1, "state index must be 0 or 1");
-  if (!h->st[i] && h->tiered()) {
-    // the HBM part has the rows' shape (H slots + the per-call rows); the rest is host memory
-    const size_t bytes = (h->H + h->scratch) * (size_t)h->D * sizeof(float);
-    HCTR_HIP(hipMalloc(&h->st[i], bytes));
-    HCTR_HIP(hipMemsetAsync(h->st[i], 0, bytes, as_stream(stream)));
-    if (!lru_host_alloc(h, 1 + i, (h->C - h->H) * (size_t)h->D * sizeof(float), &h->hst[i])) {
+  LruTbl& T = h->T;
+  if (!T.st[i]) {
+    // tiered: the HBM part has the rows' shape (H slots + the per-call rows), the rest is host
+    // memory; untiered: the C slots
+    const size_t bytes = (h->tiered() ? T.H + h->scratch : T.C) * h->row_bytes();
+    HCTR_HIP(hipMalloc(&T.st[i], bytes));
+    HCTR_HIP(hipMemsetAsync(T.st[i], 0, bytes, as_stream(stream)));
+    if (h->tiered() && !lru_host_alloc(h, 1 + i, (T.C - T.H) * h->row_bytes(), &T.hst[i])) {
       (void)hipGetLastError();
       set_error("hctr_lru_state: host allocation failed");
       return HCTR_ERR_HIP;
     }
-  } else if (!h->st[i]) {
-    const size_t bytes = h->C * (size_t)h->D * sizeof(float);
-    HCTR_HIP(hipMalloc(&h->st[i], bytes));
-    HCTR_HIP(hipMemsetAsync(h->st[i], 0, bytes, as_stream(stream)));
   }
-  *state = h->st[i];
+  *state = T.st[i];
   return HCTR_OK;
 }
 
@@ -1131,34 +1061,31 @@ int hctr_lru_export_if(hctr_lru* h, uint64_t min_score, void* keys, uint64_t* sl
 
 int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream) {
   HCTR_REQUIRE(h && out, "null argument");
-  uint64_t v = 0;
-  HCTR_TRY(lru_read_counter(h, 0, &v, as_stream(stream)));
-  *out = (size_t)v;
-  return HCTR_OK;
+  return lru_read_word(h, h->counters + 0, as_stream(stream), out);
 }
 
 int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
   HCTR_REQUIRE(h && out, "null argument");
-  return lru_read_counter(h, 1, out, as_stream(stream));
+  return lru_read_word(h, h->counters + 1, as_stream(stream), out);
 }
 
 int hctr_lru_filtered_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream) {
   HCTR_REQUIRE(h && out, "null argument");
-  return lru_read_counter(h, 2, out, as_stream(stream));
+  return lru_read_word(h, h->counters + 2, as_stream(stream), out);
 }
 
 int hctr_lru_placement(const hctr_lru* h, size_t* hbm_slots, size_t* hbm_rows, size_t* host_rows) {
   HCTR_REQUIRE(h && hbm_slots && hbm_rows && host_rows, "null argument");
-  *hbm_slots = h->H;
-  *hbm_rows = h->H + h->scratch;
-  *host_rows = h->C - h->H;
+  *hbm_slots = h->T.H;
+  *hbm_rows = h->T.H + h->scratch;
+  *host_rows = h->T.C - h->T.H;
   return HCTR_OK;
 }
 
 int hctr_lru_host_part(const hctr_lru* h, int array, float** host) {
   HCTR_REQUIRE(h && host, "null argument");
   HCTR_REQUIRE(array >= 0 && array <= 2, "array must be 0 (rows), 1 or 2 (states)");
-  *host = array == 0 ? h->hrows : h->hst[array - 1];
+  *host = array == 0 ? h->T.hrows : h->T.hst[array - 1];
   return HCTR_OK;
 }
 
@@ -1170,9 +1097,8 @@ static int lru_slot_io(hctr_lru* h, int array, const uint64_t* slots, size_t n, 
   HCTR_REQUIRE(lru_array(h, array, &hbm, &host),
                "array must be 0 (rows) or 1 + i for an allocated state i");
   if (n == 0) return HCTR_OK;
-  hipLaunchKernelGGL(lru_slot_io_kernel, dim3(lru_blocks(n * (size_t)h->D)), dim3(kLruBlock), 0,
-                     as_stream(stream), hbm, host, (uint64_t)h->H, (uint64_t)h->C, slots, n, h->D,
-                     dir, buf);
+  hipLaunchKernelGGL(lru_slot_io_kernel, dim3(lru_blocks(n * (size_t)h->T.D)), dim3(kLruBlock), 0,
+                     as_stream(stream), hbm, host, h->T.H, h->T.C, slots, n, h->T.D, dir, buf);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -1195,21 +1121,22 @@ int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t n
   HCTR_REQUIRE(h && u, "null handle");
   HCTR_REQUIRE(nnz <= ((size_t)1 << 24), "at most 2^24 keys per call");
   HCTR_REQUIRE(nnz == 0 || slots, "slots are null");
+  const LruTbl& T = h->T;
   const int ns = optimizer == HCTR_OPT_ADAM ? 2 : (optimizer == HCTR_OPT_SGD ? 0 : 1);
-  HCTR_REQUIRE((ns < 1 || h->st[0]) && (ns < 2 || h->st[1]),
+  HCTR_REQUIRE((ns < 1 || T.st[0]) && (ns < 2 || T.st[1]),
                "the optimizer's states are not allocated (hctr_lru_state)");
   if (!h->tiered() || nnz == 0)
     return hctr_updater_update(u, buckets, nnz, bucket_range, slots, grad, grad_dtype, optimizer,
                                HCTR_UPDATE_LOCAL, lr, beta1, beta2, epsilon, momentum_factor,
-                               scaler, times, h->rows, h->st[0], h->st[1], stream);
+                               scaler, times, T.rows, T.st[0], T.st[1], stream);
   const hipStream_t s = as_stream(stream);
   HCTR_TRY(lru_reserve(h, nnz + 1, s));
   const size_t m = h->ws_n;
   uint32_t *ka = h->ws, *kb = h->ws + m, *va = h->ws + 2 * m, *vb = h->ws + 3 * m,
            *first = h->ws + 4 * m, *off = h->ws + 5 * m;
-  const uint64_t host_slots = h->C - h->H;
+  const uint64_t host_slots = T.C - T.H;
   hipLaunchKernelGGL(lru_step_keys_kernel, dim3(lru_blocks(nnz)), dim3(kLruBlock), 0, s, slots,
-                     nnz, (uint64_t)h->H, (uint64_t)h->C, ka, va, h->ws_rows);
+                     nnz, T.H, T.C, ka, va, h->ws_rows);
   HCTR_LAUNCH_CHECK();
   // host slots in ascending order (stable: positions of one slot keep their order)
   int end_bit = 1;
@@ -1219,25 +1146,24 @@ int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t n
                      (uint32_t)host_slots, first);
   HCTR_LAUNCH_CHECK();
   HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(first, nnz, h->ws_tiles, h->d_total, off, s));
-  const int gl = lru_group_lanes(h->D);
+  const int gl = lru_group_lanes(T.D);
   const int blocks = lru_blocks(nnz * (size_t)gl);
-  hipLaunchKernelGGL(lru_step_stage_kernel<true>, dim3(blocks), dim3(kLruBlock), 0, s, h->tbl(), kb,
-                     vb, first, off, nnz, gl, h->ws_rows);
+  hipLaunchKernelGGL(lru_step_stage_kernel<true>, dim3(blocks), dim3(kLruBlock), 0, s, T, kb, vb,
+                     first, off, nnz, gl, h->ws_rows);
   HCTR_LAUNCH_CHECK();
   HCTR_TRY(hctr_updater_update(u, buckets, nnz, bucket_range, h->ws_rows, grad, grad_dtype,
                                optimizer, HCTR_UPDATE_LOCAL, lr, beta1, beta2, epsilon,
-                               momentum_factor, scaler, times, h->rows, h->st[0], h->st[1],
-                               stream));
-  hipLaunchKernelGGL(lru_step_stage_kernel<false>, dim3(blocks), dim3(kLruBlock), 0, s, h->tbl(),
-                     kb, vb, first, off, nnz, gl, h->ws_rows);
+                               momentum_factor, scaler, times, T.rows, T.st[0], T.st[1], stream));
+  hipLaunchKernelGGL(lru_step_stage_kernel<false>, dim3(blocks), dim3(kLruBlock), 0, s, T, kb, vb,
+                     first, off, nnz, gl, h->ws_rows);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
 
 int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size) {
   HCTR_REQUIRE(h && capacity && bucket_size, "null argument");
-  *capacity = h->C;
-  *bucket_size = h->S;
+  *capacity = h->T.C;
+  *bucket_size = (size_t)h->T.S;
   return HCTR_OK;
 }
 

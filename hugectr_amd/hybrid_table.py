@@ -84,6 +84,11 @@ class HybridTable:
     def tiered(self) -> bool:
         return self.hbm_slots < self.capacity
 
+    def update_rows(self, staged: int) -> int:
+        """the row bound of an hctr_updater that serves apply_update calls of up to `staged` keys:
+        the slots in HBM and, on a tiered table, the host slots staged after them"""
+        return self.hbm_slots + (int(staged) if self.tiered else 0)
+
     def placement(self) -> Tuple[int, int, int]:
         """(hbm_slots, rows of the HBM row store (slots + per-call rows), host rows)"""
         a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
@@ -117,28 +122,18 @@ class HybridTable:
         idx = torch.empty(n, dtype=torch.int64, device=keys.device)
         if insert:
             self.call_ns.append(int(self.clock()))
-        if admit is not None and insert:
-            ab = admit_below(admit)
-            if not evict:
-                check(lib.hctr_lru_lookup_index_filtered(self._h, ptr(keys), n, ab, ptr(idx), None,
-                                                         None, None, stream_ptr()))
-                return idx
+        ek = ev = m = None
+        if evict:
             ek = torch.empty(n, dtype=self.key_dtype, device=keys.device)
             ev = torch.empty((n, self.dim), dtype=torch.float32, device=keys.device)
             m = ctypes.c_size_t()
-            check(lib.hctr_lru_lookup_index_filtered(self._h, ptr(keys), n, ab, ptr(idx), ptr(ek),
-                                                     ptr(ev), ctypes.byref(m), stream_ptr()))
-            return idx, ek[:m.value], ev[:m.value]
-        if not evict:
-            check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, ptr(idx),
-                                            None, None, None, stream_ptr()))
-            return idx
-        ek = torch.empty(n, dtype=self.key_dtype, device=keys.device)
-        ev = torch.empty((n, self.dim), dtype=torch.float32, device=keys.device)
-        m = ctypes.c_size_t()
-        check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, ptr(idx),
-                                        ptr(ek), ptr(ev), ctypes.byref(m), stream_ptr()))
-        return idx, ek[:m.value], ev[:m.value]
+        out = (ptr(idx), ptr(ek), ptr(ev), ctypes.byref(m) if evict else None, stream_ptr())
+        if admit is not None and insert:
+            check(lib.hctr_lru_lookup_index_filtered(self._h, ptr(keys), n, admit_below(admit),
+                                                     *out))
+        else:
+            check(lib.hctr_lru_lookup_index(self._h, ptr(keys), n, 1 if insert else 0, *out))
+        return (idx, ek[:m.value], ev[:m.value]) if evict else idx
 
     def compact(self, offsets: torch.Tensor, rows: torch.Tensor, keys: torch.Tensor,
                 weights: Optional[torch.Tensor] = None):
@@ -208,21 +203,24 @@ class HybridTable:
             ptr(grads.contiguous()), _lib.F32, optimizer, hp["lr"], hp["beta1"], hp["beta2"],
             hp["epsilon"], hp["momentum"], hp["scaler"], int(times), stream_ptr()))
 
-    def export(self, with_slots: bool = False):
-        """(keys, rows [n, dim]) of the occupied slots in slot order; with_slots=True adds their
-        slots and scores (int64)"""
-        n = self.size()
+    def _export(self, min_score: int, n: int):
+        """(keys, rows [g, dim], slots, scores) of the first n exported slots (hctr_lru_export_if)"""
         keys = torch.empty(n, dtype=self.key_dtype, device="cuda")
         slots = torch.empty(n, dtype=torch.int64, device="cuda")
         scores = torch.empty(n, dtype=torch.int64, device="cuda")
         rows = torch.empty((n, self.dim), dtype=torch.float32, device="cuda")
         got = ctypes.c_size_t()
-        check(lib.hctr_lru_export(self._h, ptr(keys), ptr(slots), ptr(scores), ptr(rows), n,
-                                  ctypes.byref(got), stream_ptr()))
+        if n:
+            check(lib.hctr_lru_export_if(self._h, min_score, ptr(keys), ptr(slots), ptr(scores),
+                                         ptr(rows), n, ctypes.byref(got), None, stream_ptr()))
         g = got.value
-        if with_slots:
-            return keys[:g], rows[:g], slots[:g], scores[:g]
-        return keys[:g], rows[:g]
+        return keys[:g], rows[:g], slots[:g], scores[:g]
+
+    def export(self, with_slots: bool = False):
+        """(keys, rows [n, dim]) of the occupied slots in slot order; with_slots=True adds their
+        slots and scores (int64)"""
+        out = self._export(0, self.size())
+        return out if with_slots else out[:2]
 
     def export_if(self, min_score: int):
         """(keys, rows [n, dim], slots, scores) of the occupied slots with score >= min_score, in
@@ -231,16 +229,7 @@ class HybridTable:
         ms = max(int(min_score), 0)
         check(lib.hctr_lru_export_if(self._h, ms, None, None, None, None, 0, ctypes.byref(got),
                                      ctypes.byref(matched), stream_ptr()))
-        n = matched.value
-        keys = torch.empty(n, dtype=self.key_dtype, device="cuda")
-        slots = torch.empty(n, dtype=torch.int64, device="cuda")
-        scores = torch.empty(n, dtype=torch.int64, device="cuda")
-        rows = torch.empty((n, self.dim), dtype=torch.float32, device="cuda")
-        if n:
-            check(lib.hctr_lru_export_if(self._h, ms, ptr(keys), ptr(slots), ptr(scores), ptr(rows),
-                                         n, ctypes.byref(got), None, stream_ptr()))
-        g = got.value if n else 0
-        return keys[:g], rows[:g], slots[:g], scores[:g]
+        return self._export(ms, matched.value)
 
     def filtered_count(self) -> int:
         out = ctypes.c_uint64()

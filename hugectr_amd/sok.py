@@ -259,14 +259,10 @@ class DynamicVariable(_VariableBase):
         return self._lru is not None and self._lru.tiered
 
     def _table(self) -> torch.Tensor:
-        if self.tiered:
-            # the HBM slots and the per-call rows the last lookup handed out
+        if self._lru is not None:
+            # the slots in HBM and the per-call rows the last lookup handed out
             p, _ = self._lru.rows_ptr()
             return _view_f32(p, (self._lru.placement()[1], self.dimension))
-        if self._lru is not None:
-            # (the scratch rows after the slots are addressed through the pointer only)
-            p, cap = self._lru.rows_ptr()
-            return _view_f32(p, (cap, self.dimension))
         p, cap = ctypes.c_void_p(), ctypes.c_size_t()
         check(lib.hctr_det_rows(self._det._h, 0, ctypes.byref(p), ctypes.byref(cap)))
         return _view_f32(p.value, (cap.value, self.dimension))
@@ -275,26 +271,18 @@ class DynamicVariable(_VariableBase):
         """stored keys only, as the dynamic table's scatter does"""
         idx = self._lru.find(indices.reshape(-1))
         live = idx >= 0
-        if self.tiered:
-            # slot-addressed (host slots included): distinct slots, the values summed per slot
-            # for an add as index_add_ does
-            v = values.reshape(-1, self.dimension).float()[live]
-            slots, inv = torch.unique(idx[live], return_inverse=True)
-            if add:
-                u = torch.zeros((slots.numel(), self.dimension), dtype=torch.float32,
-                                device=v.device).index_add_(0, inv, v)
-            else:
-                u = torch.empty((slots.numel(), self.dimension), dtype=torch.float32,
-                                device=v.device)
-                u[inv] = v
-            self._lru.scatter_slots(0, slots, u, add=add)
-            return
-        rows = self._table()
+        # slot-addressed (the table knows where a slot's bytes live): distinct slots, the values
+        # summed per slot for an add as index_add_ does
         v = values.reshape(-1, self.dimension).float()[live]
+        slots, inv = torch.unique(idx[live], return_inverse=True)
         if add:
-            rows.index_add_(0, idx[live], v)
+            u = torch.zeros((slots.numel(), self.dimension), dtype=torch.float32,
+                            device=v.device).index_add_(0, inv, v)
         else:
-            rows[idx[live]] = v
+            u = torch.empty((slots.numel(), self.dimension), dtype=torch.float32,
+                            device=v.device)
+            u[inv] = v
+        self._lru.scatter_slots(0, slots, u, add=add)
 
     # dynamic_variable.py:294-340
     def sparse_read(self, indices: torch.Tensor) -> torch.Tensor:
@@ -352,17 +340,12 @@ def assign(var: DynamicVariable, indices: torch.Tensor, values: torch.Tensor):
     """insert-or-overwrite (dynamic_variable.py:494-520).  On a hybrid variable the insert may
     evict other keys, and a key the table rejects is not stored."""
     if var._lru is not None:
-        idx = var._lru.lookup_index(indices.reshape(-1).contiguous(), insert=True)
-        if var.tiered:
-            # the rows handed out are per-call copies: write the stored keys' slots
-            slots = var._lru.find(indices.reshape(-1).contiguous())
-            live = slots >= 0
-            var._lru.scatter_slots(0, slots[live],
-                                   values.reshape(-1, var.dimension).float()[live])
-            return
-        cap = var._lru.capacity
-        live = idx < cap
-        var._table()[idx[live]] = values.reshape(-1, var.dimension).float()[live]
+        keys = indices.reshape(-1).contiguous()
+        var._lru.lookup_index(keys, insert=True)
+        # the rows handed out may be per-call copies: write the stored keys' slots
+        slots = var._lru.find(keys)
+        live = slots >= 0
+        var._lru.scatter_slots(0, slots[live], values.reshape(-1, var.dimension).float()[live])
         return
     var._det.lookup(indices.contiguous())       # inserts what is missing
     var._det.scatter_update(indices.contiguous(), values)
@@ -930,29 +913,18 @@ class OptimizerWrapper:
         D = var.dimension
         n = keys.numel()
         slots = var._lru.find(keys)
-        rows_p, cap = var._lru.rows_ptr()
         if var._updater is None or var._updater[1] < n:
             if var._updater is not None:
                 lib.hctr_updater_destroy(var._updater[0])
             h = ctypes.c_void_p()
             ucap = max(2 * n, 1024)
-            # tiered: the update sees the H HBM slots and up to n staged host slots after them
-            check(lib.hctr_updater_create(ucap, cap + ucap if var.tiered else cap, D,
-                                          ctypes.byref(h)))
+            check(lib.hctr_updater_create(ucap, var._lru.update_rows(ucap), D, ctypes.byref(h)))
             var._updater = (h, ucap)
-        ns = _num_state(self.code)
-        st = [ctypes.c_void_p(var._lru.state_ptr(i)) for i in range(ns)]
+        for i in range(_num_state(self.code)):
+            var._lru.state_ptr(i)
         ro = torch.arange(n + 1, dtype=torch.int64, device=kg.device)
-        if var.tiered:
-            # host slots are staged into HBM rows, updated there and written back
-            var._lru.apply_update(var._updater[0], ro, slots, kg, self.code, self.hp, self.times)
-            return
-        hp = self.hp
-        check(lib.hctr_updater_update(
-            var._updater[0], n, n, ptr(ro), ptr(slots), ptr(kg.contiguous()), _lib.F32, self.code,
-            _lib.UPDATE_LOCAL, hp["lr"], hp["beta1"], hp["beta2"], hp["epsilon"], hp["momentum"],
-            hp["scaler"], self.times, ctypes.c_void_p(rows_p), st[0] if ns >= 1 else None,
-            st[1] if ns >= 2 else None, stream_ptr()))
+        # (host slots, if any, are staged into HBM rows, updated there and written back)
+        var._lru.apply_update(var._updater[0], ro, slots, kg, self.code, self.hp, self.times)
 
     # dynamic variable: per-key gradients -> unique keys + sums (the reference's OptimizerWrapper
     # does this with tf.unique / unsorted_segment_sum, optimizer.py:170-230) -> fused HIP step
@@ -1035,14 +1007,9 @@ def _var_arrays(var, optimizer):
         order = torch.argsort(k)
         k, w, sl = k[order].to(torch.int64), w[order], sl[order]
         states = []
-        if slots and var.tiered:
-            for j in range(len(slots)):
-                var._lru.state_ptr(j)
-            states = [var._lru.gather_slots(1 + j, sl) for j in range(len(slots))]
-        elif slots:
-            cap = var._lru.capacity
-            states = [_view_f32(var._lru.state_ptr(j), (cap, D))[sl].clone()
-                      for j in range(len(slots))]
+        for j in range(len(slots)):
+            var._lru.state_ptr(j)  # (allocated, zeroed, if the optimizer has not stepped yet)
+            states.append(var._lru.gather_slots(1 + j, sl))
         return k, w, states
     if isinstance(var, DynamicVariable):
         k, w = var._det.export(0)
@@ -1136,12 +1103,8 @@ def load(path: str, load_vars, optimizer: Optional["OptimizerWrapper"] = None):
                 idx = var._lru.find(kt.to(var.key_type))
                 live = idx >= 0
                 for j, x in enumerate(states):
-                    if var.tiered:
-                        var._lru.state_ptr(j)
-                        var._lru.scatter_slots(1 + j, idx[live], torch.from_numpy(x).to(dev)[live])
-                        continue
-                    sv = _view_f32(var._lru.state_ptr(j), (var._lru.capacity, var.dimension))
-                    sv[idx[live]] = torch.from_numpy(x).to(dev)[live]
+                    var._lru.state_ptr(j)
+                    var._lru.scatter_slots(1 + j, idx[live], torch.from_numpy(x).to(dev)[live])
         elif isinstance(var, DynamicVariable):
             if kt.numel():
                 assign(var, kt.to(var.key_type), wt)
