@@ -201,6 +201,16 @@ _SIGNATURES = {
                                c_uint64, _P, _P, _P, _P]),
     "hctr_uniq_gather_rows": (c_int, [c_size_t, c_int, _P, _P, _P, c_int, _P]),
     "hctr_uniq_expand": (c_int, [c_size_t, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "hctr_ebc_uniq_plan_workspace_bytes": (c_size_t, [c_size_t]),
+    "hctr_ebc_uniq_plan": (c_int, [c_size_t, c_int, c_size_t, _P, _P, c_uint64, _P, _P, _P, _P,
+                                   c_size_t, _P]),
+    "hctr_ebc_uniq_gather_rows": (c_int, [c_size_t, c_int, _P, _P, c_uint64, _P, c_int, _P]),
+    "hctr_ebc_uniq_network_forward": (c_int, [c_size_t, c_int, c_int, c_int, _P, _P, _P, c_int, _P,
+                                              _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "hctr_ebc_uniq_backward_workspace_bytes": (c_size_t, [c_size_t, c_size_t, c_int, c_int]),
+    "hctr_ebc_uniq_network_backward": (c_int, [_P, c_size_t, c_int, c_int, c_int, _P, _P, _P, _P,
+                                               c_int, c_int, _P, _P, _P, c_size_t, c_size_t, _P,
+                                               c_int, _P, _P, c_size_t, _P]),
     "hctr_interaction_fwd_indexed": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
     "hctr_ebc_scale_average": (c_int, [c_size_t, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, _P]),
     "hctr_interaction_fwd_gather": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),

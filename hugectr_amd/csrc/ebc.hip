@@ -949,3 +949,6 @@ int hctr_ebc_local_reduce(hctr_updater* u, size_t buckets, size_t nnz, const int
 }
 
 }  // extern "C"
+
+// CompressionStrategy.Unique on several GPUs: plan / network forward / network backward
+#include "ebc_unique.hip"

@@ -24,6 +24,12 @@ that grows on demand; routing keeps the raw keys, `lookup` returns per-key row a
 the backward builds Wgrad{unique_keys, ev_start_indices, data} (hctr_ebc_local_reduce) for the
 table's fused optimizer step (hctr_det_update, all seven optimizers of optimizers.cuh).
 
+CompressionStrategy.Unique (`shard(..., compression_strategy=...)`, several GPUs): the reference's
+second model-parallel operator (R/HugeCTR/embedding/dense_model_parallel_embedding.cpp) -- the owner
+ships every distinct row once per destination GPU plus a 32-bit index per key, the receiver pools
+(hctr_ebc_uniq_network_forward), fp32 per-row gradient sums travel back; `_setup_unique` and the
+*_unique stages.  One collection is one operator: all model-parallel tables Unique, or none.
+
 Sharding: `shard_matrix[gpu][table]` in {0,1}; a table with one owner is table-wise sharded,
 with several owners row-wise (`key % num_shards` picks the owner in ascending GPU order, local row
 = key // num_shards; SURVEY q14).  All tables of one collection share `ev_size` here.
@@ -229,16 +235,27 @@ class EmbeddingCollection:
         assert global_batch % self.world == 0
         # CompressionStrategy.Unique selects the reference's unique-compressed model-parallel
         # operator (distinct rows travel, the receiver pools;
-        # R/HugeCTR/embedding/dense_model_parallel_embedding.cpp:1-279).  This runtime has ONE
-        # model-parallel operator, Reduction (the owner pools, pooled vectors travel).  On one GPU
-        # nothing travels and the two give the same output, so the request is honoured as is; on
-        # several GPUs it is refused rather than silently run as Reduction.
-        uniq = sorted(n for n, k in getattr(config, "compression", {}).items() if k == "unique")
+        # R/HugeCTR/embedding/dense_model_parallel_embedding.cpp:1-279): `_setup_unique` and the
+        # *_unique stages below.  On one GPU nothing travels and the two strategies give the same
+        # output, so the request is honoured by the direct path as is.  One collection is one
+        # operator (one grouped_lookup_params entry, R/HugeCTR/embedding/common.cpp:366-399): a
+        # config that names both strategies is refused here, before any device call.
+        comp = getattr(config, "compression", None) or {}
+        names_here = []
+        for t, _, _, _ in config.lookups:
+            if t.name not in names_here:
+                names_here.append(t.name)
+        uniq = sorted(n for n in names_here if comp.get(n) == "unique")
+        rest = sorted(n for n in names_here if comp.get(n) != "unique")
+        self._unique = False
         if uniq and self.world > 1:
-            raise _lib.HugeCTRAmdError(
-                "EmbeddingCollectionConfig.shard: CompressionStrategy.Unique for tables "
-                f"{uniq} on {self.world} GPUs is not available (model-parallel lookups run with "
-                "CompressionStrategy.Reduction only)")
+            if rest:
+                raise _lib.HugeCTRAmdError(
+                    "EmbeddingCollectionConfig.shard: CompressionStrategy.Unique for tables "
+                    f"{uniq} and CompressionStrategy.Reduction for tables {rest} in one "
+                    f"EmbeddingCollection on {self.world} GPUs: the two strategies run as separate "
+                    "collections (one operator each); hugectr.Model splits such a config itself")
+            self._unique = True
         config = self._expand_concat_lookups(config, hotness, batch_major)
         if storage is None:  # max_vocabulary_size < 0 means dynamic (embedding_storage/common.hpp:78,
             # embedding_table.cpp:27-34: one dynamic table makes the whole group dynamic)
@@ -410,12 +427,16 @@ class EmbeddingCollection:
         self._direct_avg = self._direct and any(c == 1 for c in self.combiner)
         self._map_on = False
         self.d_one_hot = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._upd_recv = ctypes.c_void_p()
+        if self._unique:
+            self._setup_unique(n_local_of)
 
     def __del__(self):
-        u = getattr(self, "_upd", None)
-        if u is not None and u.value:
-            lib.hctr_updater_destroy(u)
-            self._upd = ctypes.c_void_p()
+        for name in ("_upd", "_upd_recv"):
+            u = getattr(self, name, None)
+            if u is not None and u.value:
+                lib.hctr_updater_destroy(u)
+                setattr(self, name, ctypes.c_void_p())
 
     # -- collectives (identity for world == 1; the single-process tests drive them by hand) -------
     def _allgather_keys(self, keys, bucket_range):
@@ -466,6 +487,9 @@ class EmbeddingCollection:
     #    ebc_mp_model_forward / ebc_mp_network_forward on their own stream while the bottom MLP
     #    runs, R/HugeCTR/src/pybind/model_pipeline.cpp:299-346) -----------------------------------
     def forward_global_begin(self, gkeys: torch.Tensor, gbucket_range: torch.Tensor):
+        if self._unique:  # (the counts are read on the host before the rows can travel)
+            self._route_only(gkeys, gbucket_range)
+            return self._exchange_unique(None), None, None
         send = self.route_and_pool(gkeys, gbucket_range, False)
         recv, work = self._a2a_async(send, self.send_counts, self.recv_counts)
         return recv, work, send  # (send stays alive until the collective has read it)
@@ -473,9 +497,16 @@ class EmbeddingCollection:
     def forward_global_finish(self, recv: torch.Tensor, work) -> torch.Tensor:
         if work is not None:
             work.wait()
+        if self._unique:
+            return self.network_forward_unique(*recv)
         return self.network_forward(recv)
 
     def backward_begin(self, grad: torch.Tensor):
+        if self._unique:
+            sums = self.network_backward_unique(grad)
+            top, work = self._a2a_async(sums.reshape(-1), [u * self.ev for u in self._u_recv],
+                                        [u * self.ev for u in self._u_send])
+            return top, work, sums
         send = self.network_backward(grad)
         top, work = self._a2a_async(send, self.recv_counts, self.send_counts)
         return top, work, send
@@ -483,6 +514,8 @@ class EmbeddingCollection:
     def backward_finish(self, top: torch.Tensor, work):
         if work is not None:
             work.wait()
+        if self._unique:
+            return self.apply_row_sums(top.view(-1, self.ev))
         self.apply_gradients(top)
 
     def _a2a(self, buf, send_counts, recv_counts):
@@ -553,6 +586,9 @@ class EmbeddingCollection:
 
     def forward_global(self, gkeys: torch.Tensor, gbucket_range: torch.Tensor) -> torch.Tensor:
         """replicated global feature-major CSR -> this rank's output rows"""
+        if self._unique:
+            self._route_only(gkeys, gbucket_range)
+            return self.network_forward_unique(*self._exchange_unique(None))
         send = self.route_and_pool(gkeys, gbucket_range, self._direct)
         if self._direct:
             return send
@@ -609,7 +645,9 @@ class EmbeddingCollection:
                                     _DT[self.out_dtype], stream_ptr()))
         return send
 
-    def _forward_a2a_route(self, keys: torch.Tensor, bucket_range: torch.Tensor) -> torch.Tensor:
+    def _a2a_route_keys(self, keys: torch.Tensor, bucket_range: torch.Tensor) -> torch.Tensor:
+        """the two key all-to-alls -> the routed CSR; returns the lengths this rank sent,
+        [owner][its local lookups][b_local] = the order of the blocks it receives"""
         from .parallel import all_to_all_single
         lens, ks = self.route_send(keys, bucket_range)
         send_l = torch.cat(lens)
@@ -621,6 +659,10 @@ class EmbeddingCollection:
         all_to_all_single(recv_k, torch.cat(ks), recv_counts, [int(k.numel()) for k in ks],
                           group=self.group)
         self.route_recv(recv_l, recv_k)
+        return send_l
+
+    def _forward_a2a_route(self, keys: torch.Tensor, bucket_range: torch.Tensor) -> torch.Tensor:
+        self._a2a_route_keys(keys, bucket_range)
         return self.pool_routed()
 
     def _dynamic_pool(self, send: torch.Tensor, direct: bool = False) -> torch.Tensor:
@@ -753,6 +795,13 @@ class EmbeddingCollection:
         if self._virt is not None:  # this rank's share of the batch, user lookups -> expanded
             batch = (bucket_range.numel() - 1) // self.L_user
             keys, bucket_range = self._expand_csr(keys, bucket_range, batch)
+        if self._unique:
+            if self.key_route == "a2a" and dist.is_initialized():
+                lens = self._a2a_route_keys(keys, bucket_range)  # (the receiver sent them itself)
+            else:
+                self._route_only(*self._allgather_keys(keys, bucket_range))
+                lens = None
+            return self.network_forward_unique(*self._exchange_unique(lens))
         if self.key_route == "a2a" and self.world > 1 and dist.is_initialized():
             send = self._forward_a2a_route(keys, bucket_range)
         else:
@@ -768,9 +817,228 @@ class EmbeddingCollection:
             if self._direct_avg:  # scaled in a copy: the caller's gradient tensor stays as it was
                 grad = self._scale_average(grad.contiguous().clone(), False)
             return self.apply_gradients(grad, True)
+        if self._unique:
+            sums = self.network_backward_unique(grad)
+            top = self._a2a(sums.reshape(-1), [u * self.ev for u in self._u_recv],
+                            [u * self.ev for u in self._u_send])
+            return self.apply_row_sums(top.view(-1, self.ev))
         send = self.network_backward(grad)
         top = self._a2a(send, self.recv_counts, self.send_counts)
         self.apply_gradients(top)
+
+    # -- CompressionStrategy.Unique on several GPUs (csrc/ebc_unique.hip) ----------------------------
+    # owner:    route -> hctr_ebc_uniq_plan (per destination: distinct rows ascending + a 32-bit
+    #           index per key) -> counts [world, world] read on the host ONCE (the variable
+    #           all-to-all needs host-side sizes; dense_data_distribution_op_impl.cu:232-235 reads
+    #           the same) -> hctr_ebc_uniq_gather_rows -> all-to-all(rows), all-to-all(indices),
+    #           all-to-all(bucket lengths) unless the receiver sent them itself (key_route "a2a")
+    # receiver: hctr_ebc_uniq_network_forward pools;  backward: hctr_ebc_uniq_network_backward ->
+    #           fp32 sums per received row -> all-to-all (counts transposed)
+    # owner:    the normal sparse optimizer step on (row, sum) entries, a row's entries added in
+    #           ascending source order
+    def _setup_unique(self, n_local_of):
+        if self.dynamic and not (self._dyn_flat and self.optimizer in _FLAT_STEP):
+            raise _lib.HugeCTRAmdError(
+                "CompressionStrategy.Unique on dynamic tables runs the optimizers whose step works "
+                "on the flat row store (SGD, AdaGrad, Adam, MomentumSGD); Nesterov, RMSProp and "
+                "Ftrl need a key per distinct row (hctr_det_update): use "
+                "CompressionStrategy.Reduction for these tables")
+        i32, i64 = torch.int32, torch.int64
+        src = [r for r in range(self.world) for _ in n_local_of[r]]
+        lk = [l for r in range(self.world) for l in n_local_of[r]]
+        self.d_blk_src = torch.tensor(src or [0], dtype=i32, device=self.dev)
+        self.d_blk_lookup = torch.tensor(lk or [0], dtype=i32, device=self.dev)
+        self._any_avg = 1 if any(c == 1 for c in self.combiner) else 0
+        n = max(self.max_nnz, 1)
+        self._u_ws = torch.empty(lib.hctr_ebc_uniq_plan_workspace_bytes(n), dtype=torch.uint8,
+                                 device=self.dev)
+        self.urow = torch.empty(n, dtype=i64, device=self.dev)
+        self.ridx = torch.empty(n, dtype=i32, device=self.dev)  # (uint32 values)
+        self.peer_off = torch.zeros(self.world + 1, dtype=i64, device=self.dev)
+        # keys of my samples: what this rank can receive in one step
+        self._recv_cap = max(self.max_nnz // self.world, 1)
+        check(lib.hctr_updater_create(self._recv_cap, self._recv_cap, self.ev,
+                                      ctypes.byref(self._upd_recv)))
+        self._u_send = self._k_send = self._u_recv = None
+        self._rx = None
+        self._bwd_ws = None
+        self.last_exchange = None  # what this rank shipped in the last step (exchange_report)
+
+    def _route_only(self, gkeys: torch.Tensor, gbucket_range: torch.Tensor):
+        """global CSR -> the routed CSR of my shards (out_range, indices), nothing pooled"""
+        if self._virt is not None and gbucket_range.numel() == self.L_user * self.B + 1:
+            gkeys, gbucket_range = self._expand_csr(gkeys, gbucket_range, self.B)
+        kt = _lib.KEY_I64 if gkeys.dtype == torch.int64 else _lib.KEY_U32
+        check(lib.hctr_ebc_bucket_counts(self.B, self.world, self.rank, self.L, ptr(gbucket_range),
+                                         kt, ptr(self.counts), stream_ptr()))
+        if self.n_local:
+            check(lib.hctr_ebc_route_keys(self.B, self.world, self.n_local, ptr(self.d_desc),
+                                          ptr(self.d_row_start), ptr(gkeys), ptr(gbucket_range), kt,
+                                          ptr(self.out_range), ptr(self.indices), ptr(self.d_nnz),
+                                          ptr(self.ws), stream_ptr()))
+        self._nnz_host = int(gkeys.numel())  # upper bound; the live count stays on the device
+
+    def _plan_unique(self) -> torch.Tensor:
+        """routed CSR -> urow / peer_off / ridx on the device; returns the device counts
+        [world, 2] = (distinct rows, keys) of every destination"""
+        rows, max_row = self.indices, self.local_rows - 1
+        if self.dynamic:
+            max_row = 0xFFFFFFEF
+            if self.n_local:  # (offsets read on the host as _dynamic_pool does)
+                seg = self.out_range[0:self.nb + 1:self.bpg].tolist()
+                self._nnz_host = seg[-1]
+                if seg[-1]:
+                    _, rows, base = self.det.lookup_rows(self.indices[:seg[-1]], self.seg_class, seg,
+                                                         insert=self.training, want_ptrs=False)
+                    self._dyn_rows, self._dyn_base = rows, base
+        n = self._nnz_host if self.n_local else 0
+        nbp = self.n_local * self.bpg
+        check(lib.hctr_ebc_uniq_plan(n, self.world, nbp, ptr(self.out_range), ptr(rows), max_row,
+                                     ptr(self.urow), ptr(self.peer_off), ptr(self.ridx),
+                                     ptr(self._u_ws), self._u_ws.numel(), stream_ptr()))
+        if nbp:
+            koff = self.out_range[0:self.nb + 1:nbp]
+        else:
+            koff = torch.zeros(self.world + 1, dtype=torch.int64, device=self.dev)
+        return torch.stack([self.peer_off[1:] - self.peer_off[:-1], koff[1:] - koff[:-1]], 1)
+
+    def _gather_unique(self, n_send: int) -> torch.Tensor:
+        rows = torch.empty((max(n_send, 1), self.ev), dtype=self.out_dtype, device=self.dev)
+        if n_send:
+            if self.dynamic:
+                table, bound = self.det.row_store()
+            else:
+                table, bound = ptr(self.table), self.local_rows
+            check(lib.hctr_ebc_uniq_gather_rows(n_send, self.ev, ptr(self.urow), table, bound,
+                                                ptr(rows), _DT[self.out_dtype], stream_ptr()))
+        return rows[:n_send]
+
+    def compress_routed(self) -> dict:
+        """owner stage on the routed CSR (after route_recv or _route_only): plan, the counts read
+        on the host, gather.  -> rows [U, ev] (peer-major, ascending inside a peer), ridx [keys],
+        lens [world * n_local * bpg], u_counts / k_counts per destination"""
+        c = self._plan_unique().tolist()  # host read (counts)
+        self._u_send, self._k_send = [x[0] for x in c], [x[1] for x in c]
+        lens = self.out_range[1:self.nb + 1] - self.out_range[:self.nb]
+        return dict(rows=self._gather_unique(sum(self._u_send)), ridx=self.ridx[:sum(self._k_send)],
+                    lens=lens, u_counts=self._u_send, k_counts=self._k_send)
+
+    def route_and_compress(self, gkeys: torch.Tensor, gbucket_range: torch.Tensor) -> dict:
+        self._route_only(gkeys, gbucket_range)
+        return self.compress_routed()
+
+    def _exchange_unique(self, lens_recv):
+        """plan + the collectives of the forward; lens_recv: the bucket lengths of my blocks when
+        this rank already holds them (key_route "a2a"), else they travel too"""
+        cnt = self._plan_unique()
+        staged = dist.get_backend(self.group) == "gloo"  # host staging: tests only
+        cdev = torch.device("cpu") if staged else self.dev
+        allc = torch.empty((self.world, self.world, 2), dtype=torch.int64, device=cdev)
+        dist.all_gather_into_tensor(allc.view(-1), cnt.reshape(-1).to(cdev), group=self.group)
+        allc = allc.tolist()  # THE host read of the step: [owner][destination] -> (rows, keys)
+        r, W, ev = self.rank, self.world, self.ev
+        self._u_send, self._k_send = [allc[r][d][0] for d in range(W)], [allc[r][d][1] for d in range(W)]
+        self._u_recv, k_recv = [allc[o][r][0] for o in range(W)], [allc[o][r][1] for o in range(W)]
+        rows = self._gather_unique(sum(self._u_send))
+        rows_recv = self._a2a(rows.reshape(-1), [u * ev for u in self._u_send],
+                              [u * ev for u in self._u_recv]).view(-1, ev)
+        ridx_recv = self._a2a(self.ridx[:sum(self._k_send)], self._k_send, k_recv)
+        lens_bytes = 0
+        if lens_recv is None:
+            lens_bytes = (W - 1) * self.n_local * self.bpg * 8
+            lens = self.out_range[1:self.nb + 1] - self.out_range[:self.nb]
+            lens_recv = self._a2a(lens, [self.n_local * self.bpg] * W,
+                                  [n * self.bpg for n in self.n_local_of])
+        esz = rows.element_size()
+        out_rows = sum(self._u_send) - self._u_send[r]
+        self.last_exchange = dict(
+            distinct_rows_out=out_rows, keys_out=sum(self._k_send) - self._k_send[r],
+            bytes_out_forward=out_rows * ev * esz + (sum(self._k_send) - self._k_send[r]) * 4 +
+            lens_bytes,
+            bytes_out_backward=(sum(self._u_recv) - self._u_recv[r]) * ev * 4)
+        return rows_recv, ridx_recv, lens_recv, self._u_recv
+
+    def network_forward_unique(self, rows: torch.Tensor, ridx: torch.Tensor, lens: torch.Tensor,
+                               u_recv) -> torch.Tensor:
+        """rows [sum(u_recv), ev]: the distinct rows of every source, source-major; ridx: one
+        index per key position of my buckets [source][its local lookups][b_local]; lens: the
+        lengths of those buckets; u_recv: rows per source (host)"""
+        nbk = self.total_blocks * self.bpg
+        rr = torch.zeros(nbk + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(lens, 0, out=rr[1:])
+        off = [0]
+        for u in u_recv:
+            off.append(off[-1] + int(u))
+        r_off = torch.tensor(off, dtype=torch.int64, device=self.dev)
+        one_hot = (lens == 1).all().to(torch.int32).view(1)  # (a device word: no host read)
+        rows, ridx = rows.contiguous(), ridx.contiguous()
+        self._u_recv = [int(u) for u in u_recv]
+        self._rx = dict(range=rr, ridx=ridx, r_off=r_off, n_rows=off[-1],
+                        positions=int(ridx.numel()), rows=rows)
+        shape = (self.bpg, self.L, self.ev) if self.batch_major else (self.L, self.bpg, self.ev)
+        out = torch.empty(shape, dtype=self.out_dtype, device=self.dev)
+        check(lib.hctr_ebc_uniq_network_forward(
+            self.bpg, self.L, self.ev, self.max_shards, ptr(self.d_src_blocks), ptr(self.d_combiner),
+            ptr(self.counts), 1 if self.batch_major else 0, ptr(rr), ptr(ridx), ptr(r_off),
+            ptr(self.d_blk_src), ptr(one_hot), ptr(rows), ptr(out), _DT[self.out_dtype],
+            stream_ptr()))
+        return out
+
+    def network_backward_unique(self, grad: torch.Tensor) -> torch.Tensor:
+        """gradient of my output -> fp32 sums [received rows, ev], the order of the rows received
+        in the forward (still carrying the loss scaler)"""
+        rx = self._rx
+        n_rows, pos = rx["n_rows"], rx["positions"]
+        sums = torch.empty((max(n_rows, 1), self.ev), dtype=torch.float32, device=self.dev)
+        if n_rows == 0:
+            return sums[:0]
+        if pos > self._recv_cap:
+            raise _lib.HugeCTRAmdError(f"{pos} keys received, the collection was sized for "
+                                       f"{self._recv_cap} (hotness / max_hotness)")
+        need = lib.hctr_ebc_uniq_backward_workspace_bytes(pos, self.bpg, self.L, self.ev)
+        if self._bwd_ws is None or self._bwd_ws.numel() < need:  # (grown on demand, then kept)
+            self._bwd_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        ws = self._bwd_ws
+        grad = grad.contiguous()
+        check(lib.hctr_ebc_uniq_network_backward(
+            self._upd_recv, self.bpg, self.L, self.ev, self.total_blocks, ptr(self.d_blk_lookup),
+            ptr(self.d_blk_src), ptr(self.d_combiner), ptr(self.counts),
+            1 if self.batch_major else 0, self._any_avg, ptr(rx["range"]), ptr(rx["ridx"]),
+            ptr(rx["r_off"]), pos, n_rows, ptr(grad), _DT[grad.dtype], ptr(sums), ptr(ws),
+            ws.numel(), stream_ptr()))
+        return sums[:n_rows]
+
+    def apply_row_sums(self, sums: torch.Tensor):
+        """sums [sum(u_send), ev] fp32: per destination the gradient sums of the rows sent to it,
+        the order of urow.  One (row, sum) entry each; the entries of a row are added in ascending
+        source order by the stable sort of the sparse update."""
+        n = sum(self._u_send)
+        if self.n_local == 0 or n == 0:
+            return
+        assert sums.shape[0] == n and sums.dtype == torch.float32
+        self._times += 1
+        if self._map_on:
+            check(lib.hctr_updater_set_grad_map(self._upd, 0, 0))
+            self._map_on = False
+        sums = sums.contiguous()
+        ro = torch.arange(n + 1, dtype=torch.int64, device=self.dev)
+        if self.dynamic:
+            store, total = self.det.row_store()
+            s0 = s1 = None
+            if self.optimizer != _lib.OPT_SGD:
+                s0, s1 = self.det.state_store(2 if self.optimizer == _lib.OPT_ADAM else 1)
+            self._dyn_times += 1
+            check(lib.hctr_updater_set_row_bound(self._upd, total))
+            check(lib.hctr_updater_update(self._upd, n, n, ptr(ro), ptr(self.urow), ptr(sums),
+                                          _lib.F32, self.optimizer, _lib.UPDATE_LOCAL, self.lr,
+                                          self.beta1, self.beta2, self.epsilon,
+                                          self.momentum_factor, self.scaler, self._dyn_times, store,
+                                          s0, s1, stream_ptr()))
+            return
+        check(lib.hctr_updater_update(self._upd, n, n, ptr(ro), ptr(self.urow), ptr(sums), _lib.F32,
+                                      self.optimizer, _lib.UPDATE_LOCAL, self.lr, 0.9, 0.999,
+                                      self.epsilon, 0.0, self.scaler, self._times, ptr(self.table),
+                                      ptr(self.accum), ptr(self.ftrl_z), stream_ptr()))
 
 
 class DataParallelCollection:

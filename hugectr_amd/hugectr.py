@@ -903,6 +903,13 @@ class Model:
                          (ux.P - ux.P // self.world) * 8,
                          bytes_out_backward=(sum(ur) - ur[self.rank]) * D * gsz)
             out[name] = r
+        # collections under CompressionStrategy.Unique: what this rank shipped in the last step
+        for i, rt in enumerate(getattr(self, "_ebc", [])):
+            e = rt["train"]
+            if getattr(e, "_unique", False):
+                r = {"payload": "unique rows", "tables": [t.name for t in e.tables]}
+                r.update(e.last_exchange or {})
+                out[f"embedding_collection{i}"] = r
         return out
 
     def _split_by_ev_size(self, cfg: EmbeddingCollectionConfig):
@@ -917,7 +924,15 @@ class Model:
         dp_names = {n for n in dp_names
                     if all(t.max_vocabulary_size >= 0 for t, _, _, _ in cfg.lookups if t.name == n)}
         sizes = sorted({t.ev_size for t, _, _, _ in cfg.lookups})
-        if len(sizes) == 1 and not dp_names:
+        # one collection is one model-parallel operator (one grouped_lookup_params entry of the
+        # reference, R/HugeCTR/embedding/common.cpp:366-399): tables under
+        # CompressionStrategy.Unique and under Reduction run as separate collections, and every
+        # sub-config carries its tables' strategy
+        # (one GPU: nothing travels, the direct path serves both, nothing is split)
+        comp = (getattr(cfg, "compression", None) or {}) if self.world > 1 else {}
+        strategies = sorted({comp.get(t.name, "reduction") for t, _, _, _ in cfg.lookups
+                             if t.name not in dp_names})
+        if len(sizes) == 1 and not dp_names and len(strategies) <= 1:
             return [(cfg, list(range(len(cfg.lookups))))]
         tables = []
         for t, _, _, _ in cfg.lookups:
@@ -933,13 +948,16 @@ class Model:
                 sub.lookups = [cfg.lookups[l] for l in ids]
                 sub.shard_strategy = "dp"
                 out.append((sub, ids))
-        for ev in sizes:
+        for ev, strategy in [(e, k) for e in sizes for k in strategies]:
             ids = [l for l, (t, _, _, _) in enumerate(cfg.lookups)
-                   if t.ev_size == ev and t.name not in dp_names]
+                   if t.ev_size == ev and t.name not in dp_names and
+                   comp.get(t.name, "reduction") == strategy]
             if not ids:
                 continue
             sub = EmbeddingCollectionConfig()
             sub.lookups = [cfg.lookups[l] for l in ids]
+            full = getattr(cfg, "compression", None) or {}
+            sub.compression = {t.name: full[t.name] for t, _, _, _ in sub.lookups if t.name in full}
             sub_tables = []
             for t, _, _, _ in sub.lookups:
                 if t not in sub_tables:

@@ -430,6 +430,70 @@ int hctr_updater_reduce_presorted(hctr_updater* u, size_t positions, size_t buck
                                   const int64_t* row_offset, const uint32_t* sorted_rows,
                                   const uint32_t* sorted_buckets, const void* grad, int grad_dtype,
                                   size_t n_rows, float* out_sum, hctr_stream_t stream);
+/* ---- CompressionStrategy.Unique of embedding_collection on several GPUs (csrc/ebc_unique.hip): the
+ * reference's DenseUniformModelParallelEmbedding (R/HugeCTR/embedding/
+ * dense_model_parallel_embedding.cpp:1-279; key side R/HugeCTR/embedding/data_distributor/
+ * dense_data_distribution_op_impl.cu) for ragged multi-hot buckets, several lookups per table and
+ * row-sharded tables: the owner ships every distinct row once per destination GPU plus a 32-bit
+ * index per key position, the receiver pools, fp32 per-row gradient sums travel back.  Two
+ * deliberate differences from the reference: every sum is ordered, fp32 and rounded once (the
+ * reference's receiver adds with one_to_one_atomic in arrival order and, for a 16-bit output, in
+ * the 16-bit type: network_forward.cu:525-528, generic_lookup.cuh:126-248), and the rows are
+ * de-duplicated on the OWNER per destination (the reference hashes on the sender before the key
+ * exchange, dense_data_distribution_op_impl.cu partition_and_unique_on_dp_input), so the keys
+ * travel as with Reduction.  The collectives stay the caller's.
+ *
+ * hctr_ebc_uniq_plan -- owner (replaces the unique / bucket-range side of
+ * dense_data_distribution_op_impl.cu:150-260).  bucket_range [world * buckets_per_peer + 1]
+ * (device) is the routed CSR of hctr_ebc_route_keys, buckets ordered [peer][local lookup][b_local];
+ * rows [positions] the row of every key (positions = a HOST upper bound of the key count; entries
+ * behind bucket_range's last value are ignored), every row <= max_row <= 2^32 - 17 (a larger value
+ * is the dynamic table's "no row" and stays one entry that the gather fills with zeros; only
+ * max_row's bits are sorted, so a caller whose rows may hold "no row" passes max_row = 2^32 - 17).
+ * Outputs: urow = distinct rows, peer-major, ascending inside a peer; peer_off [world + 1]
+ * (device); ridx [positions] = index of key j's row inside its peer's list.  workspace: device,
+ * hctr_ebc_uniq_plan_workspace_bytes(positions) bytes; no allocation and no synchronisation. */
+size_t hctr_ebc_uniq_plan_workspace_bytes(size_t max_positions);
+int hctr_ebc_uniq_plan(size_t positions, int world, size_t buckets_per_peer,
+                       const int64_t* bucket_range, const uint64_t* rows, uint64_t max_row,
+                       uint64_t* urow, int64_t* peer_off, uint32_t* ridx, void* workspace,
+                       size_t workspace_bytes, hctr_stream_t stream);
+/* owner: out[i][:] = table[urow[i]][:] in out_dtype, zeros where urow[i] >= row_bound (model_comm
+ * buffer of dense_model_parallel_embedding.cpp:120-160; static flat table or hctr_det_row_store) */
+int hctr_ebc_uniq_gather_rows(size_t n_rows, int ev_size, const uint64_t* urow, const float* table,
+                              uint64_t row_bound, void* out, int out_dtype, hctr_stream_t stream);
+/* receiver (replaces network_forward.cu:500-540 for this operator): arguments as
+ * hctr_ebc_network_forward plus the received CSR -- recv_range [blocks * batch_per_gpu + 1] over
+ * the buckets [source][its local lookup][b], ridx per received key position, r_off [world + 1]
+ * first row of every source in `rows`, d_block_source [blocks] source rank of a block, d_one_hot
+ * (device word or NULL): != 0 when every received bucket holds exactly one key (no range is read).
+ * out[l][b] = (sum over the shards of l's table, ascending, of (sum of the shard's rows in key
+ * order)) / key count for Average, fp32, rounded once. */
+int hctr_ebc_uniq_network_forward(size_t batch_per_gpu, int num_lookup, int ev_size, int max_shards,
+                                  const int32_t* d_src_blocks, const int32_t* d_combiner,
+                                  const int64_t* d_bucket_counts, int batch_major,
+                                  const int64_t* recv_range, const uint32_t* ridx,
+                                  const int64_t* r_off, const int32_t* d_block_source,
+                                  const uint32_t* d_one_hot, const void* rows, void* out, int dtype,
+                                  hctr_stream_t stream);
+/* receiver backward (replaces network_backward.cu + the atomic local reduce of
+ * dense_model_parallel_embedding.cpp:200-279): out_sum [n_rows][ev] fp32 = per received row the
+ * sum, in ascending key position, of its buckets' gradients (divided by the key count for Average
+ * when any_average != 0).  u: an updater of vector size ev_size and capacity >= positions (its
+ * segmented reduce sums the runs: 32-position tiles, a longer run is summed by several lane groups
+ * and the partials added in tile order).  d_block_lookup [blocks] = global lookup of a block.
+ * positions must be EXACTLY recv_range[blocks * batch_per_gpu], the number of received keys (not an
+ * upper bound as hctr_ebc_uniq_plan accepts: every one of the `positions` entries is sorted). */
+size_t hctr_ebc_uniq_backward_workspace_bytes(size_t max_positions, size_t batch_per_gpu,
+                                              int num_lookup, int ev_size);
+int hctr_ebc_uniq_network_backward(hctr_updater* u, size_t batch_per_gpu, int num_lookup,
+                                   int ev_size, int num_blocks, const int32_t* d_block_lookup,
+                                   const int32_t* d_block_source, const int32_t* d_combiner,
+                                   const int64_t* d_bucket_counts, int batch_major, int any_average,
+                                   const int64_t* recv_range, const uint32_t* ridx,
+                                   const int64_t* r_off, size_t positions, size_t n_rows,
+                                   const void* grad, int grad_dtype, float* out_sum,
+                                   void* workspace, size_t workspace_bytes, hctr_stream_t stream);
 /* owner: index stage only (hctr_emb_forward without the gather), and the sparse update driven by
  * (row, gradient) entries: entry i updates rows[i] with grad[i][:] (row_offset = arange(n + 1)) */
 int hctr_emb_index(hctr_embedding* emb, int is_train, const void* row_offset, const void* keys,
