@@ -1814,6 +1814,15 @@ int inter_waves_per_cu(int which) {
                            }()};
   return v[which];
 }
+// a kernel that is launched with more than 64 KB of dynamic LDS has to be told first (per device
+// and cheap: asked on every such launch rather than remembered per process)
+template <typename K>
+int allow_dyn_lds(K kernel, size_t lds) {
+  if (lds > 65536)
+    HCTR_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds));
+  return HCTR_OK;
+}
 }  // namespace
 }  // namespace hctr
 
@@ -1885,20 +1894,24 @@ static int interaction_fwd_impl(size_t batch, int n_emb, int width, const void* 
   } else {
     const size_t lds = (size_t)kWavesPerBlock * n_ins * (width + 1) * 4;
     HCTR_REQUIRE(lds <= 160 * 1024, "interaction: tile does not fit LDS");
-    if (dtype == HCTR_EMB_F32)
+    if (dtype == HCTR_EMB_F32) {
+      HCTR_TRY(allow_dyn_lds(interaction_fwd_generic_kernel<float>, lds));
       hipLaunchKernelGGL(interaction_fwd_generic_kernel<float>, dim3(grid), dim3(kBlock), lds, s,
                          batch, n_emb, width, (const float*)mlp, (const float*)emb, (float*)out,
                          out_len);
-    else if (dtype == HCTR_EMB_F16)
+    } else if (dtype == HCTR_EMB_F16) {
+      HCTR_TRY(allow_dyn_lds(interaction_fwd_generic_kernel<__half>, lds));
       hipLaunchKernelGGL(interaction_fwd_generic_kernel<__half>, dim3(grid), dim3(kBlock), lds, s,
                          batch, n_emb, width, (const __half*)mlp, (const __half*)emb, (__half*)out,
                          out_len);
-    else if (dtype == HCTR_EMB_BF16)
+    } else if (dtype == HCTR_EMB_BF16) {
+      HCTR_TRY(allow_dyn_lds(interaction_fwd_generic_kernel<__hip_bfloat16>, lds));
       hipLaunchKernelGGL(interaction_fwd_generic_kernel<__hip_bfloat16>, dim3(grid), dim3(kBlock),
                          lds, s, batch, n_emb, width, (const __hip_bfloat16*)mlp,
                          (const __hip_bfloat16*)emb, (__hip_bfloat16*)out, out_len);
-    else
+    } else {
       HCTR_REQUIRE(false, "dtype");
+    }
   }
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
@@ -2099,21 +2112,25 @@ static int interaction_bwd_impl(size_t batch, int n_emb, int width, const void* 
   } else {
     const size_t lds = (size_t)kWavesPerBlock * (n_ins * (width + 1) + n_ins * n_ins) * 4;
     HCTR_REQUIRE(lds <= 160 * 1024, "interaction: tile does not fit LDS");
-    if (dtype == HCTR_EMB_F32)
+    if (dtype == HCTR_EMB_F32) {
+      HCTR_TRY(allow_dyn_lds(interaction_bwd_generic_kernel<float>, lds));
       hipLaunchKernelGGL(interaction_bwd_generic_kernel<float>, dim3(grid), dim3(kBlock), lds, s,
                          batch, n_emb, width, (const float*)mlp, (const float*)emb,
                          (const float*)top_grad, (float*)mlp_grad, (float*)emb_grad, out_len);
-    else if (dtype == HCTR_EMB_F16)
+    } else if (dtype == HCTR_EMB_F16) {
+      HCTR_TRY(allow_dyn_lds(interaction_bwd_generic_kernel<__half>, lds));
       hipLaunchKernelGGL(interaction_bwd_generic_kernel<__half>, dim3(grid), dim3(kBlock), lds, s,
                          batch, n_emb, width, (const __half*)mlp, (const __half*)emb,
                          (const __half*)top_grad, (__half*)mlp_grad, (__half*)emb_grad, out_len);
-    else if (dtype == HCTR_EMB_BF16)
+    } else if (dtype == HCTR_EMB_BF16) {
+      HCTR_TRY(allow_dyn_lds(interaction_bwd_generic_kernel<__hip_bfloat16>, lds));
       hipLaunchKernelGGL(interaction_bwd_generic_kernel<__hip_bfloat16>, dim3(grid), dim3(kBlock),
                          lds, s, batch, n_emb, width, (const __hip_bfloat16*)mlp,
                          (const __hip_bfloat16*)emb, (const __hip_bfloat16*)top_grad,
                          (__hip_bfloat16*)mlp_grad, (__hip_bfloat16*)emb_grad, out_len);
-    else
+    } else {
       HCTR_REQUIRE(false, "dtype");
+    }
   }
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;

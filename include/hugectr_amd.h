@@ -517,7 +517,10 @@ int hctr_emb_update_rows(hctr_embedding* emb, size_t n, const int64_t* row_offse
 /* ------------------------------------------------------------------------------------------ */
 /* InteractionLayer<T>::fprop / bprop (R/HugeCTR/src/layers/interaction_layer.cu:1046-1237).
  * mlp [B][W], emb [B][n_emb][W] -> out [B][W + n_ins(n_ins-1)/2 + 1], n_ins = n_emb+1; pairs
- * row-major over the strict lower triangle, last column zero. dtype: f32/f16/bf16 */
+ * row-major over the strict lower triangle, last column zero. dtype: f32/f16/bf16.
+ * Any width and n_emb: shapes outside the MFMA kernels' (width 16/32/64/128, n_ins <= 32, 16-byte
+ * aligned buffers) take a generic kernel whose LDS tile -- 4 n_ins (W + 1) floats, backward plus
+ * 4 n_ins^2 -- must fit 160 KiB ("interaction: tile does not fit LDS" otherwise). */
 int hctr_interaction_fwd(size_t batch, int n_emb, int width, const void* mlp, const void* emb,
                          void* out, int dtype, hctr_stream_t stream);
 int hctr_interaction_bwd(size_t batch, int n_emb, int width, const void* mlp, const void* emb,
