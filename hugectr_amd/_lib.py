@@ -265,6 +265,9 @@ _SIGNATURES = {
     "hctr_lru_export_if": (c_int, [_P, c_uint64, _P, _P, _P, _P, c_size_t, _SZP, _SZP, _P]),
     "hctr_lru_create_tiered": (c_int, [c_size_t, c_size_t, c_int, c_int, c_char_p, c_uint64,
                                        c_size_t, POINTER(_P)]),
+    "hctr_lru_create_growing": (c_int, [c_size_t, c_size_t, c_float, c_size_t, c_int, c_int,
+                                        c_char_p, c_uint64, c_size_t, POINTER(_P)]),
+    "hctr_lru_growth": (c_int, [_P, _SZP, _SZP, POINTER(c_uint64)]),
     "hctr_lru_placement": (c_int, [_P, _SZP, _SZP, _SZP]),
     "hctr_lru_host_part": (c_int, [_P, c_int, POINTER(_P)]),
     "hctr_lru_gather_slots": (c_int, [_P, c_int, _P, c_size_t, _P, _P]),

@@ -34,6 +34,12 @@
 // slots of a step into rows H + u (u = rank in slot order), runs the sparse optimizer there and
 // writes them back.
 //
+// Growth (hctr_lru_create_growing): the table starts with C0 slots, Cmax = C0 * 2^j.  An inserting
+// call below Cmax first probes (find in kLruProbe mode, sort, count: nothing is written), reads
+// occ and m = its distinct new keys back, and doubles C while C < Cmax and occ + m > L * C
+// (lru_double: lru_split_kernel + lru_move_kernel per doubling); then it runs as on a fixed
+// table.  hctr_lru_create(_tiered) are the case j = 0, which never takes that path.
+//
 // One table, one code path: hctr_lru holds the LruTbl the kernels take, and an untiered table is the
 // case H = C of it (no host arrays, every slot an HBM slot).  Every host function serves both
 // kinds; where they differ it is in which kernels a lookup launches:
@@ -121,7 +127,9 @@ struct LruTbl {
   uint64_t seed;
 };
 
-enum { kLruFind = 0, kLruRead = 1, kLruInsert = 2 };
+// kLruProbe: kLruInsert's outputs without its side effects (no score, no filtered count): the pass
+// by which a table below its largest capacity counts a call's new keys before it decides to grow
+enum { kLruFind = 0, kLruRead = 1, kLruInsert = 2, kLruProbe = 3 };
 
 // One thread per key: the bucket's digest line (S bytes, 16 B per load), then the key of every
 // slot whose digest matches.  kLruFind: slot or kInvalidIndex.  kLruRead: slot, or a scratch row
@@ -192,11 +200,13 @@ __global__ void __launch_bounds__(kLruBlock)
   if (Filter) {
     filtered = live && slot == kInvalidIndex && lru_admit_draw(T.seed, key, t) >= admit_below;
     const uint64_t fm = __ballot(filtered);
-    if (fm && (threadIdx.x % kWave) == 0) atomicAdd(&counters[2], (unsigned long long)__popcll(fm));
+    if (fm && mode != kLruProbe && (threadIdx.x % kWave) == 0)
+      atomicAdd(&counters[2], (unsigned long long)__popcll(fm));
     if (!live) return;
     if (filtered) slot = kLruFiltered;
   }
-  if (slot != kInvalidIndex && !filtered) T.scores[slot] = t;  // every writer writes the same t
+  // (every writer writes the same t)
+  if (slot != kInvalidIndex && !filtered && mode != kLruProbe) T.scores[slot] = t;
   idx[i] = slot;
   sbkt[i] = slot != kInvalidIndex ? (uint32_t)T.nb : (uint32_t)b;
   slo[i] = (uint32_t)key;
@@ -224,12 +234,14 @@ __device__ __forceinline__ uint32_t lru_lower_bound_u32(const uint32_t* a, uint3
 }
 
 // One wave per bucket: its run [lo, hi) in the sorted missing keys, and how many of its distinct
-// keys will evict: min(max(distinct - empty, 0), slots with score < t).
+// keys will evict: min(max(distinct - empty, 0), slots with score < t).  miss (may be null) gathers
+// the distinct keys of all buckets, one atomic per bucket that has some.
 template <typename K>
 __global__ void __launch_bounds__(kLruBlock)
     lru_count_kernel(LruTbl T, const K* __restrict__ in, const uint32_t* __restrict__ sbkt,
                      const uint32_t* __restrict__ perm, uint32_t n, uint64_t t,
-                     uint32_t* __restrict__ rng, uint32_t* __restrict__ evict_cnt) {
+                     uint32_t* __restrict__ rng, uint32_t* __restrict__ evict_cnt,
+                     unsigned long long* __restrict__ miss) {
   const uint64_t b = blockIdx.x * (uint64_t)kLruWavesPerBlock + threadIdx.x / kWave;
   const int lane = threadIdx.x % kWave;
   if (b >= T.nb) return;
@@ -253,6 +265,7 @@ __global__ void __launch_bounds__(kLruBlock)
     }
     distinct += (uint32_t)__popcll(__ballot(first));
   }
+  if (miss && lane == 0 && distinct) atomicAdd(miss, (unsigned long long)distinct);
   uint32_t empty = 0, elig = 0;
   const uint64_t base = b * (uint64_t)T.S;
   for (int j = 0; j < T.S / kWave; j++) {
@@ -596,6 +609,75 @@ __global__ void __launch_bounds__(kLruBlock)
     *p = *p + buf[i];
 }
 
+// ---- growth: one doubling C -> 2C ------------------------------------------------------------------
+// One wave per old bucket b (T.nb, T.C: the table before the doubling; its arrays already have room
+// for 2C slots, the upper half empty).  A key whose hash % (2 nb) is b + nb moves: the movers of a
+// bucket, in ascending slot order, take slots (b + nb) * S + 0, 1, ... with their score and digest,
+// and leave an empty slot.  Lane l owns slots l, l + 64, ... as in lru_insert_kernel; a mover's rank
+// is the movers of the earlier slot groups plus those on lower lanes of its own.  Every (source,
+// destination) pair goes into `list` for lru_move_kernel; a bucket reserves its run of the list
+// with one atomic, so the list's order varies and its contents do not.
+template <typename K>
+__global__ void __launch_bounds__(kLruBlock)
+    lru_split_kernel(LruTbl T, uint32_t* __restrict__ list, unsigned long long* __restrict__ list_n) {
+  const uint64_t b = blockIdx.x * (uint64_t)kLruWavesPerBlock + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (b >= T.nb) return;
+  const int spl = T.S / kWave;
+  const uint64_t base = b * (uint64_t)T.S, nbase = (b + T.nb) * (uint64_t)T.S;
+  uint64_t k[kLruMaxSlotsPerLane], mv[kLruMaxSlotsPerLane];
+  uint32_t total = 0;
+#pragma unroll
+  for (int q = 0; q < kLruMaxSlotsPerLane; q++) {
+    k[q] = q < spl ? T.keys[base + q * kWave + lane] : kLruEmpty;
+    const bool moves = k[q] != kLruEmpty && (uint64_t)murmur3_key((K)k[q]) % (2 * T.nb) != b;
+    mv[q] = __ballot(moves);
+    total += (uint32_t)__popcll(mv[q]);
+  }
+  if (total == 0) return;
+  unsigned long long first = 0;
+  if (lane == 0) first = atomicAdd(list_n, (unsigned long long)total);
+  first = __shfl(first, 0);
+  uint32_t before = 0;
+#pragma unroll
+  for (int q = 0; q < kLruMaxSlotsPerLane; q++) {
+    if ((mv[q] >> lane) & 1ull) {
+      const uint32_t rank = before + (uint32_t)__popcll(mv[q] & ((1ull << lane) - 1ull));
+      const uint64_t src = base + (uint64_t)(q * kWave + lane), dst = nbase + rank;
+      T.keys[dst] = k[q];
+      T.scores[dst] = T.scores[src];
+      T.digests[dst] = T.digests[src];
+      T.keys[src] = kLruEmpty;
+      T.scores[src] = 0;
+      T.digests[src] = 0;
+      list[2 * (first + rank)] = (uint32_t)src;
+      list[2 * (first + rank) + 1] = (uint32_t)dst;
+    }
+    before += (uint32_t)__popcll(mv[q]);
+  }
+}
+
+// the rows and every allocated state of the pairs lru_split_kernel listed, a group of gl lanes per
+// pair; either end may be in either tier (slot < H at run time, as lru_slot_io_kernel).  Sources
+// lie below the old capacity and destinations above it, so one pass has no hazards.  The grid covers
+// max_n >= *list_n pairs (the occupied slots, which the host knows).
+__global__ void __launch_bounds__(kLruBlock)
+    lru_move_kernel(LruTbl T, const uint32_t* __restrict__ list,
+                    const unsigned long long* __restrict__ list_n, size_t max_n, int gl) {
+  const size_t p = (blockIdx.x * (size_t)kLruBlock + threadIdx.x) / (size_t)gl;
+  const int l = (int)(threadIdx.x % (unsigned)gl);
+  if (p >= max_n || p >= *list_n) return;
+  const uint64_t src = list[2 * p], dst = list[2 * p + 1], D = (uint64_t)T.D;
+  float* hbm[3] = {T.rows, T.st[0], T.st[1]};
+  float* host[3] = {T.hrows, T.hst[0], T.hst[1]};
+  for (int a = 0; a < 3; a++) {
+    if (!hbm[a]) continue;
+    const float* from = src < T.H ? hbm[a] + src * D : host[a] + (src - T.H) * D;
+    float* to = dst < T.H ? hbm[a] + dst * D : host[a] + (dst - T.H) * D;
+    for (int e = l; e < T.D; e += gl) to[e] = from[e];
+  }
+}
+
 inline int lru_blocks(size_t n) { return (int)ceil_div<size_t>(n > 0 ? n : 1, (size_t)kLruBlock); }
 
 }  // namespace
@@ -606,15 +688,20 @@ using namespace hctr;
 struct hctr_lru {
   // what the kernels see, passed to them as it stands.  Slots [H, C) keep rows and states in
   // pinned, device-mapped host memory; the HBM arrays of rows (and, tiered, of states) hold H slots
-  // plus `scratch` per-call rows.  H = C: untiered.
+  // plus `scratch` per-call rows.  H = C: untiered.  T.C is the capacity now: it doubles, up to
+  // Cmax, when an inserting call would load the table beyond L (lru_double), and H = min(C, Hb).
   LruTbl T{};
+  uint64_t Cmax = 0, Hb = 0;  // largest capacity; HBM budget in slots (>= Cmax: never tiered)
+  double L = 0.5;             // max_load_factor
+  uint64_t doublings = 0;
   int key_type = HCTR_KEY_I64;
   size_t scratch = 0;  // rows after the H slots
   void* host_alloc[3] = {nullptr, nullptr, nullptr};  // the pinned allocations behind hrows / hst
   uint64_t* ws_rows = nullptr;            // [ws_n] staged rows of a step (tiered)
   uint64_t t = 0;  // inserting calls so far
-  unsigned long long* counters = nullptr;  // [0] occupied slots, [1] rejected keys, [2] filtered
-  unsigned long long* h_word = nullptr;    // pinned host word
+  // [0] occupied slots, [1] rejected keys, [2] filtered, [3] a growing call's distinct new keys
+  unsigned long long* counters = nullptr;
+  unsigned long long* h_word = nullptr;    // pinned host words (4)
   // per-call workspace (n keys)
   size_t ws_n = 0;
   uint32_t* ws = nullptr;  // 8 arrays of ws_n
@@ -629,6 +716,7 @@ struct hctr_lru {
   unsigned long long* d_total = nullptr;
 
   bool tiered() const { return T.H < T.C; }
+  bool tiers() const { return Hb < Cmax; }  // tiered now, or once it has grown past Hb
   int key_bytes() const { return key_type == HCTR_KEY_I64 ? 8 : 4; }
   size_t row_bytes() const { return (size_t)T.D * sizeof(float); }
 };
@@ -690,7 +778,7 @@ int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
     HCTR_HIP(hipMalloc(&h->ws_tiles, (cap / 1024 + 2) * sizeof(unsigned long long)));
     h->sort_temp_bytes = radix_sort_temp_bytes(cap);
     HCTR_HIP(hipMalloc(&h->sort_temp, h->sort_temp_bytes));
-    if (h->tiered()) {
+    if (h->tiers()) {
       if (h->ws_rows) HCTR_HIP(hipFree(h->ws_rows));
       h->ws_rows = nullptr;
       HCTR_HIP(hipMalloc(&h->ws_rows, cap * sizeof(uint64_t)));
@@ -712,20 +800,199 @@ int lru_reserve(hctr_lru* h, size_t n, hipStream_t s) {
 // lru_find_kernel over n keys, idx[i] = kLruFind: slot or kInvalidIndex; kLruRead: row; kLruInsert
 // (call h->t, through the filter when admit_below < kLruAdmitAll): slot, kInvalidIndex for the
 // insert step or kLruFiltered, and the sort's inputs (bucket, key low / high word, position) in
-// the first four arrays of ws
+// the first four arrays of ws; kLruProbe: the same for the call to come, h->t + 1
 template <typename K>
 int lru_launch_find(hctr_lru* h, const K* keys, size_t n, int mode, uint64_t admit_below,
                     uint64_t* idx, hipStream_t s) {
   uint32_t* w[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (mode == kLruInsert)
+  if (mode >= kLruInsert)
     for (int a = 0; a < 4; a++) w[a] = h->ws + a * h->ws_n;
   if (sizeof(K) != 8) w[2] = nullptr;
-  auto kernel = mode == kLruInsert && admit_below < kLruAdmitAll ? lru_find_kernel<K, true>
+  auto kernel = mode >= kLruInsert && admit_below < kLruAdmitAll ? lru_find_kernel<K, true>
                                                                   : lru_find_kernel<K, false>;
-  hipLaunchKernelGGL(kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->T, keys, n, mode, h->t,
+  // (a probe comes before its call is numbered)
+  const uint64_t t = mode == kLruProbe ? h->t + 1 : h->t;
+  hipLaunchKernelGGL(kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, h->T, keys, n, mode, t,
                      idx, w[0], w[1], w[2], w[3], admit_below, h->counters);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
+}
+
+// what lru_find_kernel(kLruInsert / kLruProbe) left in ws, in (bucket, key) order by three stable
+// passes: key low word, key high word, bucket.  *buckets = the buckets in sorted order, *positions
+// = the positions
+template <typename K>
+int lru_sort_missing(hctr_lru* h, size_t n, hipStream_t s, uint32_t** buckets,
+                     uint32_t** positions) {
+  const size_t m = h->ws_n;
+  uint32_t *bkt = h->ws, *klo = h->ws + m, *khi = h->ws + 2 * m, *seq = h->ws + 3 * m,
+           *g = h->ws + 4 * m, *tk = h->ws + 5 * m, *pa = h->ws + 6 * m, *pb = h->ws + 7 * m;
+  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, klo, tk, seq, pa, n, 32, s));
+  if (sizeof(K) == 8) {
+    hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, khi, pa, n,
+                       g);
+    HCTR_LAUNCH_CHECK();
+    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, 32, s));
+    std::swap(pa, pb);
+  }
+  hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, bkt, pa, n, g);
+  HCTR_LAUNCH_CHECK();
+  int end_bit = 1;
+  while (end_bit < 32 && ((uint64_t)1 << end_bit) <= h->T.nb) end_bit++;
+  HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, end_bit, s));
+  *buckets = tk;
+  *positions = pb;
+  return HCTR_OK;
+}
+
+// what a new capacity needs, freed again unless the table took it over
+struct LruGrown {
+  uint64_t *keys = nullptr, *scores = nullptr;
+  uint8_t* digests = nullptr;
+  float* hbm[3] = {nullptr, nullptr, nullptr};   // rows, state 0, state 1
+  void* host[3] = {nullptr, nullptr, nullptr};   // their pinned host parts
+  float* host_dev[3] = {nullptr, nullptr, nullptr};
+  uint32_t *rng = nullptr, *evict_cnt = nullptr, *evict_off = nullptr, *list = nullptr;
+  unsigned long long* tile_sums = nullptr;
+  ~LruGrown() {
+    void* dev[] = {keys, scores, digests, hbm[0], hbm[1], hbm[2], rng, evict_cnt, evict_off, list,
+                   tile_sums};
+    for (void* p : dev)
+      if (p) (void)hipFree(p);
+    for (void* p : host)
+      if (p) (void)hipHostFree(p);
+  }
+};
+
+// The table grows from C to C2 = C * 2^k slots in one step.  Arrays of the final size are
+// allocated beside the current ones (if that fails the table is as it was), the current contents
+// become their first C slots, and k passes of lru_split_kernel + lru_move_kernel, each doubling
+// the bucket count, run inside them.  H becomes min(C2, Hb): slots the table had stay in their
+// tier (there was no host part yet, or H = Hb already), a key that moves lands in its new slot's.
+// occ = the occupied slots, which bound the moves of a pass.  Synchronises the stream.
+template <typename K>
+int lru_double(hctr_lru* h, uint64_t C2, size_t occ, hipStream_t s) {
+  LruTbl& T = h->T;
+  const uint64_t C = T.C, H = T.H, S = (uint64_t)T.S, nb2 = C2 / S;
+  const uint64_t H2 = C2 < h->Hb ? C2 : h->Hb;
+  const bool tier2 = H2 < C2;
+  const size_t rb = h->row_bytes();
+  // HBM rows of the row store, and of a state (untiered: its C slots; tiered: the rows' shape)
+  const size_t hbm_rows[3] = {(size_t)H2 + h->scratch, tier2 ? (size_t)H2 + h->scratch : (size_t)C2,
+                              tier2 ? (size_t)H2 + h->scratch : (size_t)C2};
+  float* const cur[3] = {T.rows, T.st[0], T.st[1]};
+  LruGrown g;
+  bool ok = true;
+  auto dev = [&](auto** p, size_t bytes) {
+    if (ok) ok = hipMalloc(p, bytes) == hipSuccess;
+  };
+  dev(&g.keys, C2 * 8);
+  dev(&g.scores, C2 * 8);
+  dev(&g.digests, C2);
+  dev(&g.rng, 2 * nb2 * sizeof(uint32_t));
+  dev(&g.evict_cnt, nb2 * sizeof(uint32_t));
+  dev(&g.evict_off, (nb2 + 1) * sizeof(uint32_t));
+  dev(&g.tile_sums, (nb2 / 1024 + 2) * 8);
+  dev(&g.list, (C2 / 2) * 2 * sizeof(uint32_t));  // the last pass moves at most C2 / 2 keys
+  for (int a = 0; a < 3; a++) {
+    if (!cur[a]) continue;
+    dev(&g.hbm[a], hbm_rows[a] * rb);
+    if (ok && tier2)
+      ok = hipHostMalloc(&g.host[a], (C2 - H2) * rb, hipHostMallocMapped | hipHostMallocPortable) ==
+               hipSuccess &&
+           hipHostGetDevicePointer((void**)&g.host_dev[a], g.host[a], 0) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    set_error("hctr_lru: out of memory growing the table from " + std::to_string(C) + " to " +
+              std::to_string(C2) + " slots");
+    return HCTR_ERR_HIP;
+  }
+  HCTR_HIP(hipMemcpyAsync(g.keys, T.keys, C * 8, hipMemcpyDeviceToDevice, s));
+  HCTR_HIP(hipMemcpyAsync(g.scores, T.scores, C * 8, hipMemcpyDeviceToDevice, s));
+  HCTR_HIP(hipMemcpyAsync(g.digests, T.digests, C, hipMemcpyDeviceToDevice, s));
+  HCTR_HIP(hipMemsetAsync(g.digests + C, 0, C2 - C, s));
+  hipLaunchKernelGGL(lru_clear_kernel, dim3(lru_blocks(C2 - C)), dim3(kLruBlock), 0, s, g.keys + C,
+                     g.scores + C, (size_t)(C2 - C));
+  HCTR_LAUNCH_CHECK();
+  for (int a = 0; a < 3; a++) {
+    if (!cur[a]) continue;
+    if (H) HCTR_HIP(hipMemcpyAsync(g.hbm[a], cur[a], H * rb, hipMemcpyDeviceToDevice, s));
+    HCTR_HIP(hipMemsetAsync(g.hbm[a] + H * (size_t)T.D, 0, (hbm_rows[a] - H) * rb, s));
+  }
+  HCTR_HIP(hipStreamSynchronize(s));  // the host parts are copied by the host
+  for (int a = 0; a < 3; a++) {
+    if (!g.host[a]) continue;
+    memset(g.host[a], 0, (C2 - H2) * rb);
+    if (H < C) memcpy(g.host[a], h->host_alloc[a], (C - H) * rb);
+  }
+  // the table takes the new arrays over; g keeps the old ones until the passes are done
+  std::swap(T.keys, g.keys);
+  std::swap(T.scores, g.scores);
+  std::swap(T.digests, g.digests);
+  std::swap(T.rows, g.hbm[0]);
+  std::swap(T.st[0], g.hbm[1]);
+  std::swap(T.st[1], g.hbm[2]);
+  std::swap(h->rng, g.rng);
+  std::swap(h->evict_cnt, g.evict_cnt);
+  std::swap(h->evict_off, g.evict_off);
+  std::swap(h->tile_sums, g.tile_sums);
+  for (int a = 0; a < 3; a++) std::swap(h->host_alloc[a], g.host[a]);
+  T.hrows = g.host_dev[0];
+  T.hst[0] = g.host_dev[1];
+  T.hst[1] = g.host_dev[2];
+  T.H = H2;
+  const int gl = lru_group_lanes(T.D);
+  for (uint64_t c = C; c < C2; c *= 2, h->doublings++) {
+    T.C = c;
+    T.nb = c / S;
+    if (occ == 0) continue;
+    HCTR_HIP(hipMemsetAsync(h->d_total, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(lru_split_kernel<K>,
+                       dim3((int)ceil_div<size_t>(T.nb, (size_t)kLruWavesPerBlock)),
+                       dim3(kLruBlock), 0, s, T, g.list, h->d_total);
+    HCTR_LAUNCH_CHECK();
+    const size_t pairs = occ < c ? occ : (size_t)c;
+    hipLaunchKernelGGL(lru_move_kernel, dim3(lru_blocks(pairs * (size_t)gl)), dim3(kLruBlock), 0, s,
+                       T, g.list, h->d_total, pairs, gl);
+    HCTR_LAUNCH_CHECK();
+  }
+  T.C = C2;
+  T.nb = nb2;
+  if (T.init_mode == 0 && !tier2) {
+    // the one per-call row of a constant initializer follows the slots
+    hipLaunchKernelGGL(lru_fill_kernel, dim3(lru_blocks((size_t)T.D)), dim3(kLruBlock), 0, s,
+                       T.rows + C2 * (size_t)T.D, (size_t)T.D, T.init_val);
+    HCTR_LAUNCH_CHECK();
+  }
+  HCTR_HIP(hipStreamSynchronize(s));  // before g frees the old arrays and the list
+  return HCTR_OK;
+}
+
+// Below Cmax an inserting call first counts its distinct new keys m (a probe: find, sort, count;
+// nothing is written to the table) and reads (occ, m) back -- one host synchronisation -- then
+// doubles C while C < Cmax and occ + m > L * C.  *sorted: the table did not grow, so the sort still
+// stands for the call itself.
+template <typename K>
+int lru_grow_for_call(hctr_lru* h, const K* keys, size_t n, uint64_t admit_below, uint64_t* idx,
+                      uint32_t** tk, uint32_t** pb, bool* sorted, hipStream_t s) {
+  HCTR_HIP(hipMemsetAsync(h->counters + 3, 0, sizeof(unsigned long long), s));
+  HCTR_TRY(lru_launch_find(h, keys, n, kLruProbe, admit_below, idx, s));
+  HCTR_TRY(lru_sort_missing<K>(h, n, s, tk, pb));
+  const int wb = (int)ceil_div<size_t>(h->T.nb, (size_t)kLruWavesPerBlock);
+  hipLaunchKernelGGL(lru_count_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->T, keys, *tk, *pb,
+                     (uint32_t)n, h->t + 1, h->rng, h->evict_cnt, h->counters + 3);
+  HCTR_LAUNCH_CHECK();
+  HCTR_HIP(hipMemcpyAsync(h->h_word, h->counters, 4 * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, s));
+  HCTR_HIP(hipStreamSynchronize(s));
+  const uint64_t occ = h->h_word[0], m = h->h_word[3];
+  uint64_t C2 = h->T.C;
+  while (C2 < h->Cmax && (double)(occ + m) > h->L * (double)C2) C2 *= 2;
+  *sorted = C2 == h->T.C;
+  if (*sorted) return HCTR_OK;
+  HCTR_TRY(lru_double<K>(h, C2, (size_t)occ, s));
+  return lru_reserve(h, n, s);  // a table that has become tiered needs a per-call row per key
 }
 
 template <typename K>
@@ -733,37 +1000,24 @@ int lru_lookup(hctr_lru* h, const K* keys, size_t n, int insert, uint64_t admit_
                uint64_t* row_index, void* ev_keys, float* ev_rows, size_t* n_evicted,
                hipStream_t s) {
   HCTR_TRY(lru_reserve(h, n, s));
+  if (n_evicted) *n_evicted = 0;
+  uint32_t *tk = nullptr, *pb = nullptr;
+  bool sorted = false;
+  if (insert && h->T.C < h->Cmax)
+    HCTR_TRY(lru_grow_for_call(h, keys, n, admit_below, row_index, &tk, &pb, &sorted, s));
   // tiered: the find / insert kernels write slots to ws_rows, lru_stage_kernel the rows
   uint64_t* const slot_out = h->tiered() ? h->ws_rows : row_index;
-  if (n_evicted) *n_evicted = 0;
   if (!insert) {
     HCTR_TRY(lru_launch_find(h, keys, n, h->tiered() ? kLruFind : kLruRead, kLruAdmitAll, slot_out,
                              s));
   } else {
     const uint64_t t = ++h->t;
     HCTR_TRY(lru_launch_find(h, keys, n, kLruInsert, admit_below, slot_out, s));
-    const size_t m = h->ws_n;
-    uint32_t *bkt = h->ws, *klo = h->ws + m, *khi = h->ws + 2 * m, *seq = h->ws + 3 * m,
-             *g = h->ws + 4 * m, *tk = h->ws + 5 * m, *pa = h->ws + 6 * m, *pb = h->ws + 7 * m;
-    // (bucket, key) order by three stable passes: key low word, key high word, bucket
-    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, klo, tk, seq, pa, n, 32, s));
-    if (sizeof(K) == 8) {
-      hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, khi, pa,
-                         n, g);
-      HCTR_LAUNCH_CHECK();
-      HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, 32, s));
-      std::swap(pa, pb);
-    }
-    hipLaunchKernelGGL(lru_permute_kernel, dim3(lru_blocks(n)), dim3(kLruBlock), 0, s, bkt, pa, n,
-                       g);
-    HCTR_LAUNCH_CHECK();
-    int end_bit = 1;
-    while (end_bit < 32 && ((uint64_t)1 << end_bit) <= h->T.nb) end_bit++;
-    HCTR_TRY(radix_sort_pairs_u32(h->sort_temp, h->sort_temp_bytes, g, tk, pa, pb, n, end_bit, s));
     // tk = buckets in sorted order, pb = positions
+    if (!sorted) HCTR_TRY(lru_sort_missing<K>(h, n, s, &tk, &pb));
     const int wb = (int)ceil_div<size_t>(h->T.nb, (size_t)kLruWavesPerBlock);
     hipLaunchKernelGGL(lru_count_kernel<K>, dim3(wb), dim3(kLruBlock), 0, s, h->T, keys, tk, pb,
-                       (uint32_t)n, t, h->rng, h->evict_cnt);
+                       (uint32_t)n, t, h->rng, h->evict_cnt, (unsigned long long*)nullptr);
     HCTR_LAUNCH_CHECK();
     HCTR_TRY(exclusive_scan_to_offsets<uint32_t>(h->evict_cnt, h->T.nb, h->tile_sums, h->d_total,
                                                  h->evict_off, s));
@@ -888,6 +1142,14 @@ int hctr_lru_create(size_t capacity, size_t bucket_size, int dim, int key_type,
 int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key_type,
                            const char* initializer, uint64_t seed, size_t hbm_slots,
                            hctr_lru** out) {
+  return hctr_lru_create_growing(capacity, capacity, 0.5f, bucket_size, dim, key_type, initializer,
+                                 seed, hbm_slots, out);
+}
+
+int hctr_lru_create_growing(size_t init_capacity, size_t max_capacity, float max_load_factor,
+                            size_t bucket_size, int dim, int key_type, const char* initializer,
+                            uint64_t seed, size_t hbm_slots, hctr_lru** out) {
+  const size_t capacity = max_capacity;
   HCTR_REQUIRE(out, "out is null");
   HCTR_REQUIRE(bucket_size > 0 && bucket_size % kWave == 0 &&
                    bucket_size <= (size_t)kWave * kLruMaxSlotsPerLane,
@@ -895,13 +1157,26 @@ int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key
   HCTR_REQUIRE(capacity > 0, "capacity");
   HCTR_REQUIRE(dim > 0 && dim <= 16384, "dim out of range (1 .. 16384)");
   HCTR_REQUIRE(key_type == HCTR_KEY_U32 || key_type == HCTR_KEY_I64, "key_type");
-  const size_t C = ceil_div(capacity, bucket_size) * bucket_size;
-  HCTR_REQUIRE(C < 0xFFFFFFFFull, "capacity must stay below 2^32 slots");
-  HCTR_REQUIRE(hbm_slots >= C || hbm_slots % bucket_size == 0,
+  const size_t Cmax = ceil_div(capacity, bucket_size) * bucket_size;
+  HCTR_REQUIRE(Cmax < 0xFFFFFFFFull, "capacity must stay below 2^32 slots");
+  HCTR_REQUIRE(hbm_slots >= Cmax || hbm_slots % bucket_size == 0,
                "hbm_slots must be a multiple of bucket_size");
+  HCTR_REQUIRE(init_capacity > 0, "init_capacity");
+  const size_t C = ceil_div(init_capacity, bucket_size) * bucket_size;
+  size_t reach = C;
+  while (reach < Cmax) reach *= 2;
+  HCTR_REQUIRE(reach == Cmax, "max_capacity (" + std::to_string(max_capacity) +
+                                  ") must be init_capacity (" + std::to_string(init_capacity) +
+                                  ") times a power of two, both in whole buckets of " +
+                                  std::to_string(bucket_size) + " slots");
+  HCTR_REQUIRE(max_load_factor > 0.f && max_load_factor <= 1.f,
+               "max_load_factor must be in (0, 1]");
   hctr_lru* h = new hctr_lru();
   LruTbl& T = h->T;
   T.C = C;
+  h->Cmax = Cmax;
+  h->Hb = hbm_slots < Cmax ? hbm_slots : Cmax;
+  h->L = (double)max_load_factor;
   T.H = hbm_slots < C ? hbm_slots : C;
   T.S = (int)bucket_size;
   T.nb = C / bucket_size;
@@ -930,18 +1205,18 @@ int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key
             hipMalloc(&T.scores, C * 8) == hipSuccess &&
             hipMalloc(&T.digests, C) == hipSuccess &&
             hipMalloc(&T.rows, hbm_bytes) == hipSuccess &&
-            hipMalloc(&h->counters, 3 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMalloc(&h->counters, 4 * sizeof(unsigned long long)) == hipSuccess &&
             hipMalloc(&h->rng, 2 * T.nb * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&h->evict_cnt, T.nb * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&h->evict_off, (T.nb + 1) * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&h->tile_sums, (T.nb / 1024 + 2) * 8) == hipSuccess &&
             hipMalloc(&h->d_total, sizeof(unsigned long long)) == hipSuccess &&
-            hipHostMalloc(&h->h_word, sizeof(unsigned long long)) == hipSuccess;
+            hipHostMalloc(&h->h_word, 4 * sizeof(unsigned long long)) == hipSuccess;
   if (ok && h->tiered()) ok = lru_host_alloc(h, 0, (C - T.H) * h->row_bytes(), &T.hrows);
   if (ok)
     ok = hipMemset(T.digests, 0, C) == hipSuccess &&
          hipMemset(T.rows, 0, hbm_bytes) == hipSuccess &&
-         hipMemset(h->counters, 0, 3 * sizeof(unsigned long long)) == hipSuccess;
+         hipMemset(h->counters, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     set_error("hctr_lru_create: out of device memory");
@@ -1162,8 +1437,17 @@ int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t n
 
 int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size) {
   HCTR_REQUIRE(h && capacity && bucket_size, "null argument");
-  *capacity = h->T.C;
+  *capacity = h->Cmax;  // the bound size can reach; hctr_lru_growth tells the capacity now
   *bucket_size = (size_t)h->T.S;
+  return HCTR_OK;
+}
+
+int hctr_lru_growth(const hctr_lru* h, size_t* capacity_now, size_t* capacity_max,
+                    uint64_t* doublings) {
+  HCTR_REQUIRE(h && capacity_now && capacity_max && doublings, "null argument");
+  *capacity_now = h->T.C;
+  *capacity_max = h->Cmax;
+  *doublings = h->doublings;
   return HCTR_OK;
 }
 

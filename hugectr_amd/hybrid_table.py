@@ -57,36 +57,62 @@ class HybridTable:
     frees the device memory; __del__ only does so as a fallback outside interpreter shutdown.
     call_ns[t - 1] is clock() (time.time_ns unless replaced) when inserting call t was issued.
     hbm_slots=H < capacity (a multiple of bucket_size): slots >= H keep their rows and optimizer
-    states in host memory (hctr_lru_create_tiered); None or H >= capacity: all in HBM."""
+    states in host memory (hctr_lru_create_tiered); None or H >= capacity: all in HBM.
+    init_capacity=C0 < capacity (capacity = C0 * 2^j in whole buckets): the table starts with C0
+    slots and an inserting call doubles it, up to capacity, while the occupied slots plus the
+    call's new keys exceed max_load_factor times the slots (hctr_lru_create_growing).  capacity
+    stays the bound size can reach; current_capacity and doublings follow the table, and so do
+    hbm_slots and placement(): at current_capacity C the HBM slots are min(C, H)."""
 
     def __init__(self, capacity: int, dim: int, initializer: str = "", bucket_size: int = 128,
                  key_dtype=torch.int64, seed: int = 0, clock: Optional[Callable[[], int]] = None,
-                 hbm_slots: Optional[int] = None):
+                 hbm_slots: Optional[int] = None, *, init_capacity: Optional[int] = None,
+                 max_load_factor: float = 0.5):
         self.dim = int(dim)
         self.clock = clock or time.time_ns
         self.call_ns: List[int] = []
         self.key_dtype = key_dtype
         self._h = ctypes.c_void_p()
         kt = _lib.KEY_I64 if key_dtype == torch.int64 else _lib.KEY_U32
-        if hbm_slots is None:
-            check(lib.hctr_lru_create(int(capacity), int(bucket_size), self.dim, kt,
-                                      str(initializer).encode(), int(seed), ctypes.byref(self._h)))
-        else:
-            check(lib.hctr_lru_create_tiered(int(capacity), int(bucket_size), self.dim, kt,
-                                             str(initializer).encode(), int(seed), int(hbm_slots),
-                                             ctypes.byref(self._h)))
+        # (no budget: SIZE_MAX, never tiered)
+        budget = ctypes.c_size_t(-1).value if hbm_slots is None else int(hbm_slots)
+        check(lib.hctr_lru_create_growing(
+            int(capacity if init_capacity is None else init_capacity), int(capacity),
+            float(max_load_factor), int(bucket_size), self.dim, kt, str(initializer).encode(),
+            int(seed), budget, ctypes.byref(self._h)))
         c, s = ctypes.c_size_t(), ctypes.c_size_t()
         check(lib.hctr_lru_capacity(self._h, ctypes.byref(c), ctypes.byref(s)))
         self.capacity, self.bucket_size = int(c.value), int(s.value)
-        self.hbm_slots = self.placement()[0]
+        self._hbm_budget = min(budget, self.capacity)
+
+    def _growth(self) -> Tuple[int, int, int]:
+        a, b, d = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint64()
+        check(lib.hctr_lru_growth(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(d)))
+        return int(a.value), int(b.value), int(d.value)
+
+    @property
+    def current_capacity(self) -> int:
+        """the slots the table has now (capacity once it has grown all the way)"""
+        return self._growth()[0]
+
+    @property
+    def doublings(self) -> int:
+        return self._growth()[2]
+
+    @property
+    def hbm_slots(self) -> int:
+        """the slots whose rows are in HBM at the capacity the table has now"""
+        return self.placement()[0]
 
     @property
     def tiered(self) -> bool:
-        return self.hbm_slots < self.capacity
+        """part of the table's slots are, or will be once it has grown, in host memory"""
+        return self._hbm_budget < self.capacity
 
     def update_rows(self, staged: int) -> int:
         """the row bound of an hctr_updater that serves apply_update calls of up to `staged` keys:
-        the slots in HBM and, on a tiered table, the host slots staged after them"""
+        the slots in HBM and, on a tiered table, the host slots staged after them.  It grows with
+        the table until the table has reached its capacity or its HBM budget."""
         return self.hbm_slots + (int(staged) if self.tiered else 0)
 
     def placement(self) -> Tuple[int, int, int]:

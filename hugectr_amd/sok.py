@@ -180,16 +180,20 @@ class DynamicVariable(_VariableBase):
     var_type="hybrid": a table of fixed capacity that evicts its least recently used entries
     (hybrid_table.py, hctr_lru_*).  Keyword options: max_capacity (required; rounded up to whole
     buckets), max_bucket_size=128, evict_strategy="kLru" (the only strategy), filter_ratio=1.0 (the
-    admission probability of lookup_sparse(..., use_low_frequency_filter=True)).  init_capacity is
-    accepted and ignored: the store is allocated once, at max_capacity.  max_hbm_for_vectors=G
+    admission probability of lookup_sparse(..., use_low_frequency_filter=True)).  init_capacity
+    (default: max_capacity) is where the table starts: an inserting call doubles it, up to
+    max_capacity, while the occupied slots plus the call's new keys exceed max_load_factor (0.5, in
+    (0, 1]) times the slots, and only a table at max_capacity evicts; max_capacity must be
+    init_capacity times a power of two, in whole buckets.  max_hbm_for_vectors=G
     (GiB, int or float, >= 0): the rows of H = min(C, floor(G * 2^30 / (dimension * 4) / S) * S)
     slots, and their optimizer states, stay in HBM and the others live in pinned host memory
     (DESIGN.md "Hybrid table"); without it everything is in HBM (the reference defaults to 16).
-    The reference's other options (max_load_factor, ...) are kept in config_dict.  Evicted pairs go
+    The reference's other options are kept in config_dict.  Evicted pairs go
     back to the caller (sparse_read_and_evict), not to host memory."""
 
     def __init__(self, dimension: int, initializer: Union[str, float, None] = None,
-                 key_type=torch.int64, init_capacity: int = 1 << 20, mode: Optional[str] = None,
+                 key_type=torch.int64, init_capacity: Optional[int] = None,
+                 mode: Optional[str] = None,
                  seed: int = 0, name: Optional[str] = None, *, var_type: Optional[str] = None,
                  **kwargs):
         if var_type not in (None, "hbm", "hybrid"):
@@ -204,6 +208,14 @@ class DynamicVariable(_VariableBase):
         self.filter_ratio = float(ratio)
         if var_type == "hybrid" and "max_hbm_for_vectors" in kwargs:
             check_hbm_budget(kwargs["max_hbm_for_vectors"])
+        load = kwargs.get("max_load_factor", 0.5)
+        if isinstance(load, bool) or not isinstance(load, (int, float)) or \
+                not 0.0 < float(load) <= 1.0:
+            raise ValueError(f"max_load_factor must be a number in (0, 1], not {load!r}")
+        cap = kwargs.get("max_capacity")
+        if var_type == "hybrid" and cap is not None and init_capacity is not None and \
+                int(init_capacity) > int(cap):
+            raise ValueError(f"init_capacity {init_capacity} is above max_capacity {cap}")
         super().__init__(name)
         self.dimension = int(dimension)
         self.key_type = key_type
@@ -212,7 +224,8 @@ class DynamicVariable(_VariableBase):
             self.target_gpu = int(mode.split(":")[1]) if ":" in mode else 0
         self.initializer_str = "" if initializer is None else str(initializer)
         self._var_type = var_type or "hbm"
-        self.config_dict = dict(kwargs, var_type=self._var_type, init_capacity=init_capacity)
+        self.config_dict = dict(kwargs, var_type=self._var_type,
+                                init_capacity=1 << 20 if init_capacity is None else init_capacity)
         self._det: Optional[DynamicEmbeddingTable] = None
         self._lru: Optional[HybridTable] = None
         if self._var_type == "hybrid":
@@ -228,14 +241,16 @@ class DynamicVariable(_VariableBase):
                 # every rank tiers its own shard of max_capacity slots with the same budget
                 hbm = hbm_slots_for(kwargs["max_hbm_for_vectors"], self.dimension,
                                     int(kwargs["max_capacity"]), bucket)
-            self._lru = HybridTable(int(kwargs["max_capacity"]), self.dimension,
-                                    self.initializer_str, bucket, key_type, seed=seed,
-                                    hbm_slots=hbm)
+            self._lru = HybridTable(int(cap), self.dimension, self.initializer_str, bucket, key_type,
+                                    seed=seed, hbm_slots=hbm, init_capacity=init_capacity,
+                                    max_load_factor=float(load))
         else:
             self._det = DynamicEmbeddingTable([self.dimension], self.initializer_str,
-                                              init_capacity, key_type, seed=seed + 1000003 * _RANK)
+                                              1 << 20 if init_capacity is None else init_capacity,
+                                              key_type, seed=seed + 1000003 * _RANK)
         self._opt: Optional[DynamicTableOptimizer] = None
-        self._updater = None  # (hctr_updater handle, capacity) of the gradient reduce
+        # (hctr_updater handle, capacity[, row bound: hybrid]) of the gradient reduce
+        self._updater = None
 
     @property
     def backend_type(self) -> str:
@@ -913,13 +928,15 @@ class OptimizerWrapper:
         D = var.dimension
         n = keys.numel()
         slots = var._lru.find(keys)
-        if var._updater is None or var._updater[1] < n:
+        # (the row bound follows a table that is still growing)
+        ucap = max(2 * n, 1024) if var._updater is None or var._updater[1] < n else var._updater[1]
+        bound = var._lru.update_rows(ucap)
+        if var._updater is None or var._updater[1] < ucap or var._updater[2] < bound:
             if var._updater is not None:
                 lib.hctr_updater_destroy(var._updater[0])
             h = ctypes.c_void_p()
-            ucap = max(2 * n, 1024)
-            check(lib.hctr_updater_create(ucap, var._lru.update_rows(ucap), D, ctypes.byref(h)))
-            var._updater = (h, ucap)
+            check(lib.hctr_updater_create(ucap, bound, D, ctypes.byref(h)))
+            var._updater = (h, ucap, bound)
         for i in range(_num_state(self.code)):
             var._lru.state_ptr(i)
         ro = torch.arange(n + 1, dtype=torch.int64, device=kg.device)

@@ -886,7 +886,9 @@ int hctr_uvm_size(hctr_uvm* u, hctr_stream_t stream, size_t* out); /* keys held;
  * semantics (DESIGN.md "Hybrid table"; restated sequentially in tests/lru_oracle.py):
  * capacity C = capacity rounded up to a multiple of bucket_size S (64, 128, 192 or 256); key k lives
  * in bucket MurmurHash3_32(k) % (C / S) (hctr_hash_keys); slot s owns row s of ONE [C][dim] fp32
- * store allocated at create, so the table never grows.  Every inserting call t (1, 2, ...):
+ * store.  hctr_lru_create / hctr_lru_create_tiered allocate it once, at C; a table made by
+ * hctr_lru_create_growing starts smaller and doubles up to C (see there).  Every inserting call t
+ * (1, 2, ...):
  *   1. keys already stored get score t;
  *   2. the distinct missing keys of a bucket, ascending, take the lowest empty slot, else the slot
  *      with the smallest (score, slot) among scores < t -- its (key, row) is evicted -- else are
@@ -912,12 +914,15 @@ int hctr_lru_lookup_index(hctr_lru* h, const void* keys, size_t n, int insert, u
  * optimizer step drops such keys' gradients through it) */
 int hctr_lru_find(hctr_lru* h, const void* keys, size_t n, uint64_t* row_index,
                   hctr_stream_t stream);
-/* the row store (*capacity = C slot rows; the scratch rows follow them).  The pointer is stable
- * unless a call brings more keys than any before it with a key-dependent initializer, which moves
- * the store once to make room for that many scratch rows. */
+/* the row store (*capacity = the slot rows in HBM now: C, or H on a tiered table; the scratch rows
+ * follow them).  The pointer is stable unless a call brings more keys than any before it with a
+ * key-dependent initializer, which moves the store once to make room for that many scratch rows,
+ * and, on a growing table below its max_capacity, only until the next inserting call. */
 int hctr_lru_rows(hctr_lru* h, float** rows, size_t* capacity);
 /* optimizer state i (0 or 1): [C][dim] fp32 sharing the slot numbers, zero-filled on first request;
- * a newly inserted key's state rows are zeroed.  Fixed for the table's life. */
+ * a newly inserted key's state rows are zeroed.  Fixed for the table's life, except on a growing
+ * table below its max_capacity: there the pointer holds until the next inserting call, and the
+ * array has the current capacity's rows. */
 int hctr_lru_state(hctr_lru* h, int i, float** state, hctr_stream_t stream);
 /* occupied slots in slot order: keys (key_type), slots and scores (uint64) and rows
  * ([max_keys][dim]); any of them may be NULL; *exported = how many (host sync) */
@@ -925,6 +930,8 @@ int hctr_lru_export(hctr_lru* h, void* keys, uint64_t* slots, uint64_t* scores, 
                     size_t max_keys, size_t* exported, hctr_stream_t stream);
 int hctr_lru_size(hctr_lru* h, size_t* out, hctr_stream_t stream);              /* host sync */
 int hctr_lru_rejected_count(hctr_lru* h, uint64_t* out, hctr_stream_t stream);  /* host sync */
+/* *capacity = C, the bound hctr_lru_size can reach (a growing table's max_capacity in whole
+ * buckets, whatever its capacity now: hctr_lru_growth) */
 int hctr_lru_capacity(const hctr_lru* h, size_t* capacity, size_t* bucket_size);
 /* Low-frequency admission filter (SOK lookup_sparse(..., use_low_frequency_filter=True)).  An
  * inserting call t as hctr_lru_lookup_index(insert=1), except that a key which is not stored is
@@ -972,7 +979,7 @@ int hctr_lru_create_tiered(size_t capacity, size_t bucket_size, int dim, int key
                            const char* initializer, uint64_t seed, size_t hbm_slots,
                            hctr_lru** out);
 /* *hbm_slots = H (C untiered), *hbm_rows = rows of the HBM row store (H slots + per-call rows),
- * *host_rows = C - H */
+ * *host_rows = C - H; on a growing table all three are those of the capacity now */
 int hctr_lru_placement(const hctr_lru* h, size_t* hbm_slots, size_t* hbm_rows, size_t* host_rows);
 /* device address of an array's host part (rows [C - H][dim] for array 0, state array - 1 for 1, 2;
  * row s - H is slot s), NULL on an untiered table or for a state not allocated yet */
@@ -991,13 +998,43 @@ int hctr_lru_scatter_slots(hctr_lru* h, int array, const uint64_t* slots, size_t
  * distinct host slots among `slots`, in ascending order, are staged into the per-call rows H + u
  * (u = rank), the update runs there, and they are written back; the renumbering is monotone in
  * the slot, so the update sees the same segments and computes the same bits as on the untiered
- * table.  u must have been created with max_rows >= H + nnz (capacity C when untiered).  Uses the
- * handle's workspace; no host synchronisation. */
+ * table.  u must have been created with max_rows >= H + nnz (capacity C when untiered), H and C
+ * being those of the capacity now on a growing table.  Uses the handle's workspace; no host
+ * synchronisation. */
 int hctr_lru_apply_update(hctr_lru* h, hctr_updater* u, size_t buckets, size_t nnz,
                           const int64_t* bucket_range, const uint64_t* slots, const void* grad,
                           int grad_dtype, int optimizer, float lr, float beta1, float beta2,
                           float epsilon, float momentum_factor, float scaler, uint64_t times,
                           hctr_stream_t stream);
+/* Growth (the reference's init_capacity / max_capacity / max_load_factor,
+ * R/sparse_operation_kit/kit_src/variable/impl/variable_base.cu:44-63).  C0 = init_capacity and
+ * Cmax = max_capacity, each rounded up to whole buckets; Cmax / S must be (C0 / S) * 2^j, j >= 0,
+ * else an error naming both.  L = max_load_factor in (0, 1], widened to double.  The table starts
+ * with C = C0 slots.  An inserting call t first takes occ = the occupied slots and m = the call's
+ * distinct keys that are not stored (in a filtered call: the admitted ones; the reserved key is
+ * not counted) and, while C < Cmax and occ + m > L * C, doubles C; occ and m are taken once.  Then
+ * the call runs as above on the capacity reached.  Read-only and empty calls never grow the table.
+ * A doubling C -> 2C (nb = C / S buckets become 2 nb): a key of bucket b now hashes to b or to
+ * b + nb.  A key that stays keeps its slot, score, row and states.  The keys of b that move take, in
+ * ascending old-slot order, slots (b + nb) * S + 0, 1, ... with their score, digest, row and
+ * allocated states, and leave empty slots.  Nothing is evicted or rejected, and t, the size and
+ * the rejected / filtered counts do not change.
+ * hbm_slots is the HBM budget Hb (a multiple of S, or >= Cmax: never tiered): at capacity C the
+ * slots [0, H), H = min(C, Hb), are in HBM and [H, C) in host memory; a key that stays never
+ * changes tier, one that moves lands in its new slot's.  Every observable of a tiered growing
+ * table is that of its untiered growing twin, row numbers of HBM slots aside.
+ * While C < Cmax the pointers of hctr_lru_rows, hctr_lru_state and hctr_lru_host_part are valid
+ * until the next inserting call, which also costs one host synchronisation (occ and m are read
+ * back); at Cmax the table is the one hctr_lru_create(_tiered) makes, which are the j = 0 case.
+ * If the memory of a doubling cannot be had the call returns HCTR_ERR_HIP, the message names the
+ * capacity it could not reach, and the table, t included, is as before the call.
+ * Argument errors are reported before any device call. */
+int hctr_lru_create_growing(size_t init_capacity, size_t max_capacity, float max_load_factor,
+                            size_t bucket_size, int dim, int key_type, const char* initializer,
+                            uint64_t seed, size_t hbm_slots, hctr_lru** out);
+/* the capacity now, the largest it can reach (hctr_lru_capacity's), the doublings so far */
+int hctr_lru_growth(const hctr_lru* h, size_t* capacity_now, size_t* capacity_max,
+                    uint64_t* doublings);
 
 /* ------------------------------------------------------------------------------------------ */
 /* SOK dense lookups (sok.all2all_dense_embedding, sok.group_lookup)                           */
