@@ -277,6 +277,17 @@ _SIGNATURES = {
                                       c_uint64, _P]),
     "hctr_dist_select": (c_int, [_P, c_int, c_size_t, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "hctr_indexed_row_copy": (c_int, [POINTER(RowCopyTask), c_int, c_int, c_int, _P]),
+    "hctr_ebc_io_create": (c_int, [c_size_t, c_int, c_int, POINTER(_P)]),
+    "hctr_ebc_io_destroy": (c_int, [_P]),
+    "hctr_ebc_io_chunk": (c_int, [_P, c_int, POINTER(_P), POINTER(_P), POINTER(_P), POINTER(_P)]),
+    "hctr_ebc_io_wait": (c_int, [_P, c_int]),
+    "hctr_ebc_io_check": (c_int, [_P, c_int, c_size_t, c_int, c_int, c_uint64, _P, _P]),
+    "hctr_ebc_io_import_static": (c_int, [_P, c_int, c_size_t, c_int, c_int, c_uint64, c_uint64, _P,
+                                          _P, _P, _P]),
+    "hctr_ebc_io_select": (c_int, [_P, c_int, c_size_t, c_int, c_int, c_uint64, _P, _P, _P, _P, _SZP,
+                                   _P]),
+    "hctr_ebc_io_scatter_rows": (c_int, [c_size_t, c_int, _P, _P, _P, c_uint64, _P]),
+    "hctr_ebc_io_export_static": (c_int, [_P, c_int, c_size_t, c_uint64, c_uint64, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -952,3 +952,6 @@ int hctr_ebc_local_reduce(hctr_updater* u, size_t buckets, size_t nnz, const int
 
 // CompressionStrategy.Unique on several GPUs: plan / network forward / network backward
 #include "ebc_unique.hip"
+
+// embedding_dump / embedding_load: pinned chunks read over the host link (check, import, select)
+#include "ebc_io.hip"

@@ -46,6 +46,7 @@ import torch.distributed as dist
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
+from .ebc_io import TableIO
 
 _DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 # optimizers whose step on a dynamic table runs in the static tables' sparse update, on the flat
@@ -139,7 +140,7 @@ class EmbeddingCollectionConfig:
         return own
 
 
-class EmbeddingCollection:
+class EmbeddingCollection(TableIO):
     """Runtime of one rank.  keys / bucket_range passed to forward are this rank's data-parallel
     share in feature-major order: bucket = lookup * (batch/world) + b_local."""
 
@@ -430,6 +431,24 @@ class EmbeddingCollection:
         self._upd_recv = ctypes.c_void_p()
         if self._unique:
             self._setup_unique(n_local_of)
+
+    # -- embedding_dump / embedding_load (ebc_io.TableIO: export_table / import_table) ---------------
+    def _io_layout(self, t: int):
+        """where table t (position in self.tables) lives on this rank; None: not held here"""
+        if t not in self.local_tables:
+            return None
+        owners = self.owners[t]
+        lay = dict(dynamic=self.dynamic, num_shards=len(owners), shard_id=owners.index(self.rank),
+                   writes=True)
+        if self.dynamic:
+            lay.update(vocab=1 << 63, cls=self.class_of_table[t])
+        else:
+            lay.update(vocab=int(self.tables[t].max_vocabulary_size),
+                       row_start=self.row_start_of_table[t])
+        return lay
+
+    def _io_state_arrays(self):
+        return [a for a in (self.accum, self.ftrl_z) if a is not None]
 
     def __del__(self):
         for name in ("_upd", "_upd_recv"):
@@ -1041,7 +1060,7 @@ class EmbeddingCollection:
                                       ptr(self.accum), ptr(self.ftrl_z), stream_ptr()))
 
 
-class DataParallelCollection:
+class DataParallelCollection(TableIO):
     """Replicated ("dp") tables of an embedding_collection
     (R/HugeCTR/embedding/data_parallel_embedding.cpp; shard_strategy ("dp", [...]) of
     EmbeddingCollectionConfig.shard): every GPU holds the whole table -- identically initialised,
@@ -1082,6 +1101,7 @@ class DataParallelCollection:
             starts.append(rows)
             rows += t.max_vocabulary_size
         self.rows = max(rows, 1)
+        self.row_start_of_table = starts
         self.table = torch.empty((self.rows, self.ev), dtype=torch.float32, device=self.dev)
         g = torch.Generator(device=self.dev)
         g.manual_seed(seed * 1000003 + 99991)  # replica-uniform: the SAME stream on every rank
@@ -1113,6 +1133,16 @@ class DataParallelCollection:
         if optimizer == _lib.OPT_FTRL:
             check(lib.hctr_updater_set_ftrl(self._apply, *self.ftrl))
         self._times = 0
+
+    # -- embedding_dump / embedding_load: a replicated table is written once, by rank 0
+    #    (parameter_IO.cpp:300-349), and every rank imports the whole file (num_shards = 1) ----------
+    def _io_layout(self, t: int):
+        return dict(dynamic=False, num_shards=1, shard_id=0, writes=self.rank == 0,
+                    vocab=int(self.tables[t].max_vocabulary_size),
+                    row_start=self.row_start_of_table[t])
+
+    def _io_state_arrays(self):
+        return [a for a in (self.accum, self.ftrl_z) if a is not None]
 
     def __del__(self):
         for name in ("_reduce", "_apply"):

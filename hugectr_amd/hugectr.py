@@ -2024,6 +2024,114 @@ class Model:
             blobs = [b.detach().float().contiguous().flatten() for b, _ in self._dense_blobs()]
             torch.cat(blobs).cpu().numpy().astype("<f4").tofile(f"{prefix}_dense_{iteration}.model")
 
+    # -- embedding_collection checkpoints: the reference's embedding_dump / embedding_load
+    #    (R/HugeCTR/include/pybind/model_wrapper.hpp:167-173, R/HugeCTR/src/pybind/model.cpp:521-665;
+    #    bytes: hugectr_amd/embedding_io.py, deviations: INTEGRATION.md) -------------------------------
+    def _ebc_io_plan(self, table_names):
+        """per user config c (the order the configs were added): {table id: (name, runtime
+        collection, position in its tables)} of the tables asked for.  A table's id is its
+        position in the USER's config, in order of first appearance in config.lookups
+        (emb_table_config_list_, embedding_collection.hpp:205-214) -- whatever runtime collections
+        the config was split into (by ev_size, mp / dp placement, compression strategy)."""
+        assert self._compiled, "call compile() first"
+        wanted = [str(n) for n in (table_names or [])]
+        plan, known = [], set()
+        for cfg in self.ebc_configs:
+            tables = []
+            for t, _, _, _ in cfg.lookups:
+                if t not in tables:
+                    tables.append(t)
+            entries = {}
+            for rt in self._ebc:
+                if rt["parent"] is not cfg:
+                    continue
+                e = rt["train"]
+                for k, tc in enumerate(e.tables):
+                    known.add(tc.name)
+                    if not wanted or tc.name in wanted:
+                        entries[tables.index(tc)] = (tc.name, e, k)
+            plan.append(entries)
+        unknown = [n for n in wanted if n not in known]
+        if unknown:
+            raise RuntimeError(f"embedding_dump / embedding_load: no embedding table named "
+                               f"{unknown}; the model's tables are {sorted(known)}")
+        return plan
+
+    def embedding_dump(self, path: str, table_names: Sequence[str] = (),
+                       optimizer_states: bool = False):
+        """Model::embedding_dump: <path>/embedding_collection_<c>/{meta_data, key<i>, weight<i>}
+        for every EmbeddingCollectionConfig c of the model, one key and one weight file per table,
+        independent of the sharding and of how the config was split into runtime collections.
+        table_names: EmbeddingTableConfig names (empty: every table).  optimizer_states=True also
+        writes opt_state<i> (not in the reference).  Several ranks: rank 0 creates the files at full
+        size, then every owner writes its portion at its offset (the scheme of
+        save_params_to_files)."""
+        from . import embedding_io
+        self._drain_prefetch()
+        self.check_overflow()
+        plan = self._ebc_io_plan(table_names)
+        if optimizer_states:  # refused before anything is written
+            for entries in plan:
+                for _, e, _ in entries.values():
+                    e.io_check_optimizer_states()
+        for c, entries in enumerate(plan):
+            if not entries:
+                continue
+            ids = sorted(entries)
+            mine = [entries[i][1].table_key_count(entries[i][2]) for i in ids]
+            counts = [mine]
+            if self.world > 1:
+                counts = [None] * self.world
+                dist.all_gather_object(counts, mine)
+            e0 = entries[ids[0]][1]
+            kd = "<i8" if getattr(e0, "key_dtype", torch.int64) == torch.int64 else "<u4"
+            meta = embedding_io.MetaData(
+                ids, {i: sum(r[j] for r in counts) for j, i in enumerate(ids)},
+                {i: entries[i][1].ev for i in ids}, np.dtype(kd))
+            opt = (e0.io_state_count(), int(e0.optimizer)) if optimizer_states else None
+            if self.rank == 0:
+                embedding_io.create_collection(path, c, meta, opt)
+            if self.world > 1:
+                dist.barrier()
+            for j, i in enumerate(ids):
+                name, e, k = entries[i]
+                if mine[j] == 0:
+                    continue
+                with embedding_io.TableFiles(path, c, i, "r+", name=name) as f:
+                    e.export_table(k, f, sum(r[j] for r in counts[:self.rank]), optimizer_states)
+            torch.cuda.synchronize()
+            if self.world > 1:
+                dist.barrier()
+
+    def embedding_load(self, path: str, table_names: Sequence[str] = ()):
+        """Model::embedding_load: every rank keeps the keys it owns (key % num_shards ==
+        shard_id; a replicated table loads whole on every rank).  The tables are written in place
+        -- a captured graph stays valid -- and only after every table asked for has been
+        validated.  Optimizer state is loaded where the dump holds it for the model's optimizer."""
+        from . import embedding_io
+        self._drain_prefetch()
+        self.check_overflow()
+        plan = self._ebc_io_plan(table_names)
+        opened = []
+        try:
+            for c, entries in enumerate(plan):
+                if not entries:
+                    continue
+                meta = embedding_io.read_meta(path, c)
+                for i in sorted(entries):
+                    name, e, k = entries[i]
+                    opened.append((e, k, embedding_io.TableFiles(path, c, i, "r", meta, name)))
+            for e, k, f in opened:
+                e.validate_table(k, f)
+            for e, k, f in opened:
+                e.import_table(k, f, validated=True)
+        finally:
+            for _, _, f in opened:
+                f.close()
+        torch.cuda.synchronize()
+        if self.world > 1:
+            dist.barrier()
+
     def _dense_blobs(self):
         """the trainable dense tensors in the order and orientation of the reference's dense model
         file (what R/onnx_converter/hugectr2onnx/hugectr_loader.py:336-520 reads back): per layer

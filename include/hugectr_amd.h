@@ -1093,6 +1093,52 @@ typedef struct {
 int hctr_indexed_row_copy(const hctr_row_copy_task* tasks, int num_tasks, int src_dtype,
                           int dst_dtype, hctr_stream_t stream);
 
+/* ---- embedding_dump / embedding_load of embedding_collection tables (csrc/ebc_io.hip) -----------
+ * The files (hugectr_amd/embedding_io.py; EmbeddingParameterIO, R/HugeCTR/embedding_storage/
+ * weight_io/parameter_IO.cpp) hold a table's keys and rows in an order that does not depend on the
+ * sharding, so the keys a GPU owns arrive interleaved with foreign ones.  The handle owns TWO
+ * pinned, device-mapped host chunks (hipHostMalloc Mapped | Portable, as hctr_tiered_create) of
+ * chunk_rows x (key + row + two state rows): the caller fills one from the files while the
+ * kernels read the other one directly over the host link -- there is no staging copy.
+ * hctr_ebc_io_chunk: the HOST addresses of chunk `which` (0 | 1): keys (key_type), rows / state0 /
+ * state1 [chunk_rows][ev_size] fp32.  Every call below that works on a chunk marks it on `stream`;
+ * hctr_ebc_io_wait blocks the host until that work is done (then the chunk may be refilled or,
+ * after an export, read).
+ * Ownership is the collection's: key < vocab is owned when key % num_shards ==
+ * shard_id and lives in row row_start + key / num_shards.
+ *   check          d_counts (DEVICE uint64[3], caller-zeroed) += {owned, foreign, out of range
+ *                  (key < 0 or >= vocab)} of the chunk's first n keys; reads the keys only
+ *   import_static  every owned key's row -> table, and its state rows -> state0 / state1 (NULL =
+ *                  no such array); one row per lane group, 16-byte accesses when ev_size % 4 == 0,
+ *                  element-wise otherwise; foreign and out-of-range keys write nothing
+ *   select         stable compaction of the owned keys (as int64) and their rows / state rows into
+ *                  DEVICE buffers of at least n entries; *selected on the HOST (one stream
+ *                  synchronisation) -- the dynamic table stores them from there (hctr_det_lookup_rows
+ *                  with insert, hctr_det_scatter_update; load_by_id, dynamic_embedding.cu:432-472)
+ *   scatter_rows   dst[row_index[i]][:] = src[i][:] for row_index[i] < row_bound, all DEVICE (the
+ *                  state rows of a dynamic table at the row numbers of hctr_det_lookup_rows)
+ *   export_static  n consecutive rows starting at table_rows (and state0 / state1) -> the chunk by
+ *                  asynchronous copies; its keys first_key + j * key_step written by the host */
+typedef struct hctr_ebc_io hctr_ebc_io;
+int hctr_ebc_io_create(size_t chunk_rows, int ev_size, int key_type, hctr_ebc_io** out);
+int hctr_ebc_io_destroy(hctr_ebc_io* io);
+int hctr_ebc_io_chunk(hctr_ebc_io* io, int which, void** keys, float** rows, float** state0,
+                      float** state1);
+int hctr_ebc_io_wait(hctr_ebc_io* io, int which);
+int hctr_ebc_io_check(hctr_ebc_io* io, int which, size_t n, int num_shards, int shard_id,
+                      uint64_t vocab, uint64_t* d_counts, hctr_stream_t stream);
+int hctr_ebc_io_import_static(hctr_ebc_io* io, int which, size_t n, int num_shards, int shard_id,
+                              uint64_t vocab, uint64_t row_start, float* table, float* state0,
+                              float* state1, hctr_stream_t stream);
+int hctr_ebc_io_select(hctr_ebc_io* io, int which, size_t n, int num_shards, int shard_id,
+                       uint64_t vocab, int64_t* out_keys, float* out_rows, float* out_state0,
+                       float* out_state1, size_t* selected, hctr_stream_t stream);
+int hctr_ebc_io_scatter_rows(size_t n, int ev_size, const uint64_t* row_index, const float* src,
+                             float* dst, uint64_t row_bound, hctr_stream_t stream);
+int hctr_ebc_io_export_static(hctr_ebc_io* io, int which, size_t n, uint64_t first_key,
+                              uint64_t key_step, const float* table_rows, const float* state0,
+                              const float* state1, hctr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
