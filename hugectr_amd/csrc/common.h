@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -78,6 +80,19 @@ static inline T ceil_div(T a, T b) {
 }
 
 static inline hipStream_t as_stream(hctr_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// an integer knob from the environment: its value if positive, else dflt.  `field` picks an entry
+// of a comma-separated list and exists for one knob only (HCTR_INTER_WAVES=forward,backward).
+// Not cached here: a caller that reads once keeps the result in a static.
+static inline int env_int(const char* name, int dflt, int field = 0) {
+  const char* e = getenv(name);
+  for (; e && field > 0; field--) {
+    e = strchr(e, ',');
+    if (e) e++;
+  }
+  const int v = e ? atoi(e) : 0;
+  return v > 0 ? v : dflt;
+}
 
 // grid cap for grid-stride memory-bound kernels: 256 CUs x 8 blocks
 constexpr int kMaxGrid = 2048;

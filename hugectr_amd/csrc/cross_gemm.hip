@@ -34,10 +34,8 @@
 //       EPI_RESIDUAL  C = (T)(acc + R)
 //   * block id -> tile: column tiles of one row panel are consecutive on ONE XCD (block b runs on
 //     XCD b % 8), so the panel of A is fetched from HBM once per XCD L2.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
 #include "common.h"
+#include "cvt16.h"
 
 namespace hctr {
 namespace {
@@ -53,35 +51,21 @@ constexpr int kGemmBN = 128;
 constexpr int kGemmBK = 64;  // 16-bit elements: 128 bytes per LDS row
 constexpr int kEpiPlain = 0, kEpiCross = 1, kEpiResidual = 2;
 
+// H16<BF> (cvt16.h) with the type's MFMA on packed words
 template <bool BF>
 struct Cg16;
 template <>
-struct Cg16<false> {
+struct Cg16<false> : hctr::H16<false> {
   __device__ __forceinline__ static cg_f32x16 mfma(cg_u32x4 a, cg_u32x4 b, cg_f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<cg_f16x8*>(&a),
                                                   *reinterpret_cast<cg_f16x8*>(&b), c, 0, 0, 0);
   }
-  __device__ __forceinline__ static float to_f32(unsigned short u) {
-    _Float16 h = *reinterpret_cast<_Float16*>(&u);
-    return (float)h;
-  }
-  __device__ __forceinline__ static unsigned short from_f32(float v) {
-    _Float16 h = (_Float16)v;
-    return *reinterpret_cast<unsigned short*>(&h);
-  }
 };
 template <>
-struct Cg16<true> {
+struct Cg16<true> : hctr::H16<true> {
   __device__ __forceinline__ static cg_f32x16 mfma(cg_u32x4 a, cg_u32x4 b, cg_f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<cg_bf16x8*>(&a),
                                                    *reinterpret_cast<cg_bf16x8*>(&b), c, 0, 0, 0);
-  }
-  __device__ __forceinline__ static float to_f32(unsigned short u) {
-    return __uint_as_float((unsigned)u << 16);
-  }
-  __device__ __forceinline__ static unsigned short from_f32(float v) {
-    __bf16 h = (__bf16)v;
-    return *reinterpret_cast<unsigned short*>(&h);
   }
 };
 

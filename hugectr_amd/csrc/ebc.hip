@@ -20,6 +20,7 @@
 
 #include "block_prims.h"
 #include "common.h"
+#include "cvt16.h"
 #include "radix_sort.h"
 #include "scan.h"
 #include "sparse_update.h"
@@ -209,27 +210,6 @@ __global__ void __launch_bounds__(kBlock)
 
 // recv / send blocks: block t holds [bpg][ev] vectors of (source rank, its local lookup).
 // src_blocks[l * max_shards + s] = block index of shard s of global lookup l, or -1.
-template <typename T>
-__device__ __forceinline__ float ld_as_f32(const T* p);
-template <>
-__device__ __forceinline__ float ld_as_f32<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ld_as_f32<__half>(const __half* p) { return __half2float(*p); }
-template <>
-__device__ __forceinline__ float ld_as_f32<__hip_bfloat16>(const __hip_bfloat16* p) {
-  return __bfloat162float(*p);
-}
-template <typename T>
-__device__ __forceinline__ void st_from_f32(T* p, float v);
-template <>
-__device__ __forceinline__ void st_from_f32<float>(float* p, float v) { *p = v; }
-template <>
-__device__ __forceinline__ void st_from_f32<__half>(__half* p, float v) { *p = __float2half_rn(v); }
-template <>
-__device__ __forceinline__ void st_from_f32<__hip_bfloat16>(__hip_bfloat16* p, float v) {
-  *p = __float2bfloat16(v);
-}
-
 template <typename T, bool FWD>
 __global__ void __launch_bounds__(kBlock)
     ebc_network_kernel(size_t bpg, int num_lookup, int ev, int max_shards,

@@ -1,4 +1,4 @@
-"""The dot interaction's kernels (hugectr_amd/csrc/dense_ops.hip) against a float64 restatement of
+"""The dot interaction's kernels (hugectr_amd/csrc/interaction.hip) against a float64 restatement of
 the operation, in every branch their dispatch can take and with batches larger than one grid.
 
   * the reference is `_ref_fwd` / `_ref_bwd` below (numpy float64), never a kernel, torch on the
