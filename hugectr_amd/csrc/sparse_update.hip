@@ -2302,6 +2302,10 @@ __global__ void __launch_bounds__(kBlock)
       if (n > 1) {
         const float sc = 1.0f / (float)n;
         g = g * (D % 2 == 0 ? Load4<GradT>::rnd(sc) : sc);
+        // the product first, THEN the conversion: without the barrier the compiler folds
+        // convert * scaler -> convert into one mixed-precision fma(g, sc, +0), and -0 + +0 is
+        // +0: a gradient of -0.0 came back as +0.0 (the reference's __hmul2 keeps the sign)
+        asm volatile("" : "+v"(g));
       }
     }
     if constexpr (std::is_same<GradT, float>::value) wgrad[i] = g;
