@@ -1,5 +1,7 @@
 // common.h -- shared host/device helpers for libhugectr_amd (gfx950 only).
 #pragma once
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -7,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hugectr_amd.h"
@@ -92,6 +95,24 @@ static inline int env_int(const char* name, int dflt, int field = 0) {
   }
   const int v = e ? atoi(e) : 0;
   return v > 0 ? v : dflt;
+}
+
+// run-time value -> template argument: f(std::true_type / std::false_type) for a flag,
+// f((T*)nullptr) for the element type of an HCTR_EMB_* dtype
+template <typename F>
+void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case HCTR_EMB_F32: return f((float*)nullptr);
+    case HCTR_EMB_F16: return f((__half*)nullptr);
+    case HCTR_EMB_BF16: return f((__hip_bfloat16*)nullptr);
+  }
+  HCTR_REQUIRE(false, "dtype");
+  return HCTR_OK;  // (not reached)
 }
 
 // grid cap for grid-stride memory-bound kernels: 256 CUs x 8 blocks

@@ -1190,11 +1190,3 @@ int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* d
 }
 
 }  // extern "C"
-
-// The host interpreter of tests/emu (test infrastructure, a plain C++ compiler) compiles
-// interaction.hip as a unit of its own, like hipcc, and says so (HCTR_EMU_INTERACTION_UNIT).  A test
-// tree whose unit list predates interaction.hip -- the previous commit's, which has to keep building
-// a complete interpreter library from this directory -- gets the interaction through this unit.
-#if !defined(__HIPCC__) && !defined(HCTR_EMU_INTERACTION_UNIT)
-#include "interaction.hip"
-#endif

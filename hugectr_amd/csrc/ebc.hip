@@ -838,7 +838,7 @@ int hctr_updater_reduce_presorted(hctr_updater* u, size_t positions, size_t buck
   // out_sum[row] = sum of grad[bucket] over the row's run: the segmented reduce of the sparse
   // update with a store-only "optimizer" (rows that own no position keep the zero of the memset)
   OptState o;
-  o.optimizer = kOptStoreSumId;
+  o.optimizer = kOptStoreSum;
   o.update_type = HCTR_UPDATE_LOCAL;
   o.lr = 0.0f;
   o.scaler = 1.0f;

@@ -886,27 +886,12 @@ int sample_grid(size_t batch, int waves_per_cu) {
   return (int)(batch < gmax ? batch : gmax);
 }
 
-// run-time value -> template argument: f(std::integral_constant<int, W>{}) for the W of Ws that
-// equals width (the caller has checked that one does), f(std::true_type / std::false_type) for a
-// flag, f((T*)nullptr) for the element type of an HCTR_EMB_* dtype
+// run-time value -> template argument (see with_bool / with_dtype, common.h):
+// f(std::integral_constant<int, W>{}) for the W of Ws that equals width (the caller has checked
+// that one does)
 template <int... Ws, typename F>
 void with_width(int width, F&& f) {
   (void)((width == Ws && (f(std::integral_constant<int, Ws>{}), true)) || ...);
-}
-template <typename F>
-void with_bool(bool v, F&& f) {
-  if (v) f(std::true_type{});
-  else f(std::false_type{});
-}
-template <typename F>
-int with_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case HCTR_EMB_F32: return f((float*)nullptr);
-    case HCTR_EMB_F16: return f((__half*)nullptr);
-    case HCTR_EMB_BF16: return f((__hip_bfloat16*)nullptr);
-  }
-  HCTR_REQUIRE(false, "dtype");
-  return HCTR_OK;  // (not reached)
 }
 
 int interaction_fwd_impl(size_t batch, int n_emb, int width, const void* mlp, const void* emb,

@@ -17,7 +17,13 @@ struct OptState {
   int state_half = 0;  // optimizer state holds fp16 values (fp16 embeddings)
 };
 
-constexpr int kOptStoreSumId = 1000;  // internal: table[row] = per-row gradient sum
+// internal pseudo-optimizer of hctr_updater_reduce_presorted: table[row] = per-row gradient sum
+// (no read of the row)
+constexpr int kOptStoreSum = 1000;
+
+// what the hot / cold path keeps between updates: its buffers, the cold chain's stream, the plan of
+// the batch in hand (sparse_update.hip)
+struct HotColdState;
 
 struct SparseUpdater {
   size_t max_nnz = 0;
@@ -46,6 +52,7 @@ struct SparseUpdater {
   uint32_t* big_list = nullptr;    // [4][tiles] runs longer than kCombBigTiles tiles (seg_combine_big)
   size_t big_stride = 0;
   Profiler* prof = nullptr;
+  std::vector<void*> owned;  // the device buffers above, as create() allocated them
   bool allow_ftrl = false;  // the legacy embedding rejects Ftrl as the reference does (q9)
   // the (row, bucket) sort needs only the index stage's output, not the gradients: presort() runs
   // it on a side stream while the caller's stream does the gather and the dense tower
@@ -66,37 +73,14 @@ struct SparseUpdater {
   // is skipped (RsFirst).  nullptr = unknown: the pairs are expanded.
   const uint32_t* one_hot_flag = nullptr;
   // hot rows of one-hot batches (sparse_update.hip, "hot rows of a one-hot batch"): positions whose
-  // row is < hot_rows are summed per (stream, chunk) by hot_chunk_kernel and never sorted.
+  // row is < hot_rows are summed per (stream, chunk) and never sorted; the positions of the other
+  // rows are counted per row ("cold rows of a one-key-per-position batch").
   // hot_streams: 0 = layout unknown (no hot path); S = the batch is sample-major with S buckets
   // per sample (all positions p with the same p % S come from one table); 1 = positions as they lie
   uint32_t hot_streams = 0;
-  uint32_t hot_rows = 0;        // H; 0 = off (HCTR_HOT_ROWS, default 8192, at most 16384)
-  hipStream_t hot_side = nullptr;  // the cold pairs' chain (default priority)
-  size_t hot_min_n = 0;         // batches with fewer positions keep the plain path (HCTR_HOT_MIN)
-  uint32_t hot_chunks_max = 0;  // chunks the tables below have room for
-  uint16_t* hot_loc = nullptr;        // [hot_rows][hot_chunks_max] partial number of (row, chunk)
-  uint32_t* hot_S = nullptr;           // [hot_chunks_max][4096] a chunk's hot entries, sorted
-  uint32_t* hot_meta = nullptr;        // [hot_chunks_max][2] entries, first pool slot
-  uint32_t* hot_tpref = nullptr;       // [hot_chunks_max][129] run starts in front of a tile
-  uint32_t* hot_items = nullptr;       // tiles with entries (work list of hot_reduce_kernel)
-  uint32_t* hot_loc_blk = nullptr;     // [hot_rows] blocks of 32 chunks that hold a partial of the row
-  uint32_t* hot_joins = nullptr;       // [.][3] runs that cross tile borders (hot_join_kernel)
-  uint32_t* hot_counts = nullptr;      // two alternating sets {pool slots, items, joins, -}
-  uint32_t hot_parity = 0;             // set the next update takes
-  float* hot_head = nullptr;           // [hot_chunks_max * 128][D] tile partials of runs that
-  float* hot_tail = nullptr;           //   cross tile borders inside a chunk
-  // cold rows of the same batches (sparse_update.hip, "cold rows of a one-key-per-position batch"):
-  // counted per row instead of sorted.
-  uint32_t* cold_cnt = nullptr;     // [max_vocab] per-row counter / base word, zero between updates
-  uint32_t* cold_rank = nullptr;    // [max_nnz]
-  uint32_t* cold_plist = nullptr;   // [max_nnz]
-  uint32_t* cold_bkt = nullptr;     // [max_nnz]
-  void* cold_dlist = nullptr;       // [max_nnz] uint2
-  void* cold_singles = nullptr;     // [max_nnz] uint2
-  void* cold_segs = nullptr;        // [max_nnz / 2 + 1] uint4
-  void* cold_longs = nullptr;       // [max_nnz / 2 + 1] uint4 (runs longer than short_max >= 8)
-  uint32_t* cold_counts = nullptr;  // two alternating sets of counters
-  void* pre_plan = nullptr;         // geometry / buffers / events of the batch in hand (PrePlan)
+  uint32_t hot_rows = 0;  // H; 0 = off (HCTR_HOT_ROWS, default 8192, at most 16384)
+  size_t hot_min_n = 0;   // batches with fewer positions keep the plain path (HCTR_HOT_MIN)
+  HotColdState* hot_cold = nullptr;  // set up by hot_buffers()
   size_t early_n = 0;  // > 0: sort_*_out hold the sorted pairs of (early_vi, early_buckets)
   const uint64_t* early_vi = nullptr;
   size_t early_buckets = 0;
@@ -109,6 +93,7 @@ struct SparseUpdater {
   // the path never does it that way.
   int create(size_t max_nnz, size_t max_vocab, int D, bool eager_hot = false);
   int hot_buffers(hipStream_t s);
+  // frees what create() / hot_buffers() got as far as allocating and resets the object
   int destroy();
   // optional: start sorting n >= live nnz (row, bucket) pairs now, concurrently with stream s
   int presort(size_t buckets, size_t n, const void* row_offset, int key_type,

@@ -8,73 +8,32 @@
 // accumulating), the run count stays on the device (persistent grid-stride over runs), and a
 // "group" of D/4 lanes owns a row with 16-byte accesses.  Gradient accumulation per row is in
 // ascending bucket id, exactly the reference's order (stable sort), then / scaler.
-#include "sparse_update.h"
+//
+// This unit: SparseUpdater, where a batch goes (update_typed), the (row, bucket) pairs and their
+// sort, the hot / cold path of one-hot batches with its host state, and the small kernels -- any-D
+// update, atomic SGD, global sweeps, wgrad.  The segmented family, the one that needs the
+// row-offset type at compile time, is a unit of its own (su_units.h).
+//
+// A test tree from before that unit existed (commit cc146d1: its tests/emu/Makefile compiles
+// this file three times, -DHCTR_SU_PART=0/1/2, and knows no su_*.hip) must still get a complete
+// interpreter library: a non-hipcc build that does not announce the unit (HCTR_EMU_SU_UNITS)
+// takes it in at the end of part 0, and parts 1 and 2 are empty.  The next split removes this.
+#if !defined(__HIPCC__) && !defined(HCTR_EMU_SU_UNITS)
+#define HCTR_SU_ONE_UNIT
+#endif
+#if !(defined(HCTR_SU_ONE_UNIT) && HCTR_SU_PART != 0)
+#include "su_device.h"
 #include "radix_sort.h"
 
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 
 #include "block_prims.h"
 
 namespace hctr {
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kTile = 1024;
-
-template <typename GradT>
-struct Load4;
-template <>
-struct Load4<float> {
-  typedef float4 raw;  // 4 elements as they sit in memory
-  __device__ __forceinline__ static raw ld_raw(const float* p) {
-    return *reinterpret_cast<const float4*>(p);
-  }
-  __device__ __forceinline__ static float4 cvt(raw r) { return r; }
-  __device__ __forceinline__ static float4 ld(const float* p) {
-    return *reinterpret_cast<const float4*>(p);
-  }
-  __device__ __forceinline__ static float ld1(const float* p) { return *p; }
-  __device__ __forceinline__ static float rnd(float v) { return v; }
-};
-template <>
-struct Load4<__half> {
-  typedef uint2 raw;
-  __device__ __forceinline__ static raw ld_raw(const __half* p) {
-    return *reinterpret_cast<const uint2*>(p);
-  }
-  __device__ __forceinline__ static float4 cvt(raw u) {
-    __half2 a = *reinterpret_cast<__half2*>(&u.x), b = *reinterpret_cast<__half2*>(&u.y);
-    float2 fa = __half22float2(a), fb = __half22float2(b);
-    return make_float4(fa.x, fa.y, fb.x, fb.y);
-  }
-  __device__ __forceinline__ static float4 ld(const __half* p) { return cvt(ld_raw(p)); }
-  __device__ __forceinline__ static float ld1(const __half* p) { return __half2float(*p); }
-  __device__ __forceinline__ static float rnd(float v) { return __half2float(__float2half_rn(v)); }
-};
-template <>
-struct Load4<__hip_bfloat16> {
-  typedef uint2 raw;
-  __device__ __forceinline__ static raw ld_raw(const __hip_bfloat16* p) {
-    return *reinterpret_cast<const uint2*>(p);
-  }
-  __device__ __forceinline__ static float4 cvt(raw u) {
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
-                       __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
-  }
-  __device__ __forceinline__ static float4 ld(const __hip_bfloat16* p) { return cvt(ld_raw(p)); }
-  __device__ __forceinline__ static float ld1(const __hip_bfloat16* p) {
-    return __bfloat162float(*p);
-  }
-  __device__ __forceinline__ static float rnd(float v) {
-    return __bfloat162float(__float2bfloat16(v));
-  }
-};
 
 // ---- step 1: (row index, bucket id) pairs (sample_id_expand_kernel :189-200) ------------------
 template <typename OffT>
@@ -169,856 +128,6 @@ __global__ void __launch_bounds__(kBlock)
       uint32_t ex = block_exclusive_scan<uint32_t, kBlock>(f ? 1u : 0u, smem, &tot);
       if (f) run_start[run + ex] = (uint32_t)i;
       run += tot;
-    }
-  }
-}
-
-// ---- step 3: per-row ordered reduce + optimizer -------------------------------------------------
-struct OptConst {
-  int optimizer, update_type;
-  float lr, beta1, beta2, epsilon, mf, scaler;
-  float alpha_t;         // lr * adam.bias()
-  float alpha_t_common;  // lr / (1 - beta1) (lazy adam)
-  float ftrl_l1, ftrl_l2b;  // lambda1, lambda2 + beta / lr
-  unsigned long long times;
-  int state_half;  // optimizer state carries fp16 values
-};
-
-// OptimizerTensor<TypeEmbeddingComp> (R/HugeCTR/include/optimizer.hpp:284-296): with fp16 embeddings
-// the reference keeps m / v / accumulators in fp16 -- every kernel converts the stored value to
-// float, computes in float and converts the result back on the store; the weight update of the
-// same step uses the unrounded float.  Here too (round 4): with state_half the state arrays ARE
-// __half arrays (half the footprint and the traffic of the fp32 arrays rounds 1-3 kept); the
-// pointers travel as float* and are re-typed where they are dereferenced (ld_state / st_state).
-__device__ __forceinline__ float state_store(int state_half, float x) {
-  if (!state_half) return x;
-  // the fp32 result first, THEN the conversion (two roundings, as the reference's float math +
-  // TypeConvertFunc does): without the barrier the compiler folds a preceding multiply into one
-  // mixed-precision instruction that rounds the exact product straight to fp16
-  asm volatile("" : "+v"(x));
-  return __half2float(__float2half_rn(x));
-}
-
-// element f of a state array / the four elements from f on (f a multiple of 4)
-__device__ __forceinline__ float ld_state1(const float* base, size_t f, int half) {
-  return half ? __half2float(reinterpret_cast<const __half*>(base)[f]) : base[f];
-}
-__device__ __forceinline__ void st_state1(float* base, size_t f, int half, float v) {
-  if (half) reinterpret_cast<__half*>(base)[f] = __float2half_rn(v);  // (v is fp16-valued: exact)
-  else base[f] = v;
-}
-__device__ __forceinline__ float4 ld_state4(const float* base, size_t f, int half) {
-  if (half)
-    return Load4<__half>::cvt(
-        *reinterpret_cast<const uint2*>(reinterpret_cast<const __half*>(base) + f));
-  return *reinterpret_cast<const float4*>(base + f);
-}
-__device__ __forceinline__ void st_state4(float* base, size_t f, int half, const float4& v) {
-  if (half) {
-    const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
-    uint2 u;
-    u.x = *reinterpret_cast<const uint32_t*>(&a);
-    u.y = *reinterpret_cast<const uint32_t*>(&b);
-    *reinterpret_cast<uint2*>(reinterpret_cast<__half*>(base) + f) = u;
-  } else {
-    *reinterpret_cast<float4*>(base + f) = v;
-  }
-}
-
-// internal pseudo-optimizer of hctr_updater_reduce_presorted: table[row] = gradient sum (no read)
-constexpr int kOptStoreSum = 1000;
-
-// one element of one row; formulas cite sparse_optimizer.cu
-__device__ __forceinline__ void apply_opt(const OptConst& o, float gi, float& w, float* s0p,
-                                          float* s1p, unsigned long long* ptp) {
-  switch (o.optimizer) {
-    case HCTR_OPT_SGD:  // opt_sgd_kernel :497-518
-      w += -o.lr * gi;
-      break;
-    case kOptStoreSum:
-      w = gi;
-      break;
-    case HCTR_OPT_FTRL: {  // FtrlOptimizer::update, ragged_static_embedding.cu:159-290 (s0 = n, s1 = z)
-      float ni = *s0p;
-      const float sq = sqrtf(ni + 1.1920929e-07f);
-      ni = ni + gi * gi;
-      const float sqn = sqrtf(ni + 1.1920929e-07f);
-      const float sigma = (sqn - sq) / o.lr;
-      const float zi = *s1p + gi - sigma * w;
-      const float p = (1.f - 2.f * (float)signbit(zi)) * o.ftrl_l1 - zi;
-      const float q = sqn / o.lr + o.ftrl_l2b;
-      w = p / q * (float)signbit(o.ftrl_l1 - fabsf(zi));
-      *s0p = state_store(o.state_half, ni);
-      *s1p = state_store(o.state_half, zi);
-    } break;
-    case HCTR_OPT_ADAGRAD: {  // opt_adagrad_kernel :410-437 (Global == Local)
-      float accum = *s0p + gi * gi;
-      *s0p = state_store(o.state_half, accum);
-      w += -o.lr * gi / (sqrtf(accum) + o.epsilon);
-    } break;
-    case HCTR_OPT_ADAM:
-      if (o.update_type == HCTR_UPDATE_LOCAL) {  // opt_adam_kernel :379-408
-        float mi = o.beta1 * *s0p + (1.0f - o.beta1) * gi;
-        float vi = o.beta2 * *s1p + (1.0f - o.beta2) * gi * gi;
-        *s0p = state_store(o.state_half, mi);
-        *s1p = state_store(o.state_half, vi);
-        w += -o.alpha_t * mi / (sqrtf(vi) + o.epsilon);
-      } else if (o.update_type == HCTR_UPDATE_GLOBAL) {  // opt_adam_kernel_global :241-265
-        *s0p = state_store(o.state_half, *s0p + (1.0f - o.beta1) * gi / o.beta1);
-        *s1p = state_store(o.state_half, *s1p + (1.0f - o.beta2) * gi * gi / o.beta2);
-      } else {  // opt_adam_kernel_lazy :524-561
-        unsigned long long pt = *ptp;
-        *ptp = o.times;
-        unsigned long long skipped = o.times - pt;
-        float b1ps = powf(o.beta1, (float)skipped);
-        float a = o.alpha_t_common * sqrtf(1.0f - powf(o.beta2, (float)pt)) /
-                  (1.0f - powf(o.beta1, (float)pt)) * (1.0f - b1ps);
-        float mi = *s0p, vi = *s1p;
-        w += -a * mi / (sqrtf(vi) + o.epsilon);
-        mi = b1ps * mi + (1.0f - o.beta1) * gi;
-        vi = powf(o.beta2, (float)skipped) * vi + (1.0f - o.beta2) * gi * gi;
-        *s0p = state_store(o.state_half, mi);
-        *s1p = state_store(o.state_half, vi);
-      }
-      break;
-    case HCTR_OPT_MOMENTUM_SGD:
-      if (o.update_type == HCTR_UPDATE_LOCAL) {  // opt_momentum_sgd_kernel :440-465
-        float mo = o.mf * *s0p - o.lr * gi;
-        *s0p = state_store(o.state_half, mo);
-        w += mo;
-      } else {  // opt_momentum_sgd_kernel_global :292-312
-        *s0p = state_store(o.state_half, *s0p - o.lr * gi / o.mf);
-      }
-      break;
-    case HCTR_OPT_NESTEROV:
-      if (o.update_type == HCTR_UPDATE_LOCAL) {  // opt_nesterov_kernel :468-494
-        float accm_old = *s0p;
-        float accm_new = o.mf * accm_old - o.lr * gi;
-        *s0p = state_store(o.state_half, accm_new);
-        w += -o.mf * accm_old + (1.0f + o.mf) * accm_new;
-      } else {  // nesterov_local_update_kernel_global :352-375
-        float accm = *s0p;
-        accm -= o.lr * gi;
-        *s0p = state_store(o.state_half, accm);
-        w -= (1.0f + o.mf) * (o.lr * gi);
-      }
-      break;
-    default: break;
-  }
-}
-
-__device__ __forceinline__ bool needs_s0(const OptConst& o) {
-  return o.optimizer != HCTR_OPT_SGD && o.optimizer != kOptStoreSum;
-}
-__device__ __forceinline__ bool needs_s1(const OptConst& o) {
-  return o.optimizer == HCTR_OPT_ADAM || o.optimizer == HCTR_OPT_FTRL;
-}
-__device__ __forceinline__ bool needs_pt(const OptConst& o) {
-  return o.optimizer == HCTR_OPT_ADAM && o.update_type == HCTR_UPDATE_LAZY_GLOBAL;
-}
-
-// Row update shared by seg_apply_kernel and seg_combine_kernel, split in load / compute / store so
-// that callers can keep several rows in flight: gi = acc / scaler, then the optimizer on the 4
-// elements this lane owns.
-struct RowRegs {
-  float4 w, s0, s1;
-  unsigned long long pt[4];
-};
-
-template <int LPR>
-__device__ __forceinline__ void row_load(const OptConst& o, uint64_t row, int l, RowRegs& r,
-                                         const float* __restrict__ table,
-                                         const float* __restrict__ state0,
-                                         const float* __restrict__ state1,
-                                         const unsigned long long* __restrict__ prev_time) {
-  constexpr int D = LPR * 4;
-  const size_t f = row * (uint64_t)D + l * 4;
-  r.s0 = make_float4(0.f, 0.f, 0.f, 0.f);
-  r.w = r.s0;
-  if (o.optimizer != kOptStoreSum) r.w = *reinterpret_cast<const float4*>(table + f);
-  r.s1 = r.s0;
-  r.pt[0] = r.pt[1] = r.pt[2] = r.pt[3] = 1ull;
-  if (needs_s0(o)) r.s0 = ld_state4(state0, f, o.state_half);
-  if (needs_s1(o)) r.s1 = ld_state4(state1, f, o.state_half);
-  if (needs_pt(o)) {
-#pragma unroll
-    for (int t = 0; t < 4; t++) r.pt[t] = prev_time[f + t];
-  }
-}
-
-__device__ __forceinline__ void row_compute(const OptConst& o, float4 gi, RowRegs& r) {
-  gi.x /= o.scaler;
-  gi.y /= o.scaler;
-  gi.z /= o.scaler;
-  gi.w /= o.scaler;
-  apply_opt(o, gi.x, r.w.x, &r.s0.x, &r.s1.x, &r.pt[0]);
-  apply_opt(o, gi.y, r.w.y, &r.s0.y, &r.s1.y, &r.pt[1]);
-  apply_opt(o, gi.z, r.w.z, &r.s0.z, &r.s1.z, &r.pt[2]);
-  apply_opt(o, gi.w, r.w.w, &r.s0.w, &r.s1.w, &r.pt[3]);
-}
-
-template <int LPR>
-__device__ __forceinline__ void row_store(const OptConst& o, uint64_t row, int l, const RowRegs& r,
-                                          float* __restrict__ table, float* __restrict__ state0,
-                                          float* __restrict__ state1,
-                                          unsigned long long* __restrict__ prev_time) {
-  constexpr int D = LPR * 4;
-  const size_t f = row * (uint64_t)D + l * 4;
-  const bool w_written = !((o.optimizer == HCTR_OPT_ADAM || o.optimizer == HCTR_OPT_MOMENTUM_SGD) &&
-                           o.update_type == HCTR_UPDATE_GLOBAL);
-  if (w_written) *reinterpret_cast<float4*>(table + f) = r.w;
-  if (needs_s0(o)) st_state4(state0, f, o.state_half, r.s0);
-  if (needs_s1(o)) st_state4(state1, f, o.state_half, r.s1);
-  if (needs_pt(o)) {
-#pragma unroll
-    for (int t = 0; t < 4; t++) prev_time[f + t] = r.pt[t];
-  }
-}
-
-// A key that found no row (hash table overflow, or an unseen key of an index-only call) carries
-// kInvalidIndex; as a 32-bit sort key that is 0xFFFFFFFF, which create() keeps out of the legal row
-// range.  Such positions sort behind every live row and their run is dropped by every writer.
-constexpr uint64_t kNoRow = 0xFFFFFFFFull;
-
-template <int LPR>
-__device__ __forceinline__ void apply_row_vec4(const OptConst& o, uint64_t row, int l, float4 gi,
-                                               float* __restrict__ table,
-                                               float* __restrict__ state0,
-                                               float* __restrict__ state1,
-                                               unsigned long long* __restrict__ prev_time) {
-  if (row == kNoRow) return;
-  RowRegs r;
-  row_load<LPR>(o, row, l, r, table, state0, state1, prev_time);
-  row_compute(o, gi, r);
-  row_store<LPR>(o, row, l, r, table, state0, state1, prev_time);
-}
-
-// Tile-based segmented reduce + optimizer.  The sorted (row, bucket) list is cut into tiles of
-// kSegTile positions; a group of LPR lanes walks one tile in order, so every group performs about
-// the same number of gradient-row reads no matter how skewed the key distribution is (the
-// reference gives one block to each unique row, sparse_optimizer.cu:223-237 -- a power-law head
-// row with 20k duplicates is then one serial 20k-iteration loop).
-//   * A run (= all gradients of one row) that starts in tile t is OWNED by tile t's group.  The
-//     owner follows it up to one tile past its own tile end; the next tile's group skips those
-//     leading positions.  So every run that ends before the end of tile t+1 is reduced by one group
-//     in ascending bucket order (the reference's order, stable sort) and applied at once.
-//   * A run that reaches beyond tile t+1 is "long": the owner stores the sum of its own part in
-//     tail[t] and appends t to span_list; every later tile the run touches stores its part in
-//     head[t'].  seg_combine_kernel adds tail + heads in a fixed order (deterministic).
-constexpr int kSegTile = 32;
-
-// number of keys in bucket b (the mean combiner's divisor)
-__device__ __forceinline__ int bucket_len(const void* row_offset_v, bool off_is_u32, uint32_t b) {
-  if (off_is_u32) {
-    const uint32_t* ro = (const uint32_t*)row_offset_v;
-    return (int)(ro[b + 1] - ro[b]);
-  }
-  const long long* ro = (const long long*)row_offset_v;
-  return (int)(ro[b + 1] - ro[b]);
-}
-
-template <typename GradT>
-__device__ __forceinline__ float4 scaled_grad(typename Load4<GradT>::raw r, int combiner, int n) {
-  float4 v = Load4<GradT>::cvt(r);
-  if (combiner == 1) {
-    // backward_mean_align2_kernel (backward_functor.cu:83-104): the scaler is rounded to the
-    // gradient type before the multiply; fp32 gradients: rnd() is the identity
-    const float sc = Load4<GradT>::rnd(n > 1 ? 1.0f / (float)n : 1.0f);
-    v.x = Load4<GradT>::rnd(v.x * sc);
-    v.y = Load4<GradT>::rnd(v.y * sc);
-    v.z = Load4<GradT>::rnd(v.z * sc);
-    v.w = Load4<GradT>::rnd(v.w * sc);
-  }
-  return v;
-}
-
-// Phase A: segmented sums.  Pure load/accumulate/store -- no read-modify-write of table rows
-// inside the walk.  The kernel is bound by DEPENDENT memory round trips per tile, not by bytes, so
-// everything a tile may need is fetched in as few trips as possible:
-//   trip 1: the tile's 32 (row, bucket) pairs, one per lane (coalesced), the NEXT tile's pairs
-//           (for the run that overhangs the tile end) and the four neighbour rows that decide
-//           ownership -- run starts / overhang length become 32-bit ballot masks;
-//   trips 2..: the 32 gradient rows of the tile plus the first kSegAhead rows of the overhang,
-//           issued back to back in batches of QB raw (unconverted) fragments, clamped to a row the
-//           batch reads anyway where a position is not needed.
-// The only sequential part is the fp32 add chain, which is what fixes the summation order.
-// The sum of a run its owner finishes goes to gsum[start position]; seg_apply_kernel picks it up.
-constexpr int kSegAhead = 8;
-
-// row id of tile position q (0..31): the metadata lane that holds it broadcasts it to the group
-template <int NPL, int ML>
-__device__ __forceinline__ uint32_t seg_row_at(const uint32_t (&mrow)[NPL], int q, int gshift) {
-  uint32_t src = mrow[0];
-#pragma unroll
-  for (int j = 1; j < NPL; j++) src = (q / ML == j) ? mrow[j] : src;
-  return (uint32_t)__shfl((int)src, gshift + (q % ML), 64);
-}
-
-constexpr int kFuseNone = 0, kFuseSgd = 1, kFuseAdaGrad = 2;
-
-template <int LPR, typename OffT, typename GradT, int kFuse>
-__global__ void __launch_bounds__(kBlock)
-    seg_reduce_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                      const uint32_t* __restrict__ sorted_rows,
-                      const uint32_t* __restrict__ sorted_buckets, int combiner,
-                      const GradT* __restrict__ grad, float* __restrict__ gsum,
-                      float* __restrict__ head, float* __restrict__ tail,
-                      uint32_t* __restrict__ span_list, uint32_t* __restrict__ span_count,
-                      float* __restrict__ direct_out, const OffT* __restrict__ scale_ro,
-                      OptConst fuse_o, float* __restrict__ fuse_state0) {
-  // kFuse (kFuseSgd / kFuseAdaGrad): the optimizer applied where a run's sum is complete --
-  // e.g. table[row] += -lr * (sum / scaler) -- right here (direct_out = the table) instead of
-  // parking the sum in gsum for seg_apply.  Every row is one run owned by one lane group, so
-  // nobody else touches it; the arithmetic is seg_apply's (apply_opt), bit for bit, without the
-  // gsum round trip (2 x D x 4 bytes per unique row).  Optimizers with two state vectors or
-  // time stamps keep the two-pass form (their row registers would cost the gather its occupancy).
-  // Measured (MI355X): one-hot Criteo-1TB update 231 -> 209 us, embedding_collection one-hot
-  // backward+update 365 -> 295 us, multi-hot MLPerf shape 2.15 -> 1.84 ms.  (No-return fp32
-  // atomic adds in place of the read-modify-write were 2x SLOWER: 496 us / 4.2 ms.)
-  // scale_ro: the CSR whose bucket lengths divide a mean gradient.  The distributed embedding
-  // divides by the bucket's key count over ALL GPUs (backward() with the all-reduced row offsets,
-  // distributed_slot_sparse_embedding_hash.hpp:216-221), not by this rank's filtered count.
-  // direct_out != nullptr (hctr_updater_reduce_presorted): the sum of a finished run goes to
-  // direct_out[row] instead of gsum[run start] -- no apply pass is needed afterwards
-  typedef typename Load4<GradT>::raw Raw;
-  constexpr int D = LPR * 4;
-  constexpr int GPB = kBlock / LPR;
-  constexpr int T = kSegTile;
-  constexpr int LA = kSegAhead;
-  constexpr int ML = LPR < T ? LPR : T;  // lanes of a group that carry tile metadata
-  constexpr int NPL = T / ML;            // metadata entries per such lane
-  constexpr int QB = sizeof(Raw) == 8 ? 20 : 10;  // fragments in flight per lane: 40 VGPRs
-  constexpr bool kOff32 = sizeof(OffT) == 4;
-  static_assert(T == 32 && (T + LA) % QB == 0, "masks are 32-bit; batches tile T + LA");
-  const int g = threadIdx.x / LPR;
-  const int l = threadIdx.x % LPR;
-  const int gshift = ((threadIdx.x & 63) / LPR) * LPR;  // first lane of my group in the wave
-  constexpr unsigned long long kGroupMask = ML >= 64 ? ~0ull : ((1ull << ML) - 1ull);
-  const size_t nnz = (size_t)row_offset[buckets];
-  const size_t n_tiles = (nnz + T - 1) / T;
-  // kFuse: the row update of a finished run is completed when the NEXT run finishes -- its row
-  // (and accumulator) read travels while the next run's gradients are added, instead of stalling
-  // the lane group (one-hot update 205 -> 195 us, multi-hot backward + update 1.73 -> 1.59 ms)
-  uint32_t pend_row = 0xFFFFFFFFu;
-  float4 pend_w = make_float4(0.f, 0.f, 0.f, 0.f), pend_d = pend_w;
-  RowRegs pend_rr;  // kFuseAdaGrad: row + accumulator in flight, pend_d = the run's gradient sum
-  auto pend_flush = [&]() {
-    if (pend_row != 0xFFFFFFFFu) {
-      if constexpr (kFuse == kFuseAdaGrad) {
-        OptConst oo = fuse_o;
-        oo.optimizer = HCTR_OPT_ADAGRAD;  // (compile-time: the state loads / stores fold)
-        row_compute(oo, pend_d, pend_rr);
-        row_store<LPR>(oo, (uint64_t)pend_row, l, pend_rr, direct_out, fuse_state0, nullptr, nullptr);
-      } else {
-        pend_w.x += pend_d.x;
-        pend_w.y += pend_d.y;
-        pend_w.z += pend_d.z;
-        pend_w.w += pend_d.w;
-        *reinterpret_cast<float4*>(direct_out + (size_t)pend_row * D + l * 4) = pend_w;
-      }
-    }
-  };
-  for (size_t tile = (size_t)blockIdx.x * GPB + g; tile < n_tiles;
-       tile += (size_t)gridDim.x * GPB) {
-    const size_t base = tile * T;
-    const size_t end = (base + T < nnz) ? base + T : nnz;
-    const size_t limit = (end + T < nnz) ? end + T : nnz;
-    const int nvalid = (int)(end - base);
-    // ---- trip 1: all metadata --------------------------------------------------------------
-    uint32_t mrow[NPL], mbkt[NPL], prow[NPL], nrow[NPL], nbkt[NPL];
-#pragma unroll
-    for (int j = 0; j < NPL; j++) {
-      const size_t pos = base + (size_t)j * ML + l;
-      const bool valid = l < ML && pos < end;
-      mrow[j] = valid ? (uint32_t)sorted_rows[pos] : 0xFFFFFFFFu;
-      mbkt[j] = valid ? sorted_buckets[pos] : 0u;
-      prow[j] = (valid && pos > 0) ? (uint32_t)sorted_rows[pos - 1] : 0xFFFFFFFFu;
-      const size_t np = end + (size_t)j * ML + l;
-      const bool nval = l < ML && np < limit;
-      nrow[j] = nval ? (uint32_t)sorted_rows[np] : 0xFFFFFFFFu;
-      nbkt[j] = nval ? sorted_buckets[np] : 0u;
-    }
-    // rows at base-T, base-T-1 (who owns a run that enters this tile) and at limit (does the
-    // overhanging run reach beyond tile+1); 0xFFFFFFFF never equals a live row
-    const uint32_t row_pt = base >= (size_t)T ? (uint32_t)sorted_rows[base - T] : 0xFFFFFFFFu;
-    const uint32_t row_pt1 = base > (size_t)T ? (uint32_t)sorted_rows[base - T - 1] : 0xFFFFFFFFu;
-    const uint32_t row_lim = limit < nnz ? (uint32_t)sorted_rows[limit] : 0xFFFFFFFFu;
-
-    uint32_t startmask = 0u;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) {
-      const size_t pos = base + (size_t)j * ML + l;
-      const bool valid = l < ML && pos < end;
-      const bool is_start = valid && (pos == 0 || prow[j] != mrow[j]);
-      const unsigned long long bal = __ballot(is_start);
-      startmask |= (uint32_t)((bal >> gshift) & kGroupMask) << (j * ML);
-    }
-    const uint32_t row0 = (uint32_t)__shfl((int)mrow[0], gshift, 64);
-    const uint32_t cur_row =
-        (uint32_t)__shfl((int)mrow[(nvalid - 1) / ML], gshift + ((nvalid - 1) % ML), 64);
-    const uint32_t next_row0 = (uint32_t)__shfl((int)nrow[0], gshift, 64);
-#define HCTR_RUN_DST(q_)                                                                        \
-  ((direct_out != nullptr && seg_row_at<NPL, ML>(mrow, (q_), gshift) != 0xFFFFFFFFu)             \
-       ? direct_out + (size_t)seg_row_at<NPL, ML>(mrow, (q_), gshift) * D                       \
-       : gsum + (base + (size_t)(q_)) * D) /* a run of keys without a row has no output row */
-    auto emit_run = [&](int q_run, const float4& a) {
-      if constexpr (kFuse == kFuseSgd) {
-        const uint32_t r = seg_row_at<NPL, ML>(mrow, q_run, gshift);
-        if (r != 0xFFFFFFFFu) {
-          pend_flush();
-          pend_d.x = -fuse_o.lr * (a.x / fuse_o.scaler);
-          pend_d.y = -fuse_o.lr * (a.y / fuse_o.scaler);
-          pend_d.z = -fuse_o.lr * (a.z / fuse_o.scaler);
-          pend_d.w = -fuse_o.lr * (a.w / fuse_o.scaler);
-          pend_row = r;
-          pend_w = *reinterpret_cast<const float4*>(direct_out + (size_t)r * D + l * 4);
-        }
-      } else if constexpr (kFuse == kFuseAdaGrad) {
-        const uint32_t r = seg_row_at<NPL, ML>(mrow, q_run, gshift);
-        if (r != 0xFFFFFFFFu) {
-          pend_flush();
-          OptConst oo = fuse_o;
-          oo.optimizer = HCTR_OPT_ADAGRAD;
-          pend_d = a;
-          pend_row = r;
-          row_load<LPR>(oo, (uint64_t)r, l, pend_rr, direct_out, fuse_state0, nullptr, nullptr);
-        }
-      } else {
-        *reinterpret_cast<float4*>(HCTR_RUN_DST(q_run) + l * 4) = a;
-      }
-    };
-    const bool ends_at_tile_end = end == nnz || next_row0 != cur_row;
-    int q0 = 0;
-    bool head_mode = false;
-    if (base > 0 && (startmask & 1u) == 0u) {
-      // the tile starts inside a run begun earlier: owned by the previous tile AND ending inside
-      // this tile -> its owner reduces it, skip it; otherwise it is (part of) a long run.
-      const bool owner_prev = row_pt != row0 || base == (size_t)T || row_pt1 != row0;
-      const bool whole_tile = startmask == 0u;
-      const bool ends_inside = !whole_tile || ends_at_tile_end;
-      if (owner_prev && ends_inside) q0 = whole_tile ? nvalid : __ffs((int)startmask) - 1;
-      else head_mode = true;
-    }
-    if (q0 >= nvalid) continue;  // the whole tile belonged to the previous tile's run
-    // overhang: leading positions of the next tile that continue this tile's last run
-    uint32_t matchmask = 0u;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) {
-      const unsigned long long bal = __ballot(nrow[j] == cur_row);
-      matchmask |= (uint32_t)((bal >> gshift) & kGroupMask) << (j * ML);
-    }
-    const bool whole_head = head_mode && startmask == 0u;  // one earlier run covers the tile
-    int cnt = (~matchmask == 0u) ? T : __ffs((int)~matchmask) - 1;  // leading ones
-    if (ends_at_tile_end || whole_head) cnt = 0;
-    const int cnt_la = cnt < LA ? cnt : LA;
-
-    // ---- trips 2..: gradient rows, QB fragments in flight ---------------------------------
-    int run_start = q0;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 own_part = acc;
-    const uint32_t b_q0 = (uint32_t)__shfl((int)mbkt[q0 / ML], gshift + (q0 % ML), 64);
-#pragma unroll
-    for (int qb = 0; qb < T + LA; qb += QB) {
-      Raw v[QB];
-      int nb[QB];
-#pragma unroll
-      for (int k = 0; k < QB; k++) {
-        const int q = qb + k;
-        uint32_t bsel;
-        if (q < T) {
-          const uint32_t bq = (uint32_t)__shfl((int)mbkt[q / ML], gshift + (q % ML), 64);
-          bsel = (q >= q0 && q < nvalid) ? bq : b_q0;
-        } else {
-          const uint32_t bq =
-              (uint32_t)__shfl((int)nbkt[(q - T) / ML], gshift + ((q - T) % ML), 64);
-          bsel = (q - T) < cnt_la ? bq : b_q0;
-        }
-        v[k] = Load4<GradT>::ld_raw(grad + (size_t)bsel * D + l * 4);
-        nb[k] = combiner == 1 ? bucket_len(scale_ro, kOff32, bsel) : 1;
-      }
-#pragma unroll
-      for (int k = 0; k < QB; k++) {
-        const int q = qb + k;
-        if (q == T) own_part = acc;
-        if (q < T) {
-          if (q >= q0 && q < nvalid) {
-            if (((startmask >> q) & 1u) != 0u && q != q0) {
-              if (head_mode) *reinterpret_cast<float4*>(head + tile * D + l * 4) = acc;
-              else emit_run(run_start, acc);
-              acc = make_float4(0.f, 0.f, 0.f, 0.f);
-              run_start = q;
-              head_mode = false;
-            }
-            const float4 f = scaled_grad<GradT>(v[k], combiner, nb[k]);
-            acc.x += f.x;
-            acc.y += f.y;
-            acc.z += f.z;
-            acc.w += f.w;
-          }
-        } else if ((q - T) < cnt_la) {
-          const float4 f = scaled_grad<GradT>(v[k], combiner, nb[k]);
-          acc.x += f.x;
-          acc.y += f.y;
-          acc.z += f.z;
-          acc.w += f.w;
-        }
-      }
-    }
-    if (head_mode) {  // one run covers the whole tile
-      *reinterpret_cast<float4*>(head + tile * D + l * 4) = acc;
-      continue;
-    }
-    if (cnt == 0) {  // the last run ends with the tile
-      emit_run(run_start, acc);
-      continue;
-    }
-    // the last run of this tile continues: this group owns it and follows it through tile+1
-    if (cnt > LA) {
-      constexpr int QC = 8;
-#pragma unroll 1
-      for (int qb = LA; qb < cnt; qb += QC) {
-        Raw v[QC];
-        int nb[QC];
-#pragma unroll
-        for (int k = 0; k < QC; k++) {
-          const int q = (qb + k) < cnt ? qb + k : cnt - 1;
-          // NPL > 1: the register index is dynamic here -> select with a small unrolled scan
-          uint32_t src = nbkt[0];
-#pragma unroll
-          for (int j = 1; j < NPL; j++) src = (q / ML == j) ? nbkt[j] : src;
-          const uint32_t bsel = (uint32_t)__shfl((int)src, gshift + (q % ML), 64);
-          v[k] = Load4<GradT>::ld_raw(grad + (size_t)bsel * D + l * 4);
-          nb[k] = combiner == 1 ? bucket_len(scale_ro, kOff32, bsel) : 1;
-        }
-#pragma unroll
-        for (int k = 0; k < QC; k++) {
-          if (qb + k < cnt) {
-            const float4 f = scaled_grad<GradT>(v[k], combiner, nb[k]);
-            acc.x += f.x;
-            acc.y += f.y;
-            acc.z += f.z;
-            acc.w += f.w;
-          }
-        }
-      }
-    }
-    // long <=> the run reaches beyond the end of tile+1
-    const bool runs_on = cnt == T && limit < nnz && row_lim == cur_row;
-    if (!runs_on) {
-      emit_run(run_start, acc);
-    } else {
-      *reinterpret_cast<float4*>(tail + tile * D + l * 4) = own_part;
-      if (l == 0) span_list[atomicAdd(span_count, 1u)] = (uint32_t)tile;
-    }
-  }
-  if constexpr (kFuse != kFuseNone) pend_flush();
-}
-#undef HCTR_RUN_DST
-
-// Phase B: one lane inspects one sorted position; run starts of runs that are not "long" are
-// compacted with a wave ballot and handed to lane groups, which read the run's gradient sum from
-// gsum[position] and apply the optimizer to the row (one coalesced D*4-byte RMW per row).
-// kSgd: plain SGD known at compile time -- one float4 of state per row instead of the generic
-// RowRegs (w, two state vectors, four time stamps: 148 VGPRs, 3 waves per SIMD), 8 rows per lane
-// group in flight instead of 4 (93 VGPRs).  Same arithmetic, same bits; seg_apply 98 -> 70 us at
-// the bench shape.
-template <int LPR, typename OffT, bool kSgd>
-__global__ void __launch_bounds__(kBlock)
-    seg_apply_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                     const uint32_t* __restrict__ sorted_rows, const float* __restrict__ gsum,
-                     OptConst o, float* __restrict__ table, float* __restrict__ state0,
-                     float* __restrict__ state1, unsigned long long* __restrict__ prev_time) {
-  constexpr int D = LPR * 4;
-  constexpr int G = 64 / LPR;  // groups per wavefront
-  constexpr int T = kSegTile;
-  const int lane = threadIdx.x & 63;
-  const int g = lane / LPR;
-  const int l = lane % LPR;
-  const size_t nnz = (size_t)row_offset[buckets];
-  const size_t wave = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const size_t nwaves = ((size_t)gridDim.x * kBlock) >> 6;
-  for (size_t c0 = wave * 64; c0 < nnz; c0 += nwaves * 64) {
-    const size_t p = c0 + lane;
-    uint32_t row = 0;
-    bool active = false;
-    if (p < nnz) {
-      row = sorted_rows[p];
-      const bool is_start = p == 0 || sorted_rows[p - 1] != row;
-      if (is_start) {
-        const size_t e2 = (p / T + 2) * T;  // first position after the tile following p's tile
-        const bool is_long = e2 < nnz && sorted_rows[e2] == row;
-        active = !is_long && (uint64_t)row != kNoRow;
-      }
-    }
-    unsigned long long mask = __ballot(active);
-    // R rows per group per step: all gsum / table / state reads of a step are issued before the
-    // first optimizer evaluation
-    constexpr int R = kSgd ? 8 : 4;
-    while (mask != 0ull) {
-      int src[R];
-#pragma unroll
-      for (int k = 0; k < R; k++) {
-        src[k] = -1;
-#pragma unroll
-        for (int q = 0; q < G; q++) {
-          if (mask != 0ull) {
-            const int bit = __ffsll((long long)mask) - 1;
-            mask &= mask - 1ull;
-            if (q == g) src[k] = bit;
-          }
-        }
-      }
-      uint32_t r2[R];
-      float4 gi[R];
-      if constexpr (kSgd) {
-        float4 w[R];
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          r2[k] = (uint32_t)__shfl((int)row, src[k] < 0 ? 0 : src[k], 64);
-          if (src[k] >= 0) {
-            gi[k] = *reinterpret_cast<const float4*>(gsum + (c0 + src[k]) * D + l * 4);
-            w[k] = *reinterpret_cast<const float4*>(table + (uint64_t)r2[k] * D + l * 4);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          if (src[k] >= 0) {  // row_compute + apply_opt(HCTR_OPT_SGD): w += -lr * (g / scaler)
-            w[k].x += -o.lr * (gi[k].x / o.scaler);
-            w[k].y += -o.lr * (gi[k].y / o.scaler);
-            w[k].z += -o.lr * (gi[k].z / o.scaler);
-            w[k].w += -o.lr * (gi[k].w / o.scaler);
-            *reinterpret_cast<float4*>(table + (uint64_t)r2[k] * D + l * 4) = w[k];
-          }
-        }
-      } else {
-        RowRegs rr[R];
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          r2[k] = (uint32_t)__shfl((int)row, src[k] < 0 ? 0 : src[k], 64);
-          if (src[k] >= 0) {
-            gi[k] = *reinterpret_cast<const float4*>(gsum + (c0 + src[k]) * D + l * 4);
-            row_load<LPR>(o, (uint64_t)r2[k], l, rr[k], table, state0, state1, prev_time);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-          if (src[k] >= 0) {
-            row_compute(o, gi[k], rr[k]);
-            row_store<LPR>(o, (uint64_t)r2[k], l, rr[k], table, state0, state1, prev_time);
-          }
-        }
-      }
-    }
-  }
-}
-
-// Long runs (listed in span_list by the tile they start in): tail[t0] + head[t0+1] + head[t0+2] ...
-// With power-law keys most long runs are a few tiles long while a handful (the rows of 3- or
-// 10-row tables) span hundreds of tiles.  seg_combine_kernel gives one lane group to each run: it
-// measures the run (how many following tiles begin with the same row) and adds the head partials
-// in order, 8 reads in flight; runs of more than kCombBigTiles tiles are parked in big_list and
-// taken by seg_combine_big_kernel, one 1024-thread workgroup per run: group q adds heads q,
-// q+GPB, ...; the GPB sums are added in the fixed order q = 0..GPB-1.  Both orders are fixed, so
-// the result does not depend on scheduling.
-constexpr int kCombBigTiles = 64;
-constexpr int kCombBlock = 1024;
-constexpr int kCombBigChunk = 2048;  // tile partials one workgroup of the big kernel adds
-
-template <int LPR, typename OffT>
-__global__ void __launch_bounds__(kBlock)
-    seg_combine_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                       const uint32_t* __restrict__ sorted_rows, OptConst o,
-                       float* __restrict__ table, float* __restrict__ state0,
-                       float* __restrict__ state1, unsigned long long* __restrict__ prev_time,
-                       const float* __restrict__ head, const float* __restrict__ tail,
-                       const uint32_t* __restrict__ span_list, uint32_t* __restrict__ span_count,
-                       uint32_t* __restrict__ big_list, size_t big_stride) {
-  constexpr int D = LPR * 4;
-  constexpr int GPB = kBlock / LPR;
-  constexpr int CU = 8;
-  constexpr unsigned long long kGroupMask = LPR >= 64 ? ~0ull : ((1ull << LPR) - 1ull);
-  const int g = threadIdx.x / LPR;
-  const int l = threadIdx.x % LPR;
-  const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
-  const size_t nnz = (size_t)row_offset[buckets];
-  const size_t n_tiles = (nnz + kSegTile - 1) / kSegTile;
-  const uint32_t n_span = span_count[0];
-  for (size_t si = (size_t)blockIdx.x * GPB + g; si < n_span; si += (size_t)gridDim.x * GPB) {
-    const size_t t0 = span_list[si];
-    const uint32_t row = sorted_rows[(t0 + 1) * kSegTile - 1];
-    float4 acc = *reinterpret_cast<const float4*>(tail + t0 * D + l * 4);
-    size_t n_heads = 0;
-    bool parked = false;
-    for (;;) {
-      const size_t tt = t0 + 1 + n_heads + l;
-      const bool match = tt < n_tiles && sorted_rows[tt * kSegTile] == row;
-      const unsigned long long gm = (__ballot(match) >> gshift) & kGroupMask;
-      const int ld = gm == kGroupMask ? LPR : __ffsll((long long)~gm) - 1;
-      n_heads += (size_t)ld;
-      if (ld < LPR) break;
-      if (n_heads > (size_t)kCombBigTiles) {
-        parked = true;
-        break;
-      }
-    }
-    if (parked) {
-      // a big run: measure it to the end (LPR evenly spaced probes per round; tiles < lo begin
-      // with `row`, tile hi does not) and register its chunks of kCombBigChunk tile partials --
-      // seg_combine_big_kernel gives every chunk a workgroup of its own
-      size_t lo = t0 + 1 + n_heads, hi = n_tiles;
-      while (lo < hi) {
-        const size_t step = (hi - lo + LPR - 1) / LPR;
-        const size_t probe = lo + (size_t)l * step;
-        const bool match = probe < hi && sorted_rows[probe * kSegTile] == row;
-        const unsigned long long gm = (__ballot(match) >> gshift) & kGroupMask;
-        const int m = gm == kGroupMask ? LPR : __ffsll((long long)~gm) - 1;
-        if (m == 0) {
-          hi = lo;
-        } else {
-          const size_t first_miss = lo + (size_t)m * step;
-          lo = lo + (size_t)(m - 1) * step + 1;
-          if (first_miss < hi) hi = first_miss;
-        }
-      }
-      if (l == 0) {
-        const size_t n = lo - (t0 + 1);
-        const unsigned long long nch = (n + kCombBigChunk - 1) / kCombBigChunk;
-        // one 64-bit counter: runs in the upper half, chunks in the lower -- the chunk bases
-        // then ascend with the slot numbers (binary search in the big kernel)
-        const unsigned long long old = atomicAdd(
-            reinterpret_cast<unsigned long long*>(span_count + 2), (1ull << 32) | nch);
-        const size_t slot = (size_t)(old >> 32);
-        big_list[slot] = (uint32_t)t0;
-        big_list[big_stride + slot] = (uint32_t)n;
-        big_list[2 * big_stride + slot] = (uint32_t)(old & 0xFFFFFFFFull);
-      }
-      continue;
-    }
-    for (size_t i = 0; i < n_heads; i += CU) {
-      float4 h[CU];
-#pragma unroll
-      for (int c = 0; c < CU; c++) {
-        const size_t tt = t0 + 1 + (i + c < n_heads ? i + c : i);  // clamp: always a legal read
-        h[c] = *reinterpret_cast<const float4*>(head + tt * D + l * 4);
-      }
-#pragma unroll
-      for (int c = 0; c < CU; c++) {
-        if (i + c < n_heads) {
-          acc.x += h[c].x;
-          acc.y += h[c].y;
-          acc.z += h[c].z;
-          acc.w += h[c].w;
-        }
-      }
-    }
-    apply_row_vec4<LPR>(o, (uint64_t)row, l, acc, table, state0, state1, prev_time);
-  }
-}
-
-template <int LPR, typename OffT>
-__global__ void __launch_bounds__(kCombBlock)
-    seg_combine_big_kernel(size_t buckets, const OffT* __restrict__ row_offset,
-                           const uint32_t* __restrict__ sorted_rows, OptConst o,
-                           float* __restrict__ table, float* __restrict__ state0,
-                           float* __restrict__ state1, unsigned long long* __restrict__ prev_time,
-                           float* head, const float* __restrict__ tail, uint32_t* big_list,
-                           size_t big_stride, const uint32_t* __restrict__ span_count) {
-  // Work item = one chunk (kCombBigChunk tile partials) of one big run.  A row with a million
-  // gradients is 30 000 partials: one workgroup adding them all was the tail of the whole update
-  // (a single CU's bandwidth); now its chunks run side by side.  Every chunk sum has a fixed order
-  // (group q adds partials q, q + GPB, ...; the GPB group sums are added q = 0..GPB-1), a chunk's
-  // sum is parked in the slot of its own first partial, and the workgroup that finishes LAST (a
-  // counter per run) adds tail + chunk sums in chunk order and applies the optimizer: the result
-  // does not depend on which workgroup that is.
-  constexpr int D = LPR * 4;
-  constexpr int GPB = kCombBlock / LPR;
-  constexpr int CU = 8;
-  __shared__ float4 part[kCombBlock];
-  __shared__ int is_last;
-  const int g = threadIdx.x / LPR;
-  const int l = threadIdx.x % LPR;
-  const unsigned long long ctr = *reinterpret_cast<const unsigned long long*>(span_count + 2);
-  const uint32_t n_big = (uint32_t)(ctr >> 32);
-  const uint32_t total = (uint32_t)(ctr & 0xFFFFFFFFull);
-  const uint32_t* big_t0 = big_list;
-  const uint32_t* big_len = big_list + big_stride;
-  const uint32_t* big_base = big_list + 2 * big_stride;
-  uint32_t* big_done = big_list + 3 * big_stride;
-  for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
-    uint32_t lo = 0, hi = n_big;  // the run whose chunks include w: last slot with base <= w
-    while (hi - lo > 1u) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (big_base[mid] <= w) lo = mid;
-      else hi = mid;
-    }
-    const uint32_t slot = lo;
-    const size_t t0 = big_t0[slot];
-    const size_t n_heads = big_len[slot];
-    const uint32_t c = w - big_base[slot];
-    const uint32_t nch = (uint32_t)((n_heads + kCombBigChunk - 1) / kCombBigChunk);
-    const uint32_t row = sorted_rows[(t0 + 1) * kSegTile - 1];
-    const size_t h0 = (size_t)c * kCombBigChunk;
-    const size_t h1 = h0 + kCombBigChunk < n_heads ? h0 + kCombBigChunk : n_heads;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (size_t i = h0 + (size_t)g; i < h1; i += (size_t)GPB * CU) {
-      float4 h[CU];
-#pragma unroll
-      for (int k = 0; k < CU; k++) {
-        const size_t ii = i + (size_t)k * GPB;
-        const size_t tt = t0 + 1 + (ii < h1 ? ii : i);
-        h[k] = *reinterpret_cast<const float4*>(head + tt * D + l * 4);
-      }
-#pragma unroll
-      for (int k = 0; k < CU; k++) {
-        if (i + (size_t)k * GPB < h1) {
-          acc.x += h[k].x;
-          acc.y += h[k].y;
-          acc.z += h[k].z;
-          acc.w += h[k].w;
-        }
-      }
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (g == 0) {
-      float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (nch == 1u) tot = *reinterpret_cast<const float4*>(tail + t0 * D + l * 4);
-#pragma unroll 8
-      for (int q = 0; q < GPB; q++) {
-        const float4 pq = part[q * LPR + l];
-        tot.x += pq.x;
-        tot.y += pq.y;
-        tot.z += pq.z;
-        tot.w += pq.w;
-      }
-      if (nch == 1u) {
-        apply_row_vec4<LPR>(o, (uint64_t)row, l, tot, table, state0, state1, prev_time);
-      } else {  // every partial of this chunk has been read (the barrier above): reuse slot h0
-        *reinterpret_cast<float4*>(head + (t0 + 1 + h0) * D + l * 4) = tot;
-        __threadfence();
-      }
-    }
-    __syncthreads();
-    if (nch > 1u) {
-      if (threadIdx.x == 0) is_last = atomicAdd(big_done + slot, 1u) == nch - 1u ? 1 : 0;
-      __syncthreads();
-      if (is_last != 0) {
-        if (g == 0) {
-          __threadfence();
-          float4 tot = *reinterpret_cast<const float4*>(tail + t0 * D + l * 4);
-          for (uint32_t c2 = 0; c2 < nch; c2++) {
-            float* p = head + (t0 + 1 + (size_t)c2 * kCombBigChunk) * D + l * 4;
-            // (sums other workgroups parked: read past this CU's vector cache)
-            tot.x += __hip_atomic_load(p + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tot.y += __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tot.z += __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tot.w += __hip_atomic_load(p + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          apply_row_vec4<LPR>(o, (uint64_t)row, l, tot, table, state0, state1, prev_time);
-        }
-        if (threadIdx.x == 0) big_done[slot] = 0u;  // clean for the next update
-      }
-      __syncthreads();
     }
   }
 }
@@ -1990,42 +1099,6 @@ __global__ void __launch_bounds__(kBlock)
 
 }
 
-// D / 4 lanes per row as a compile-time constant: f(std::integral_constant<int, LPR>{}) for
-// LPR = lpr in {1, 2, 4, 8, 16, 32, 64} (lpr_supported; anything else is taken as 64)
-inline bool lpr_supported(int D) {
-  const int lpr = D / 4;
-  return D % 4 == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0;
-}
-template <typename F>
-inline auto with_lpr(int lpr, F&& f) {
-  switch (lpr) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 32: return f(std::integral_constant<int, 32>{});
-    default: return f(std::integral_constant<int, 64>{});
-  }
-}
-
-// What the hot / cold kernels of one batch share: geometry, buffers, counter sets.  Built once per
-// batch -- by SparseUpdater::prework() right after the index stage (the grouping work needs the
-// rows only, not the gradients: hot_sort_kernel and the cold rows' count / base / scatter then run
-// on side streams under the dense tower) or by the update itself.
-struct PrePlan {
-  bool valid = false;  // the grouping kernels of (vi, n, buckets) are enqueued; the reduces are not
-  const uint64_t* vi = nullptr;
-  size_t n = 0, buckets = 0;
-  size_t n_chunks = 0;
-  int lpr = 0;
-  HotGeom hg;
-  HotBufs hb;
-  ColdGeom cg;
-  ColdBufs cb;
-  hipEvent_t ev_hot = nullptr, ev_cold = nullptr;
-};
-
 __global__ void __launch_bounds__(kBlock) cold_clear_kernel(ColdBufs cb) {
   const uint32_t nd = cb.counts[kCcRows];
   for (uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x; i < nd;
@@ -2033,9 +1106,42 @@ __global__ void __launch_bounds__(kBlock) cold_clear_kernel(ColdBufs cb) {
     cb.cnt[cb.dlist[i].x] = 0u;
 }
 
+// chunks the per-chunk tables have room for
+inline uint32_t hot_chunks_max(const SparseUpdater& u) {
+  return (uint32_t)(ceil_div<size_t>(u.max_nnz, (size_t)kHotChunk) + kHotMaxStreams);
+}
+
+}  // namespace
+
+// What the hot / cold path keeps between calls.  The buffers are the structs the kernels take; the
+// plan is what the kernels of one batch share (geometry, this batch's counter sets), built once per
+// batch -- by SparseUpdater::prework() right after the index stage (the grouping work needs the
+// rows only, not the gradients: hot_sort_kernel and the cold rows' count / base / scatter then run
+// on side streams under the dense tower) or by the update itself.
+struct HotColdState {
+  std::vector<void*> owned;       // the device buffers below, as hot_buffers() allocated them
+  hipStream_t cold_s = nullptr;   // the cold pairs' chain (default priority)
+  HotBufs hb = {};                // (hb.loc != nullptr <=> the set is complete)
+  ColdBufs cb = {};
+  uint32_t* hot_counts = nullptr;   // two alternating sets {pool slots, items, joins, -}
+  uint32_t* cold_counts = nullptr;  // two alternating sets of kCcWords
+  uint32_t parity = 0;              // set the next batch takes
+  // ---- the batch in hand --------------------------------------------------------------------
+  bool valid = false;  // the grouping kernels of (vi, n, buckets) are enqueued; the reduces are not
+  const uint64_t* vi = nullptr;
+  size_t n = 0, buckets = 0;
+  size_t n_chunks = 0;
+  int lpr = 0;
+  HotGeom hg = {};
+  ColdGeom cg = {};
+  hipEvent_t ev_hot = nullptr, ev_cold = nullptr;
+};
+
+namespace {
+
 // everything the path asks of a batch except what only the update knows (gradient alignment,
 // store-only mode)
-inline bool plan_possible(const SparseUpdater& u, size_t buckets, size_t nnz) {
+bool plan_possible(const SparseUpdater& u, size_t buckets, size_t nnz) {
   const uint32_t G = u.hot_streams;
   if (!(u.hot_rows > 0 && u.one_hot_flag != nullptr && G > 0 && G <= kHotMaxStreams &&
         nnz == buckets && nnz >= u.hot_min_n && nnz < 0x7FFFFFF0ull && lpr_supported(u.D) &&
@@ -2047,91 +1153,75 @@ inline bool plan_possible(const SparseUpdater& u, size_t buckets, size_t nnz) {
   if (u.map_inner != 0u) return false;
   const size_t per_g = ceil_div<size_t>(nnz, (size_t)G);
   const size_t n_chunks = (size_t)G * ceil_div<size_t>(per_g, (size_t)kHotChunk);
-  return n_chunks <= (size_t)u.hot_chunks_max && n_chunks <= (size_t)kHotApplyChunks;
+  return n_chunks <= (size_t)hot_chunks_max(u) && n_chunks <= (size_t)kHotApplyChunks;
 }
 
-inline void plan_build(SparseUpdater& u, PrePlan& pp, size_t buckets, size_t nnz, int combiner,
+inline void plan_build(SparseUpdater& u, HotColdState& hc, size_t buckets, size_t nnz, int combiner,
                        bool off_is_u32, const uint64_t* vi) {
   const uint32_t G = u.hot_streams;
   const size_t per_g = ceil_div<size_t>(nnz, (size_t)G);
   const size_t cpg = ceil_div<size_t>(per_g, (size_t)kHotChunk);
-  pp.vi = vi;
-  pp.n = nnz;
-  pp.buckets = buckets;
-  pp.n_chunks = (size_t)G * cpg;
-  pp.lpr = u.D / 4;
-  pp.hg.n = (uint32_t)nnz;
-  pp.hg.G = G;
-  pp.hg.cpg = (uint32_t)cpg;
-  pp.hg.rows = u.hot_rows;
-  pp.hg.map_inner = u.map_inner;
-  pp.hg.map_outer = u.map_outer;
-  pp.hg.loc_stride = u.hot_chunks_max;
-  pp.hb.S = u.hot_S;
-  pp.hb.meta = u.hot_meta;
-  pp.hb.tpref = u.hot_tpref;
-  pp.hb.items = u.hot_items;
-  pp.hb.loc_blk = u.hot_loc_blk;
-  pp.hb.joins = u.hot_joins;
-  // counter sets alternate: [0..3] / [4..7]
-  pp.hb.counts = u.hot_counts + 4 * (u.hot_parity & 1u);
-  pp.hb.counts_next = u.hot_counts + 4 * ((u.hot_parity + 1u) & 1u);
-  pp.hb.loc = u.hot_loc;
-  pp.hb.head = u.hot_head;
-  pp.hb.tail = u.hot_tail;
-  pp.cg.n = (uint32_t)nnz;
-  pp.cg.hot_rows = u.hot_rows;
-  pp.cg.max_vocab = (uint32_t)u.max_vocab;
-  pp.cg.map_inner = u.map_inner;
-  pp.cg.map_outer = u.map_outer;
-  pp.cg.short_max =
-      (uint32_t)with_lpr(pp.lpr, [](auto L) { return ColdShape<decltype(L)::value>::kShortMax; });
-  pp.cg.off_is_u32 = off_is_u32 ? 1 : 0;
-  pp.cg.combiner = combiner;
-  pp.cg.buckets = buckets;
-  pp.cb.cnt = u.cold_cnt;
-  pp.cb.rank = u.cold_rank;
-  pp.cb.plist = u.cold_plist;
-  pp.cb.bkt = u.cold_bkt;
-  pp.cb.dlist = (uint2*)u.cold_dlist;
-  pp.cb.singles = (uint2*)u.cold_singles;
-  pp.cb.segs = (uint4*)u.cold_segs;
-  pp.cb.longs = (uint4*)u.cold_longs;
-  pp.cb.counts = u.cold_counts + kCcWords * (u.hot_parity & 1u);
-  pp.cb.counts_next = u.cold_counts + kCcWords * ((u.hot_parity + 1u) & 1u);
-  u.hot_parity++;
+  hc.vi = vi;
+  hc.n = nnz;
+  hc.buckets = buckets;
+  hc.n_chunks = (size_t)G * cpg;
+  hc.lpr = u.D / 4;
+  hc.hg.n = (uint32_t)nnz;
+  hc.hg.G = G;
+  hc.hg.cpg = (uint32_t)cpg;
+  hc.hg.rows = u.hot_rows;
+  hc.hg.map_inner = u.map_inner;
+  hc.hg.map_outer = u.map_outer;
+  hc.hg.loc_stride = hot_chunks_max(u);
+  hc.cg.n = (uint32_t)nnz;
+  hc.cg.hot_rows = u.hot_rows;
+  hc.cg.max_vocab = (uint32_t)u.max_vocab;
+  hc.cg.map_inner = u.map_inner;
+  hc.cg.map_outer = u.map_outer;
+  hc.cg.short_max =
+      (uint32_t)with_lpr(hc.lpr, [](auto L) { return ColdShape<decltype(L)::value>::kShortMax; });
+  hc.cg.off_is_u32 = off_is_u32 ? 1 : 0;
+  hc.cg.combiner = combiner;
+  hc.cg.buckets = buckets;
+  // counter sets alternate: hot [0..3] / [4..7], cold [0..kCcWords) / [kCcWords..)
+  hc.hb.counts = hc.hot_counts + 4 * (hc.parity & 1u);
+  hc.hb.counts_next = hc.hot_counts + 4 * ((hc.parity + 1u) & 1u);
+  hc.cb.counts = hc.cold_counts + kCcWords * (hc.parity & 1u);
+  hc.cb.counts_next = hc.cold_counts + kCcWords * ((hc.parity + 1u) & 1u);
+  hc.parity++;
 }
 
 // the grouping kernels of a planned batch: the hot rows' chunk sort on hs, the cold rows' count /
 // base / scatter on cs
-inline int plan_launch_grouping(SparseUpdater& u, PrePlan& pp, const void* ro, hipStream_t hs,
+inline int plan_launch_grouping(SparseUpdater& u, HotColdState& hc, const void* ro, hipStream_t hs,
                                 hipStream_t cs) {
-  hipLaunchKernelGGL(hot_sort_kernel, dim3((unsigned)pp.n_chunks), dim3(kHotBlock), 0, hs, pp.hg,
-                     u.one_hot_flag, pp.vi, pp.hb);
+  hipLaunchKernelGGL(hot_sort_kernel, dim3((unsigned)hc.n_chunks), dim3(kHotBlock), 0, hs, hc.hg,
+                     u.one_hot_flag, hc.vi, hc.hb);
   HCTR_LAUNCH_CHECK();
-  const unsigned pgrid = (unsigned)ceil_div<size_t>(pp.n, (size_t)(kColdBlock * kColdPer));
-  const unsigned bgrid = (unsigned)grid_for(pp.n, kColdBlock * kColdBasePer, 256);
-  hipLaunchKernelGGL(cold_count_kernel, dim3(pgrid), dim3(kColdBlock), 0, cs, pp.cg,
-                     u.one_hot_flag, ro, pp.vi, pp.cb);
+  const unsigned pgrid = (unsigned)ceil_div<size_t>(hc.n, (size_t)(kColdBlock * kColdPer));
+  const unsigned bgrid = (unsigned)grid_for(hc.n, kColdBlock * kColdBasePer, 256);
+  hipLaunchKernelGGL(cold_count_kernel, dim3(pgrid), dim3(kColdBlock), 0, cs, hc.cg,
+                     u.one_hot_flag, ro, hc.vi, hc.cb);
   HCTR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cold_base_kernel, dim3(bgrid), dim3(kColdBlock), 0, cs, pp.cg, pp.cb);
+  hipLaunchKernelGGL(cold_base_kernel, dim3(bgrid), dim3(kColdBlock), 0, cs, hc.cg, hc.cb);
   HCTR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cold_scatter_kernel, dim3(pgrid), dim3(kColdBlock), 0, cs, pp.cg,
-                     u.one_hot_flag, pp.vi, pp.cb);
+  hipLaunchKernelGGL(cold_scatter_kernel, dim3(pgrid), dim3(kColdBlock), 0, cs, hc.cg,
+                     u.one_hot_flag, hc.vi, hc.cb);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
 
 // a batch whose grouping kernels ran ahead but whose update takes another path (or never comes):
-// the per-row words go back to zero
-inline int plan_discard(SparseUpdater& u, PrePlan& pp, hipStream_t s) {
-  if (!pp.valid) return HCTR_OK;
-  HCTR_HIP(hipStreamWaitEvent(s, pp.ev_hot, 0));
-  HCTR_HIP(hipStreamWaitEvent(s, pp.ev_cold, 0));
-  hipLaunchKernelGGL(cold_clear_kernel, dim3(grid_for(pp.n, kBlock, 1024)), dim3(kBlock), 0, s,
-                     pp.cb);
+// the per-row words go back to zero.  Nothing grouped ahead: a no-op
+int plan_discard(SparseUpdater& u, hipStream_t s) {
+  HotColdState* hc = u.hot_cold;
+  if (hc == nullptr || !hc->valid) return HCTR_OK;
+  HCTR_HIP(hipStreamWaitEvent(s, hc->ev_hot, 0));
+  HCTR_HIP(hipStreamWaitEvent(s, hc->ev_cold, 0));
+  hipLaunchKernelGGL(cold_clear_kernel, dim3(grid_for(hc->n, kBlock, 1024)), dim3(kBlock), 0, s,
+                     hc->cb);
   HCTR_LAUNCH_CHECK();
-  pp.valid = false;
+  hc->valid = false;
   return HCTR_OK;
 }
 
@@ -2314,7 +1404,6 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-
 // (row, bucket) pairs -> stable radix sort by row (sparse_optimizer.cu:657-676); stage 2 of the
 // profiler brackets the sort
 template <typename OffT>
@@ -2345,28 +1434,6 @@ int sort_stage(SparseUpdater& u, size_t buckets, size_t n, const OffT* ro, const
                                 in_place ? &first : nullptr));
   if (u.prof) u.prof->end(2, s);
   return HCTR_OK;
-}
-
-inline OptConst opt_const(const OptState& opt) {
-  OptConst o;
-  o.optimizer = opt.optimizer;
-  o.update_type = opt.update_type;
-  o.lr = opt.lr;
-  o.beta1 = opt.beta1;
-  o.beta2 = opt.beta2;
-  o.epsilon = opt.epsilon;
-  o.mf = opt.momentum_factor;
-  o.scaler = opt.scaler;
-  o.times = opt.times;
-  // AdamOptHyperParams::bias() (optimizer.hpp:58-60): double pow, rounded to float, times lr
-  const float bias = (float)(std::sqrt(1.0 - std::pow((double)opt.beta2, (double)opt.times)) /
-                             (1.0 - std::pow((double)opt.beta1, (double)opt.times)));
-  o.alpha_t = opt.lr * bias;
-  o.alpha_t_common = opt.lr / (1.0f - opt.beta1);
-  o.ftrl_l1 = opt.ftrl_lambda1;
-  o.ftrl_l2b = opt.ftrl_lambda2 + opt.ftrl_beta / opt.lr;
-  o.state_half = opt.state_half;
-  return o;
 }
 
 // Global update types sweep the table (sparse_optimizer.cu:269-347 run over all
@@ -2423,15 +1490,6 @@ int update_sgd_atomic(const SparseUpdater& u, size_t buckets, int combiner, cons
   return HCTR_OK;
 }
 
-// the (row, bucket) list the sorted paths walk: ascending rows, n entries (padding behind the live
-// ones); need_sort: it still has to be made, into sort_keys_out / sort_vals_out (sort_stage)
-struct SortedPairs {
-  const uint32_t* rows;
-  const uint32_t* buckets;
-  size_t n;
-  bool need_sort;
-};
-
 inline int pairs_source(SparseUpdater& u, size_t buckets, size_t nnz, const uint64_t* vi,
                         hipStream_t s, SortedPairs& p) {
   p = {u.sort_keys_out, u.sort_vals_out, nnz, false};
@@ -2456,50 +1514,47 @@ inline int pairs_source(SparseUpdater& u, size_t buckets, size_t nnz, const uint
 // cold_count_kernel) on the side stream; they touch disjoint rows.  pre: prework() enqueued the
 // grouping kernels of this batch already.  Stage 2 of the profiler = fork .. join, all of the
 // update.
-template <typename OffT, typename GradT>
-int update_hot_cold(SparseUpdater& u, PrePlan& pp, bool pre, size_t buckets, size_t nnz,
-                    int combiner, const OffT* ro, const uint64_t* vi, const GradT* grad,
-                    const OptConst& o, float* table, float* state0, float* state1,
-                    uint64_t* prev_time, hipStream_t s) {
-  if (!pre) plan_build(u, pp, buckets, nnz, combiner, sizeof(OffT) == 4, vi);
-  hipStream_t cs = u.hot_side;  // the cold chain's stream
+template <typename GradT>
+int update_hot_cold(SparseUpdater& u, HotColdState& hc, bool pre, size_t buckets, size_t nnz,
+                          int combiner, const void* ro, bool off_is_u32, const uint64_t* vi,
+                          const GradT* grad, const OptConst& o, float* table, float* state0,
+                          float* state1, uint64_t* prev_time, hipStream_t s) {
+  if (!pre) plan_build(u, hc, buckets, nnz, combiner, off_is_u32, vi);
+  hipStream_t cs = hc.cold_s;  // the cold chain's stream
   if (u.prof) u.prof->begin(2, s);
   HCTR_HIP(hipEventRecord(u.ev_fork, s));
   HCTR_HIP(hipStreamWaitEvent(cs, u.ev_fork, 0));
   if (pre) {  // grouped ahead (prework): the reduces wait for their chain's kernels only
-    HCTR_HIP(hipStreamWaitEvent(s, pp.ev_hot, 0));
-    HCTR_HIP(hipStreamWaitEvent(cs, pp.ev_cold, 0));
-    pp.valid = false;
+    HCTR_HIP(hipStreamWaitEvent(s, hc.ev_hot, 0));
+    HCTR_HIP(hipStreamWaitEvent(cs, hc.ev_cold, 0));
+    hc.valid = false;
   } else {
-    HCTR_TRY(plan_launch_grouping(u, pp, (const void*)ro, s, cs));
+    HCTR_TRY(plan_launch_grouping(u, hc, ro, s, cs));
   }
   float* pool_end = u.gsum + u.max_nnz * (size_t)u.D;
-  const size_t items_max = nnz / kHotTile + pp.n_chunks;
+  const size_t items_max = nnz / kHotTile + hc.n_chunks;
   // the hot rows' reduce is a grid-stride loop over a bounded number of workgroups: a kernel
   // that queues one workgroup per tile fills every wave slot of the device and the other
   // chain only trickles in (measured, round 4: its scatter 21 -> 96 us; 768 workgroups: 60)
   constexpr int kColdGrid = 2048, kHotGrid = 768;
-  HCTR_TRY(with_lpr(pp.lpr, [&](auto L) -> int {
+  HCTR_TRY(with_lpr(hc.lpr, [&](auto L) -> int {
     constexpr int LPR = decltype(L)::value;
     constexpr int GPB = kBlock / LPR;
-    if (o.optimizer == HCTR_OPT_SGD)
-      hipLaunchKernelGGL((cold_reduce_kernel<LPR, GradT, true>), dim3(kColdGrid), dim3(kBlock), 0,
-                         cs, pp.cg, u.one_hot_flag, (const void*)ro, vi, grad, o, table, state0,
-                         state1, (unsigned long long*)prev_time, u.gsum, pp.cb);
-    else
-      hipLaunchKernelGGL((cold_reduce_kernel<LPR, GradT, false>), dim3(kColdGrid), dim3(kBlock),
-                         0, cs, pp.cg, u.one_hot_flag, (const void*)ro, vi, grad, o, table, state0,
-                         state1, (unsigned long long*)prev_time, u.gsum, pp.cb);
+    with_bool(o.optimizer == HCTR_OPT_SGD, [&](auto sgd) {
+      hipLaunchKernelGGL((cold_reduce_kernel<LPR, GradT, decltype(sgd)::value>), dim3(kColdGrid),
+                         dim3(kBlock), 0, cs, hc.cg, u.one_hot_flag, ro, vi, grad, o, table, state0,
+                         state1, (unsigned long long*)prev_time, u.gsum, hc.cb);
+    });
     HCTR_LAUNCH_CHECK();
     hipLaunchKernelGGL((hot_reduce_kernel<LPR, GradT>), dim3(grid_for(items_max, GPB, kHotGrid)),
-                       dim3(kBlock), 0, s, pp.hg, u.one_hot_flag, grad, pool_end, pp.hb);
+                       dim3(kBlock), 0, s, hc.hg, u.one_hot_flag, grad, pool_end, hc.hb);
     HCTR_LAUNCH_CHECK();
     hipLaunchKernelGGL((hot_join_kernel<LPR>), dim3(grid_for(items_max / 8 + 1, GPB, 2048)),
-                       dim3(kBlock), 0, s, pp.hg, u.one_hot_flag, pool_end, pp.hb);
+                       dim3(kBlock), 0, s, hc.hg, u.one_hot_flag, pool_end, hc.hb);
     HCTR_LAUNCH_CHECK();
     hipLaunchKernelGGL((hot_apply_kernel<LPR>), dim3(grid_for(u.hot_rows, GPB)), dim3(kBlock), 0,
-                       s, pp.hg, (uint32_t)pp.n_chunks, u.one_hot_flag, o, table, state0, state1,
-                       (unsigned long long*)prev_time, (const float*)pool_end, pp.hb);
+                       s, hc.hg, (uint32_t)hc.n_chunks, u.one_hot_flag, o, table, state0, state1,
+                       (unsigned long long*)prev_time, (const float*)pool_end, hc.hb);
     HCTR_LAUNCH_CHECK();
     return HCTR_OK;
   }));
@@ -2508,64 +1563,6 @@ int update_hot_cold(SparseUpdater& u, PrePlan& pp, bool pre, size_t buckets, siz
   HCTR_HIP(hipStreamWaitEvent(s, u.ev_sorted, 0));
   if (u.prof) u.prof->end(2, s);
   return HCTR_OK;
-}
-
-// the sorted list, D a supported multiple of 4 (lpr_supported): segmented reduce, the apply pass
-// unless the optimizer folds into the reduce, then the runs that cross tile borders.
-// direct != nullptr: store-only mode, finished runs are written straight to their output row
-template <typename OffT, typename GradT>
-int update_segmented(SparseUpdater& u, const SortedPairs& p, size_t buckets, int combiner,
-                     const OffT* ro, const OffT* sro, const GradT* grad, const OptConst& o,
-                     float* direct, float* table, float* state0, float* state1,
-                     uint64_t* prev_time, hipStream_t s) {
-  // plain SGD: the apply pass folds into the reduce (seg_reduce_kernel<.., kFuseSgd>);
-  // HCTR_SGD_FUSED=0 keeps the two-pass form (measurements, the bit-equality test)
-  const char* fuse_env = getenv("HCTR_SGD_FUSED");  // (read per call: tests flip it in-process)
-  int fuse = kFuseNone;
-  if (!(fuse_env && fuse_env[0] == '0') && direct == nullptr) {
-    if (o.optimizer == HCTR_OPT_SGD) fuse = kFuseSgd;
-    if (o.optimizer == HCTR_OPT_ADAGRAD) fuse = kFuseAdaGrad;
-  }
-  const size_t nnz = p.n;
-  const size_t seg_tiles = ceil_div<size_t>(nnz, (size_t)kSegTile);
-  return with_lpr(u.D / 4, [&](auto L) -> int {
-    constexpr int LPR = decltype(L)::value;
-    constexpr int GPB = kBlock / LPR;
-    auto reduce = [&](auto F, float* out) {
-      hipLaunchKernelGGL((seg_reduce_kernel<LPR, OffT, GradT, decltype(F)::value>),
-                         dim3(grid_for(seg_tiles, GPB, 1 << 20)), dim3(kBlock), 0, s, buckets, ro,
-                         p.rows, p.buckets, combiner, grad, u.gsum, u.seg_head, u.seg_tail,
-                         u.span_list, u.span_count, out, sro, o, state0);
-    };
-    if (fuse == kFuseSgd) reduce(std::integral_constant<int, kFuseSgd>{}, table);
-    else if (fuse == kFuseAdaGrad) reduce(std::integral_constant<int, kFuseAdaGrad>{}, table);
-    else reduce(std::integral_constant<int, kFuseNone>{}, direct);
-    HCTR_LAUNCH_CHECK();
-    if (direct == nullptr && fuse == kFuseNone) {
-      if (o.optimizer == HCTR_OPT_SGD)
-        hipLaunchKernelGGL((seg_apply_kernel<LPR, OffT, true>),
-                           dim3(grid_for(nnz, kBlock, 256 * 8)), dim3(kBlock), 0, s, buckets, ro,
-                           p.rows, u.gsum, o, table, state0, state1,
-                           (unsigned long long*)prev_time);
-      else
-        hipLaunchKernelGGL((seg_apply_kernel<LPR, OffT, false>),
-                           dim3(grid_for(nnz, kBlock, 256 * 8)), dim3(kBlock), 0, s, buckets, ro,
-                           p.rows, u.gsum, o, table, state0, state1,
-                           (unsigned long long*)prev_time);
-      HCTR_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL((seg_combine_kernel<LPR, OffT>), dim3(grid_for(seg_tiles, GPB * 4, 1024)),
-                       dim3(kBlock), 0, s, buckets, ro, p.rows, o, table, state0, state1,
-                       (unsigned long long*)prev_time, u.seg_head, u.seg_tail, u.span_list,
-                       u.span_count, u.big_list, u.big_stride);
-    HCTR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((seg_combine_big_kernel<LPR, OffT>), dim3(256), dim3(kCombBlock), 0, s,
-                       buckets, ro, p.rows, o, table, state0, state1,
-                       (unsigned long long*)prev_time, u.seg_head, u.seg_tail, u.big_list,
-                       u.big_stride, u.span_count);
-    HCTR_LAUNCH_CHECK();
-    return HCTR_OK;
-  });
 }
 
 // any other embedding_vec_size: run detection + one wavefront per unique row
@@ -2592,11 +1589,11 @@ int update_generic(SparseUpdater& u, const SortedPairs& p, size_t buckets, int c
   return HCTR_OK;
 }
 
-template <typename OffT, typename GradT>
-int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const OffT* ro,
-                 const uint64_t* vi, const GradT* grad, const OptState& opt, float* table,
-                 float* state0, float* state1, uint64_t* prev_time, hipStream_t s) {
-  const OffT* sro = u.scale_row_offset ? (const OffT*)u.scale_row_offset : ro;
+int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const void* ro,
+                 int key_type, const uint64_t* vi, const void* grad, int grad_dtype,
+                 const OptState& opt, float* table, float* state0, float* state1,
+                 uint64_t* prev_time, hipStream_t s) {
+  const void* sro = u.scale_row_offset ? u.scale_row_offset : ro;
   const OptConst o = opt_const(opt);
   if (u.map_inner != 0u) {
     if (combiner != 0 || u.ext_rows != nullptr || (opt.optimizer == HCTR_OPT_SGD && opt.atomic_update) ||
@@ -2605,106 +1602,83 @@ int update_typed(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, con
       return HCTR_ERR_INVALID_ARG;
     }
   }
+  const bool u32 = key_type == HCTR_KEY_U32;
   if (opt.optimizer == HCTR_OPT_SGD && opt.atomic_update)
-    return update_sgd_atomic(u, buckets, combiner, ro, sro, vi, grad, opt, table, s);
+    return with_types(key_type, grad_dtype, [&](auto* off, auto* g) -> int {
+      return update_sgd_atomic(u, buckets, combiner, (decltype(off))ro, (decltype(off))sro, vi,
+                               (decltype(g))grad, opt, table, s);
+    });
   HCTR_TRY(global_sweep_before(u, opt, table, state0, s));
   if (nnz > 0) {
     SortedPairs p;
     HCTR_TRY(pairs_source(u, buckets, nnz, vi, s, p));
     const bool a16 = reinterpret_cast<uintptr_t>(grad) % 16 == 0;
     float* direct = (opt.optimizer == kOptStoreSum && opt.scaler == 1.0f) ? table : nullptr;
-    PrePlan* pp = (PrePlan*)u.pre_plan;
+    const HotColdState* hc = u.hot_cold;
     const bool hot = p.need_sort && a16 && direct == nullptr && plan_possible(u, buckets, nnz);
-    const bool pre = hot && pp != nullptr && pp->valid && pp->vi == vi && pp->n == nnz &&
-                     pp->buckets == buckets;
-    if (pp != nullptr && pp->valid && !pre) HCTR_TRY(plan_discard(u, *pp, s));
+    const bool pre = hot && hc != nullptr && hc->valid && hc->vi == vi && hc->n == nnz &&
+                     hc->buckets == buckets;
+    if (!pre) HCTR_TRY(plan_discard(u, s));
     if (hot) {
       HCTR_TRY(u.hot_buffers(s));
-      HCTR_TRY(update_hot_cold(u, *(PrePlan*)u.pre_plan, pre, buckets, nnz, combiner, ro, vi, grad,
-                               o, table, state0, state1, prev_time, s));
+      HCTR_TRY(with_dtype(grad_dtype, [&](auto* g) -> int {
+        return update_hot_cold(u, *u.hot_cold, pre, buckets, nnz, combiner, ro, u32, vi,
+                               (decltype(g))grad, o, table, state0, state1, prev_time, s);
+      }));
     } else {
-      if (p.need_sort) HCTR_TRY(sort_stage(u, buckets, nnz, ro, vi, s));
+      if (p.need_sort)
+        HCTR_TRY(u32 ? sort_stage(u, buckets, nnz, (const uint32_t*)ro, vi, s)
+                     : sort_stage(u, buckets, nnz, (const long long*)ro, vi, s));
       if (u.prof) u.prof->begin(3, s);
       if (a16 && lpr_supported(u.D))
-        HCTR_TRY(update_segmented(u, p, buckets, combiner, ro, sro, grad, o, direct, table, state0,
-                                  state1, prev_time, s));
+        HCTR_TRY((u32 ? update_segmented_u32 : update_segmented_i64)(
+            u, p, buckets, combiner, ro, sro, grad, grad_dtype, opt, direct, table, state0, state1,
+            prev_time, s));
       else
-        HCTR_TRY(update_generic(u, p, buckets, combiner, ro, sro, grad, o, table, state0, state1,
-                                prev_time, s));
+        HCTR_TRY(with_types(key_type, grad_dtype, [&](auto* off, auto* g) -> int {
+          return update_generic(u, p, buckets, combiner, (decltype(off))ro, (decltype(off))sro,
+                                (decltype(g))grad, o, table, state0, state1, prev_time, s);
+        }));
       if (u.prof) u.prof->end(3, s);
     }
   }
   return global_sweep_after(u, opt, o, table, state0, state1, s);
 }
 
-// row indices are sorted as 32-bit keys; create() rejects tables with >= 2^32 rows per GPU
-template <typename OffT>
-int update_grad(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const OffT* ro,
-                const uint64_t* vi, const void* grad, int grad_dtype, const OptState& opt,
-                float* table, float* s0, float* s1, uint64_t* pt, hipStream_t s) {
-  switch (grad_dtype) {
-    case HCTR_EMB_F32:
-      return update_typed<OffT, float>(u, buckets, nnz, combiner, ro, vi, (const float*)grad, opt,
-                                       table, s0, s1, pt, s);
-    case HCTR_EMB_F16:
-      return update_typed<OffT, __half>(u, buckets, nnz, combiner, ro, vi, (const __half*)grad,
-                                        opt, table, s0, s1, pt, s);
-    case HCTR_EMB_BF16:
-      return update_typed<OffT, __hip_bfloat16>(u, buckets, nnz, combiner, ro, vi,
-                                                (const __hip_bfloat16*)grad, opt, table, s0, s1,
-                                                pt, s);
+void free_hot_cold(SparseUpdater& u) {
+  HotColdState* hc = u.hot_cold;
+  if (hc == nullptr) return;
+  for (void* p : hc->owned) (void)hipFree(p);
+  if (hc->ev_hot) (void)hipEventDestroy(hc->ev_hot);
+  if (hc->ev_cold) (void)hipEventDestroy(hc->ev_cold);
+  if (hc->cold_s) {
+    (void)hipStreamSynchronize(hc->cold_s);
+    (void)hipStreamDestroy(hc->cold_s);
   }
-  set_error("grad dtype");
-  return HCTR_ERR_INVALID_ARG;
+  delete hc;
+  u.hot_cold = nullptr;
 }
 
 }  // namespace
-
-// This file is compiled three times (Makefile): HCTR_SU_PART 0 = everything but the segmented
-// update's kernel instantiations, 1 / 2 = those for 32-bit / 64-bit row offsets (63 instances of
-// seg_reduce_kernel each) -- the three objects build side by side instead of one 3-minute TU.
-#ifndef HCTR_SU_PART
-#define HCTR_SU_PART 0
-#endif
-int update_grad_u32(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const uint32_t* ro,
-                    const uint64_t* vi, const void* grad, int grad_dtype, const OptState& opt,
-                    float* table, float* s0, float* s1, uint64_t* pt, hipStream_t s);
-int update_grad_i64(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const long long* ro,
-                    const uint64_t* vi, const void* grad, int grad_dtype, const OptState& opt,
-                    float* table, float* s0, float* s1, uint64_t* pt, hipStream_t s);
-#if HCTR_SU_PART == 1
-int update_grad_u32(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const uint32_t* ro,
-                    const uint64_t* vi, const void* grad, int grad_dtype, const OptState& opt,
-                    float* table, float* s0, float* s1, uint64_t* pt, hipStream_t s) {
-  return update_grad<uint32_t>(u, buckets, nnz, combiner, ro, vi, grad, grad_dtype, opt, table, s0,
-                               s1, pt, s);
-}
-#elif HCTR_SU_PART == 2
-int update_grad_i64(SparseUpdater& u, size_t buckets, size_t nnz, int combiner, const long long* ro,
-                    const uint64_t* vi, const void* grad, int grad_dtype, const OptState& opt,
-                    float* table, float* s0, float* s1, uint64_t* pt, hipStream_t s) {
-  return update_grad<long long>(u, buckets, nnz, combiner, ro, vi, grad, grad_dtype, opt, table,
-                                s0, s1, pt, s);
-}
-#else
 
 int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager_hot) {
   max_nnz = max_nnz_ > 0 ? max_nnz_ : 1;
   max_vocab = max_vocab_;
   D = D_;
+  // row indices are sorted as 32-bit keys
   if (max_vocab >= 0xFFFFFFF0ull) {
     set_error("more than 2^32 - 16 rows per GPU are not supported by the sparse update");
     return HCTR_ERR_UNSUPPORTED;
   }
-  HCTR_HIP(hipMalloc(&sort_keys_in, max_nnz * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&sort_keys_out, max_nnz * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&sort_vals_in, max_nnz * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&sort_vals_out, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, sort_keys_in, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, sort_keys_out, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, sort_vals_in, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, sort_vals_out, max_nnz * sizeof(uint32_t)));
   sort_temp_bytes = radix_sort_temp_bytes(max_nnz);
-  HCTR_HIP(hipMalloc(&sort_temp, sort_temp_bytes));
-  HCTR_HIP(hipMalloc(&tile_sums, (ceil_div<size_t>(max_nnz, kTile) + 1) * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&run_start, (max_nnz + 2) * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&d_num_runs, sizeof(uint64_t)));
+  HCTR_TRY(dev_alloc(owned, sort_temp, sort_temp_bytes));
+  HCTR_TRY(dev_alloc(owned, tile_sums, (ceil_div<size_t>(max_nnz, kTile) + 1) * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, run_start, (max_nnz + 2) * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, d_num_runs, sizeof(uint64_t)));
   HCTR_HIP(hipMemset(d_num_runs, 0, sizeof(uint64_t)));
   {
     int lo = 0, hi = 0;  // hi = numerically lowest = most urgent
@@ -2714,17 +1688,17 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
     HCTR_HIP(hipEventCreateWithFlags(&ev_sorted, hipEventDisableTiming));
   }
   const size_t seg_tiles = ceil_div<size_t>(max_nnz, (size_t)kSegTile) + 1;
-  HCTR_HIP(hipMalloc(&seg_head, seg_tiles * (size_t)D * sizeof(float)));
-  HCTR_HIP(hipMalloc(&seg_tail, seg_tiles * (size_t)D * sizeof(float)));
-  HCTR_HIP(hipMalloc(&gsum, max_nnz * (size_t)D * sizeof(float)));
-  HCTR_HIP(hipMalloc(&span_list, seg_tiles * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, seg_head, seg_tiles * (size_t)D * sizeof(float)));
+  HCTR_TRY(dev_alloc(owned, seg_tail, seg_tiles * (size_t)D * sizeof(float)));
+  HCTR_TRY(dev_alloc(owned, gsum, max_nnz * (size_t)D * sizeof(float)));
+  HCTR_TRY(dev_alloc(owned, span_list, seg_tiles * sizeof(uint32_t)));
   // [0] long runs, [1] unused, [2..3] one 64-bit counter: big runs (upper half) / their chunks
-  HCTR_HIP(hipMalloc(&span_count, 4 * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, span_count, 4 * sizeof(uint32_t)));
   HCTR_HIP(hipMemset(span_count, 0, 4 * sizeof(uint32_t)));
   // per big run: start tile, length in tile partials, first chunk number, finished-chunk counter
   // (the counters start at zero and every update leaves them at zero)
   big_stride = seg_tiles;
-  HCTR_HIP(hipMalloc(&big_list, 4 * seg_tiles * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(owned, big_list, 4 * seg_tiles * sizeof(uint32_t)));
   HCTR_HIP(hipMemset(big_list, 0, 4 * seg_tiles * sizeof(uint32_t)));
   // hot rows of one-hot batches.  HCTR_HOT_ROWS: rows below it are hot (0 = off);
   // HCTR_HOT_MIN: batches with fewer positions keep the plain path (a small batch is launch-bound:
@@ -2739,9 +1713,8 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
     hot_rows = 0;
     // (the tables themselves: here for an owner that announces one-hot batches (eager_hot), else by
     //  the first update that takes the path -- hot_buffers(); see sparse_update.h)
-    if (rows > 0 && max_nnz >= hot_min_n && D % 4 == 0 && D / 4 <= 64 && ((D / 4) & (D / 4 - 1)) == 0) {
+    if (rows > 0 && max_nnz >= hot_min_n && lpr_supported(D)) {
       hot_rows = (uint32_t)rows;
-      hot_chunks_max = (uint32_t)(ceil_div<size_t>(max_nnz, (size_t)kHotChunk) + kHotMaxStreams);
       if (eager_hot) {
         HCTR_TRY(hot_buffers(nullptr));
         HCTR_HIP(hipDeviceSynchronize());  // (the clears above ran on the null stream)
@@ -2752,88 +1725,57 @@ int SparseUpdater::create(size_t max_nnz_, size_t max_vocab_, int D_, bool eager
 }
 
 int SparseUpdater::hot_buffers(hipStream_t s) {
-  if (hot_loc != nullptr) return HCTR_OK;
-  HCTR_HIP(hipStreamCreateWithPriority(&hot_side, hipStreamNonBlocking, 0));  // default priority
-  const size_t C = hot_chunks_max;
-  HCTR_HIP(hipMalloc(&hot_S, C * kHotChunk * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&hot_loc_blk, (size_t)hot_rows * sizeof(uint32_t)));
-  HCTR_HIP(hipMemsetAsync(hot_loc_blk, 0, (size_t)hot_rows * sizeof(uint32_t), s));
-  HCTR_HIP(hipMalloc(&hot_meta, C * 2 * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&hot_tpref, C * (kHotTiles + 1) * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&hot_items, (max_nnz / kHotTile + C + 1) * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&hot_joins, 3 * C * kHotTiles * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&hot_counts, 8 * sizeof(uint32_t)));
-  HCTR_HIP(hipMemsetAsync(hot_counts, 0, 8 * sizeof(uint32_t), s));
+  if (hot_cold != nullptr && hot_cold->hb.loc != nullptr) return HCTR_OK;
+  free_hot_cold(*this);  // (what an earlier, failed attempt left)
+  HotColdState& hc = *(hot_cold = new HotColdState());
+  HotBufs& hb = hc.hb;
+  ColdBufs& cb = hc.cb;
+  HCTR_HIP(hipStreamCreateWithPriority(&hc.cold_s, hipStreamNonBlocking, 0));  // default priority
+  const size_t C = hot_chunks_max(*this);
+  HCTR_TRY(dev_alloc(hc.owned, hb.S, C * kHotChunk * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, hb.loc_blk, (size_t)hot_rows * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(hb.loc_blk, 0, (size_t)hot_rows * sizeof(uint32_t), s));
+  HCTR_TRY(dev_alloc(hc.owned, hb.meta, C * 2 * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, hb.tpref, C * (kHotTiles + 1) * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, hb.items, (max_nnz / kHotTile + C + 1) * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, hb.joins, 3 * C * kHotTiles * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, hc.hot_counts, 8 * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(hc.hot_counts, 0, 8 * sizeof(uint32_t), s));
   const size_t part = C * kHotTiles * (size_t)D * sizeof(float);
-  HCTR_HIP(hipMalloc(&hot_head, part));
-  HCTR_HIP(hipMalloc(&hot_tail, part));
-  HCTR_HIP(hipMalloc(&cold_cnt, max_vocab * sizeof(uint32_t)));
-  HCTR_HIP(hipMemsetAsync(cold_cnt, 0, max_vocab * sizeof(uint32_t), s));
-  HCTR_HIP(hipMalloc(&cold_rank, max_nnz * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&cold_plist, max_nnz * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&cold_bkt, max_nnz * sizeof(uint32_t)));
-  HCTR_HIP(hipMalloc(&cold_dlist, max_nnz * sizeof(uint2)));
-  HCTR_HIP(hipMalloc(&cold_singles, max_nnz * sizeof(uint2)));
-  HCTR_HIP(hipMalloc(&cold_segs, (max_nnz / 2 + 1) * sizeof(uint4)));
-  HCTR_HIP(hipMalloc(&cold_longs, (max_nnz / 2 + 1) * sizeof(uint4)));
-  HCTR_HIP(hipMalloc(&cold_counts, 2 * kCcWords * sizeof(uint32_t)));
-  HCTR_HIP(hipMemsetAsync(cold_counts, 0, 2 * kCcWords * sizeof(uint32_t), s));
-  {
-    PrePlan* pp = new PrePlan();
-    HCTR_HIP(hipEventCreateWithFlags(&pp->ev_hot, hipEventDisableTiming));
-    HCTR_HIP(hipEventCreateWithFlags(&pp->ev_cold, hipEventDisableTiming));
-    pre_plan = pp;
-  }
+  HCTR_TRY(dev_alloc(hc.owned, hb.head, part));
+  HCTR_TRY(dev_alloc(hc.owned, hb.tail, part));
+  HCTR_TRY(dev_alloc(hc.owned, cb.cnt, max_vocab * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(cb.cnt, 0, max_vocab * sizeof(uint32_t), s));
+  HCTR_TRY(dev_alloc(hc.owned, cb.rank, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, cb.plist, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, cb.bkt, max_nnz * sizeof(uint32_t)));
+  HCTR_TRY(dev_alloc(hc.owned, cb.dlist, max_nnz * sizeof(uint2)));
+  HCTR_TRY(dev_alloc(hc.owned, cb.singles, max_nnz * sizeof(uint2)));
+  HCTR_TRY(dev_alloc(hc.owned, cb.segs, (max_nnz / 2 + 1) * sizeof(uint4)));
+  HCTR_TRY(dev_alloc(hc.owned, cb.longs, (max_nnz / 2 + 1) * sizeof(uint4)));
+  HCTR_TRY(dev_alloc(hc.owned, hc.cold_counts, 2 * kCcWords * sizeof(uint32_t)));
+  HCTR_HIP(hipMemsetAsync(hc.cold_counts, 0, 2 * kCcWords * sizeof(uint32_t), s));
+  HCTR_HIP(hipEventCreateWithFlags(&hc.ev_hot, hipEventDisableTiming));
+  HCTR_HIP(hipEventCreateWithFlags(&hc.ev_cold, hipEventDisableTiming));
   // (last: its presence is what marks the set complete)
-  const size_t loc_bytes = (size_t)hot_rows * hot_chunks_max * sizeof(uint16_t);
-  HCTR_HIP(hipMalloc(&hot_loc, loc_bytes));
+  const size_t loc_bytes = (size_t)hot_rows * C * sizeof(uint16_t);
+  HCTR_TRY(dev_alloc(hc.owned, hb.loc, loc_bytes));
   // kHotNone everywhere; hot_apply keeps it so.  (On the caller's stream: the kernels that follow
   // on it, and on the side stream behind its fork event, see the tables initialised)
-  HCTR_HIP(hipMemsetAsync(hot_loc, 0xFF, loc_bytes, s));
+  HCTR_HIP(hipMemsetAsync(hb.loc, 0xFF, loc_bytes, s));
   return HCTR_OK;
 }
 
 int SparseUpdater::destroy() {
-  void* ptrs[] = {sort_keys_in, sort_keys_out, sort_vals_in, sort_vals_out, sort_temp, tile_sums,
-                  run_start,    d_num_runs,    seg_head,     seg_tail,      span_list, span_count,
-                  gsum,         big_list,      hot_loc,      hot_counts,    hot_head,  hot_tail,
-                  hot_S,        hot_meta,      hot_tpref,    hot_items,     hot_joins,
-                  hot_loc_blk,  cold_cnt,      cold_rank,    cold_plist,    cold_bkt,
-                  cold_dlist,   cold_singles,  cold_segs,    cold_longs,    cold_counts};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (pre_plan) {
-    PrePlan* pp = (PrePlan*)pre_plan;
-    if (pp->ev_hot) (void)hipEventDestroy(pp->ev_hot);
-    if (pp->ev_cold) (void)hipEventDestroy(pp->ev_cold);
-    delete pp;
-    pre_plan = nullptr;
-  }
-  if (hot_side) {
-    (void)hipStreamSynchronize(hot_side);
-    (void)hipStreamDestroy(hot_side);
-    hot_side = nullptr;
-  }
+  for (void* p : owned) (void)hipFree(p);
+  free_hot_cold(*this);
   if (side) {
     (void)hipStreamSynchronize(side);
     (void)hipStreamDestroy(side);
     (void)hipEventDestroy(ev_fork);
     (void)hipEventDestroy(ev_sorted);
-    side = nullptr;
   }
-  early_n = 0;
-  sort_temp = nullptr;
-  sort_keys_in = sort_keys_out = sort_vals_in = sort_vals_out = tile_sums = run_start = nullptr;
-  d_num_runs = nullptr;
-  seg_head = seg_tail = nullptr;
-  span_list = span_count = big_list = nullptr;
-  gsum = nullptr;
-  hot_loc = nullptr;
-  hot_counts = hot_S = hot_meta = hot_tpref = hot_items = hot_joins = hot_loc_blk = nullptr;
-  hot_head = hot_tail = nullptr;
-  cold_cnt = cold_rank = cold_plist = cold_bkt = cold_counts = nullptr;
-  cold_dlist = cold_singles = cold_segs = cold_longs = nullptr;
-  hot_rows = hot_chunks_max = 0;
+  *this = SparseUpdater();
   return HCTR_OK;
 }
 
@@ -2857,22 +1799,21 @@ int SparseUpdater::presort(size_t buckets, size_t n, const void* row_offset, int
 }
 
 int SparseUpdater::prework(size_t buckets, size_t nnz, int combiner, const void* row_offset,
-                            int key_type, const uint64_t* value_index, hipStream_t s) {
-  PrePlan* pp = (PrePlan*)pre_plan;
-  if (pp == nullptr || cold_cnt == nullptr || hot_loc == nullptr || !side || !hot_side)
-    return HCTR_OK;
-  if (pp->valid) HCTR_TRY(plan_discard(*this, *pp, s));  // (a batch that was never updated)
+                           int key_type, const uint64_t* value_index, hipStream_t s) {
+  HotColdState* hc = hot_cold;
+  if (hc == nullptr || hc->hb.loc == nullptr || !side) return HCTR_OK;
+  HCTR_TRY(plan_discard(*this, s));  // (a batch that was never updated)
   if (buckets == 0 || nnz == 0 || nnz > max_nnz || !plan_possible(*this, buckets, nnz))
     return HCTR_OK;
-  plan_build(*this, *pp, buckets, nnz, combiner, key_type == HCTR_KEY_U32, value_index);
+  plan_build(*this, *hc, buckets, nnz, combiner, key_type == HCTR_KEY_U32, value_index);
   // both chains behind what s has enqueued so far (the index stage), next to what follows on it
   HCTR_HIP(hipEventRecord(ev_fork, s));
   HCTR_HIP(hipStreamWaitEvent(side, ev_fork, 0));
-  HCTR_HIP(hipStreamWaitEvent(hot_side, ev_fork, 0));
-  HCTR_TRY(plan_launch_grouping(*this, *pp, row_offset, side, hot_side));
-  HCTR_HIP(hipEventRecord(pp->ev_hot, side));
-  HCTR_HIP(hipEventRecord(pp->ev_cold, hot_side));
-  pp->valid = true;
+  HCTR_HIP(hipStreamWaitEvent(hc->cold_s, ev_fork, 0));
+  HCTR_TRY(plan_launch_grouping(*this, *hc, row_offset, side, hc->cold_s));
+  HCTR_HIP(hipEventRecord(hc->ev_hot, side));
+  HCTR_HIP(hipEventRecord(hc->ev_cold, hc->cold_s));
+  hc->valid = true;
   return HCTR_OK;
 }
 
@@ -2908,36 +1849,35 @@ int SparseUpdater::update(size_t buckets, size_t nnz, int combiner, const void* 
     set_error("lazy global update is only implemented for Adam (sparse_optimizer.cu:829-850)");
     return HCTR_ERR_UNSUPPORTED;
   }
-  if (key_type == HCTR_KEY_U32)
-    return update_grad_u32(*this, buckets, nnz, combiner, (const uint32_t*)row_offset, value_index,
-                           top_grad, grad_dtype, opt, table, state0, state1, prev_time, s);
-  if (key_type == HCTR_KEY_I64)
-    return update_grad_i64(*this, buckets, nnz, combiner, (const long long*)row_offset, value_index,
-                           top_grad, grad_dtype, opt, table, state0, state1, prev_time, s);
-  set_error("key_type");
-  return HCTR_ERR_INVALID_ARG;
+  if (key_type != HCTR_KEY_U32 && key_type != HCTR_KEY_I64) {
+    set_error("key_type");
+    return HCTR_ERR_INVALID_ARG;
+  }
+  if (grad_dtype != HCTR_EMB_F32 && grad_dtype != HCTR_EMB_F16 && grad_dtype != HCTR_EMB_BF16) {
+    set_error("grad dtype");
+    return HCTR_ERR_INVALID_ARG;
+  }
+  return update_typed(*this, buckets, nnz, combiner, row_offset, key_type, value_index, top_grad,
+                      grad_dtype, opt, table, state0, state1, prev_time, s);
 }
 
 int materialize_wgrad(size_t buckets, int D, int combiner, const void* ro, int key_type,
                       const void* top, void* wgrad, int dtype, hipStream_t s) {
   if (buckets == 0) return HCTR_OK;
   const int grid = grid_for(buckets * (size_t)D, kBlock);
-#define HCTR_WG(OffT, GradT)                                                                  \
-  hipLaunchKernelGGL((wgrad_kernel<OffT, GradT>), dim3(grid), dim3(kBlock), 0, s, buckets, D, \
-                     combiner, (const OffT*)ro, (const GradT*)top, (GradT*)wgrad)
-  if (key_type == HCTR_KEY_U32) {
-    if (dtype == HCTR_EMB_F32) HCTR_WG(uint32_t, float);
-    else if (dtype == HCTR_EMB_F16) HCTR_WG(uint32_t, __half);
-    else HCTR_WG(uint32_t, __hip_bfloat16);
-  } else {
-    if (dtype == HCTR_EMB_F32) HCTR_WG(long long, float);
-    else if (dtype == HCTR_EMB_F16) HCTR_WG(long long, __half);
-    else HCTR_WG(long long, __hip_bfloat16);
-  }
-#undef HCTR_WG
+  HCTR_TRY(with_types(key_type, dtype, [&](auto* off, auto* g) -> int {
+    hipLaunchKernelGGL((wgrad_kernel<std::remove_pointer_t<decltype(off)>,
+                                     std::remove_pointer_t<decltype(g)>>),
+                       dim3(grid), dim3(kBlock), 0, s, buckets, D, combiner, (decltype(off))ro,
+                       (decltype(g))top, (decltype(g))wgrad);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
-#endif  // HCTR_SU_PART
 
 }  // namespace hctr
+#ifdef HCTR_SU_ONE_UNIT
+#include "su_segmented.hip"
+#endif
+#endif

@@ -15,7 +15,7 @@
 //   stable radix sort -> per peer a run per distinct row; u = run index inside the peer segment
 //   meta[q] = (u, bucket on the receiver = b_local * S + s_global), rows[peer_off[j] + u]
 // Receiver: E[bucket] = rows[u] (expand), backward: sum of dE over each run (the sorted list is
-// exactly what the segmented-reduce kernels of sparse_update.hip consume), sums travel back, the
+// exactly what the segmented-reduce kernels of su_segmented.hip consume), sums travel back, the
 // owner runs its normal sparse update on (row, summed gradient) entries.
 #include <hip/hip_runtime.h>
 
