@@ -288,6 +288,11 @@ _SIGNATURES = {
                                    _P]),
     "hctr_ebc_io_scatter_rows": (c_int, [c_size_t, c_int, _P, _P, _P, c_uint64, _P]),
     "hctr_ebc_io_export_static": (c_int, [_P, c_int, c_size_t, c_uint64, c_uint64, _P, _P, _P, _P]),
+    "hctr_ebc_group_segments": (c_int, [c_size_t, c_size_t, _P, _P, _P, c_size_t, _P, _P]),
+    "hctr_ebc_hybrid_row_ptrs": (c_int, [c_size_t, c_size_t, _P, _P, _P, c_int, _P, c_int, _P,
+                                         c_size_t, _P, _P, _P]),
+    "hctr_ebc_hybrid_key_grads": (c_int, [c_size_t, c_int, _P, _P, c_size_t, _P, c_int, c_size_t,
+                                          c_size_t, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

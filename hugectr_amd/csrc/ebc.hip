@@ -935,3 +935,6 @@ int hctr_ebc_local_reduce(hctr_updater* u, size_t buckets, size_t nnz, const int
 
 // embedding_dump / embedding_load: pinned chunks read over the host link (check, import, select)
 #include "ebc_io.hip"
+
+// storage="hybrid": routed <-> grouped-by-table order around the hctr_lru_* calls
+#include "ebc_hybrid.hip"

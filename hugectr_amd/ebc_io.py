@@ -70,22 +70,25 @@ def _addr(t: torch.Tensor, row: int = 0):
 
 class TableIO:
     """Mixin of EmbeddingCollection and DataParallelCollection.  The host class provides
-    `_io_layout(t)` (dict: dynamic, num_shards, shard_id, vocab, row_start | cls, writes; None for
-    a table this rank does not hold), `_io_state_arrays()` (the static optimizer state tensors)
+    `_io_layout(t)` (dict: dynamic, num_shards, shard_id, vocab, row_start | cls | hybrid (the
+    shard's HybridTable), writes; None for a table this rank does not hold), `_io_state_arrays()` (the static optimizer state tensors)
     and `tables`, `ev`, `optimizer`, `dev`."""
 
     # -- what there is to write ---------------------------------------------------------------------
     def io_state_count(self) -> int:
         """optimizer state arrays per row that export_table(optimizer_states=True) writes"""
-        if getattr(self, "dynamic", False):
+        if getattr(self, "dynamic", False) or getattr(self, "hybrid", False):
             return {_lib.OPT_ADAM: 2, _lib.OPT_SGD: 0}.get(self.optimizer, 1)
         return {_lib.OPT_ADAGRAD: 1, _lib.OPT_FTRL: 2}.get(self.optimizer, 0)
 
     def io_check_optimizer_states(self):
         """raises where the state cannot be exported: a dynamic table whose step runs on the
         unique-key flow keeps its state in a second key -> state table, not at the row numbers of
-        the flat row store"""
+        the flat row store.  A hybrid table keeps its state at the slot numbers, either tier, for
+        every optimizer it has: always exportable."""
         from .embedding_collection import _FLAT_STEP
+        if getattr(self, "hybrid", False):
+            return
         if getattr(self, "dynamic", False) and not (self._dyn_flat and self.optimizer in _FLAT_STEP):
             raise _lib.HugeCTRAmdError(
                 "optimizer_states=True: dynamic tables keep exportable optimizer state only for "
@@ -98,6 +101,8 @@ class TableIO:
         lay = self._io_layout(t)
         if lay is None or not lay["writes"]:
             return 0
+        if lay.get("hybrid") is not None:
+            return lay["hybrid"].size()
         if lay["dynamic"]:
             return int(self.det.size_per_class()[lay["cls"]])
         return embedding_io.static_shard_key_count(lay["vocab"], lay["num_shards"], lay["shard_id"])
@@ -129,6 +134,8 @@ class TableIO:
                 raise _lib.HugeCTRAmdError(f"{files.label}: opt_state file {files.opt_state} does "
                                            f"not match ({ns}, {int(self.optimizer)})")
         R = int(chunk_rows or default_chunk_rows(self.ev))
+        if lay.get("hybrid") is not None:
+            return self._export_hybrid(lay["hybrid"], files, keys_before, ns, R)
         if lay["dynamic"]:
             return self._export_dynamic(lay, files, keys_before, ns, R)
         arrays = self._io_static_arrays(ns > 0)
@@ -169,6 +176,24 @@ class TableIO:
                 check(lib.hctr_ebc_uniq_gather_rows(n, self.ev, ptr(rows), stores[a], total, ptr(out),
                                                     _lib.F32, stream_ptr()))
                 states.append(out)
+        for start in range(0, n, R):
+            sl = slice(start, min(start + R, n))
+            files.write("key", keys_before + start,
+                        keys[sl].cpu().numpy().astype(files.key_dtype))
+            files.write("weight", keys_before + start, vals[sl].cpu().numpy())
+            for a, s in enumerate(states):
+                files.write("opt_state", keys_before + start, s[sl].cpu().numpy(), a)
+        return n
+
+    def _export_hybrid(self, tab, files, keys_before, ns, R):
+        """the occupied slots in slot order (hctr_lru_export); state rows through the slot-addressed
+        gather, which reaches host-resident slots as well (hctr_lru_gather_slots)"""
+        keys, vals, slots, _ = tab.export(with_slots=True)
+        n = int(keys.numel())
+        states = []
+        for a in range(ns if n else 0):
+            tab.state_ptr(a)  # (allocated, zeroed, if the optimizer has not stepped yet)
+            states.append(tab.gather_slots(1 + a, slots))
         for start in range(0, n, R):
             sl = slice(start, min(start + R, n))
             files.write("key", keys_before + start,
@@ -231,16 +256,25 @@ class TableIO:
                     f"outside [0, max_vocabulary_size = {lay['vocab']})")
             raise _lib.HugeCTRAmdError(f"{files.label}: {bad} of {n} keys are {what}; nothing "
                                        f"was loaded into table {self.tables[t].name!r}")
+        tab = lay.get("hybrid")
+        if tab is not None and own > tab.capacity:
+            raise _lib.HugeCTRAmdError(
+                f"{files.label}: {own} of {n} keys belong to shard {lay['shard_id']} of "
+                f"{lay['num_shards']} of hybrid table {self.tables[t].name!r}, whose max_capacity "
+                f"is {tab.capacity} slots; nothing was loaded")
         return dict(owned=own, foreign=foreign)
 
     def import_table(self, t: int, files: embedding_io.TableFiles, chunk_rows: int = None,
                      optimizer_states=None, validated: bool = False):
         """Loads the keys of `files` that this rank owns into table t, in place (addresses stay:
-        a captured graph stays valid).  Validation first (validate_table; validated=True: the
+        a captured graph stays valid; a hybrid table that is still growing may move, and the
+        collection reads its address every step).  Validation first (validate_table; validated=True: the
         caller did it), then the rows: a static table scatters every owned key's row to its place
         (rows whose key is not in the file keep their value -- the reference only inserts), a
         dynamic table inserts the owned keys (hctr_det_lookup_rows with insert) and stores their
-        rows (hctr_det_scatter_update).  Optimizer state is loaded when the dump has a state file
+        rows (hctr_det_scatter_update), a hybrid table does the same through hctr_lru_lookup_index
+        and hctr_lru_scatter_slots -- refused by validate_table, before anything is written, when
+        the shard would receive more keys than its max_capacity.  Optimizer state is loaded when the dump has a state file
         for this optimizer (optimizer_states=False: never); without one the state is left alone."""
         lay = self._io_layout(t)
         if lay is None:
@@ -253,8 +287,10 @@ class TableIO:
             return
         R = min(int(chunk_rows or default_chunk_rows(self.ev)), n)
         S, sid = lay["num_shards"], lay["shard_id"]
+        tab = lay.get("hybrid")
+        owned = []  # (hybrid) the keys this shard took from the files, chunk by chunk
         if lay["dynamic"]:
-            cls = lay["cls"]
+            cls = lay.get("cls")
             okeys = torch.empty(R, dtype=torch.int64, device=self.dev)
             obuf = [torch.empty((R, self.ev), dtype=torch.float32, device=self.dev)
                     for _ in range(1 + ns)]
@@ -285,6 +321,19 @@ class TableIO:
                 k = int(got.value)
                 if k == 0:
                     continue
+                if tab is not None:
+                    # an inserting lookup stores the owned keys (one call, one tick of LRU time,
+                    # per chunk), then rows and states go to their slots, either tier.  A key its
+                    # bucket has no room for is not stored: counted by the table (`rejected`).
+                    tab.lookup_index(okeys[:k], insert=True)
+                    owned.append(okeys[:k].clone())
+                    slots = tab.find(okeys[:k])
+                    tab.scatter_slots(0, slots, obuf[0][:k])
+                    for a in range(ns):
+                        tab.state_ptr(a)
+                        tab.scatter_slots(1 + a, slots, obuf[1 + a][:k])
+                    torch.cuda.synchronize()  # (okeys / obuf are refilled by the next chunk)
+                    continue
                 _, rows, _ = self.det.lookup_rows(okeys[:k], [cls], [0, k], insert=True,
                                                   want_ptrs=False)
                 self.det.scatter_update(okeys[:k], obuf[0][:k], [cls], [0, k])
@@ -297,6 +346,18 @@ class TableIO:
                 torch.cuda.synchronize()  # (okeys / obuf are refilled by the next chunk)
             io.wait(0)
             io.wait(1)
+        if owned:
+            # within max_capacity a key can still be lost: its bucket had no room (rejected), or a
+            # later chunk -- a later tick of LRU time -- evicted it.  Found again, all of them, or
+            # the load is reported as incomplete.
+            missing = sum(int((tab.find(k) < 0).sum()) for k in owned)
+            if missing:
+                raise _lib.HugeCTRAmdError(
+                    f"{files.label}: {missing} of {sum(int(k.numel()) for k in owned)} keys of "
+                    f"shard {sid} of {S} did not stay in hybrid table {self.tables[t].name!r} "
+                    f"(bucket overflow or eviction by a later chunk; size {tab.size()}, rejected "
+                    f"{tab.rejected_count()}, max_capacity {tab.capacity}): the table holds an "
+                    "incomplete load")
 
 
 # ---- whole collections: one process, any number of rank shards (tests, tools, Model) -------------

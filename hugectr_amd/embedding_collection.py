@@ -1,4 +1,5 @@
-"""embedding_collection (EBC) on static or dynamic tables -- the engine SparseOperationKit plugs into.
+"""embedding_collection (EBC) on static, dynamic or hybrid tables -- the engine SparseOperationKit
+plugs into.
 
 Mirrors `EmbeddingTableConfig` / `EmbeddingCollectionConfig.embedding_lookup(...).shard(...)`
 (R/HugeCTR/include/pybind/embedding_collection_wrapper.hpp:28-66) and the forward / backward /
@@ -24,6 +25,16 @@ that grows on demand; routing keeps the raw keys, `lookup` returns per-key row a
 the backward builds Wgrad{unique_keys, ev_start_indices, data} (hctr_ebc_local_reduce) for the
 table's fused optimizer step (hctr_det_update, all seven optimizers of optimizers.cuh).
 
+storage="hybrid" (every table `EmbeddingTableConfig(..., var_type="hybrid", max_capacity=...)`): each
+local table shard is one bounded LRU table (hybrid_table.HybridTable, hctr_lru_*: eviction, growth,
+host tier, optimizer state at the slots).  Keys are routed as for dynamic tables; a step regroups
+them by table (hctr_ebc_group_segments), makes ONE inserting call per table -- the table's unit of
+LRU time --, turns the row numbers into row addresses in routed order (hctr_ebc_hybrid_row_ptrs)
+for hctr_forward_pool_ptrs, and updates through hctr_ebc_hybrid_key_grads -> hctr_lru_find ->
+hctr_lru_apply_update.  Capacity and HBM budget are per owning GPU.  The evaluation runtime
+(`tables_from=`) never inserts: an unseen key reads the initializer's value (a dynamic table reads
+zeros).  `_check_hybrid` / `_setup_hybrid` and the *_hybrid stages.
+
 CompressionStrategy.Unique (`shard(..., compression_strategy=...)`, several GPUs): the reference's
 second model-parallel operator (R/HugeCTR/embedding/dense_model_parallel_embedding.cpp) -- the owner
 ships every distinct row once per destination GPU plus a 32-bit index per key, the receiver pools
@@ -38,7 +49,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from dataclasses import dataclass
+from dataclasses import KW_ONLY, dataclass
 from typing import List, Optional
 
 import torch
@@ -47,6 +58,8 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .ebc_io import TableIO
+from .hybrid_table import (HybridTable, check_capacities, check_hbm_budget, check_load_factor,
+                           hbm_slots_for)
 
 _DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 # optimizers whose step on a dynamic table runs in the static tables' sparse update, on the flat
@@ -54,13 +67,74 @@ _DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF
 _FLAT_STEP = (_lib.OPT_SGD, _lib.OPT_ADAGRAD, _lib.OPT_ADAM, _lib.OPT_MOMENTUM_SGD)
 
 
+# optimizers hctr_lru_apply_update serves: the step of a hybrid table
+_HYBRID_STEP = {_lib.OPT_SGD: "SGD", _lib.OPT_ADAGRAD: "AdaGrad", _lib.OPT_ADAM: "Adam",
+                _lib.OPT_MOMENTUM_SGD: "MomentumSGD", _lib.OPT_NESTEROV: "Nesterov"}
+_OPT_NAMES = {**_HYBRID_STEP, _lib.OPT_FTRL: "Ftrl", _lib.OPT_RMSPROP: "RMSProp"}
+HYBRID_MAX_KEYS_PER_CALL = 1 << 24  # hctr_lru_lookup_index
+
+
 @dataclass
 class EmbeddingTableConfig:
+    """One table.  max_vocabulary_size >= 0: a static table of that many rows; < 0: a table keyed
+    by raw int64 keys -- the dynamic table (var_type None / "hbm": grows on demand and keeps, in
+    HBM, every key it has seen) or, var_type="hybrid", a BOUNDED table with LRU eviction
+    (hybrid_table.py, hctr_lru_*; DESIGN.md "Hybrid table").  The keyword-only options are those of
+    sok.DynamicVariable and belong to var_type="hybrid": max_capacity (required; slots, rounded up
+    to whole buckets), init_capacity (where the table starts; it doubles up to max_capacity, which
+    must be init_capacity times a power of two in whole buckets), max_load_factor in (0, 1],
+    max_bucket_size (64, 128, 192 or 256), max_hbm_for_vectors (GiB of rows kept in HBM, the other
+    slots' rows and optimizer states live in pinned host memory; None: everything in HBM) and
+    initializer ("ones" | "zeros" | a float literal | anything else = uniform (0, 1], a function of
+    (seed, key, element)).  max_capacity, init_capacity and max_hbm_for_vectors are PER OWNING GPU,
+    exactly as for a SOK variable: every shard of a row-sharded table has max_capacity slots and
+    its own HBM budget.  A violation raises RuntimeError when the object is made."""
     name: str
     max_vocabulary_size: int
     ev_size: int
     opt_params: object = None
     init_param: object = None
+    _: KW_ONLY
+    var_type: Optional[str] = None
+    max_capacity: Optional[int] = None
+    init_capacity: Optional[int] = None
+    max_load_factor: float = 0.5
+    max_bucket_size: int = 128
+    max_hbm_for_vectors: Optional[float] = None
+    initializer: str = ""
+
+    def __post_init__(self):
+        def bad(msg):
+            raise RuntimeError(f"EmbeddingTableConfig {self.name!r}: {msg}")
+
+        if self.var_type not in (None, "hbm", "hybrid"):
+            bad(f'var_type must be None, "hbm" or "hybrid", not {self.var_type!r}')
+        if self.var_type != "hybrid":
+            given = [k for k, d in (("max_capacity", None), ("init_capacity", None),
+                                    ("max_load_factor", 0.5), ("max_bucket_size", 128),
+                                    ("max_hbm_for_vectors", None), ("initializer", ""))
+                     if getattr(self, k) is not d and getattr(self, k) != d]
+            if given:
+                bad(f'{", ".join(given)} belong to var_type="hybrid"')
+            return
+        if self.max_vocabulary_size >= 0:
+            bad('var_type="hybrid" is keyed by raw int64 keys: max_vocabulary_size must be < 0, '
+                f"not {self.max_vocabulary_size}")
+        # the checks of sok.DynamicVariable and of the table itself (hybrid_table.py), raised as
+        # this module's error type
+        try:
+            check_capacities(self.max_capacity, self.init_capacity, self.max_bucket_size)
+            check_load_factor(self.max_load_factor)
+            if self.max_hbm_for_vectors is not None:
+                check_hbm_budget(self.max_hbm_for_vectors)
+        except ValueError as e:
+            bad(str(e))
+        if not isinstance(self.initializer, (str, int, float)) or isinstance(self.initializer, bool):
+            bad(f"initializer must be a string or a number, not {self.initializer!r}")
+
+    @property
+    def hybrid(self) -> bool:
+        return self.var_type == "hybrid"
 
 
 class EmbeddingCollectionConfig:
@@ -249,6 +323,14 @@ class EmbeddingCollection(TableIO):
         uniq = sorted(n for n in names_here if comp.get(n) == "unique")
         rest = sorted(n for n in names_here if comp.get(n) != "unique")
         self._unique = False
+        hyb_names = sorted(n for n in names_here if any(
+            t.name == n and getattr(t, "var_type", None) == "hybrid" for t, _, _, _ in config.lookups))
+        want_hybrid = storage == "hybrid" or (storage is None and bool(hyb_names))
+        if want_hybrid and uniq and self.world > 1:
+            raise RuntimeError(
+                f"EmbeddingCollectionConfig.shard: CompressionStrategy.Unique for tables {uniq} on "
+                f"{self.world} GPUs is not available for hybrid tables (var_type=\"hybrid\": "
+                f"{hyb_names or uniq}); their lookups travel under CompressionStrategy.Reduction")
         if uniq and self.world > 1:
             if rest:
                 raise _lib.HugeCTRAmdError(
@@ -257,20 +339,28 @@ class EmbeddingCollection(TableIO):
                     f"EmbeddingCollection on {self.world} GPUs: the two strategies run as separate "
                     "collections (one operator each); hugectr.Model splits such a config itself")
             self._unique = True
+        if want_hybrid:  # checked on the USER's lookups (hotness has one entry per user lookup),
+            # before any device call
+            self._check_hybrid(config, optimizer, global_batch, hotness, max_hotness)
+            storage = "hybrid"
         config = self._expand_concat_lookups(config, hotness, batch_major)
         if storage is None:  # max_vocabulary_size < 0 means dynamic (embedding_storage/common.hpp:78,
             # embedding_table.cpp:27-34: one dynamic table makes the whole group dynamic)
             storage = "dynamic" if any(t.max_vocabulary_size < 0 for t, _, _, _ in config.lookups) \
                 else "static"
-        assert storage in ("static", "dynamic")
+        assert storage in ("static", "dynamic", "hybrid")
         self.dynamic = storage == "dynamic"
+        # storage="hybrid": one bounded LRU table (hybrid_table.HybridTable) per local table shard,
+        # `_setup_hybrid` and the *_hybrid stages below
+        self.hybrid = storage == "hybrid"
         self.training = True
         self.dev = torch.device("cuda", torch.cuda.current_device())
         self.B, self.bpg = global_batch, global_batch // self.world
         self.lr, self.optimizer, self.scaler, self.epsilon = lr, optimizer, scaler, epsilon
         self.beta1, self.beta2, self.momentum_factor = beta1, beta2, momentum_factor
         self.out_dtype, self.batch_major, self.key_dtype = out_dtype, batch_major, key_dtype
-        if not self.dynamic and optimizer not in (_lib.OPT_SGD, _lib.OPT_ADAGRAD, _lib.OPT_FTRL):
+        if not (self.dynamic or self.hybrid) and \
+                optimizer not in (_lib.OPT_SGD, _lib.OPT_ADAGRAD, _lib.OPT_FTRL):
             # static EBC tables: SGD / AdaGrad / Ftrl only
             raise _lib.HugeCTRAmdError("EBC static tables support SGD, AdaGrad and Ftrl")
         self.ftrl = tuple(float(x) for x in ftrl)  # (lambda1, lambda2, beta)
@@ -305,12 +395,19 @@ class EmbeddingCollection(TableIO):
         self.accum = self.ftrl_z = self.table = None
         if tables_from is not None:
             src = tables_from
-            assert src.dynamic == self.dynamic and src.local_rows == self.local_rows
+            assert src.dynamic == self.dynamic and src.hybrid == self.hybrid and \
+                (self.hybrid or self.dynamic or src.local_rows == self.local_rows)
             self.table, self.accum, self.ftrl_z = src.table, src.accum, src.ftrl_z
+            if self.hybrid:
+                self.hyb = src.hyb
+                self.local_rows = 1
             if self.dynamic:
                 self.class_of_table = src.class_of_table
                 self.det, self.det_opt = src.det, src.det_opt
                 self.local_rows = 1
+        elif self.hybrid:
+            self._setup_hybrid(tables, seed, initializer)
+            self.local_rows = 1
         elif self.dynamic:
             # one class of the dynamic table per local table shard; max_vocabulary_size is only a
             # hint here, the maps grow on demand (dynamic_embedding.cu:41-75)
@@ -352,7 +449,8 @@ class EmbeddingCollection(TableIO):
         for l in self.local_lookups:
             t = self.lookup_table[l]
             desc += [l, len(self.owners[t]), self.owners[t].index(self.rank)]
-            rs.append(-1 if self.dynamic else self.row_start_of_table[t])  # < 0: keep the key
+            # (< 0: keep the key)
+            rs.append(-1 if self.dynamic or self.hybrid else self.row_start_of_table[t])
         self.n_local = len(self.local_lookups)
         if self.dynamic:  # class of every (peer, local lookup) segment of the routed keys
             self.seg_class = [self.class_of_table[self.lookup_table[l]]
@@ -403,8 +501,12 @@ class EmbeddingCollection(TableIO):
         self._upd = ctypes.c_void_p()
         # (dynamic: the table grows -- every update names the rows handed out so far,
         #  hctr_updater_set_row_bound; the unique-row reduce numbers its rows < max_nnz)
-        check(lib.hctr_updater_create(self.max_nnz, 0xFFFFFFEF if self.dynamic else self.local_rows,
+        # (hybrid: every table steps through an updater of its own, `_hybrid_apply`)
+        check(lib.hctr_updater_create(1 if self.hybrid else self.max_nnz,
+                                      0xFFFFFFEF if self.dynamic else self.local_rows,
                                       self.ev, ctypes.byref(self._upd)))
+        if self.hybrid:
+            self._setup_hybrid_segments()
         # HCTR_DYNAMIC_FLAT=0: the pointer-per-key lookup and the unique-key optimizer step for
         # every optimizer (what Nesterov / RMSProp / Ftrl take in any case)
         self._dyn_flat = self.dynamic and os.environ.get("HCTR_DYNAMIC_FLAT", "1") != "0"
@@ -440,7 +542,9 @@ class EmbeddingCollection(TableIO):
         owners = self.owners[t]
         lay = dict(dynamic=self.dynamic, num_shards=len(owners), shard_id=owners.index(self.rank),
                    writes=True)
-        if self.dynamic:
+        if self.hybrid:  # raw keys, like a dynamic table; rows and states at the slot numbers
+            lay.update(dynamic=True, vocab=1 << 63, hybrid=self.hyb[t])
+        elif self.dynamic:
             lay.update(vocab=1 << 63, cls=self.class_of_table[t])
         else:
             lay.update(vocab=int(self.tables[t].max_vocabulary_size),
@@ -456,6 +560,9 @@ class EmbeddingCollection(TableIO):
             if u is not None and u.value:
                 lib.hctr_updater_destroy(u)
                 setattr(self, name, ctypes.c_void_p())
+        for u in (getattr(self, "_hyb_upd", None) or {}).values():
+            lib.hctr_updater_destroy(u[0])
+        self._hyb_upd = {}
 
     # -- collectives (identity for world == 1; the single-process tests drive them by hand) -------
     def _allgather_keys(self, keys, bucket_range):
@@ -572,6 +679,8 @@ class EmbeddingCollection(TableIO):
                                            ptr(gbucket_range), kt, ptr(self.out_range),
                                            ptr(self.indices), ptr(self.d_nnz), ptr(self.d_one_hot),
                                            int(gkeys.numel()), stream_ptr()))
+            if self.hybrid:
+                return self._scale_average(self._hybrid_pool(send, True), True)
             if self.dynamic:  # (row_start < 0: the pass kept the raw keys)
                 return self._scale_average(self._dynamic_pool(send, True), True)
             self._nnz_host = int(gkeys.numel())
@@ -587,6 +696,8 @@ class EmbeddingCollection(TableIO):
                                       ptr(self.d_row_start), ptr(gkeys), ptr(gbucket_range), kt,
                                       ptr(self.out_range), ptr(self.indices), ptr(self.d_nnz),
                                       ptr(self.ws), stream_ptr()))
+        if self.hybrid:
+            return self._hybrid_pool(send)
         if self.dynamic:
             return self._dynamic_pool(send)
         self._nnz_host = int(gkeys.numel())  # upper bound; the live count stays on the device
@@ -657,6 +768,8 @@ class EmbeddingCollection(TableIO):
         send = torch.empty((max(self.nb, 1), self.ev), dtype=self.out_dtype, device=self.dev)
         if self.n_local == 0:
             return send[:0]
+        if self.hybrid:
+            return self._hybrid_pool(send)
         if self.dynamic:
             return self._dynamic_pool(send)
         check(lib.hctr_forward_pool(self.nb, self.ev, 0, ptr(self.out_range), _lib.KEY_I64,
@@ -767,6 +880,191 @@ class EmbeddingCollection(TableIO):
         self.det_opt.set_learning_rate(self.lr)
         self.det_opt.update(ukey[:n], ev_start, wgrad[:n].view(-1), list(range(ncls)), off)
 
+    # -- storage="hybrid": bounded LRU tables, optionally tiered to host memory -----------------------
+    # One HybridTable (hctr_lru_*) per local table shard: own capacity, HBM budget, scores and
+    # evictions -- tables do not compete for slots.  Keys travel as for dynamic tables (raw keys,
+    # key % num_shards picks the owner).  Per step and table: ONE inserting call over the table's
+    # keys of every peer and lookup (the call is the unit of LRU time), the row numbers become row
+    # addresses in routed order (hctr_ebc_hybrid_row_ptrs) for hctr_forward_pool_ptrs(_mapped); the
+    # update finds the keys again (hctr_lru_find: a rejected key has no slot and gets no gradient)
+    # and steps through hctr_lru_apply_update, which stages host-resident slots itself.
+    # Launches per step: route (1), group (1), row_ptrs (1), pool (1), key_grads (1) plus, per
+    # table, the table's own lookup, find and update kernels.  Host synchronisations: one per step
+    # (the segment offsets), plus one per inserting call of a table that is still growing.  The
+    # segment destinations and the table descriptors reach the device through one pinned staging
+    # buffer and asynchronous copies (`_hyb_host` / `_hyb_dev`): the host never waits for them.
+    def _check_hybrid(self, config, optimizer, global_batch, hotness, max_hotness):
+        names = []
+        for t, _, _, _ in config.lookups:
+            if t.name not in names:
+                names.append(t.name)
+        plain = sorted({t.name for t, _, _, _ in config.lookups
+                        if getattr(t, "var_type", None) != "hybrid"})
+        if plain:
+            raise RuntimeError(
+                f'embedding_collection: tables {plain} are not var_type="hybrid" while '
+                f'{sorted(set(names) - set(plain))} are: one collection has one storage '
+                "(hugectr.Model splits such a config itself)")
+        if optimizer not in _HYBRID_STEP:
+            raise RuntimeError(
+                f"embedding_collection: optimizer {_OPT_NAMES.get(optimizer, optimizer)} is not "
+                f"available for hybrid tables {names}; supported: "
+                f"{', '.join(_HYBRID_STEP.values())}")
+        # keys one table can receive in one call on one rank: every sample of the global batch
+        # times the declared hotness of the table's lookups
+        hot = [int(h) for h in hotness] if hotness else [max(1, int(max_hotness))] * len(config.lookups)
+        for n in names:
+            per_call = int(global_batch) * sum(max(1, h) for (t, _, _, _), h in
+                                               zip(config.lookups, hot) if t.name == n)
+            if per_call > HYBRID_MAX_KEYS_PER_CALL:
+                raise RuntimeError(
+                    f"embedding_collection: hybrid table {n!r} can receive {per_call} keys in one "
+                    f"call (global batch {global_batch} x hotness of its lookups), above the 2^24 "
+                    "keys of one hctr_lru_lookup_index call")
+
+    def _setup_hybrid(self, tables, seed, initializer):
+        # the table seed depends on (collection seed, table position), NOT on the rank: the
+        # initializer is a pure function of (seed, key, element), so a key's first vector is the
+        # same under any sharding
+        self.hyb = {}
+        for t in self.local_tables:
+            tc = tables[t]
+            hbm = None
+            if tc.max_hbm_for_vectors is not None:
+                hbm = hbm_slots_for(tc.max_hbm_for_vectors, self.ev, tc.max_capacity,
+                                    tc.max_bucket_size)
+            self.hyb[t] = HybridTable(tc.max_capacity, self.ev, str(tc.initializer) or initializer,
+                                      tc.max_bucket_size, torch.int64,
+                                      seed=int(seed) * 1000003 + t, hbm_slots=hbm,
+                                      init_capacity=tc.init_capacity,
+                                      max_load_factor=float(tc.max_load_factor))
+
+    def _setup_hybrid_segments(self):
+        # segment = (peer, local lookup) of the routed keys; grouped order [table][peer][lookup]
+        pos_of = {t: i for i, t in enumerate(self.local_tables)}
+        seg_table = [pos_of[self.lookup_table[l]] for _ in range(self.world)
+                     for l in self.local_lookups]
+        self._hyb_groups = [[s for s, ti in enumerate(seg_table) if ti == i]
+                            for i in range(len(self.local_tables))]
+        self.d_seg_table = torch.tensor(seg_table or [0], dtype=torch.int32, device=self.dev)
+        self._hyb_upd = {}   # table -> (hctr_updater, key capacity, row bound)
+        self._hyb_step = None
+        self._hyb_times = 0
+        self._hyb_ro = None
+        # pinned staging of [segment destinations | (row store, rows) per table] and its device
+        # twin.  Reuse is safe: every step starts by reading the segment offsets on the host, which
+        # waits for the stream, the previous step's copies and kernels included.
+        n = len(seg_table) + 2 * len(self.local_tables) + 1
+        self._hyb_host = torch.zeros(n, dtype=torch.int64).pin_memory()
+        self._hyb_dev = torch.zeros(n, dtype=torch.int64, device=self.dev)
+
+    def _hybrid_stage(self, first: int, values):
+        """values -> the device twin at [first, first + len(values)), without a host wait"""
+        n = len(values)
+        self._hyb_host[first:first + n] = torch.tensor(values, dtype=torch.int64)
+        d = self._hyb_dev[first:first + n]
+        d.copy_(self._hyb_host[first:first + n], non_blocking=True)
+        return d
+
+    def table_stats(self):
+        """{table name: dict(size, capacity_now, max_capacity, hbm_slots, rejected, doublings)} of
+        the hybrid tables this rank holds a shard of (host synchronisations: a reporting call)"""
+        if not self.hybrid:
+            raise _lib.HugeCTRAmdError("table_stats: this collection has no hybrid tables")
+        out = {}
+        for t in self.local_tables:
+            h = self.hyb[t]
+            out[self.tables[t].name] = dict(
+                size=h.size(), capacity_now=h.current_capacity, max_capacity=h.capacity,
+                hbm_slots=h.hbm_slots, rejected=h.rejected_count(), doublings=h.doublings)
+        return out
+
+    def _hybrid_pool(self, send: torch.Tensor, direct: bool = False) -> torch.Tensor:
+        """self.indices holds the routed raw keys in [peer][local lookup][b_local] bucket order"""
+        seg = self.out_range[0:self.nb + 1:self.bpg].tolist()  # host sync (offsets)
+        nnz = seg[-1]
+        self._nnz_host = nnz
+        self._hyb_step = None
+        if nnz == 0:
+            return send.zero_()
+        n_seg = self.world * self.n_local
+        dst, start, pos = [0] * n_seg, [0], 0
+        for group in self._hyb_groups:
+            for s in group:
+                dst[s] = pos
+                pos += seg[s + 1] - seg[s]
+            start.append(pos)
+        d_dst = self._hybrid_stage(0, dst)
+        gkeys = torch.empty(nnz, dtype=torch.int64, device=self.dev)
+        rows = torch.empty(nnz, dtype=torch.int64, device=self.dev)
+        check(lib.hctr_ebc_group_segments(n_seg, self.bpg, ptr(self.out_range), ptr(d_dst),
+                                          ptr(self.indices), nnz, ptr(gkeys), stream_ptr()))
+        desc = []
+        for i, t in enumerate(self.local_tables):
+            a, b = start[i], start[i + 1]
+            tab = self.hyb[t]
+            if b > a:  # (the evaluation runtime never inserts: a miss reads the initializer's value)
+                tab.lookup_index(gkeys[a:b], insert=self.training, out=rows[a:b])
+            # after the call: it may have moved the row store, and on a growing table the address
+            # holds only until the next inserting call
+            desc += [tab.rows_ptr()[0] or 0, tab.placement()[1]]
+        d_desc = self._hybrid_stage(n_seg, desc)
+        ptrs = torch.empty(nnz, dtype=torch.int64, device=self.dev)
+        perm = torch.empty(nnz, dtype=torch.int32, device=self.dev)
+        check(lib.hctr_ebc_hybrid_row_ptrs(n_seg, self.bpg, ptr(self.out_range), ptr(d_dst),
+                                           ptr(self.d_seg_table), len(self.local_tables),
+                                           ptr(d_desc), self.ev, ptr(rows), nnz, ptr(ptrs),
+                                           ptr(perm), stream_ptr()))
+        self._hyb_step = (gkeys, perm, start)
+        bm = direct and self.batch_major  # one GPU: pooled straight into the batch-major output
+        check(lib.hctr_forward_pool_ptrs_mapped(self.nb, self.ev, 0, ptr(self.out_range), ptr(ptrs),
+                                                ptr(send), _DT[self.out_dtype],
+                                                self.bpg if bm else 0, self.L if bm else 0,
+                                                stream_ptr()))
+        return send
+
+    def _hybrid_apply(self, top_grad: torch.Tensor, mapped: bool):
+        nnz = self._nnz_host
+        if nnz == 0 or self._hyb_step is None:
+            return
+        gkeys, perm, start = self._hyb_step
+        # one fp32 gradient row per key, in the grouped order of the forward
+        kg = torch.empty((nnz, self.ev), dtype=torch.float32, device=self.dev)
+        check(lib.hctr_ebc_hybrid_key_grads(self.nb, self.ev, ptr(self.out_range), ptr(perm), nnz,
+                                            ptr(top_grad), _DT[self.out_dtype],
+                                            self.bpg if mapped else 0, self.L if mapped else 0,
+                                            ptr(kg), stream_ptr()))
+        self._hyb_times += 1  # (Adam's step count: updates that met keys, as for dynamic tables)
+        most = max(start[i + 1] - start[i] for i in range(len(self.local_tables)))
+        if self._hyb_ro is None or self._hyb_ro.numel() < most + 1:
+            self._hyb_ro = torch.arange(max(2 * most, 1024) + 1, dtype=torch.int64, device=self.dev)
+        hp = dict(lr=self.lr, beta1=self.beta1, beta2=self.beta2, epsilon=self.epsilon,
+                  momentum=self.momentum_factor, scaler=self.scaler)
+        n_state = {_lib.OPT_SGD: 0, _lib.OPT_ADAM: 2}.get(self.optimizer, 1)
+        for i, t in enumerate(self.local_tables):
+            a, b = start[i], start[i + 1]
+            n = b - a
+            if n == 0:
+                continue
+            tab = self.hyb[t]
+            # a key inserted in this step's forward cannot have been evicted since; a rejected one
+            # has no slot (SIZE_MAX) and its gradient is dropped
+            slots = tab.find(gkeys[a:b])
+            u = self._hyb_upd.get(t)
+            ucap = max(2 * n, 1024) if u is None or u[1] < n else u[1]
+            bound = tab.update_rows(ucap)  # (follows a table that is still growing)
+            if u is None or u[1] < ucap or u[2] < bound:
+                if u is not None:
+                    lib.hctr_updater_destroy(u[0])
+                    del self._hyb_upd[t]
+                h = ctypes.c_void_p()
+                check(lib.hctr_updater_create(ucap, bound, self.ev, ctypes.byref(h)))
+                u = self._hyb_upd[t] = (h, ucap, bound)
+            for j in range(n_state):
+                tab.state_ptr(j)
+            tab.apply_update(u[0], self._hyb_ro[:n + 1], slots, kg[a:b], self.optimizer, hp,
+                             self._hyb_times)
+
     def network_forward(self, recv: torch.Tensor) -> torch.Tensor:
         shape = (self.bpg, self.L, self.ev) if self.batch_major else (self.L, self.bpg, self.ev)
         out = torch.empty(shape, dtype=self.out_dtype, device=self.dev)
@@ -795,6 +1093,8 @@ class EmbeddingCollection(TableIO):
             return
         self._times += 1
         mapped = direct and self.batch_major
+        if self.hybrid:  # (the gradient's layout is an argument of hctr_ebc_hybrid_key_grads)
+            return self._hybrid_apply(top_grad.contiguous(), mapped)
         if mapped != self._map_on:
             check(lib.hctr_updater_set_grad_map(self._upd, self.bpg if mapped else 0,
                                                 self.L if mapped else 0))

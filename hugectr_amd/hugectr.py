@@ -932,7 +932,13 @@ class Model:
         comp = (getattr(cfg, "compression", None) or {}) if self.world > 1 else {}
         strategies = sorted({comp.get(t.name, "reduction") for t, _, _, _ in cfg.lookups
                              if t.name not in dp_names})
-        if len(sizes) == 1 and not dp_names and len(strategies) <= 1:
+        # one collection has one storage: hybrid tables (var_type="hybrid": bounded, LRU eviction,
+        # optionally tiered to host memory) form sub-collections of their own; static and dynamic
+        # tables are grouped as before -- a hybrid table does not turn its neighbours hybrid
+        def kind(t):
+            return "hybrid" if getattr(t, "var_type", None) == "hybrid" else "plain"
+        kinds = sorted({kind(t) for t, _, _, _ in cfg.lookups if t.name not in dp_names})
+        if len(sizes) == 1 and not dp_names and len(strategies) <= 1 and len(kinds) <= 1:
             return [(cfg, list(range(len(cfg.lookups))))]
         tables = []
         for t, _, _, _ in cfg.lookups:
@@ -948,10 +954,10 @@ class Model:
                 sub.lookups = [cfg.lookups[l] for l in ids]
                 sub.shard_strategy = "dp"
                 out.append((sub, ids))
-        for ev, strategy in [(e, k) for e in sizes for k in strategies]:
+        for ev, strategy, knd in [(e, k, q) for e in sizes for k in strategies for q in kinds]:
             ids = [l for l, (t, _, _, _) in enumerate(cfg.lookups)
                    if t.ev_size == ev and t.name not in dp_names and
-                   comp.get(t.name, "reduction") == strategy]
+                   comp.get(t.name, "reduction") == strategy and kind(t) == knd]
             if not ids:
                 continue
             sub = EmbeddingCollectionConfig()
@@ -975,9 +981,21 @@ class Model:
         o = self.opt
         t = Optimizer_t(o.optimizer_type)
         dynamic = any(tc.max_vocabulary_size < 0 for tc, _, _, _ in cfg.lookups)
+        # (_split_by_ev_size: a sub-config is hybrid as a whole or not at all)
+        hybrid = any(getattr(tc, "var_type", None) == "hybrid" for tc, _, _, _ in cfg.lookups)
         codes = {Optimizer_t.SGD: _lib.OPT_SGD, Optimizer_t.AdaGrad: _lib.OPT_ADAGRAD,
                  Optimizer_t.Ftrl: _lib.OPT_FTRL}
-        if dynamic:  # the dynamic table has all seven (embedding_storage/optimizers.cuh:29-233)
+        if hybrid:  # what hctr_lru_apply_update serves
+            codes = {Optimizer_t.SGD: _lib.OPT_SGD, Optimizer_t.AdaGrad: _lib.OPT_ADAGRAD,
+                     Optimizer_t.Adam: _lib.OPT_ADAM,
+                     Optimizer_t.MomentumSGD: _lib.OPT_MOMENTUM_SGD,
+                     Optimizer_t.Nesterov: _lib.OPT_NESTEROV}
+            if t not in codes:
+                raise RuntimeError(
+                    f"hybrid embedding_collection tables "
+                    f"{sorted({tc.name for tc, _, _, _ in cfg.lookups})} do not support "
+                    f"{t.name}; supported: SGD, AdaGrad, Adam, MomentumSGD, Nesterov")
+        elif dynamic:  # the dynamic table has all seven (embedding_storage/optimizers.cuh:29-233)
             codes.update({Optimizer_t.Adam: _lib.OPT_ADAM, Optimizer_t.RMSProp: _lib.OPT_RMSPROP,
                           Optimizer_t.MomentumSGD: _lib.OPT_MOMENTUM_SGD,
                           Optimizer_t.Nesterov: _lib.OPT_NESTEROV})
@@ -1007,6 +1025,8 @@ class Model:
                   batch_major=True, max_hotness=hot, seed=self.solver.seed,
                   ftrl=(o.lambda1, o.lambda2, o.beta))
         ekw = dict(kw, hotness=[p.max_nnz() for p in params])  # multi-hot concat lookups
+        if hybrid:  # (capacity, tier and initializer travel in the table configs)
+            ekw.update(beta1=o.beta1, beta2=o.beta2, momentum_factor=o.momentum_factor)
         if dynamic:
             kw.update(beta1=o.beta1, beta2=o.beta2, momentum_factor=o.momentum_factor,
                       init_capacity=1 << 16)
@@ -1033,7 +1053,9 @@ class Model:
             ev = train if (Be == B and not dynamic) else EmbeddingCollection(
                 cfg, Be, tables_from=train, **ekw)
             if ev is not train and dynamic:
-                ev.training = False  # evaluation never inserts: unseen keys read as zeros
+                # evaluation never inserts: unseen keys read as zeros (dynamic tables) or as the
+                # initializer's value (hybrid tables)
+                ev.training = False
         L, evs = train.L, train.ev  # (L counts a multi-hot concat lookup once per key slot)
         if declare_shapes:
             if cfg.top_name:
@@ -2009,7 +2031,13 @@ class Model:
             d = f"{prefix}_ebc{i}_sparse_{iteration}.model"
             os.makedirs(d, exist_ok=True)
             e = rt["train"]
-            if getattr(e, "dynamic", False):  # per local table: the keys it holds and their vectors
+            if getattr(e, "hybrid", False):  # per local table shard: its stored keys and rows
+                for t, tab in e.hyb.items():
+                    k, v = tab.export()
+                    k.cpu().numpy().astype("<i8").tofile(os.path.join(d, f"key.table{t}.rank{self.rank}"))
+                    v.cpu().numpy().astype("<f4").tofile(
+                        os.path.join(d, f"emb_vector.table{t}.rank{self.rank}"))
+            elif getattr(e, "dynamic", False):  # per local table: the keys it holds and their vectors
                 for t, c in e.class_of_table.items():
                     k, v = e.det.export(c)
                     k.cpu().numpy().astype("<i8").tofile(os.path.join(d, f"key.table{t}.rank{self.rank}"))

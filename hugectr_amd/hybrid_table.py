@@ -41,6 +41,38 @@ def check_hbm_budget(max_hbm_for_vectors) -> float:
     return float(g)
 
 
+def check_load_factor(load) -> float:
+    """max_load_factor as a float: a number in (0, 1]; anything else raises ValueError"""
+    if isinstance(load, bool) or not isinstance(load, (int, float)) or not 0.0 < float(load) <= 1.0:
+        raise ValueError(f"max_load_factor must be a number in (0, 1], not {load!r}")
+    return float(load)
+
+
+def check_capacities(max_capacity, init_capacity=None, bucket_size: int = 128):
+    """the geometry hctr_lru_create_growing accepts, checked without a device: max_capacity (and
+    init_capacity, when given) positive ints, init_capacity <= max_capacity, bucket_size 64, 128,
+    192 or 256, and max_capacity = init_capacity * 2^j in whole buckets; ValueError otherwise"""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if max_capacity is None:
+        raise ValueError('var_type="hybrid" needs max_capacity')
+    if not is_int(max_capacity) or max_capacity < 1:
+        raise ValueError(f"max_capacity must be a positive int, not {max_capacity!r}")
+    S = bucket_size
+    if not is_int(S) or S not in (64, 128, 192, 256):
+        raise ValueError(f"max_bucket_size must be 64, 128, 192 or 256, not {S!r}")
+    if init_capacity is None:
+        return
+    if not is_int(init_capacity) or init_capacity < 1:
+        raise ValueError(f"init_capacity must be a positive int, not {init_capacity!r}")
+    if init_capacity > max_capacity:
+        raise ValueError(f"init_capacity {init_capacity} is above max_capacity {max_capacity}")
+    b0, b1 = -(-init_capacity // S), -(-max_capacity // S)
+    if b1 % b0 or (b1 // b0) & (b1 // b0 - 1):
+        raise ValueError(f"max_capacity {max_capacity} must be init_capacity {init_capacity} "
+                         f"times a power of two, in whole buckets of {S}")
+
+
 def hbm_slots_for(max_hbm_for_vectors, dim: int, capacity: int, bucket_size: int) -> int:
     """H = min(C, floor(G * 2^30 / (dim * 4) / S) * S): the slots whose rows fit in G GiB of HBM,
     in whole buckets (C = capacity rounded up to whole buckets of S = bucket_size)"""
@@ -138,14 +170,16 @@ class HybridTable:
         return keys.to(self.key_dtype).contiguous()
 
     def lookup_index(self, keys: torch.Tensor, insert: bool, evict: bool = False,
-                     admit: Optional[float] = None):
+                     admit: Optional[float] = None, out: Optional[torch.Tensor] = None):
         """row numbers int64[n] (rows >= hbm_slots: per-call rows holding the initializer's value
         or, on a tiered table, a host-resident key's row);
         with evict=True also (evicted keys, evicted rows [m, dim]) -- one host synchronisation.
-        admit=p (insert only): the low-frequency filter; keys it does not admit get FILTERED."""
+        admit=p (insert only): the low-frequency filter; keys it does not admit get FILTERED.
+        out: a contiguous int64[n] tensor that receives the row numbers instead of a new one."""
         keys = self._keys(keys)
         n = keys.numel()
-        idx = torch.empty(n, dtype=torch.int64, device=keys.device)
+        idx = torch.empty(n, dtype=torch.int64, device=keys.device) if out is None else out
+        assert idx.numel() == n and idx.dtype == torch.int64 and idx.is_contiguous()
         if insert:
             self.call_ns.append(int(self.clock()))
         ek = ev = m = None

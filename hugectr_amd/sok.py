@@ -36,7 +36,8 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .dynamic_table import DynamicEmbeddingTable, DynamicTableOptimizer, _num_state
-from .hybrid_table import HybridTable, check_hbm_budget, first_call_since, hbm_slots_for
+from .hybrid_table import (HybridTable, check_hbm_budget, check_load_factor, first_call_since,
+                           hbm_slots_for)
 
 _RANK, _WORLD = 0, 1
 INVALID = -1  # 0xFFFFFFFFFFFFFFFF as int64: "row not on this GPU / unknown key"
@@ -208,10 +209,7 @@ class DynamicVariable(_VariableBase):
         self.filter_ratio = float(ratio)
         if var_type == "hybrid" and "max_hbm_for_vectors" in kwargs:
             check_hbm_budget(kwargs["max_hbm_for_vectors"])
-        load = kwargs.get("max_load_factor", 0.5)
-        if isinstance(load, bool) or not isinstance(load, (int, float)) or \
-                not 0.0 < float(load) <= 1.0:
-            raise ValueError(f"max_load_factor must be a number in (0, 1], not {load!r}")
+        load = check_load_factor(kwargs.get("max_load_factor", 0.5))
         cap = kwargs.get("max_capacity")
         if var_type == "hybrid" and cap is not None and init_capacity is not None and \
                 int(init_capacity) > int(cap):

@@ -1139,6 +1139,48 @@ int hctr_ebc_io_export_static(hctr_ebc_io* io, int which, size_t n, uint64_t fir
                               uint64_t key_step, const float* table_rows, const float* state0,
                               const float* state1, hctr_stream_t stream);
 
+/* ---- embedding_collection on hybrid tables (storage="hybrid", csrc/ebc_hybrid.hip) --------------
+ * One hctr_lru table per local table shard.  The routed keys of a step lie in bucket order
+ * [peer][local lookup][b_local]; SEGMENT s = peer * num_local_lookups + local lookup holds the
+ * routed positions [seg_offsets[s * seg_stride], seg_offsets[(s + 1) * seg_stride]) -- seg_offsets
+ * is the routed bucket_range (device int64) and seg_stride the buckets per segment (batch per GPU).
+ * Segments may be empty.  An inserting call is the table's unit of LRU time, so every table gets
+ * its keys of a step in ONE call: the GROUPED order is [table][peer][lookup], and seg_dst[s]
+ * (device int64 [n_seg]) is the grouped position of segment s's first key, computed by the host
+ * from the offsets it has read.  The descriptors must map the nnz routed positions one to one
+ * onto [0, nnz); a position mapped outside writes nothing (group_segments) or gives NULL and
+ * 0xFFFFFFFF (row_ptrs).  One lane per key, its segment found by binary search; vector stores
+ * only, no atomics, one launch each, no allocation, no host synchronisation; nnz < 2^32; nnz == 0
+ * is legal.  Argument errors are reported before any launch.
+ *   group_segments  out_keys[grouped(i)] = keys[i] for every routed position i (int64 keys; not
+ *                   in place).
+ *   hybrid_row_ptrs the inverse map.  rows [nnz] (uint64): row numbers in GROUPED order, as
+ *                   hctr_lru_lookup_index wrote them table by table; seg_table[s] (int32) = the
+ *                   table of segment s, in [0, n_tables); table_desc (device uint64 [n_tables][2])
+ *                   = {address of the table's row store, rows it holds now} (hctr_lru_rows,
+ *                   hctr_lru_placement's hbm_rows -- read AFTER the table's lookup call, which may
+ *                   have moved the store).  out_ptrs[i] = row address of routed key i for
+ *                   hctr_forward_pool_ptrs(_mapped), NULL (adds 0) for a row number that is not a
+ *                   row of its table; out_perm[i] (uint32) = grouped(i).
+ *   hybrid_key_grads the update's per-key gradients in GROUPED order: key_grads[perm[j]][0:ev] =
+ *                   fp32(grad[bucket of routed key j]), grad being [buckets][ev_size] of grad_dtype
+ *                   (hctr_emb_dtype_t); (samples, lookups) != (0, 0): the gradient of the
+ *                   batch-major output, bucket u = lookup * samples + sample read from row
+ *                   sample * lookups + lookup (hctr_forward_pool_mapped's store address).  Every
+ *                   grouped position is written once. */
+int hctr_ebc_group_segments(size_t n_seg, size_t seg_stride, const int64_t* seg_offsets,
+                            const int64_t* seg_dst, const int64_t* keys, size_t nnz,
+                            int64_t* out_keys, hctr_stream_t stream);
+int hctr_ebc_hybrid_row_ptrs(size_t n_seg, size_t seg_stride, const int64_t* seg_offsets,
+                             const int64_t* seg_dst, const int32_t* seg_table, int n_tables,
+                             const uint64_t* table_desc, int ev_size, const uint64_t* rows,
+                             size_t nnz, const float** out_ptrs, uint32_t* out_perm,
+                             hctr_stream_t stream);
+int hctr_ebc_hybrid_key_grads(size_t buckets, int ev_size, const int64_t* bucket_range,
+                              const uint32_t* perm, size_t nnz, const void* grad, int grad_dtype,
+                              size_t samples, size_t lookups, float* key_grads,
+                              hctr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
