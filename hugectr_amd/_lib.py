@@ -293,7 +293,16 @@ _SIGNATURES = {
                                          c_size_t, _P, _P, _P]),
     "hctr_ebc_hybrid_key_grads": (c_int, [c_size_t, c_int, _P, _P, c_size_t, _P, c_int, c_size_t,
                                           c_size_t, _P, _P]),
+    "hctr_metric_accumulate_temp_bytes": (c_size_t, []),
+    "hctr_metric_accumulate": (c_int, [_P, c_int, _P, c_size_t, c_int, _P, _P, c_size_t, c_size_t,
+                                       _P, _P, c_size_t, _P]),
+    "hctr_metric_auc_temp_bytes": (c_size_t, [c_size_t]),
+    "hctr_metric_auc": (c_int, [_P, c_size_t, _P, _P, c_size_t, _P, _P]),
+    "hctr_metric_ndcg_temp_bytes": (c_size_t, [c_size_t]),
+    "hctr_metric_ndcg": (c_int, [_P, c_size_t, _P, _P, c_size_t, _P, _P]),
 }
+METRIC_MAX_CLASSES = 256
+METRIC_COUNTER_WORDS = 264
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 

@@ -359,3 +359,7 @@ int hctr_radix_sort_pairs_u32(void* temp, size_t temp_bytes, const uint32_t* key
                               as_stream(stream));
 }
 }
+
+// the evaluation metrics (hctr_metric_*: accumulate, AUC words, NDCG) finalise with this sort and
+// share its unit
+#include "metrics.hip"

@@ -30,6 +30,7 @@ from .dense import FusedMLP, bce_with_logits
 from .embedding import OptParams, SparseEmbeddingHash, backward_reorder, forward_reorder
 from .embedding_collection import (DataParallelCollection, EmbeddingCollection,  # noqa: F401
                                    EmbeddingCollectionConfig, EmbeddingTableConfig)
+from .metrics import EvalMetrics
 from .layers import (MultiCrossLayer, interaction, interaction_gather, interaction_indexed,
                      regather_supported)
 from .parallel import DistributedExchange, LocalizedExchange, reorder_row_map
@@ -716,6 +717,12 @@ class Model:
             if r is not None and hasattr(r, "ebc_groups"):
                 r.ebc_groups = groups
         self._plan_execution()
+        # evaluation metrics as solver.metrics_spec names them (Model::create_metrics,
+        # R/HugeCTR/src/pybind/model_compile.cpp:915-938); the device store is allocated by the
+        # first eval()
+        self._metrics = EvalMetrics(s.metrics_spec, self.input.label_dim, self.bpg_eval,
+                                    s.max_eval_batches, num_loss_layers=len(self._loss_layers),
+                                    world=self.world, device=self.device)
         self._compiled = True
 
     def _plan_execution(self):
@@ -1854,39 +1861,39 @@ class Model:
         for _, ev in getattr(self, "_idx_ahead", {}).values():
             torch.cuda.current_stream().wait_event(ev)
 
+    @property
+    def _eval_buf(self):
+        """what eval() has accumulated since the last reset: the EvalMetrics object, falsy while it
+        is empty.  Assigning anything (`model._eval_buf = []`) clears the store and the counters."""
+        return getattr(self, "_metrics", None)
+
+    @_eval_buf.setter
+    def _eval_buf(self, _):
+        m = getattr(self, "_metrics", None)
+        if m is not None:
+            m.reset()
+
     def eval(self) -> bool:
         batch = self.reader.next_batch(train=False)
         if batch is None:
             return False
         self._drain_prefetch()
-        if not getattr(self, "_eval_buf", None):
+        if not self._eval_buf:
             self.check_overflow()
         with torch.no_grad():
             loss, prob = self._run_batch(batch, False)
-        self._eval_buf.append((prob.detach().float().flatten(), batch["label"].float().flatten(),
-                               loss.detach()))
+        # one launch files the scores away (hugectr_amd/metrics.py): no list, nothing waits
+        self._metrics.add_batch(prob, batch["label"], loss)
         return True
 
     def get_current_loss(self) -> float:
         return float(self._loss_t)
 
     def get_eval_metrics(self):
-        if not self._eval_buf:
-            return []
-        p = torch.cat([a for a, _, _ in self._eval_buf])
-        y = torch.cat([b for _, b, _ in self._eval_buf])
-        loss = torch.stack([c for _, _, c in self._eval_buf]).mean().float().view(1)
-        if self.world > 1:  # the metric is over the samples of ALL GPUs (metrics.cu gathers them)
-            staged = dist.get_backend() == "gloo"
-            dv = torch.device("cpu") if staged else self.device
-            ps = [torch.empty(p.numel(), dtype=p.dtype, device=dv) for _ in range(self.world)]
-            ys = [torch.empty(y.numel(), dtype=y.dtype, device=dv) for _ in range(self.world)]
-            dist.all_gather(ps, p.to(dv).contiguous())
-            dist.all_gather(ys, y.to(dv).contiguous())
-            p, y = torch.cat(ps).to(self.device), torch.cat(ys).to(self.device)
-            _all_reduce(loss)
-            loss /= self.world
-        return [("AUC", _auc(p, y)), ("AverageLoss", float(loss))]
+        """one (name, value) pair per type of solver.metrics_spec in enum order, then
+        ("AverageLoss", ...) unless the spec named it; over the samples of ALL GPUs.  Resets
+        nothing."""
+        return self._metrics.result()
 
     def set_learning_rate(self, lr: float):
         self._lr = lr
@@ -1931,8 +1938,9 @@ class Model:
             print(f"[HCTR][INFO] Use non-epoch mode with number of iterations: {max_iter}"
                   if num_epochs <= 0 else f"[HCTR][INFO] Use epoch mode with number of epochs: {num_epochs}")
             print(f"[HCTR][INFO] Training batchsize: {s.batchsize}, evaluation batchsize: {s.batchsize_eval}")
-        t0 = time.time()
+        t0 = t_fit = time.time()
         it = 0
+        hit_target = False
         limit = max_iter if num_epochs <= 0 else 10 ** 12
         self._eval_buf = []
         callbacks = list(getattr(s, "training_callbacks", None) or [])
@@ -1964,10 +1972,6 @@ class Model:
                         break
                 torch.cuda.synchronize()
                 metrics = self.get_eval_metrics()
-                if self.rank == 0:
-                    for name, v in metrics:
-                        print(f"[HCTR][INFO] Evaluation, {name}: {v:.6f}")
-                    print(f"[HCTR][INFO] Eval Time for {s.max_eval_batches} iters: {time.time() - te:.6f}s")
                 early = False
                 for tc in callbacks:  # model.cpp:935-943
                     early = bool(tc.on_eval_end(it - 1, dict(metrics))) or early
@@ -1976,14 +1980,36 @@ class Model:
                         tc.on_training_end(it - 1)
                     stopped = True
                     break
+                for name, v in metrics:  # model.cpp:945-979
+                    if self.rank == 0:
+                        print(f"[HCTR][INFO] Evaluation, {name}: {v:.6f}")
+                    if name != "AUC":
+                        continue
+                    per = self._metrics.per_class("AUC")
+                    if self.rank == 0 and len(per) > 1:  # print_class_aucs, model.cpp:678-689
+                        print("[HCTR][INFO] Evaluation, AUC: {" + ", ".join(f"{a:f}" for a in per) + "}")
+                    target = self._metrics.targets.get("AUC")
+                    if target is not None and v > target:
+                        if self.rank == 0:
+                            el = max(time.time() - t_fit, 1e-9)
+                            print(f"[HCTR][INFO] Hit target accuracy AUC {target:.5f} at "
+                                  f"{it - 1} / {max_iter} iterations with batchsize {s.batchsize} "
+                                  f"in {el:.2f}s. Average speed "
+                                  f"{float(it - 1) * s.batchsize / el:f} records/s.")
+                        hit_target = True
+                        break
+                if hit_target:  # the reference returns here: no on_training_end, no summary line
+                    break
+                if self.rank == 0:
+                    print(f"[HCTR][INFO] Eval Time for {s.max_eval_batches} iters: {time.time() - te:.6f}s")
             if snapshot > 0 and it % snapshot == 0 and snapshot_prefix:
                 self.save_params_to_files(snapshot_prefix, it)
-        if not stopped:
+        if not stopped and not hit_target:
             for tc in callbacks:  # model.cpp:991-994
                 tc.on_training_end(max(it - 1, 0))
         torch.cuda.synchronize()
         self.check_overflow()
-        if self.rank == 0:
+        if self.rank == 0 and not hit_target:
             print(f"[HCTR][INFO] Finish {it} iterations with batchsize: {s.batchsize} in "
                   f"{time.time() - t0:.2f}s.")
 

@@ -1181,6 +1181,45 @@ int hctr_ebc_hybrid_key_grads(size_t buckets, int ev_size, const int64_t* bucket
                               size_t samples, size_t lookups, float* key_grads,
                               hctr_stream_t stream);
 
+/* ---- evaluation metrics (csrc/metrics.hip; R/HugeCTR/src/metrics.cu) -----------------------------
+ * Stateless and asynchronous on `stream`: the caller owns the store, the counter block and the
+ * workspaces.  Argument errors (null pointers, C outside 1..256, offset + n > cap, n >= 2^31) are
+ * reported before any device call.
+ *
+ * Store of one metric object, class-major: keys uint32 [C][cap], labels float [C][cap].  The key
+ * of a score is the order-preserving image of its exact fp32 value: sign bit flipped for
+ * non-negatives, all bits for negatives, -0.0 as +0.0, every NaN 0xFFFFFFFF (NaNs tie and sort
+ * last).  Counter block: HCTR_METRIC_COUNTER_WORDS uint64 words, zeroed by the caller to reset:
+ *   [0] HitRate checked: elements with (double)pred > 0.8      [1] hits: label == 1 among them
+ *   [2] SMAPE count                 [3] SMAPE sum, the bits of a double: sum of |p - l| / ((p + l) / 2)
+ *       in fp64, a term with p + l == 0 counting 0; per-workgroup partials added in workgroup order
+ *   [4] used by the call (0 between calls)   [8 + c] labels of class c that are neither 0 nor 1
+ *
+ * accumulate  one evaluation batch in ONE launch: pred [n][C] row-major of pred_dtype
+ *             (hctr_emb_dtype_t), label [n][C] float -> store slots [c][offset + i], counters
+ *             updated.  temp: hctr_metric_accumulate_temp_bytes() bytes of device memory.
+ * auc         one class (keys / labels point at its n stored samples; left untouched): stable sort
+ *             of (key, label bits) with hctr_radix_sort_pairs_u32, then out[0] = 2U, out[1] = P,
+ *             out[2] = N (device uint64): P / N = labels that are / are not 1.0, 2U = sum over runs of
+ *             equal key of pos_run * (2 * neg_below_run + neg_run) -- Mann-Whitney with ties counted
+ *             one half.  Integers: the same bits on every call.  AUC = 2U / (2 P N).
+ * ndcg        one class, labels >= 0: out[0] = DCG = sum of label_i / log2(2 + (n - 1 - i)) over the
+ *             samples sorted ascending (stable) by key, out[1] = the same sum over the labels sorted
+ *             ascending by their own key (device double; fixed summation order). */
+#define HCTR_METRIC_MAX_CLASSES 256
+#define HCTR_METRIC_COUNTER_WORDS 264
+size_t hctr_metric_accumulate_temp_bytes(void);
+int hctr_metric_accumulate(const void* pred, int pred_dtype, const float* label, size_t n, int C,
+                           uint32_t* keys, float* labels, size_t cap, size_t offset,
+                           uint64_t* counters, void* temp, size_t temp_bytes,
+                           hctr_stream_t stream);
+size_t hctr_metric_auc_temp_bytes(size_t n);
+int hctr_metric_auc(void* temp, size_t temp_bytes, const uint32_t* keys, const float* labels,
+                    size_t n, uint64_t* out, hctr_stream_t stream);
+size_t hctr_metric_ndcg_temp_bytes(size_t n);
+int hctr_metric_ndcg(void* temp, size_t temp_bytes, const uint32_t* keys, const float* labels,
+                     size_t n, double* out, hctr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
