@@ -359,6 +359,14 @@ __global__ void __launch_bounds__(kBlock)
   o[1] = f32x4{acc[4], acc[5], acc[6], acc[7]};
 }
 
+// the dense SGD step as ONE expression for every kernel that takes it (f32x4 or float): a parameter
+// rounds the same (contraction included) whichever kernel updates it
+template <typename V>
+__device__ __forceinline__ V sgd_apply(V w, V g, float lr, float grad_scale) {
+  w -= lr * grad_scale * g;
+  return w;
+}
+
 // dense SGD step fused with the refresh of the 16-bit compute copy: w -= lr * g; w16 = (T16)w
 template <bool BF>
 __global__ void __launch_bounds__(kBlock)
@@ -369,7 +377,7 @@ __global__ void __launch_bounds__(kBlock)
        i += (size_t)gridDim.x * kBlock) {
     f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    wv -= lr * grad_scale * gv;
+    wv = sgd_apply(wv, gv, lr, grad_scale);
     reinterpret_cast<f32x4*>(w)[i] = wv;
     const unsigned lo = (unsigned)H::from_f32(wv[0]) | ((unsigned)H::from_f32(wv[1]) << 16);
     const unsigned hi = (unsigned)H::from_f32(wv[2]) | ((unsigned)H::from_f32(wv[3]) << 16);
@@ -855,6 +863,195 @@ __global__ void __launch_bounds__(1024)
   }
 }
 
+// ================================================================================================
+// Gradient finish: ONE launch per step takes every fixed-order partial sum the backward's producers
+// left (split-K weight-gradient products, bias tile partials, the logit head's and the skinny first
+// layer's block partials) to its place in the flat gradient buffer -- or, SGD = true, straight
+// through the optimizer step into the fp32 masters and their 16-bit copy.  A workgroup finds its
+// segment in the table by its block number; each segment kind adds in the order of the kernel it
+// stands in for (sum_groups / colsum_partials / logit_head_finish / skinny_fc_finish), term for
+// term, so every gradient keeps its bits.
+// ================================================================================================
+template <bool SGD>
+__device__ __forceinline__ void finish_store4(const hctr_dense_seg& sg, size_t at, f32x4 gv,
+                                              float lr, float grad_scale) {
+  if (!SGD) {
+    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(sg.g) + at) = gv;
+    return;
+  }
+  f32x4* wp = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(sg.w) + at);
+  const f32x4 wv = sgd_apply(*wp, gv, lr, grad_scale);
+  *wp = wv;
+  unsigned lo, hi;
+  if (sg.bf16) {
+    lo = (unsigned)H16<true>::from_f32(wv[0]) | ((unsigned)H16<true>::from_f32(wv[1]) << 16);
+    hi = (unsigned)H16<true>::from_f32(wv[2]) | ((unsigned)H16<true>::from_f32(wv[3]) << 16);
+  } else {
+    lo = (unsigned)H16<false>::from_f32(wv[0]) | ((unsigned)H16<false>::from_f32(wv[1]) << 16);
+    hi = (unsigned)H16<false>::from_f32(wv[2]) | ((unsigned)H16<false>::from_f32(wv[3]) << 16);
+  }
+  *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(sg.w16) + at) = make_uint2(lo, hi);
+}
+
+template <bool SGD>
+__device__ __forceinline__ void finish_store1(const hctr_dense_seg& sg, size_t at, float gv,
+                                              float lr, float grad_scale) {
+  if (!SGD) {
+    reinterpret_cast<float*>(sg.g)[at] = gv;
+    return;
+  }
+  float* wp = reinterpret_cast<float*>(sg.w) + at;
+  const float wv = sgd_apply(*wp, gv, lr, grad_scale);
+  *wp = wv;
+  reinterpret_cast<unsigned short*>(sg.w16)[at] =
+      sg.bf16 ? H16<true>::from_f32(wv) : H16<false>::from_f32(wv);
+}
+
+// sum_groups_kernel's sum for element group i
+template <bool BF>
+__device__ __forceinline__ void finish_sum_groups(int groups, size_t n8, size_t i,
+                                                  const unsigned short* __restrict__ in,
+                                                  f32x4& lo, f32x4& hi) {
+  using H = H16<BF>;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // (the usual 16 groups: all 16 loads in flight, added in group order)
+#pragma unroll 16
+  for (int g = 0; g < groups; g++) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(in + ((size_t)g * n8 + i) * 8);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      acc[2 * e] += H::to_f32((unsigned short)(v[e] & 0xFFFFu));
+      acc[2 * e + 1] += H::to_f32((unsigned short)(v[e] >> 16));
+    }
+  }
+  lo = f32x4{acc[0], acc[1], acc[2], acc[3]};
+  hi = f32x4{acc[4], acc[5], acc[6], acc[7]};
+}
+
+// the chunked block sum of logit_head_finish_kernel / skinny_fc_finish_kernel for 64 consecutive
+// columns: 16 chunk groups, each added in block order, then the groups in order.  Here a wavefront
+// takes four of the groups, one after the other (256 threads instead of 1024): the same sums.
+__device__ __forceinline__ float finish_block_chunks(float (*part)[64], int blocks, size_t stride,
+                                                     size_t col, bool live,
+                                                     const float* __restrict__ partial) {
+  const int c = threadIdx.x & 63;
+  const int chunk = (blocks + 15) / 16;
+  for (int grp = threadIdx.x >> 6; grp < 16; grp += kBlock / 64) {
+    const int b0 = grp * chunk, b1 = min(blocks, b0 + chunk);
+    float t = 0.f;
+    if (live) {
+      int b = b0;
+      for (; b + 8 <= b1; b += 8) {  // 8 independent loads in flight, added in order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = partial[(size_t)(b + u) * stride + col];
+#pragma unroll
+        for (int u = 0; u < 8; u++) t += v[u];
+      }
+      for (; b < b1; b++) t += partial[(size_t)b * stride + col];
+    }
+    part[grp][c] = t;
+  }
+  __syncthreads();
+  float tot = 0.f;
+  if (threadIdx.x < 64 && live) {
+#pragma unroll
+    for (int g = 0; g < 16; g++) tot += part[g][c];
+  }
+  return tot;
+}
+
+template <bool SGD>
+__global__ void __launch_bounds__(kBlock)
+    dense_grad_finish_kernel(const hctr_dense_seg* __restrict__ segs, int nseg, float lr,
+                             float grad_scale, float* __restrict__ loss) {
+  __shared__ f32x4 red[kBlock];  // colsum: [32 tile groups][8]; head / skinny: float [16][64]
+  // the block's segment = the last one whose first block is not past it: every wavefront looks at
+  // 64 table entries per step (one load latency, not one per segment)
+  int si = -1;
+  for (int base = 0; base < nseg; base += 64) {
+    const int t = base + (int)(threadIdx.x & 63);
+    const bool in = t < nseg && segs[t].block0 <= (long long)blockIdx.x;
+    si += (int)__popcll(__ballot(in));
+  }
+  const hctr_dense_seg sg = segs[si];
+  const int blk = (int)((long long)blockIdx.x - sg.block0);
+  const size_t dst = (size_t)sg.dst, dst2 = (size_t)sg.dst2;
+  switch ((int)sg.kind) {
+    case HCTR_DENSE_SEG_SUM_GROUPS: {
+      const size_t n8 = (size_t)sg.n / 8;
+      const size_t i = (size_t)blk * kBlock + threadIdx.x;
+      if (i >= n8) return;
+      const unsigned short* in = reinterpret_cast<const unsigned short*>(sg.src);
+      f32x4 lo, hi;
+      if (sg.src_bf16) finish_sum_groups<true>((int)sg.count, n8, i, in, lo, hi);
+      else finish_sum_groups<false>((int)sg.count, n8, i, in, lo, hi);
+      finish_store4<SGD>(sg, dst + i * 8, lo, lr, grad_scale);
+      finish_store4<SGD>(sg, dst + i * 8 + 4, hi, lr, grad_scale);
+      return;
+    }
+    case HCTR_DENSE_SEG_COLSUM: {  // colsum_partials_kernel
+      const float* partial = reinterpret_cast<const float*>(sg.src);
+      const size_t tiles = (size_t)sg.count;
+      const int n = (int)sg.n;
+      const int c4 = blk * 8 + (threadIdx.x & 7), tg = threadIdx.x >> 3;
+      const bool live = c4 * 4 < n;
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      if (live) {
+#pragma unroll 8
+        for (size_t t = tg; t < tiles; t += 32)
+          s += *reinterpret_cast<const f32x4*>(partial + t * n + c4 * 4);
+      }
+      red[threadIdx.x] = s;
+      __syncthreads();
+      if (tg == 0 && live) {
+        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 32; k++) sum += red[k * 8 + threadIdx.x];
+        finish_store4<SGD>(sg, dst + (size_t)c4 * 4, sum, lr, grad_scale);
+      }
+      return;
+    }
+    case HCTR_DENSE_SEG_LOGIT_HEAD: {  // logit_head_finish_kernel; partial [blocks][K + 2]
+      const int K = (int)sg.n;
+      const int k = blk * 64 + (int)(threadIdx.x & 63);
+      const bool live = k < K + 2;
+      const float tot = finish_block_chunks(reinterpret_cast<float(*)[64]>(red), (int)sg.count,
+                                            (size_t)(K + 2), (size_t)k, live,
+                                            reinterpret_cast<const float*>(sg.src));
+      if (threadIdx.x < 64 && live) {
+        if (k < K) finish_store1<SGD>(sg, dst + k, tot, lr, grad_scale);
+        else if (k == K) finish_store1<SGD>(sg, dst2, tot, lr, grad_scale);
+        else if (loss) *loss = tot / (float)(size_t)sg.k;
+      }
+      return;
+    }
+    case HCTR_DENSE_SEG_SKINNY: {  // skinny_fc_finish_kernel; partial [blocks][N][kSkinnyK + 1]
+      const int stride = kSkinnyK + 1;
+      const int K = (int)sg.k, total = (int)sg.n * stride;
+      const int i = blk * 64 + (int)(threadIdx.x & 63);
+      const bool live = i < total;
+      const float tot = finish_block_chunks(reinterpret_cast<float(*)[64]>(red), (int)sg.count,
+                                            (size_t)total, (size_t)i, live,
+                                            reinterpret_cast<const float*>(sg.src));
+      if (threadIdx.x < 64 && live) {
+        const int n = i / stride, kk = i % stride;
+        if (kk == kSkinnyK) finish_store1<SGD>(sg, dst2 + n, tot, lr, grad_scale);
+        else if (kk < K) finish_store1<SGD>(sg, dst + (size_t)n * K + kk, tot, lr, grad_scale);
+      }
+      return;
+    }
+    default: {  // HCTR_DENSE_SEG_DIRECT: the gradient is in g already; only the step is left
+      if (!SGD) return;
+      const size_t i = (size_t)blk * kBlock + threadIdx.x;
+      if (i >= (size_t)sg.n / 4) return;
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(sg.g) + dst + i * 4);
+      finish_store4<SGD>(sg, dst + i * 4, gv, lr, grad_scale);
+      return;
+    }
+  }
+}
+
 constexpr int kCrossBwdWaves = 256 * 4;  // waves used by the cross backward (deterministic reduce)
 
 }  // namespace
@@ -936,12 +1133,13 @@ size_t hctr_relu_bwd_bias_workspace_bytes(size_t rows, int n) {
   return ceil_div<size_t>(rows, (size_t)kRbRows) * (size_t)n * sizeof(float);
 }
 
-int hctr_relu_bwd_bias(size_t rows, int n, const void* dy, const void* y, void* dz, float* db,
-                       float* workspace, int dtype, hctr_stream_t stream) {
+// finish = false: the tile partials stay in the workspace (hctr_dense_grad_finish adds them)
+static int relu_bwd_bias_impl(size_t rows, int n, const void* dy, const void* y, void* dz, float* db,
+                              float* workspace, int dtype, bool finish, hctr_stream_t stream) {
   HCTR_REQUIRE(n > 0 && n % 8 == 0, "n must be a multiple of 8");
   HCTR_REQUIRE(dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16, "16-bit dtypes only");
   if (rows == 0) return HCTR_OK;
-  HCTR_REQUIRE(dy && y && dz && db && workspace, "null pointer");
+  HCTR_REQUIRE(dy && y && dz && (db || !finish) && workspace, "null pointer");
   hipStream_t s = as_stream(stream);
   const size_t tiles = ceil_div<size_t>(rows, (size_t)kRbRows);
   const int cw = n / 8 < kBlock ? n / 8 : kBlock;
@@ -955,10 +1153,21 @@ int hctr_relu_bwd_bias(size_t rows, int n, const void* dy, const void* y, void* 
                        rows, n, cw, rg, (const unsigned short*)dy, (const unsigned short*)y,
                        (unsigned short*)dz, workspace);
   HCTR_LAUNCH_CHECK();
+  if (!finish) return HCTR_OK;
   hipLaunchKernelGGL(colsum_partials_kernel, dim3(ceil_div<int>(n, 32)), dim3(kBlock), 0, s,
                      tiles, n, workspace, db);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
+}
+
+int hctr_relu_bwd_bias(size_t rows, int n, const void* dy, const void* y, void* dz, float* db,
+                       float* workspace, int dtype, hctr_stream_t stream) {
+  return relu_bwd_bias_impl(rows, n, dy, y, dz, db, workspace, dtype, true, stream);
+}
+
+int hctr_relu_bwd_bias_partials(size_t rows, int n, const void* dy, const void* y, void* dz,
+                                float* workspace, int dtype, hctr_stream_t stream) {
+  return relu_bwd_bias_impl(rows, n, dy, y, dz, nullptr, workspace, dtype, false, stream);
 }
 
 size_t hctr_cross_v2_bwd_step_workspace_bytes(size_t batch, int width) {
@@ -1072,21 +1281,34 @@ int hctr_bce_loss(size_t batch, const void* logit, const float* label, float gra
 
 size_t hctr_logit_head_workspace_bytes(int k) { return (size_t)kHeadBlocks * (k + 2) * sizeof(float); }
 
-int hctr_logit_head(size_t batch, int k, const void* x, const void* w, const void* bias,
-                    const float* label, float grad_scale, void* dx, float* dw, float* db,
-                    float* loss, float* workspace, int dtype, hctr_stream_t stream) {
+static int logit_head_rows(int k) {
+  const int nseg = (k + 255) / 256;
+  return nseg <= 1 ? 8 : (nseg <= 2 ? 4 : (nseg <= 4 ? 2 : 1));
+}
+
+int hctr_logit_head_blocks(size_t batch, int k) {
+  HCTR_REQUIRE(batch > 0 && k >= 4 && k % 4 == 0 && k <= 256 * kHeadMaxSeg,
+               "logit head: K must be a multiple of 4 and <= 2048");
+  return (int)std::min<size_t>((size_t)kHeadBlocks,
+                               ceil_div<size_t>(batch, (size_t)(kBlock / 64) * logit_head_rows(k)));
+}
+
+// finish = false: the block partials stay in the workspace (hctr_dense_grad_finish adds them)
+static int logit_head_impl(size_t batch, int k, const void* x, const void* w, const void* bias,
+                           const float* label, float grad_scale, void* dx, float* dw, float* db,
+                           float* loss, float* workspace, int dtype, bool finish,
+                           hctr_stream_t stream) {
   HCTR_REQUIRE(batch > 0 && k >= 4 && k % 4 == 0 && k <= 256 * kHeadMaxSeg,
                "logit head: K must be a multiple of 4 and <= 2048");
   HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "16-bit activations");
-  HCTR_REQUIRE(x && w && bias && label && dw && db && loss && workspace, "null pointer");
+  HCTR_REQUIRE(x && w && bias && label && ((dw && db && loss) || !finish) && workspace,
+               "null pointer");
   HCTR_REQUIRE(reinterpret_cast<uintptr_t>(x) % 8 == 0 && reinterpret_cast<uintptr_t>(w) % 8 == 0 &&
                    (dx == nullptr || reinterpret_cast<uintptr_t>(dx) % 8 == 0),
                "8-byte aligned buffers");
   hipStream_t s = as_stream(stream);
   const int nseg = (k + 255) / 256;
-  const int rows = nseg <= 1 ? 8 : (nseg <= 2 ? 4 : (nseg <= 4 ? 2 : 1));
-  const int blocks = (int)std::min<size_t>(
-      (size_t)kHeadBlocks, ceil_div<size_t>(batch, (size_t)(kBlock / 64) * rows));
+  const int blocks = hctr_logit_head_blocks(batch, k);
   const size_t lds = (size_t)(kBlock / 64) * (k + 2) * sizeof(float);
 #define HCTR_HEAD(T_, NSEG_, ROWS_)                                                               \
   hipLaunchKernelGGL((logit_head_kernel<T_, NSEG_, ROWS_>), dim3(blocks), dim3(kBlock), lds, s,   \
@@ -1105,10 +1327,25 @@ int hctr_logit_head(size_t batch, int k, const void* x, const void* w, const voi
 #undef HCTR_HEAD_T
 #undef HCTR_HEAD
   HCTR_LAUNCH_CHECK();
+  if (!finish) return HCTR_OK;
   hipLaunchKernelGGL(logit_head_finish_kernel, dim3(ceil_div<int>(k + 2, 64)), dim3(1024), 0, s,
                      blocks, k, batch, workspace, dw, db, loss);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
+}
+
+int hctr_logit_head(size_t batch, int k, const void* x, const void* w, const void* bias,
+                    const float* label, float grad_scale, void* dx, float* dw, float* db,
+                    float* loss, float* workspace, int dtype, hctr_stream_t stream) {
+  return logit_head_impl(batch, k, x, w, bias, label, grad_scale, dx, dw, db, loss, workspace,
+                         dtype, true, stream);
+}
+
+int hctr_logit_head_partials(size_t batch, int k, const void* x, const void* w, const void* bias,
+                             const float* label, float grad_scale, void* dx, float* workspace,
+                             int dtype, hctr_stream_t stream) {
+  return logit_head_impl(batch, k, x, w, bias, label, grad_scale, dx, nullptr, nullptr, nullptr,
+                         workspace, dtype, false, stream);
 }
 
 static int skinny_check(size_t batch, int k, int n, int dtype) {
@@ -1144,22 +1381,41 @@ size_t hctr_skinny_fc_bwd_workspace_bytes(int n) {
   return (size_t)kSkinnyBlocks * n * (kSkinnyK + 1) * sizeof(float);
 }
 
-int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* dy, const void* y,
-                       float* dw, float* db, float* workspace, int dtype, hctr_stream_t stream) {
+// which form of the backward runs and how many block partials it leaves
+static int skinny_bwd_blocks(size_t batch, int k, int n, const void* dy, const void* y, bool* mfma) {
+  // matrix-core form: needs a spare input column for db and 16-byte rows (HCTR_SKINNY_BWD=valu|mfma)
+  const char* mode = getenv("HCTR_SKINNY_BWD");
+  const bool want_mfma = mode ? strcmp(mode, "valu") != 0 : kSkinnyBwdMfmaDefault;
+  *mfma = want_mfma && k < kSkinnyK && n % 8 == 0 && reinterpret_cast<uintptr_t>(dy) % 16 == 0 &&
+          reinterpret_cast<uintptr_t>(y) % 16 == 0;
+  if (*mfma) {
+    const int rsets = (kSkinnyBwdBlock / 64) / ceil_div<int>(n, 128);
+    return (int)std::min<size_t>((size_t)kSkinnyBlocks, ceil_div<size_t>(batch, (size_t)rsets * 16));
+  }
+  return (int)std::min<size_t>((size_t)kSkinnyBlocks,
+                               ceil_div<size_t>(batch, kSkinnyBwdBlock / kSkinnyLanes));
+}
+
+int hctr_skinny_fc_bwd_blocks(size_t batch, int k, int n, const void* dy, const void* y) {
+  HCTR_REQUIRE(batch > 0 && k >= 1 && k <= kSkinnyK, "skinny fc: 1 <= K <= 16");
+  HCTR_REQUIRE(n >= 4 && n % 4 == 0 && n <= 512, "skinny fc: N a multiple of 4, <= 512");
+  bool mfma;
+  return skinny_bwd_blocks(batch, k, n, dy, y, &mfma);
+}
+
+// finish = false: the block partials stay in the workspace (hctr_dense_grad_finish adds them)
+static int skinny_fc_bwd_impl(size_t batch, int k, int n, const float* x, const void* dy,
+                              const void* y, float* dw, float* db, float* workspace, int dtype,
+                              bool finish, hctr_stream_t stream) {
   HCTR_TRY(skinny_check(batch, k, n, dtype));
-  HCTR_REQUIRE(x && dy && y && dw && db && workspace, "null pointer");
+  HCTR_REQUIRE(x && dy && y && ((dw && db) || !finish) && workspace, "null pointer");
   HCTR_REQUIRE(reinterpret_cast<uintptr_t>(dy) % 8 == 0 && reinterpret_cast<uintptr_t>(y) % 8 == 0,
                "8-byte aligned activations");
   hipStream_t s = as_stream(stream);
   const size_t lds = (size_t)n * (kSkinnyK + 1) * sizeof(float);
-  // matrix-core form: needs a spare input column for db and 16-byte rows (HCTR_SKINNY_BWD=valu|mfma)
-  const char* mode = getenv("HCTR_SKINNY_BWD");
-  const bool want_mfma = mode ? strcmp(mode, "valu") != 0 : kSkinnyBwdMfmaDefault;
-  if (want_mfma && k < kSkinnyK && n % 8 == 0 && reinterpret_cast<uintptr_t>(dy) % 16 == 0 &&
-      reinterpret_cast<uintptr_t>(y) % 16 == 0) {
-    const int rsets = (kSkinnyBwdBlock / 64) / ceil_div<int>(n, 128);
-    const int blocks = (int)std::min<size_t>((size_t)kSkinnyBlocks,
-                                             ceil_div<size_t>(batch, (size_t)rsets * 16));
+  bool mfma;
+  const int blocks = skinny_bwd_blocks(batch, k, n, dy, y, &mfma);
+  if (mfma) {
     if (dtype == HCTR_EMB_BF16)
       hipLaunchKernelGGL(skinny_fc_bwd_mfma_kernel<__hip_bfloat16>, dim3(blocks),
                          dim3(kSkinnyBwdBlock), lds, s, batch, k, n, x, (const __hip_bfloat16*)dy,
@@ -1168,13 +1424,12 @@ int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* d
       hipLaunchKernelGGL(skinny_fc_bwd_mfma_kernel<__half>, dim3(blocks), dim3(kSkinnyBwdBlock), lds,
                          s, batch, k, n, x, (const __half*)dy, (const __half*)y, workspace);
     HCTR_LAUNCH_CHECK();
+    if (!finish) return HCTR_OK;
     hipLaunchKernelGGL(skinny_fc_finish_kernel, dim3(ceil_div<int>(n * (kSkinnyK + 1), 64)),
                        dim3(1024), 0, s, blocks, k, n, workspace, dw, db);
     HCTR_LAUNCH_CHECK();
     return HCTR_OK;
   }
-  const int blocks = (int)std::min<size_t>(
-      (size_t)kSkinnyBlocks, ceil_div<size_t>(batch, kSkinnyBwdBlock / kSkinnyLanes));
   if (dtype == HCTR_EMB_BF16)
     hipLaunchKernelGGL(skinny_fc_bwd_kernel<__hip_bfloat16>, dim3(blocks), dim3(kSkinnyBwdBlock), lds, s,
                        batch, k, n, x, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)y,
@@ -1183,8 +1438,47 @@ int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* d
     hipLaunchKernelGGL(skinny_fc_bwd_kernel<__half>, dim3(blocks), dim3(kSkinnyBwdBlock), lds, s, batch, k, n,
                        x, (const __half*)dy, (const __half*)y, workspace);
   HCTR_LAUNCH_CHECK();
+  if (!finish) return HCTR_OK;
   hipLaunchKernelGGL(skinny_fc_finish_kernel, dim3(ceil_div<int>(n * (kSkinnyK + 1), 64)),
                      dim3(1024), 0, s, blocks, k, n, workspace, dw, db);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* dy, const void* y,
+                       float* dw, float* db, float* workspace, int dtype, hctr_stream_t stream) {
+  return skinny_fc_bwd_impl(batch, k, n, x, dy, y, dw, db, workspace, dtype, true, stream);
+}
+
+int hctr_skinny_fc_bwd_partials(size_t batch, int k, int n, const float* x, const void* dy,
+                                const void* y, float* workspace, int dtype, hctr_stream_t stream) {
+  return skinny_fc_bwd_impl(batch, k, n, x, dy, y, nullptr, nullptr, workspace, dtype, false,
+                            stream);
+}
+
+int hctr_dense_seg_blocks(int kind, size_t n) {
+  switch (kind) {
+    case HCTR_DENSE_SEG_SUM_GROUPS: return (int)ceil_div<size_t>(n / 8, (size_t)kBlock);
+    case HCTR_DENSE_SEG_COLSUM: return (int)ceil_div<size_t>(n, 32);
+    case HCTR_DENSE_SEG_LOGIT_HEAD: return (int)ceil_div<size_t>(n + 2, 64);
+    case HCTR_DENSE_SEG_SKINNY: return (int)ceil_div<size_t>(n * (kSkinnyK + 1), 64);
+    case HCTR_DENSE_SEG_DIRECT: return (int)ceil_div<size_t>(n / 4, (size_t)kBlock);
+    default: HCTR_REQUIRE(false, "dense finish: unknown segment kind");
+  }
+}
+
+int hctr_dense_grad_finish(const hctr_dense_seg* segs, int nseg, size_t nblocks, int sgd, float lr,
+                           float grad_scale, float* loss, hctr_stream_t stream) {
+  HCTR_REQUIRE(nseg >= 0 && nblocks <= 0x7FFFFFFFu, "dense finish: segment / block count");
+  if (nseg == 0 || nblocks == 0) return HCTR_OK;
+  HCTR_REQUIRE(segs, "null pointer");
+  hipStream_t s = as_stream(stream);
+  if (sgd)
+    hipLaunchKernelGGL(dense_grad_finish_kernel<true>, dim3((unsigned)nblocks), dim3(kBlock), 0, s,
+                       segs, nseg, lr, grad_scale, loss);
+  else
+    hipLaunchKernelGGL(dense_grad_finish_kernel<false>, dim3((unsigned)nblocks), dim3(kBlock), 0, s,
+                       segs, nseg, lr, grad_scale, loss);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }

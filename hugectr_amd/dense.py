@@ -11,6 +11,14 @@ kernels).  What this module fixes is how they are *issued* for the DLRM shapes
 * bias + ReLU ride in the GEMM epilogue (`torch._addmm_activation` -> hipBLASLt RELU_BIAS).
 * bf16 shadow copies of the fp32 master weights are refreshed once per optimizer step with one
   multi-tensor copy instead of one cast kernel per layer per pass.
+* after `FusedMLP.flatten()` masters, gradients and 16-bit copies are three flat buffers and the
+  backward's workspaces exist once per layer.  A `DenseGradFinish` over the model's flattened
+  modules then turns the finishing launches of a step (a group sum per weight gradient, a column
+  sum per bias gradient, the finish kernels of the logit head and the skinny first layer, one SGD
+  launch per module) into ONE launch, `hctr_dense_grad_finish`: the producers leave their partial
+  sums, the launch adds them in the same order as the kernels it replaces and either writes
+  `flat_g` or takes the SGD step and refreshes the 16-bit copy.  A module without a
+  `DenseGradFinish` finishes layer by layer as before.
 """
 from __future__ import annotations
 
@@ -26,26 +34,50 @@ _DT16 = {torch.float16: 1, torch.bfloat16: 2}  # hctr_emb_dtype_t
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def split_k_wgrad(dy: torch.Tensor, x: torch.Tensor, groups: int = 16,
-                  out: torch.Tensor = None) -> torch.Tensor:
-    """dW = dy^T @ x with the batch (K) dimension split into `groups` batched GEMMs (fp32 result,
-    written to `out` when given)."""
-    B, o = dy.shape
-    i = x.shape[1]
+def _count(rc: int) -> int:
+    """a count returned by the library (negative: an error code)"""
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def _split_k_groups(B: int, o: int, i: int, groups: int) -> int:
+    """groups the batch dimension is split into for dW[o, i]; 0 = one plain GEMM"""
     g = groups
     while g > 1 and B % g != 0:
         g //= 2
-    if g <= 1 or min(o, i) < 8:
-        # degenerate outputs (the logit layer, out = 1): the batched-GEMM path of the library
-        # spends ~11 ms per call on the HOST for M = 1 (tools/gemm_probe2.py); one GEMV-like call
-        # is 50-100 us
+    # degenerate outputs (the logit layer, out = 1): the batched-GEMM path of the library
+    # spends ~11 ms per call on the HOST for M = 1 (tools/gemm_probe2.py); one GEMV-like call
+    # is 50-100 us
+    return g if g > 1 and min(o, i) >= 8 else 0
+
+
+def split_k_wgrad(dy: torch.Tensor, x: torch.Tensor, groups: int = 16,
+                  out: torch.Tensor = None, part: torch.Tensor = None,
+                  finish: bool = True):
+    """dW = dy^T @ x with the batch (K) dimension split into `groups` batched GEMMs (fp32 result,
+    written to `out` when given).  part: a preallocated 16-bit buffer of >= groups * out * in
+    elements for the partial products.  finish = False: when the partial products can be left in
+    `part` for `DenseGradFinish` (16-bit, out * in a multiple of 8) they are, and the number of
+    groups is returned instead of dW."""
+    B, o = dy.shape
+    i = x.shape[1]
+    g = _split_k_groups(B, o, i, groups)
+    if g == 0:
         r = dy.t() @ x
         if out is not None:
             out.copy_(r)
             return out
         return r
-    p = torch.bmm(dy.view(g, B // g, o).transpose(1, 2), x.view(g, B // g, i))
-    if p.is_cuda and p.dtype in _DT16 and (o * i) % 8 == 0:
+    a, b = dy.view(g, B // g, o).transpose(1, 2), x.view(g, B // g, i)
+    hip = dy.is_cuda and dy.dtype in _DT16 and (o * i) % 8 == 0
+    if hip and part is not None and part.dtype == dy.dtype:
+        p = torch.bmm(a, b, out=part[:g * o * i].view(g, o, i))
+        if not finish:
+            return g
+    else:
+        p = torch.bmm(a, b)
+    if hip:
         if out is None:
             out = torch.empty((o, i), dtype=torch.float32, device=p.device)
         check(lib.hctr_sum_groups(g, o * i, ptr(p), _DT16[p.dtype], ptr(out), stream_ptr()))
@@ -73,15 +105,42 @@ def bce_with_logits(logit: torch.Tensor, label: torch.Tensor, grad_scale: float)
     return loss, dlogit
 
 
+# segment kinds of hctr_dense_grad_finish (include/hugectr_amd.h)
+_SEG_SUM, _SEG_COLSUM, _SEG_HEAD, _SEG_SKINNY, _SEG_DIRECT = range(5)
+
+
+class _LayerWS:
+    """Workspaces of one layer of a flattened FusedMLP (allocated once, stable addresses: nothing is
+    allocated per call, a captured graph replays on them) and what the last backward left in them:
+    `w_seg` / `b_seg` = (kind, tensor, count, k) as `DenseGradFinish` needs it, None = the
+    gradient itself is in `flat_g`."""
+
+    def __init__(self, mlp, idx: int, wpart: torch.Tensor):
+        self.mlp, self.idx, self.wpart = mlp, idx, wpart
+        self._ws = None
+        self.w_seg = self.b_seg = None
+
+    @property
+    def defer(self) -> bool:
+        return self.mlp._finisher is not None
+
+    def ws(self, nbytes: int) -> torch.Tensor:
+        if self._ws is None or self._ws.numel() * 4 < nbytes:
+            self._ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.wpart.device)
+        return self._ws
+
+
 class _LinearFn(torch.autograd.Function):
     """y = act(x @ W^T + b) on 16-bit shadow weights; gradients returned for the fp32 masters."""
 
     @staticmethod
-    def forward(ctx, x, w_master, b_master, w16, b16, relu: bool, groups: int, gw=None, gb=None):
+    def forward(ctx, x, w_master, b_master, w16, b16, relu: bool, groups: int, gw=None, gb=None,
+                lw=None):
         """gw / gb: views of the module's flat gradient buffer; when given, backward writes the
-        weight / bias gradients there and returns no gradient for the masters"""
+        weight / bias gradients there and returns no gradient for the masters.  lw: the layer's
+        _LayerWS (flattened module)"""
         x = x.contiguous()
-        ctx.gw, ctx.gb = gw, gb
+        ctx.gw, ctx.gb, ctx.lw = gw, gb, lw
         if relu:
             y = torch._addmm_activation(b16, x, w16.t(), use_gelu=False)
         else:
@@ -95,15 +154,26 @@ class _LinearFn(torch.autograd.Function):
         x, w16, y = ctx.saved_tensors
         dy = dy.contiguous()
         n = dy.shape[1]
+        lw = ctx.lw
+        defer = lw is not None and lw.defer
+        if lw is not None:
+            lw.w_seg = lw.b_seg = None
         if ctx.relu and n % 8 == 0 and dy.dtype in _DT16 and dy.is_cuda:
             # fused ReLU backward + bias gradient (HIP): one pass instead of two
             dz = torch.empty_like(dy)
-            db = ctx.gb if ctx.gb is not None else torch.empty(n, dtype=torch.float32,
-                                                             device=dy.device)
-            ws = torch.empty(lib.hctr_relu_bwd_bias_workspace_bytes(dy.shape[0], n) // 4,
-                             dtype=torch.float32, device=dy.device)
-            check(lib.hctr_relu_bwd_bias(dy.shape[0], n, ptr(dy), ptr(y), ptr(dz), ptr(db), ptr(ws),
-                                         _DT16[dy.dtype], stream_ptr()))
+            nbytes = lib.hctr_relu_bwd_bias_workspace_bytes(dy.shape[0], n)
+            ws = lw.ws(nbytes) if lw is not None else \
+                torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
+            if defer:  # the tile partials wait for the step's one finish launch
+                check(lib.hctr_relu_bwd_bias_partials(dy.shape[0], n, ptr(dy), ptr(y), ptr(dz),
+                                                      ptr(ws), _DT16[dy.dtype], stream_ptr()))
+                lw.b_seg = (_SEG_COLSUM, ws, nbytes // (4 * n), 0)
+                db = None
+            else:
+                db = ctx.gb if ctx.gb is not None else torch.empty(n, dtype=torch.float32,
+                                                                 device=dy.device)
+                check(lib.hctr_relu_bwd_bias(dy.shape[0], n, ptr(dy), ptr(y), ptr(dz), ptr(db),
+                                             ptr(ws), _DT16[dy.dtype], stream_ptr()))
             dy = dz
         else:
             if ctx.relu:
@@ -112,10 +182,13 @@ class _LinearFn(torch.autograd.Function):
             if ctx.gb is not None:
                 ctx.gb.copy_(db)
         dx = dy @ w16 if ctx.needs_input_grad[0] else None
-        dw = split_k_wgrad(dy, x, ctx.groups, out=ctx.gw)
+        dw = split_k_wgrad(dy, x, ctx.groups, out=ctx.gw, part=lw.wpart if lw is not None else None,
+                           finish=not defer)
+        if defer and isinstance(dw, int):
+            lw.w_seg = (_SEG_SUM, lw.wpart, dw, 0)
         if ctx.gw is not None:  # gradients live in the flat buffer; nothing for autograd to keep
-            return dx, None, None, None, None, None, None, None, None
-        return dx, dw.float(), db, None, None, None, None, None, None
+            return dx, None, None, None, None, None, None, None, None, None
+        return dx, dw.float(), db, None, None, None, None, None, None, None
 
 
 class _SkinnyFirstFn(torch.autograd.Function):
@@ -125,7 +198,7 @@ class _SkinnyFirstFn(torch.autograd.Function):
     hctr_skinny_fc_fwd."""
 
     @staticmethod
-    def forward(ctx, x, w_master, b_master, w16, b16, gw=None, gb=None):
+    def forward(ctx, x, w_master, b_master, w16, b16, gw=None, gb=None, lw=None):
         x = x.contiguous()
         B, K = x.shape
         N = w16.shape[0]
@@ -135,7 +208,7 @@ class _SkinnyFirstFn(torch.autograd.Function):
                                          _DT16[w16.dtype], stream_ptr()))
         else:  # the library GEMM is the faster forward at 13 -> 512 (30 us against 43 us)
             y = torch._addmm_activation(b16, x.to(w16.dtype), w16.t(), use_gelu=False)
-        ctx.gw, ctx.gb = gw, gb
+        ctx.gw, ctx.gb, ctx.lw = gw, gb, lw
         ctx.save_for_backward(x, y)
         return y
 
@@ -146,15 +219,25 @@ class _SkinnyFirstFn(torch.autograd.Function):
         B, K = x.shape
         N = y.shape[1]
         dev = x.device
+        lw = ctx.lw
+        nbytes = lib.hctr_skinny_fc_bwd_workspace_bytes(N)
+        ws = lw.ws(nbytes) if lw is not None else \
+            torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        if lw is not None and lw.defer:  # the block partials wait for the step's finish launch
+            check(lib.hctr_skinny_fc_bwd_partials(B, K, N, ptr(x), ptr(dy), ptr(y), ptr(ws),
+                                                  _DT16[y.dtype], stream_ptr()))
+            blocks = _count(lib.hctr_skinny_fc_bwd_blocks(B, K, N, ptr(dy), ptr(y)))
+            lw.w_seg, lw.b_seg = (_SEG_SKINNY, ws, blocks, K), None
+            return None, None, None, None, None, None, None, None
+        if lw is not None:
+            lw.w_seg = lw.b_seg = None
         dw = ctx.gw if ctx.gw is not None else torch.empty((N, K), dtype=torch.float32, device=dev)
         db = ctx.gb if ctx.gb is not None else torch.empty(N, dtype=torch.float32, device=dev)
-        ws = torch.empty(lib.hctr_skinny_fc_bwd_workspace_bytes(N) // 4, dtype=torch.float32,
-                         device=dev)
         check(lib.hctr_skinny_fc_bwd(B, K, N, ptr(x), ptr(dy), ptr(y), ptr(dw), ptr(db), ptr(ws),
                                      _DT16[y.dtype], stream_ptr()))
         if ctx.gw is not None:
-            return None, None, None, None, None, None, None
-        return None, dw, db, None, None, None, None
+            return None, None, None, None, None, None, None, None
+        return None, dw, db, None, None, None, None, None
 
 
 class _LogitHeadFn(torch.autograd.Function):
@@ -163,21 +246,37 @@ class _LogitHeadFn(torch.autograd.Function):
     assumes the unit upstream gradient of `loss.backward()` -- scale through grad_scale."""
 
     @staticmethod
-    def forward(ctx, x, w_master, b_master, w16, b16, label, grad_scale: float, gw=None, gb=None):
+    def forward(ctx, x, w_master, b_master, w16, b16, label, grad_scale: float, gw=None, gb=None,
+                lw=None):
         x = x.contiguous()
         B, K = x.shape
         dev = x.device
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nbytes = lib.hctr_logit_head_workspace_bytes(K)
+        ws = lw.ws(nbytes) if lw is not None else \
+            torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        label = label.contiguous()
+        ctx.flat = gw is not None
+        ctx.dx = dx
+        if lw is not None and lw.defer:
+            # dw / db / the loss are block partials until the step's finish launch, which writes
+            # the loss too: it is valid on the stream after DenseGradFinish.finish()
+            check(lib.hctr_logit_head_partials(B, K, ptr(x), ptr(w16), ptr(b16), ptr(label),
+                                               float(grad_scale), ptr(dx), ptr(ws), _DT16[x.dtype],
+                                               stream_ptr()))
+            lw.w_seg = (_SEG_HEAD, ws, _count(lib.hctr_logit_head_blocks(B, K)), B)
+            lw.b_seg = None
+            lw.mlp._loss_out = loss
+            ctx.dw = ctx.db = None
+            return loss
+        if lw is not None:
+            lw.w_seg = lw.b_seg = None
         dw = gw if gw is not None else torch.empty((1, K), dtype=torch.float32, device=dev)
         db = gb if gb is not None else torch.empty(1, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ws = torch.empty(lib.hctr_logit_head_workspace_bytes(K) // 4, dtype=torch.float32, device=dev)
-        label = label.contiguous()
         check(lib.hctr_logit_head(B, K, ptr(x), ptr(w16), ptr(b16), ptr(label),
                                   float(grad_scale), ptr(dx), ptr(dw), ptr(db), ptr(loss), ptr(ws),
                                   _DT16[x.dtype], stream_ptr()))
-        ctx.flat = gw is not None
-        ctx.dx = dx
         ctx.dw, ctx.db = (None, None) if ctx.flat else (dw, db)
         return loss
 
@@ -185,7 +284,7 @@ class _LogitHeadFn(torch.autograd.Function):
     def backward(ctx, _grad_loss):
         dx, dw, db = ctx.dx, ctx.dw, ctx.db
         ctx.dx = ctx.dw = ctx.db = None
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 class FusedMLP(torch.nn.Module):
@@ -212,11 +311,16 @@ class FusedMLP(torch.nn.Module):
         self.flat_w = self.flat_g = self.flat_w16 = None
         self._gw: List[torch.Tensor] = []
         self._gb: List[torch.Tensor] = []
+        self._lw: List[_LayerWS] = []
+        self._finisher = None  # a DenseGradFinish: backward leaves partial sums for its launch
+        self._loss_out = None
 
     def flatten(self):
         """Move masters, gradients and 16-bit copies into three flat buffers (parameters become
         views).  Afterwards backward writes gradients straight into `flat_g`, `sgd_step` is one
-        kernel (update + shadow refresh), and a data-parallel all-reduce runs on `flat_g` as is."""
+        kernel (update + shadow refresh), and a data-parallel all-reduce runs on `flat_g` as is.
+        The backward's workspaces (split-K partial products, bias tile partials) are allocated
+        here, once per layer."""
         dev = self.weights[0].device
         sizes = [p.numel() for p in list(self.weights) + list(self.biases)]
         offs, tot = [], 0
@@ -239,6 +343,15 @@ class FusedMLP(torch.nn.Module):
         gviews = [self.flat_g[o:o + n].view_as(p) for p, o, n in zip(params, offs, sizes)]
         self._gw, self._gb = gviews[:nl], gviews[nl:]
         self.flat_w16.copy_(self.flat_w)
+        self._offs = (offs[:nl], offs[nl:])
+        # split-K partial products [groups][out][in] of every layer, slices 512-byte aligned
+        need = [self.wgrad_groups * w.numel() if min(w.shape) >= 8 else 0 for w in self.weights]
+        starts, at = [], 0
+        for n in need:
+            starts.append(at)
+            at += (n + 255) // 256 * 256
+        part = torch.empty(max(at, 1), dtype=self.dtype, device=dev)
+        self._lw = [_LayerWS(self, i, part[starts[i]:starts[i] + need[i]]) for i in range(nl)]
         return self
 
     def sgd_step(self, lr: float, grad_scale: float = 1.0):
@@ -270,13 +383,14 @@ class FusedMLP(torch.nn.Module):
     def _layer(self, i, x):
         gw = self._gw[i] if self._gw else None
         gb = self._gb[i] if self._gb else None
+        lw = self._lw[i] if self._lw else None
         if i == 0 and self._skinny_first(x):
             return _SkinnyFirstFn.apply(x, self.weights[0], self.biases[0], self._w16[0],
-                                        self._b16[0], gw, gb)
+                                        self._b16[0], gw, gb, lw)
         if x.dtype != self.dtype:
             x = x.to(self.dtype)
         return _LinearFn.apply(x, self.weights[i], self.biases[i], self._w16[i], self._b16[i],
-                               self.relu[i], self.wgrad_groups, gw, gb)
+                               self.relu[i], self.wgrad_groups, gw, gb, lw)
 
     def can_fuse_bce_head(self) -> bool:
         k = self.dims[-2]
@@ -297,7 +411,8 @@ class FusedMLP(torch.nn.Module):
             x = x.to(self.dtype)
         return _LogitHeadFn.apply(x, self.weights[-1], self.biases[-1], self._w16[-1], self._b16[-1],
                                   label, grad_scale, self._gw[-1] if self._gw else None,
-                                  self._gb[-1] if self._gb else None)
+                                  self._gb[-1] if self._gb else None,
+                                  self._lw[-1] if self._lw else None)
 
     def forward(self, x):
         if not self._w16:
@@ -305,3 +420,81 @@ class FusedMLP(torch.nn.Module):
         for i in range(len(self.weights)):
             x = self._layer(i, x)
         return x
+
+
+class DenseGradFinish:
+    """The gradient finish of a set of flattened FusedMLPs as ONE launch per step
+    (hctr_dense_grad_finish).  While a module belongs to one, its backward leaves what its kernels
+    produce -- split-K partial products, bias tile partials, the block partials of the logit head
+    and of the skinny first layer -- where they are; `finish()` adds every one of them in the
+    order of the kernel that used to, into `flat_g` (sgd = False: before an all-reduce) or through
+    w -= lr * grad_scale * g into the masters and the 16-bit copies (sgd = True; `flat_g` is not
+    written).  The loss of a fused BCE head is written by the same launch.
+
+    The segment table lives on the device and is rebuilt only when the backward left something
+    else than last time (another batch size, a reallocated workspace)."""
+
+    _FIELDS = 16  # int64 per hctr_dense_seg
+
+    def __init__(self, mlps: Sequence["FusedMLP"]):
+        self.mlps = list(mlps)
+        for m in self.mlps:
+            assert m.flat_w is not None, "DenseGradFinish: flatten() the module first"
+            m._finisher = self
+        self._sig = None
+        self._table = None
+        self._nseg = self._nblocks = 0
+
+    def release(self):
+        for m in self.mlps:
+            m._finisher = None
+
+    def _segments(self):
+        segs = []
+        for m in self.mlps:
+            base = (m.flat_g.data_ptr(), m.flat_w.data_ptr(), m.flat_w16.data_ptr(),
+                    int(m.dtype == torch.bfloat16))
+            offw, offb = m._offs
+            for i, lw in enumerate(m._lw):
+                nw, nb = m.weights[i].numel(), m.biases[i].numel()
+                ws, bs = lw.w_seg, lw.b_seg
+                if ws is None:
+                    segs.append((_SEG_DIRECT, 0, 0, (nw + 3) // 4 * 4, 0, offw[i], 0, 0) + base)
+                elif ws[0] == _SEG_SUM:
+                    segs.append((_SEG_SUM, ws[1].data_ptr(), ws[2], nw, 0, offw[i], 0,
+                                 int(ws[1].dtype == torch.bfloat16)) + base)
+                elif ws[0] == _SEG_HEAD:   # n = K, k = batch; db at dst2
+                    segs.append((_SEG_HEAD, ws[1].data_ptr(), ws[2], nw, ws[3], offw[i], offb[i],
+                                 0) + base)
+                else:                      # _SEG_SKINNY: n = N, k = K; db at dst2
+                    segs.append((_SEG_SKINNY, ws[1].data_ptr(), ws[2], nb, ws[3], offw[i], offb[i],
+                                 0) + base)
+                if ws is not None and ws[0] in (_SEG_HEAD, _SEG_SKINNY):
+                    continue  # (the bias gradient rides in the same segment)
+                if bs is None:
+                    segs.append((_SEG_DIRECT, 0, 0, (nb + 3) // 4 * 4, 0, offb[i], 0, 0) + base)
+                else:
+                    segs.append((_SEG_COLSUM, bs[1].data_ptr(), bs[2], nb, 0, offb[i], 0, 0) + base)
+        return tuple(segs)
+
+    def _build(self, segs):
+        import numpy as np
+        t = np.zeros((len(segs), self._FIELDS), dtype=np.int64)
+        block0 = 0
+        for r, (kind, src, count, n, k, dst, dst2, src_bf, g, w, w16, bf) in enumerate(segs):
+            t[r, :13] = (kind, src, count, n, k, block0, g, w, w16, dst, dst2, bf, src_bf)
+            block0 += _count(lib.hctr_dense_seg_blocks(kind, n))
+        self._table = torch.from_numpy(t).to(self.mlps[0].flat_w.device)
+        self._nseg, self._nblocks = len(segs), block0
+
+    def finish(self, sgd: bool, lr: float = 0.0, grad_scale: float = 1.0):
+        segs = self._segments()
+        if segs != self._sig:
+            self._build(segs)
+            self._sig = segs
+        loss = None
+        for m in self.mlps:
+            if m._loss_out is not None:
+                loss, m._loss_out = m._loss_out, None
+        check(lib.hctr_dense_grad_finish(ptr(self._table), self._nseg, self._nblocks, int(sgd),
+                                         float(lr), float(grad_scale), ptr(loss), stream_ptr()))

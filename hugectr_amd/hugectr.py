@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .dense import FusedMLP, bce_with_logits
+from .dense import DenseGradFinish, FusedMLP, bce_with_logits
 from .embedding import OptParams, SparseEmbeddingHash, backward_reorder, forward_reorder
 from .embedding_collection import (DataParallelCollection, EmbeddingCollection,  # noqa: F401
                                    EmbeddingCollectionConfig, EmbeddingTableConfig)
@@ -729,9 +729,11 @@ class Model:
         """what the training step may fuse and overlap, decided once from the graph:
 
         * dense SGD on flat buffers: when every trainable dense tensor lives in a 16-bit FusedMLP
-          and the optimizer is SGD (the reference's DLRM configurations), backward writes the
-          gradients into one flat buffer per MLP, the data-parallel all-reduce runs on it as is
-          and the step + refresh of the 16-bit copy is one kernel (`hctr_sgd_shadow`);
+          and the optimizer is SGD (the reference's DLRM configurations), the backward's
+          kernels leave their partial sums and ONE launch per step (`hctr_dense_grad_finish`,
+          `DenseGradFinish`) finishes every gradient of every MLP: on one GPU straight through the
+          SGD step and the refresh of the 16-bit copies; on N > 1 into one flat gradient buffer
+          per MLP, on which the data-parallel all-reduce runs as is, then `hctr_sgd_shadow`;
         * logit head: an MLP whose last layer (K -> 1, no activation) feeds only the
           BinaryCrossEntropyLoss computes that layer, the loss and both backward products in one
           pass (`hctr_logit_head`);
@@ -764,6 +766,8 @@ class Model:
                 m.flatten()
             self._flat_mlps = mlps
             self._dense_opt = None
+            # every partial sum the backward's kernels leave is finished by one launch per step
+            self._dense_finish = DenseGradFinish(mlps)
         # -- logit head -----------------------------------------------------------------------------
         self._head_layer = None
         if fused_ok and self._loss_layer is not None and s.use_mixed_precision:
@@ -1629,7 +1633,7 @@ class Model:
             loss = torch.nn.functional.binary_cross_entropy_with_logits(logit, label)
             return loss, torch.sigmoid(logit)
         elif loss is not None:      # logit layer + loss + their backward already done in one pass
-            loss.backward()
+            loss.backward(self._unit_grad(loss))
         elif logit.is_cuda and label.shape == logit.shape:
             # fused BCE forward + logit gradient (two launches instead of ~20)
             lg = tensors[self._loss_layer.bottom_names[0]]
@@ -1672,7 +1676,7 @@ class Model:
             loss, _ = self._multi_task_loss(tensors)
             (loss * self.solver.scaler).backward()
         elif loss is not None:
-            loss.backward()
+            loss.backward(self._unit_grad(loss))
         else:
             lg = tensors[self._loss_layer.bottom_names[0]]
             loss, dlogit = bce_with_logits(lg, G["label"], gscale)
@@ -1763,9 +1767,18 @@ class Model:
         if self.world == 1 or getattr(self, "_dense_frozen", False) or not self._intra or \
                 dist.get_backend() == "gloo":
             return None
+        if self._flat_mlps:
+            self._dense_finish.finish(sgd=False)  # the partial sums -> flat_g
         ts = [m.flat_g for m in self._flat_mlps] if self._flat_mlps else \
             [q.grad for q in self._dense_params if q.grad is not None]
         return [dist.all_reduce(t, async_op=True) for t in ts]
+
+    def _unit_grad(self, loss):
+        """the upstream gradient of `loss.backward()`, made once instead of filled every step"""
+        g = getattr(self, "_unit_grad_t", None)
+        if g is None or g.device != loss.device or g.dtype != loss.dtype or g.shape != loss.shape:
+            g = self._unit_grad_t = torch.ones_like(loss)
+        return g
 
     def _dense_step(self, skip: bool = False, reduced=None):
         frozen = getattr(self, "_dense_frozen", False) or skip
@@ -1773,10 +1786,15 @@ class Model:
             for w in reduced:
                 w.wait()
         if self._flat_mlps:
-            if frozen:
+            # one GPU: the finish launch takes the partial sums through the SGD step; N > 1 (or no
+            # step): it leaves the gradients in flat_g, the all-reduce and hctr_sgd_shadow follow
+            one = self.world == 1 and not frozen
+            if reduced is None:
+                self._dense_finish.finish(one, self._lr, 1.0 / self.solver.scaler)
+            if frozen or one:
                 return
             for m in self._flat_mlps:  # gradients are shares of the global-batch mean: plain sum
-                if self.world > 1 and reduced is None:
+                if reduced is None:
                     _all_reduce(m.flat_g)
                 m.sgd_step(self._lr, 1.0 / self.solver.scaler)
             return

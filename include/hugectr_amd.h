@@ -757,6 +757,51 @@ size_t hctr_skinny_fc_bwd_workspace_bytes(int n);
 int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* dy, const void* y,
                        float* dw, float* db, float* workspace, int dtype, hctr_stream_t stream);
 
+/* The first kernel only of hctr_relu_bwd_bias / hctr_logit_head / hctr_skinny_fc_bwd: the partial
+ * sums stay in `workspace` (same size and layout as the full entry's) for hctr_dense_grad_finish.
+ * hctr_logit_head_blocks / hctr_skinny_fc_bwd_blocks: how many block partials the launch leaves
+ * (hctr_relu_bwd_bias leaves workspace_bytes / (n * 4) tiles). */
+int hctr_relu_bwd_bias_partials(size_t rows, int n, const void* dy, const void* y, void* dz,
+                                float* workspace, int dtype, hctr_stream_t stream);
+int hctr_logit_head_blocks(size_t batch, int k);
+int hctr_logit_head_partials(size_t batch, int k, const void* x, const void* w, const void* bias,
+                             const float* label, float grad_scale, void* dx, float* workspace,
+                             int dtype, hctr_stream_t stream);
+int hctr_skinny_fc_bwd_blocks(size_t batch, int k, int n, const void* dy, const void* y);
+int hctr_skinny_fc_bwd_partials(size_t batch, int k, int n, const float* x, const void* dy,
+                                const void* y, float* workspace, int dtype, hctr_stream_t stream);
+
+/* Gradient finish of the dense tower: one launch takes every partial sum of a step's backward to
+ * its place in the flat fp32 gradient buffer (sgd = 0), or through the SGD step
+ * w -= lr * grad_scale * g into the fp32 masters and their 16-bit copy (sgd = 1; g is not written
+ * then).  Each segment adds in the order of the entry it stands in for, term for term:
+ *   SUM_GROUPS  hctr_sum_groups: src 16-bit [count groups][n], n % 8 == 0 -> dst
+ *   COLSUM      the db of hctr_relu_bwd_bias: src fp32 [count tiles][n], n % 8 == 0 -> dst
+ *   LOGIT_HEAD  hctr_logit_head: src [count blocks][n + 2], n = K -> dw at dst, db at dst2,
+ *               *loss = sum / k (k = batch)
+ *   SKINNY      hctr_skinny_fc_bwd: src [count blocks][n][17], n = N, k = K -> dw at dst, db at dst2
+ *   DIRECT      n elements (n % 4 == 0) at dst of g hold the gradient already (sgd = 1: stepped)
+ * g / w / w16 are the flat buffers' device addresses, dst / dst2 element offsets into them (dst a
+ * multiple of 4); block0 = the sum of hctr_dense_seg_blocks over the segments in front.  The
+ * table lives in device memory. */
+enum {
+  HCTR_DENSE_SEG_SUM_GROUPS = 0,
+  HCTR_DENSE_SEG_COLSUM = 1,
+  HCTR_DENSE_SEG_LOGIT_HEAD = 2,
+  HCTR_DENSE_SEG_SKINNY = 3,
+  HCTR_DENSE_SEG_DIRECT = 4
+};
+typedef struct {
+  int64_t kind, src, count, n, k, block0;
+  int64_t g, w, w16, dst, dst2;
+  int64_t bf16;     /* 16-bit copy: 1 bf16, 0 fp16 */
+  int64_t src_bf16; /* SUM_GROUPS: type of the partial products */
+  int64_t reserved[3];
+} hctr_dense_seg;
+int hctr_dense_seg_blocks(int kind, size_t n);
+int hctr_dense_grad_finish(const hctr_dense_seg* segs, int nseg, size_t nblocks, int sgd, float lr,
+                           float grad_scale, float* loss, hctr_stream_t stream);
+
 /* The GEMMs of MultiCrossLayer v2 with the elementwise work the reference fuses into its GEMM
  * epilogues (MultiCrossForwardFunctorv2 / MultiCrossBackwardFunctorv2,
  * R/HugeCTR/src/layers/multi_cross_layer.cu:582-700, 732-812; fused_mul_fma3 :391-424), as this
