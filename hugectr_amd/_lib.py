@@ -308,9 +308,17 @@ _SIGNATURES = {
     "hctr_metric_auc": (c_int, [_P, c_size_t, _P, _P, c_size_t, _P, _P]),
     "hctr_metric_ndcg_temp_bytes": (c_size_t, [c_size_t]),
     "hctr_metric_ndcg": (c_int, [_P, c_size_t, _P, _P, c_size_t, _P, _P]),
+    "hctr_raw_decode_tile": (c_size_t, [c_size_t]),
+    "hctr_raw_decode": (c_int, [_P, c_size_t, c_size_t, _P, c_int, _P, _P]),
 }
 METRIC_MAX_CLASSES = 256
 METRIC_COUNTER_WORDS = 264
+# hctr_raw_decode: segment kinds, launch bound, and hctr_raw_segment as a numpy record
+RAW_BITS, RAW_I2F, RAW_LOG1P, RAW_KEY_I64, RAW_KEY_I32, RAW_RAWKEY_I64 = range(6)
+RAW_DECODE_MAX_BLOCKS = 1024
+RAW_DECODE_MAX_SEGMENTS = 4096
+RAW_SEGMENT_FIELDS = [("col0", "<u4"), ("ncols", "<u4"), ("kind", "<u4"), ("reserved", "<u4"),
+                      ("sample0", "<u8"), ("sample1", "<u8"), ("dst_offset", "<u8")]
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 

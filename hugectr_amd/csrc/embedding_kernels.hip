@@ -867,3 +867,6 @@ int hctr_backward_reorder(size_t batch_per_gpu, int slot_num, int vec_size, int 
 
 // the dense lookups' kernels (hctr_dist_select, hctr_indexed_row_copy) share this unit
 #include "dense_lookup.hip"
+
+// the Raw reader's batch split (hctr_raw_decode) shares this unit too
+#include "raw_decode.hip"

@@ -18,9 +18,14 @@ R/HugeCTR/src/data_readers/data_collector.cu:86-113) and its own slice of dense/
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
+import queue
 import struct
+import sys
+import threading
+import time
 from dataclasses import dataclass, field
 from typing import Sequence
 
@@ -363,9 +368,113 @@ def write_raw(path, label, dense, cats, float_label_dense=True):
     rec.astype("<u4").tofile(path)
 
 
+def _up256(n: int) -> int:
+    return (n + 255) & ~255
+
+
+def raw_decode_plan(label_dim, dense_dim, params, ebc_groups, slot_offsets, batch, rank, world,
+                    float_label, float_dense, i64_key):
+    """What one hctr_raw_decode launch writes for one global batch (include/hugectr_amd.h), worked
+    out once per reader.  params: [(top_name, [hotness per slot])] in record order; ebc_groups:
+    per collection the top_names of its lookups' inputs; slot_offsets: one per slot.
+    -> {"width", "segments" (hctr_raw_segment records), "addend" (int64 per column),
+        "arena_bytes", "label" / "dense": (byte offset, shape), "sparse": {name: (offset, n)},
+        "ebc": [(offset, n)]}; every output starts on a 256-byte boundary of the arena."""
+    from . import _lib
+    L, Dn, B = int(label_dim), int(dense_dim), int(batch)
+    bpg = B // world
+    width = L + Dn + sum(sum(h) for _, h in params)
+    segs, addend, top = [], np.zeros(width, np.int64), [0]
+
+    def take(nbytes):
+        off = top[0]
+        top[0] = _up256(off + nbytes)
+        return off
+
+    def seg(col0, ncols, kind, s0, s1, off):
+        if ncols > 0 and s1 > s0:
+            segs.append((col0, ncols, kind, 0, s0, s1, off))
+
+    plan = {"width": width, "sparse": {}, "ebc": []}
+    plan["label"] = (take(bpg * L * 4), (bpg, L))
+    seg(0, L, _lib.RAW_BITS if float_label else _lib.RAW_I2F, rank * bpg, (rank + 1) * bpg,
+        plan["label"][0])
+    plan["dense"] = (take(bpg * Dn * 4), (bpg, Dn))
+    seg(L, Dn, _lib.RAW_BITS if float_dense else _lib.RAW_LOG1P, rank * bpg, (rank + 1) * bpg,
+        plan["dense"][0])
+    ksz, kind = (8, _lib.RAW_KEY_I64) if i64_key else (4, _lib.RAW_KEY_I32)
+    col, s0, col_of = L + Dn, 0, {}
+    for name, hot in params:
+        w = sum(hot)
+        addend[col:col + w] = np.repeat(np.asarray(slot_offsets[s0:s0 + len(hot)], np.int64), hot)
+        off = take(B * w * ksz)
+        seg(col, w, kind, 0, B, off)
+        plan["sparse"][name] = (off, B * w)
+        col_of[name] = (col, w)
+        col += w
+        s0 += len(hot)
+    for names in ebc_groups:
+        n = sum(col_of[nm][1] for nm in names) * B
+        off = take(n * 8)
+        plan["ebc"].append((off, n))
+        for nm in names:  # bucket = lookup * batch + sample: one segment per lookup, back to back
+            c0, w = col_of[nm]
+            seg(c0, w, _lib.RAW_RAWKEY_I64, 0, B, off)
+            off += B * w * 8
+    plan["arena_bytes"] = max(top[0], 256)
+    plan["segments"] = np.array(segs, dtype=np.dtype(_lib.RAW_SEGMENT_FIELDS))
+    plan["addend"] = addend
+    if not 1 <= len(segs) <= _lib.RAW_DECODE_MAX_SEGMENTS:
+        raise RuntimeError(f"raw reader: {len(segs)} output segments (1..4096 supported)")
+    esz = {_lib.RAW_KEY_I64: 8, _lib.RAW_RAWKEY_I64: 8}
+    for g in plan["segments"]:  # every destination range lies inside the arena
+        end = int(g["dst_offset"]) + int(g["sample1"] - g["sample0"]) * int(g["ncols"]) * \
+            esz.get(int(g["kind"]), 4)
+        assert end <= plan["arena_bytes"] and int(g["col0"]) + int(g["ncols"]) <= width
+    return plan
+
+
+class _Latch:
+    """counts the parts of one fill down; the training thread waits for zero"""
+
+    def __init__(self, parts):
+        self.left, self.lock, self.done, self.error = parts, threading.Lock(), threading.Event(), None
+
+    def part_done(self, error=None):
+        with self.lock:
+            self.left -= 1
+            if error is not None:
+                self.error = error
+            if self.left == 0:
+                self.done.set()
+
+
+def _fill_worker(tasks):
+    """worker thread of the asynchronous reader: (event of the slot's last decode, destination rows
+    of the pinned slot, source rows of the memmap, latch).  Holds no reference to the reader."""
+    while True:
+        t = tasks.get()
+        if t is None:
+            return
+        ev, dst, src, latch = t
+        try:
+            if ev is not None:
+                ev.synchronize()  # the slot is free once its last batch has been decoded
+            np.copyto(dst, src)   # (releases the GIL)
+            latch.part_done()
+        except BaseException as e:  # handed to next_batch()
+            latch.part_done(e)
+        del t, ev, dst, src, latch
+
+
 class RawReader:
     """DataReaderType_t.RawAsync: streams batches of a Raw file (np.memmap; the reference uses
-    Linux AIO worker threads -- I/O engines are outside the scope contract, the FORMAT is not)."""
+    Linux AIO worker threads -- I/O engines are outside the scope contract, the FORMAT is not).
+
+    On a CUDA device the reader is asynchronous (DESIGN.md "Raw reader"): worker threads copy the
+    records of the coming batches into a ring of pinned slots, a side stream copies a slot up and
+    splits it with ONE launch (hctr_raw_decode), and next_batch() only makes the consumer's stream
+    wait for that launch.  On a CPU device the batch is decoded on the host, as it always was."""
 
     def __init__(self, path: str, inp, slot_size_array, batch, rank, world, device, num_samples,
                  float_label_dense: bool, repeat: bool, async_param=None, i64_key: bool = True):
@@ -404,7 +513,7 @@ class RawReader:
         # lookups in lookup order; the reader then hands over the collection's global
         # feature-major CSR (raw keys, bucket = lookup * batch + sample) ready-made -- cutting it
         # out of 26 per-input tensors on the GPU costs ~100 tiny launches per step
-        self.ebc_groups = []
+        self._ebc_groups = []
         self._col_of = {}
         col, s0 = inp.label_dim + inp.dense_dim, 0
         for p in inp.sparse_params:
@@ -412,8 +521,216 @@ class RawReader:
             self._col_of[p.top_name] = (col, sum(hot), p.slot_num)
             col += sum(hot)
             s0 += p.slot_num
+        self._batches, self._wait_s = 0, 0.0
+        self._async = torch.device(device).type == "cuda"
+        self._threads, self._closed = [], False
+        if self._async:
+            self._start_async(async_param)
+
+    def _start_async(self, async_param):
+        """ring, side stream and fill workers.  AsyncParam: num_batches_per_thread = slots of the
+        ring (at least 2), num_threads = fill workers (at most 8; never sized by the machine)"""
+        self._ring = max(2, int(getattr(async_param, "num_batches_per_thread", 0) or 0))
+        nthreads = max(1, min(8, int(getattr(async_param, "num_threads", 0) or 2)))
+        self._stream = torch.cuda.Stream(device=self.device)
+        self._slots = []
+        for _ in range(self._ring):
+            pin = torch.empty((self.batch, self.width), dtype=torch.int32, pin_memory=True)
+            # the device raw buffers (and the plan, _build_plan) are used on the side stream only,
+            # so they come from its pool: dropped with a decode in flight, their memory goes
+            # back to the stream that still uses it
+            with torch.cuda.stream(self._stream):
+                dev = torch.empty((self.batch, self.width), dtype=torch.int32, device=self.device)
+            self._slots.append((pin, pin.numpy().view(np.uint32), dev))
+        self._tasks = queue.Queue()
+        self._threads = [threading.Thread(target=_fill_worker, args=(self._tasks,), daemon=True,
+                                          name=f"hctr-raw-fill-{i}") for i in range(nthreads)]
+        for t in self._threads:
+            t.start()
+        self._plan = None       # built by the first next_batch(): ebc_groups is set after
+        self._pending = []      # batches in flight, oldest first
+        self._slot_event = [None] * self._ring
+        self._seq = 0           # batches planned so far (slot = seq % ring)
+
+    @property
+    def ebc_groups(self):
+        return self._ebc_groups
+
+    @ebc_groups.setter
+    def ebc_groups(self, groups):
+        self._ebc_groups = groups
+        if self._async and self._plan is not None:
+            self._rewind()  # (batches in flight were split by the old plan)
+            self._plan = None
+
+    def stats(self):
+        """decode: where a batch is split; ring / threads: slots and fill workers of the
+        asynchronous path (0 on the host path); batches: handed out so far; wait_ms: total time
+        next_batch() waited for a fill worker"""
+        return {"decode": "device" if self._async else "host",
+                "ring": self._ring if self._async else 0, "threads": len(self._threads),
+                "batches": self._batches, "wait_ms": self._wait_s * 1e3}
+
+    def close(self):
+        """stops the fill workers (idempotent; also run when the reader is dropped)"""
+        if getattr(self, "_closed", True):
+            return
+        self._closed = True
+        for _ in self._threads:
+            self._tasks.put(None)
+        if not sys.is_finalizing():  # (at interpreter exit daemon threads no longer run)
+            for t in self._threads:
+                t.join()
+        self._threads = []
+        if self._async:
+            self._pending = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the asynchronous path ---------------------------------------------------------------------
+    def _params(self):
+        """[(top_name, [hotness per slot])] in record order"""
+        params, s0 = [], 0
+        for p in self.inp.sparse_params:
+            params.append((p.top_name, [int(h) for h in self.hot[s0:s0 + p.slot_num]]))
+            s0 += p.slot_num
+        return params
+
+    def decode_plan(self):
+        """raw_decode_plan of this reader's configuration (host arrays only)"""
+        for names in self._ebc_groups:
+            for n in names:
+                assert self._col_of[n][2] == 1, "embedding_collection inputs carry one slot per lookup"
+        return raw_decode_plan(self.inp.label_dim, self.inp.dense_dim, self._params(),
+                               self._ebc_groups, self.slot_offsets, self.batch, self.rank,
+                               self.world, self.float_label, self.float_dense,
+                               self.key_dtype == torch.int64)
+
+    def _build_plan(self):
+        params, pl = self._params(), self.decode_plan()
+        blob = np.concatenate([pl["segments"].view(np.uint8).reshape(-1),
+                               pl["addend"].view(np.uint8)])
+        with torch.cuda.stream(self._stream):  # (read by the decode launches of that stream)
+            pl["device"] = torch.from_numpy(blob).to(self.device)
+        # row offsets / bucket ranges follow from the static hotness alone: built once with the
+        # host path's arithmetic and handed out with every batch (nothing downstream writes them)
+        B = self.batch
+        pl["ro"] = {}
+        for name, hot in params:
+            ro = np.concatenate([[0], np.cumsum(np.tile(hot, B))]).astype(np.int64)
+            pl["ro"][name] = torch.from_numpy(ro).to(self.device, self.key_dtype)
+        pl["gbr"] = []
+        for names in self._ebc_groups:
+            lens = [np.full(B, self._col_of[n][1], np.int64) for n in names]
+            gbr = np.zeros(len(names) * B + 1, np.int64)
+            np.cumsum(np.concatenate(lens), out=gbr[1:])
+            pl["gbr"].append(torch.from_numpy(gbr).to(self.device))
+        self._plan = pl
+
+    def _plan_next(self):
+        """file position of the next batch, as the host path walks the file; None at its end"""
+        B = self.batch
+        if self._pos + B > self.n:  # incomplete tail dropped, as the reference does
+            if not self.repeat:
+                return None
+            self._pos = 0
+        pos = self._pos
+        self._pos += B
+        return pos
+
+    def _submit_fill(self):
+        """plans the next batch and hands its records to the workers, each a contiguous range of
+        samples; the slot's last decode must be through before a worker writes into it"""
+        pos = self._plan_next()
+        if pos is None:
+            return
+        slot = self._seq % self._ring
+        assert all(j["slot"] != slot or j["event"] is not None for j in self._pending)
+        self._seq += 1
+        B, T = self.batch, len(self._threads)
+        cuts = [B * i // T for i in range(T + 1)]
+        parts = [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+        latch = _Latch(len(parts))
+        dst = self._slots[slot][1]
+        for a, b in parts:
+            self._tasks.put((self._slot_event[slot], dst[a:b], self.data[pos + a:pos + b], latch))
+        self._pending.append({"pos": pos, "slot": slot, "latch": latch, "event": None})
+
+    def _issue(self, job):
+        """side stream: pinned slot -> device, one decode launch into a fresh arena, an event"""
+        from . import _lib
+        t0 = time.perf_counter()
+        job["latch"].done.wait()
+        self._wait_s += time.perf_counter() - t0
+        if job["latch"].error is not None:
+            raise job["latch"].error
+        pin, _, dev = self._slots[job["slot"]]
+        pl = self._plan
+        with torch.cuda.stream(self._stream):
+            dev.copy_(pin, non_blocking=True)
+            arena = torch.empty(pl["arena_bytes"], dtype=torch.uint8, device=self.device)
+            _lib.check(_lib.lib.hctr_raw_decode(
+                _lib.ptr(dev), self.batch, self.width, _lib.ptr(pl["device"]), len(pl["segments"]),
+                _lib.ptr(arena), ctypes.c_void_p(self._stream.cuda_stream)))
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+        job["arena"], job["event"] = arena, ev
+        self._slot_event[job["slot"]] = ev
+
+    def _rewind(self):
+        """forgets the batches in flight: the next one handed out is read again"""
+        for job in self._pending:
+            job["latch"].done.wait()
+        if self._pending:
+            self._pos = self._pending[0]["pos"]
+        self._pending = []
+
+    def _next_async(self):
+        if self._closed:
+            raise RuntimeError("RawReader: next_batch() after close()")
+        if self._plan is None:
+            self._build_plan()
+        while len(self._pending) < self._ring:  # (first call, or after a rewind)
+            n = len(self._pending)
+            self._submit_fill()
+            if len(self._pending) == n:
+                break
+        if not self._pending:
+            return None
+        # this batch and the next one are on the side stream before this one is handed over
+        for job in self._pending[:2]:
+            if job["event"] is None:
+                self._issue(job)
+                self._submit_fill()  # the slot's next batch: its workers wait for this decode
+        job = self._pending.pop(0)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(job["event"])
+        arena, pl = job["arena"], self._plan
+        arena.record_stream(cur)  # allocated on the side stream, consumed on this one
+
+        def cut(off, n, dtype, esz):
+            return arena[off:off + n * esz].view(dtype)
+
+        (lo, lshape), (do, dshape) = pl["label"], pl["dense"]
+        out = {"label": cut(lo, lshape[0] * lshape[1], torch.float32, 4).view(*lshape),
+               "dense": cut(do, dshape[0] * dshape[1], torch.float32, 4).view(*dshape),
+               "sparse": {}}
+        ksz = 8 if self.key_dtype == torch.int64 else 4
+        for name, (off, n) in pl["sparse"].items():
+            out["sparse"][name] = (pl["ro"][name], cut(off, n, self.key_dtype, ksz))
+        if self._ebc_groups:
+            out["ebc"] = [(cut(off, n, torch.int64, 8), pl["gbr"][g])
+                          for g, (off, n) in enumerate(pl["ebc"])]
+        self._batches += 1
+        return out
 
     def next_batch(self):
+        if self._async:
+            return self._next_async()
         B = self.batch
         if self._pos + B > self.n:  # incomplete tail dropped, as the reference does
             if not self.repeat:
@@ -456,6 +773,7 @@ class RawReader:
                 np.cumsum(np.concatenate(lens), out=gbr[1:])
                 out["ebc"].append((torch.from_numpy(np.concatenate(ks)).to(self.device),
                                    torch.from_numpy(gbr).to(self.device)))
+        self._batches += 1
         return out
 
 

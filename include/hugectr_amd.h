@@ -1265,6 +1265,48 @@ size_t hctr_metric_ndcg_temp_bytes(size_t n);
 int hctr_metric_ndcg(void* temp, size_t temp_bytes, const uint32_t* keys, const float* labels,
                      size_t n, double* out, hctr_stream_t stream);
 
+/* ---- Raw reader: one launch splits one batch of records (csrc/raw_decode.hip) ----------------------
+ * The reference splits the staged records of its asynchronous reader with split_feat_major_kernel
+ * (R/HugeCTR/src/data_readers/multi_hot/split_batch.cu:42-84, one thread per word, integer dense
+ * features through logf(x + 1.f), :35).  Here a workgroup stages a tile of samples x columns in LDS
+ * with 16-byte loads and writes every output range of the tile coalesced.
+ *
+ * raw       device, 16-byte aligned: the GLOBAL batch as uint32 [batch][width] records
+ *           label[L] dense[Dn] keys[sum of hotness]
+ * plan      device, 8-byte aligned, built once per reader: n_segments hctr_raw_segment entries
+ *           followed by int64 addend[width] (the slot offset of every key column, 0 elsewhere)
+ * out_base  device, 8-byte aligned: the arena every segment's dst_offset counts from
+ *
+ * A segment copies the columns [col0, col0 + ncols) of the samples [sample0, sample1) to
+ * dst[(sample - sample0) * ncols + (col - col0)] at out_base + dst_offset: sample-major for a legacy
+ * sparse param (all its slots), the rank's slice for label and dense, and one segment per lookup of
+ * a collection group, laid one behind the other (bucket = lookup * batch + sample).  Every position
+ * is written once, with plain stores.  Ranges outside the batch / the record are clipped; the
+ * caller guarantees that every dst range lies inside its arena.
+ *
+ * hctr_raw_decode_tile(width): samples per workgroup tile (what the tests place batches around);
+ * at most HCTR_RAW_DECODE_MAX_BLOCKS workgroups are launched, further tiles are grid-strided. */
+enum {
+  HCTR_RAW_BITS = 0,     /* 4-byte word copied (float label / float dense) */
+  HCTR_RAW_I2F = 1,      /* (float)(int32) */
+  HCTR_RAW_LOG1P = 2,    /* log((float)(int32) + 1.f): fp32 sum, fp64 logarithm rounded to fp32 */
+  HCTR_RAW_KEY_I64 = 3,  /* int64: zero-extended word + addend[col] (64-bit add) */
+  HCTR_RAW_KEY_I32 = 4,  /* int32: the low 32 bits of that sum */
+  HCTR_RAW_RAWKEY_I64 = 5 /* int64: zero-extended word, no addend (collection groups) */
+};
+typedef struct {
+  uint32_t col0, ncols;
+  uint32_t kind; /* HCTR_RAW_* */
+  uint32_t reserved;
+  uint64_t sample0, sample1;
+  uint64_t dst_offset; /* bytes from out_base; a multiple of the destination's element size */
+} hctr_raw_segment;
+#define HCTR_RAW_DECODE_MAX_BLOCKS 1024
+#define HCTR_RAW_DECODE_MAX_SEGMENTS 4096
+size_t hctr_raw_decode_tile(size_t width);
+int hctr_raw_decode(const uint32_t* raw, size_t batch, size_t width, const void* plan,
+                    int n_segments, void* out_base, hctr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
