@@ -36,10 +36,13 @@ import os
 import numpy as np
 import pytest
 
+# the device-buffer plumbing is shared with the other matrix files
+from util import DevIn as _In, DevOut as _Out, assert_bits as _assert_bits
+from util import lib_code as _code, torch_dtype as _torch_dtype
+
 pytestmark = pytest.mark.gpu
 
 EMU = os.environ.get("HCTR_EMU") == "1"
-GUARD = 64
 U = 2.0 ** -24  # unit roundoff of fp32
 LPR_D = [4, 8, 16, 32, 64, 128, 256]     # the seven vec4 cases of every switch
 MOD4_GENERIC_D = [12, 20, 512]           # D % 4 == 0 outside the switch -> generic
@@ -49,94 +52,6 @@ DTYPES = ["f32", "f16", "bf16"]
 
 def _grid(cases):
     return [] if EMU else cases
-
-
-# ---- plumbing ------------------------------------------------------------------------------------
-def _torch_dtype(dt):
-    import torch
-    return {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dt]
-
-
-def _code(dt):
-    from hugectr_amd import _lib
-    return {"f32": _lib.F32, "f16": _lib.F16, "bf16": _lib.BF16}[dt]
-
-
-class _In:
-    """a device copy of a host array (kept next to it: the call must leave it unchanged);
-    mis: the device data starts that many elements into its allocation"""
-
-    def __init__(self, a, mis=0):
-        import torch
-        self.host = np.array(a)
-        raw = self.host
-        if raw.dtype == np.uint64:
-            raw = raw.view(np.int64)
-        elif raw.dtype == np.uint32:
-            raw = raw.view(np.int32)
-        flat = torch.from_numpy(raw.reshape(-1))
-        base = torch.zeros(flat.numel() + mis, dtype=flat.dtype)
-        base[mis:] = flat
-        self.base = base.to("cuda")
-        self.t = self.base[mis:]
-        self.raw = raw.reshape(-1)
-
-    @property
-    def p(self):
-        from hugectr_amd import _lib
-        return _lib.ptr(self.t)
-
-    def assert_unchanged(self, what):
-        got = self.t.cpu().numpy()
-        assert got.tobytes() == self.raw.tobytes(), f"the call changed its input {what}"
-
-
-class _Out:
-    """rows x D output behind a poison fill, GUARD rows of poison after it; mis as for _In"""
-
-    def __init__(self, rows, D, dt, mis=0, int_bits=False):
-        import torch
-        self.rows, self.D, self.mis, self.int_bits = rows, D, mis, int_bits
-        n = (rows + GUARD) * D
-        if int_bits:  # reorder: raw 16 / 32-bit patterns, poison = all ones (a NaN in every type)
-            tdt = torch.int32 if dt == "f32" else torch.int16
-            self.base = torch.full((n + mis + 8,), -1, dtype=tdt, device="cuda")
-        else:
-            self.base = torch.full((n + mis + 8,), float("nan"), dtype=_torch_dtype(dt),
-                                   device="cuda")
-        self.t = self.base[mis:mis + n]
-
-    @property
-    def p(self):
-        from hugectr_amd import _lib
-        return _lib.ptr(self.t)
-
-    def result(self):
-        """the rows as fp32 (or raw integers); asserts that everything around them is untouched"""
-        b = self.base if self.int_bits else self.base.float()
-        b = b.cpu().numpy()
-        lo, hi = self.mis, self.mis + self.rows * self.D
-        around = np.concatenate([b[:lo], b[hi:]])
-        assert around.size >= GUARD * self.D
-        if self.int_bits:
-            assert (around == -1).all(), "write outside the output rows"
-        else:
-            assert np.isnan(around).all(), "write outside the output rows"
-        return b[lo:hi].reshape(self.rows, self.D)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _assert_bits(got, want, what):
-    g, w = _bits(got), _bits(want)
-    assert g.shape == w.shape
-    if not (g == w).all():
-        bad = np.argwhere(g != w)
-        r, c = bad[0]
-        raise AssertionError(f"{what}: {len(bad)} of {g.size} elements differ, first at row {r} "
-                             f"col {c}: got {got[r, c]!r} want {want[r, c]!r}")
 
 
 # ---- inputs (built once per shape, never written again) ------------------------------------------
