@@ -98,7 +98,8 @@ static inline int env_int(const char* name, int dflt, int field = 0) {
 }
 
 // run-time value -> template argument: f(std::true_type / std::false_type) for a flag,
-// f((T*)nullptr) for the element type of an HCTR_EMB_* dtype
+// f((T*)nullptr) for the element type of an HCTR_EMB_* dtype or the key / offset type of an
+// HCTR_KEY_* key_type
 template <typename F>
 void with_bool(bool v, F&& f) {
   if (v) f(std::true_type{});
@@ -112,6 +113,15 @@ int with_dtype(int dtype, F&& f) {
     case HCTR_EMB_BF16: return f((__hip_bfloat16*)nullptr);
   }
   HCTR_REQUIRE(false, "dtype");
+  return HCTR_OK;  // (not reached)
+}
+template <typename F>
+int with_key_type(int key_type, F&& f) {
+  switch (key_type) {
+    case HCTR_KEY_U32: return f((uint32_t*)nullptr);
+    case HCTR_KEY_I64: return f((long long*)nullptr);
+  }
+  HCTR_REQUIRE(false, "key_type");
   return HCTR_OK;  // (not reached)
 }
 

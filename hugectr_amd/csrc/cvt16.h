@@ -61,6 +61,11 @@ __device__ __forceinline__ void st4_from_f32(T* p, float4 v) {
   T h[4] = {from_f32<T>(v.x), from_f32<T>(v.y), from_f32<T>(v.z), from_f32<T>(v.w)};
   *reinterpret_cast<uint2*>(p) = *reinterpret_cast<const uint2*>(h);
 }
+// (fp32: the four values are 16 bytes, 16-byte aligned)
+template <>
+__device__ __forceinline__ void st4_from_f32<float>(float* p, float4 v) {
+  *reinterpret_cast<float4*>(p) = v;
+}
 
 // ---- raw: kernels that move 16-bit data as unsigned short / packed words ---------------------------
 template <bool BF>

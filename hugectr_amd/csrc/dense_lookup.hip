@@ -1,6 +1,6 @@
 // dense_lookup.hip -- the two kernels behind SOK's dense lookups (sok.all2all_dense_embedding,
 // sok.group_lookup): a stable partition of keys by owner GPU and a batched indexed row copy.
-// Compiled as part of embedding_kernels.hip (it uses that unit's Store4).
+// Compiled as part of embedding_kernels.hip.
 //
 // hctr_dist_select replaces the DistSelect op
 // (R/sparse_operation_kit/kit_src/lookup/impl/select_kernel.cu:22-170, kernels/select.cc:41-70).
@@ -22,6 +22,7 @@
 // its round trip, not by bytes: DESIGN.md section 8, items 3 and 11).
 #include "block_prims.h"
 #include "common.h"
+#include "cvt16.h"
 #include "scan.h"
 
 namespace hctr {
@@ -270,9 +271,9 @@ __device__ __forceinline__ void rc_chunk(const RcTask& T, uint64_t chunk) {
       if (!(put[u] && vok)) continue;
       const float4 y = live[u] ? x[u] : make_float4(0.f, 0.f, 0.f, 0.f);
       if (W == 4)
-        Store4<D>::st(dst + d[u] * dim + e, y);
+        st4_from_f32<D>(dst + d[u] * dim + e, y);
       else
-        Store4<D>::st1(dst + d[u] * dim + e, y.x);
+        st_from_f32<D>(dst + d[u] * dim + e, y.x);
     }
   }
 }

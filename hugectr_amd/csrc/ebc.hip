@@ -476,14 +476,12 @@ int hctr_ebc_keys_to_indices(const void* keys, int key_type, size_t n, int64_t t
   if (n == 0) return HCTR_OK;
   HCTR_REQUIRE(keys && out, "null pointer");
   hipStream_t s = as_stream(stream);
-  if (key_type == HCTR_KEY_U32)
-    hipLaunchKernelGGL(keys_to_indices_kernel<uint32_t>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0,
-                       s, n, (const uint32_t*)keys, (long long)table_start, num_shards, out);
-  else if (key_type == HCTR_KEY_I64)
-    hipLaunchKernelGGL(keys_to_indices_kernel<long long>, dim3(grid_for(n, kBlock)), dim3(kBlock),
-                       0, s, n, (const long long*)keys, (long long)table_start, num_shards, out);
-  else
-    HCTR_REQUIRE(false, "key_type");
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(keys_to_indices_kernel<K>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n,
+                       (const K*)keys, (long long)table_start, num_shards, out);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -546,33 +544,17 @@ int hctr_ebc_route_keys(size_t batch, int world, int num_local_lookups, const in
   const long long* rs = (const long long*)row_start;
   const size_t bpg = batch / world;
   const int grid = grid_for(nb, kBlock);
-  int rc = HCTR_OK;
-  if (key_type == HCTR_KEY_U32) {
-    hipLaunchKernelGGL(ebc_count_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, batch, bpg,
-                       num_local_lookups, d3, rs, (const uint32_t*)keys,
-                       (const uint32_t*)bucket_range, lens);
-    rc = exclusive_scan_to_offsets<long long>(lens, nb, tile_sums, d_total,
-                                              (long long*)out_bucket_range, s);
-    if (rc == HCTR_OK)
-      hipLaunchKernelGGL(ebc_index_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, batch, bpg,
-                         num_local_lookups, d3, rs, (const uint32_t*)keys,
-                         (const uint32_t*)bucket_range, (const long long*)out_bucket_range,
-                         out_indices);
-  } else if (key_type == HCTR_KEY_I64) {
-    hipLaunchKernelGGL(ebc_count_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, batch, bpg,
-                       num_local_lookups, d3, rs, (const long long*)keys,
-                       (const long long*)bucket_range, lens);
-    rc = exclusive_scan_to_offsets<long long>(lens, nb, tile_sums, d_total,
-                                              (long long*)out_bucket_range, s);
-    if (rc == HCTR_OK)
-      hipLaunchKernelGGL(ebc_index_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, batch, bpg,
-                         num_local_lookups, d3, rs, (const long long*)keys,
-                         (const long long*)bucket_range, (const long long*)out_bucket_range,
-                         out_indices);
-  } else {
-    set_error("key_type");
-    rc = HCTR_ERR_INVALID_ARG;
-  }
+  int rc = with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(ebc_count_kernel<K>, dim3(grid), dim3(kBlock), 0, s, batch, bpg,
+                       num_local_lookups, d3, rs, (const K*)keys, (const K*)bucket_range, lens);
+    HCTR_TRY(exclusive_scan_to_offsets<long long>(lens, nb, tile_sums, d_total,
+                                                  (long long*)out_bucket_range, s));
+    hipLaunchKernelGGL(ebc_index_kernel<K>, dim3(grid), dim3(kBlock), 0, s, batch, bpg,
+                       num_local_lookups, d3, rs, (const K*)keys, (const K*)bucket_range,
+                       (const long long*)out_bucket_range, out_indices);
+    return HCTR_OK;
+  });
   if (rc == HCTR_OK && hipGetLastError() != hipSuccess) {
     set_error("ebc route launch failed");
     rc = HCTR_ERR_HIP;
@@ -598,20 +580,14 @@ int hctr_ebc_route_whole(size_t batch, int num_lookups, const int64_t* row_start
   HCTR_REQUIRE(row_start && bucket_range && out_bucket_range && out_indices, "null pointer");
   const size_t avg = nnz_hint > 0 ? (nnz_hint + nb - 1) / nb : 1;  // wavefronts per bucket chunk
   const dim3 grid(grid_for(nb, kBlock), (unsigned)(avg > 16 ? 16 : avg));
-  if (key_type == HCTR_KEY_U32) {
-    hipLaunchKernelGGL(ebc_route_whole_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, nb, batch,
-                       (const long long*)row_start, (const uint32_t*)keys,
-                       (const uint32_t*)bucket_range, (long long*)out_bucket_range, out_indices,
-                       (unsigned long long*)d_nnz, one_hot);
-  } else if (key_type == HCTR_KEY_I64) {
-    hipLaunchKernelGGL(ebc_route_whole_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, nb, batch,
-                       (const long long*)row_start, (const long long*)keys,
-                       (const long long*)bucket_range, (long long*)out_bucket_range, out_indices,
-                       (unsigned long long*)d_nnz, one_hot);
-  } else {
-    set_error("key_type");
-    return HCTR_ERR_INVALID_ARG;
-  }
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(ebc_route_whole_kernel<K>, dim3(grid), dim3(kBlock), 0, s, nb, batch,
+                       (const long long*)row_start, (const K*)keys, (const K*)bucket_range,
+                       (long long*)out_bucket_range, out_indices, (unsigned long long*)d_nnz,
+                       one_hot);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -640,14 +616,12 @@ int hctr_ebc_bucket_counts(size_t batch, int world, int rank, int num_lookup,
   if (total == 0) return HCTR_OK;
   HCTR_REQUIRE(bucket_range && counts, "null pointer");
   hipStream_t s = as_stream(stream);
-  if (key_type == HCTR_KEY_U32)
-    hipLaunchKernelGGL(ebc_bucket_count_kernel<uint32_t>, dim3(grid_for(total, kBlock)),
-                       dim3(kBlock), 0, s, batch, bpg, num_lookup, rank,
-                       (const uint32_t*)bucket_range, (long long*)counts);
-  else
-    hipLaunchKernelGGL(ebc_bucket_count_kernel<long long>, dim3(grid_for(total, kBlock)),
-                       dim3(kBlock), 0, s, batch, bpg, num_lookup, rank,
-                       (const long long*)bucket_range, (long long*)counts);
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(ebc_bucket_count_kernel<K>, dim3(grid_for(total, kBlock)), dim3(kBlock), 0,
+                       s, batch, bpg, num_lookup, rank, (const K*)bucket_range, (long long*)counts);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -663,38 +637,25 @@ static int ebc_network(bool fwd, size_t bpg, int num_lookup, int ev, int max_sha
   const size_t esz = dtype == HCTR_EMB_F32 ? 4 : 2;
   const bool vec = ((size_t)ev * esz) % 16 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(out) % 16 == 0;
-#define HCTR_NET(T)                                                                             \
-  if (vec) {                                                                                    \
-    const int row16 = (int)((size_t)ev * sizeof(T) / 16);                                       \
-    const int vgrid = grid_for((size_t)num_lookup * bpg * row16, kBlock, 8192);                 \
-    if (fwd)                                                                                    \
-      hipLaunchKernelGGL((ebc_network_vec_kernel<T, true>), dim3(vgrid), dim3(kBlock), 0, s,    \
-                         bpg, num_lookup, row16, max_shards, src_blocks, combiner,              \
-                         (const long long*)bucket_counts, batch_major, (const uint4*)in,        \
-                         (uint4*)out);                                                          \
-    else                                                                                        \
-      hipLaunchKernelGGL((ebc_network_vec_kernel<T, false>), dim3(vgrid), dim3(kBlock), 0, s,   \
-                         bpg, num_lookup, row16, max_shards, src_blocks, combiner,              \
-                         (const long long*)bucket_counts, batch_major, (const uint4*)in,        \
-                         (uint4*)out);                                                          \
-  } else if (fwd)                                                                               \
-    hipLaunchKernelGGL((ebc_network_kernel<T, true>), dim3(grid), dim3(kBlock), 0, s, bpg,      \
-                       num_lookup, ev, max_shards, src_blocks, combiner,                        \
-                       (const long long*)bucket_counts, batch_major, (const T*)in, (T*)out);    \
-  else                                                                                          \
-    hipLaunchKernelGGL((ebc_network_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s, bpg,     \
-                       num_lookup, ev, max_shards, src_blocks, combiner,                        \
-                       (const long long*)bucket_counts, batch_major, (const T*)in, (T*)out);
-  if (dtype == HCTR_EMB_F32) {
-    HCTR_NET(float)
-  } else if (dtype == HCTR_EMB_F16) {
-    HCTR_NET(__half)
-  } else if (dtype == HCTR_EMB_BF16) {
-    HCTR_NET(__hip_bfloat16)
-  } else {
-    HCTR_REQUIRE(false, "dtype");
-  }
-#undef HCTR_NET
+  HCTR_TRY(with_dtype(dtype, [&](auto* t) -> int {
+    using T = std::remove_pointer_t<decltype(t)>;
+    with_bool(fwd, [&](auto f) {
+      constexpr bool FWD = decltype(f)::value;
+      const long long* counts = (const long long*)bucket_counts;
+      if (vec) {
+        const int row16 = (int)((size_t)ev * sizeof(T) / 16);
+        const int vgrid = grid_for((size_t)num_lookup * bpg * row16, kBlock, 8192);
+        hipLaunchKernelGGL((ebc_network_vec_kernel<T, FWD>), dim3(vgrid), dim3(kBlock), 0, s, bpg,
+                           num_lookup, row16, max_shards, src_blocks, combiner, counts, batch_major,
+                           (const uint4*)in, (uint4*)out);
+      } else {
+        hipLaunchKernelGGL((ebc_network_kernel<T, FWD>), dim3(grid), dim3(kBlock), 0, s, bpg,
+                           num_lookup, ev, max_shards, src_blocks, combiner, counts, batch_major,
+                           (const T*)in, (T*)out);
+      }
+    });
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -708,25 +669,15 @@ int hctr_ebc_scale_average(size_t batch_per_gpu, int num_lookup, int ev_size,
   HCTR_REQUIRE(d_combiner && d_bucket_counts && data, "null pointer");
   hipStream_t s = as_stream(stream);
   const int grid = grid_for(total, kBlock, 8192);
-#define HCTR_SCALE(T)                                                                          \
-  if (forward)                                                                                 \
-    hipLaunchKernelGGL((ebc_scale_average_kernel<T, true>), dim3(grid), dim3(kBlock), 0, s,    \
-                       batch_per_gpu, num_lookup, ev_size, d_combiner,                         \
-                       (const long long*)d_bucket_counts, batch_major, (T*)data);              \
-  else                                                                                         \
-    hipLaunchKernelGGL((ebc_scale_average_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s,   \
-                       batch_per_gpu, num_lookup, ev_size, d_combiner,                         \
-                       (const long long*)d_bucket_counts, batch_major, (T*)data);
-  if (dtype == HCTR_EMB_F32) {
-    HCTR_SCALE(float)
-  } else if (dtype == HCTR_EMB_F16) {
-    HCTR_SCALE(__half)
-  } else if (dtype == HCTR_EMB_BF16) {
-    HCTR_SCALE(__hip_bfloat16)
-  } else {
-    HCTR_REQUIRE(false, "dtype");
-  }
-#undef HCTR_SCALE
+  HCTR_TRY(with_dtype(dtype, [&](auto* t) -> int {
+    using T = std::remove_pointer_t<decltype(t)>;
+    with_bool(forward != 0, [&](auto f) {
+      hipLaunchKernelGGL((ebc_scale_average_kernel<T, decltype(f)::value>), dim3(grid),
+                         dim3(kBlock), 0, s, batch_per_gpu, num_lookup, ev_size, d_combiner,
+                         (const long long*)d_bucket_counts, batch_major, (T*)data);
+    });
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }

@@ -9,52 +9,13 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
-#include <cstdlib>
-
 #include "common.h"
+#include "cvt16.h"
 
 namespace hctr {
 namespace {
 
 constexpr int kBlock = 256;
-
-template <typename OutT>
-struct Store4;
-template <>
-struct Store4<float> {
-  __device__ __forceinline__ static void st(float* p, float4 v) {
-    *reinterpret_cast<float4*>(p) = v;
-  }
-  __device__ __forceinline__ static void st1(float* p, float v) { *p = v; }
-};
-template <>
-struct Store4<__half> {
-  __device__ __forceinline__ static void st(__half* p, float4 v) {
-    __half2 a = __float22half2_rn(make_float2(v.x, v.y));
-    __half2 b = __float22half2_rn(make_float2(v.z, v.w));
-    uint2 u;
-    u.x = *reinterpret_cast<uint32_t*>(&a);
-    u.y = *reinterpret_cast<uint32_t*>(&b);
-    *reinterpret_cast<uint2*>(p) = u;
-  }
-  __device__ __forceinline__ static void st1(__half* p, float v) { *p = __float2half_rn(v); }
-};
-template <>
-struct Store4<__hip_bfloat16> {
-  __device__ __forceinline__ static void st(__hip_bfloat16* p, float4 v) {
-    __hip_bfloat16 a = __float2bfloat16(v.x), b = __float2bfloat16(v.y);
-    __hip_bfloat16 c = __float2bfloat16(v.z), d = __float2bfloat16(v.w);
-    uint2 u;
-    u.x = (uint32_t) * reinterpret_cast<uint16_t*>(&a) |
-          ((uint32_t) * reinterpret_cast<uint16_t*>(&b) << 16);
-    u.y = (uint32_t) * reinterpret_cast<uint16_t*>(&c) |
-          ((uint32_t) * reinterpret_cast<uint16_t*>(&d) << 16);
-    *reinterpret_cast<uint2*>(p) = u;
-  }
-  __device__ __forceinline__ static void st1(__hip_bfloat16* p, float v) {
-    *p = __float2bfloat16(v);
-  }
-};
 
 // Mean of a 16-bit output, even embedding_vec_size (forward_mean_align2_kernel,
 // forward_per_gpu_functor.cu:136-176): the fp32 sum and the scaler are BOTH rounded to the output
@@ -92,7 +53,124 @@ __device__ __forceinline__ float4 ld4(const float* p) {
   return *reinterpret_cast<const float4*>(p);
 }
 
-// LPR lanes per row (D = 4*LPR), BU buckets per group per iteration.
+// The end of a bucket of n keys: the mean's scale, then lane l's four values of output row
+// out_row(u, om).
+template <typename OutT>
+__device__ __forceinline__ void finish_store(OutT* __restrict__ out, size_t u, OutMap om, int D,
+                                             int l, float4 acc, int n, int combiner) {
+  if (combiner == 1 && n > 1) {
+    const float sc = 1.0f / (float)n;
+    acc.x = mean_product<OutT>(acc.x, sc);
+    acc.y = mean_product<OutT>(acc.y, sc);
+    acc.z = mean_product<OutT>(acc.z, sc);
+    acc.w = mean_product<OutT>(acc.w, sc);
+  }
+  st4_from_f32<OutT>(out + out_row(u, om) * (size_t)D + l * 4, acc);
+}
+
+// Where the row of the key at position q comes from; nullptr = the key is absent (it contributes 0
+// and still counts for the mean).  IndexedRows: row value_index[q] of one flat table, absent =
+// kInvalidIndex.  PointerRows: the key carries its row's address (the ILookup::lookup(..., float**
+// embedding_vec) seam, R/HugeCTR/embedding/embedding_table.hpp:22-33, consumed by
+// generic_lookup.cuh:318-416: the rows of a dynamic table live in per-class stores).
+// The members are plain pointers: the kernels take value_index / table / rows as __restrict__
+// parameters and copy them in here.  Register counts of the vec4 kernels move by a few VGPRs
+// against reading the parameters directly (profiles/pool_refactor_resources.txt); occupancy does
+// not, and these paths measured no slower (profiles/pool_refactor_ab.txt).
+struct IndexedRows {
+  const uint64_t* value_index;
+  const float* table;
+  __device__ __forceinline__ const float* row(long long q, int D) const {
+    const uint64_t idx = value_index[q];
+    return idx != kInvalidIndex ? table + idx * (uint64_t)D : nullptr;
+  }
+};
+struct PointerRows {
+  const float* const* rows;
+  __device__ __forceinline__ const float* row(long long q, int) const { return rows[q]; }
+};
+
+// LPR lanes per row (D = 4*LPR), BU buckets per group per iteration: the offsets of all BU buckets,
+// then their first rows, then the tails.
+template <int LPR, int BU, typename Rows, typename OffT, typename OutT>
+__device__ __forceinline__ void pool_vec4_body(size_t buckets, int combiner,
+                                               const OffT* __restrict__ row_offset, Rows src,
+                                               OutT* __restrict__ out, OutMap om) {
+  constexpr int D = LPR * 4;
+  constexpr int GPB = kBlock / LPR;  // groups per block
+  const int g = threadIdx.x / LPR;
+  const int l = threadIdx.x % LPR;
+  const size_t stride = (size_t)gridDim.x * GPB * BU;
+  for (size_t u0 = ((size_t)blockIdx.x * GPB + g) * BU; u0 < buckets; u0 += stride) {
+    long long off[BU];
+    int n[BU];
+    const float* r0[BU];
+    float4 acc[BU];
+#pragma unroll
+    for (int k = 0; k < BU; k++) {
+      const size_t u = u0 + k;
+      if (u < buckets) {
+        off[k] = (long long)row_offset[u];
+        n[k] = (int)((long long)row_offset[u + 1] - off[k]);
+      } else {
+        off[k] = 0;
+        n[k] = 0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < BU; k++) r0[k] = (n[k] > 0) ? src.row(off[k], D) : nullptr;
+#pragma unroll
+    for (int k = 0; k < BU; k++) {
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (r0[k] != nullptr) r = ld4(r0[k] + l * 4);
+      // sum starts at 0.0f and adds in key order, as the reference does
+      acc[k] = make_float4(0.f + r.x, 0.f + r.y, 0.f + r.z, 0.f + r.w);
+    }
+#pragma unroll
+    for (int k = 0; k < BU; k++) {
+      for (int j = 1; j < n[k]; j++) {
+        const float* p = src.row(off[k] + j, D);
+        if (p != nullptr) {
+          const float4 r = ld4(p + l * 4);
+          acc[k].x += r.x;
+          acc[k].y += r.y;
+          acc[k].z += r.z;
+          acc[k].w += r.w;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < BU; k++)
+      if (u0 + k < buckets) finish_store(out, u0 + k, om, D, l, acc[k], n[k], combiner);
+  }
+}
+
+// any embedding_vec_size: one wavefront per bucket, lanes stride over the vector
+template <typename Rows, typename OffT, typename OutT>
+__device__ __forceinline__ void pool_generic_body(size_t buckets, int D, int combiner,
+                                                  const OffT* __restrict__ row_offset, Rows src,
+                                                  OutT* __restrict__ out, OutMap om) {
+  const int lane = threadIdx.x & 63;
+  const size_t wave = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+  const size_t nwaves = ((size_t)gridDim.x * kBlock) >> 6;
+  for (size_t u = wave; u < buckets; u += nwaves) {
+    const long long off = (long long)row_offset[u];
+    const int n = (int)((long long)row_offset[u + 1] - off);
+    const float sc = (combiner == 1 && n > 1) ? 1.0f / (float)n : 1.0f;
+    for (int v = lane; v < D; v += 64) {
+      float sum = 0.0f;
+      for (int j = 0; j < n; j++) {
+        const float* r = src.row(off + j, D);
+        sum += (r != nullptr) ? r[v] : 0.0f;
+      }
+      // even sizes take the reference's align2 rule also here (e.g. D = 6, 10)
+      const float m = (D % 2 == 0) ? mean_product<OutT>(sum, sc) : sum * sc;
+      st_from_f32<OutT>(out + out_row(u, om) * (size_t)D + v, (combiner == 1) ? m : sum);
+    }
+  }
+}
+
+// The indexed vec4 kernel: the one-hot loop, else pool_vec4_body.
 //
 // one_hot (device flag, may be NULL): set by the caller's index stage when EVERY bucket of the batch
 // holds exactly one key (the Criteo / DLRM case).  Then bucket u's only key sits at position u, the
@@ -138,66 +216,13 @@ __global__ void __launch_bounds__(kBlock)
           // sum = 0.0f + row, one key: mean == sum (n = 1)
           const float4 v = make_float4(0.f + (live ? r[k].x : 0.f), 0.f + (live ? r[k].y : 0.f),
                                        0.f + (live ? r[k].z : 0.f), 0.f + (live ? r[k].w : 0.f));
-          Store4<OutT>::st(out + out_row(u0 + k, om) * (size_t)D + l * 4, v);
+          finish_store(out, u0 + k, om, D, l, v, 1, combiner);
         }
       }
     }
     return;
   }
-  for (size_t u0 = ((size_t)blockIdx.x * GPB + g) * BU; u0 < buckets; u0 += stride) {
-    long long off[BU];
-    int n[BU];
-    uint64_t idx0[BU];
-    float4 acc[BU];
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      const size_t u = u0 + k;
-      if (u < buckets) {
-        off[k] = (long long)row_offset[u];
-        n[k] = (int)((long long)row_offset[u + 1] - off[k]);
-      } else {
-        off[k] = 0;
-        n[k] = 0;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < BU; k++) idx0[k] = (n[k] > 0) ? value_index[off[k]] : kInvalidIndex;
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx0[k] != kInvalidIndex) r = ld4(table + idx0[k] * (uint64_t)D + l * 4);
-      // sum starts at 0.0f and adds in key order, as the reference does
-      acc[k] = make_float4(0.f + r.x, 0.f + r.y, 0.f + r.z, 0.f + r.w);
-    }
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      for (int j = 1; j < n[k]; j++) {
-        const uint64_t idx = value_index[off[k] + j];
-        if (idx != kInvalidIndex) {
-          float4 r = ld4(table + idx * (uint64_t)D + l * 4);
-          acc[k].x += r.x;
-          acc[k].y += r.y;
-          acc[k].z += r.z;
-          acc[k].w += r.w;
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      const size_t u = u0 + k;
-      if (u < buckets) {
-        float4 v = acc[k];
-        if (combiner == 1 && n[k] > 1) {
-          const float sc = 1.0f / (float)n[k];
-          v.x = mean_product<OutT>(v.x, sc);
-          v.y = mean_product<OutT>(v.y, sc);
-          v.z = mean_product<OutT>(v.z, sc);
-          v.w = mean_product<OutT>(v.w, sc);
-        }
-        Store4<OutT>::st(out + out_row(u, om) * (size_t)D + l * 4, v);
-      }
-    }
-  }
+  pool_vec4_body<LPR, BU>(buckets, combiner, row_offset, IndexedRows{value_index, table}, out, om);
 }
 
 // Multi-hot variant.  A lane group owns NB consecutive buckets = one contiguous range of keys and
@@ -252,17 +277,7 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
           for (int i = 0; i < NB - 1; i++) b += (p >= e[i]) ? 1 : 0;
           if (b != cur) {
-            if (cur >= 0) {
-              float4 v = acc;
-              if (combiner == 1 && cnt > 1) {
-                const float sc = 1.0f / (float)cnt;
-                v.x = mean_product<OutT>(v.x, sc);
-                v.y = mean_product<OutT>(v.y, sc);
-                v.z = mean_product<OutT>(v.z, sc);
-                v.w = mean_product<OutT>(v.w, sc);
-              }
-              Store4<OutT>::st(out + out_row(u0 + (size_t)cur, om) * (size_t)D + l * 4, v);
-            }
+            if (cur >= 0) finish_store(out, u0 + (size_t)cur, om, D, l, acc, cnt, combiner);
             acc = make_float4(0.f, 0.f, 0.f, 0.f);
             cur = b;
             cnt = 0;
@@ -277,108 +292,33 @@ __global__ void __launch_bounds__(kBlock)
         }
       }
     }
-    if (cur >= 0) {
-      float4 v = acc;
-      if (combiner == 1 && cnt > 1) {
-        const float sc = 1.0f / (float)cnt;
-        v.x = mean_product<OutT>(v.x, sc);
-        v.y = mean_product<OutT>(v.y, sc);
-        v.z = mean_product<OutT>(v.z, sc);
-        v.w = mean_product<OutT>(v.w, sc);
-      }
-      Store4<OutT>::st(out + out_row(u0 + (size_t)cur, om) * (size_t)D + l * 4, v);
-    }
+    if (cur >= 0) finish_store(out, u0 + (size_t)cur, om, D, l, acc, cnt, combiner);
     // empty buckets pool to zeros
 #pragma unroll
     for (int i = 0; i < NB; i++) {
       const int len = e[i] - (i > 0 ? e[i - 1] : 0);
       if (i < nb && len == 0)
-        Store4<OutT>::st(out + out_row(u0 + (size_t)i, om) * (size_t)D + l * 4,
-                         make_float4(0.f, 0.f, 0.f, 0.f));
+        finish_store(out, u0 + (size_t)i, om, D, l, make_float4(0.f, 0.f, 0.f, 0.f), 0, combiner);
     }
   }
 }
 
-// any embedding_vec_size: one wavefront per bucket, lanes stride over the vector
 template <typename OffT, typename OutT>
 __global__ void __launch_bounds__(kBlock)
     pool_generic_kernel(size_t buckets, int D, int combiner, const OffT* __restrict__ row_offset,
                         const uint64_t* __restrict__ value_index, const float* __restrict__ table,
                         OutT* __restrict__ out, OutMap om) {
-  const int lane = threadIdx.x & 63;
-  const size_t wave = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const size_t nwaves = ((size_t)gridDim.x * kBlock) >> 6;
-  for (size_t u = wave; u < buckets; u += nwaves) {
-    const long long off = (long long)row_offset[u];
-    const int n = (int)((long long)row_offset[u + 1] - off);
-    const float sc = (combiner == 1 && n > 1) ? 1.0f / (float)n : 1.0f;
-    for (int v = lane; v < D; v += 64) {
-      float sum = 0.0f;
-      for (int j = 0; j < n; j++) {
-        const uint64_t idx = value_index[off + j];
-        sum += (idx != kInvalidIndex) ? table[idx * (uint64_t)D + v] : 0.0f;
-      }
-      // even sizes take the reference's align2 rule also here (e.g. D = 6, 10)
-      const float m = (D % 2 == 0) ? mean_product<OutT>(sum, sc) : sum * sc;
-      Store4<OutT>::st1(out + out_row(u, om) * (size_t)D + v, (combiner == 1) ? m : sum);
-    }
-  }
+  pool_generic_body(buckets, D, combiner, row_offset, IndexedRows{value_index, table}, out, om);
 }
 
-// ---- pooling through per-key row pointers (the ILookup::lookup(..., float** embedding_vec) seam,
-//      R/HugeCTR/embedding/embedding_table.hpp:22-33, consumed by generic_lookup.cuh:318-416): the
-//      rows of a dynamic table live in per-class stores, so a key carries its row's address.
-//      nullptr = key not in the table (contributes 0, still counts for the mean).
+// ---- pooling through per-key row pointers (PointerRows): the two bodies on the addresses a
+//      dynamic table's lookup returned
 template <int LPR, int BU, typename OutT>
 __global__ void __launch_bounds__(kBlock)
     pool_ptrs_vec4_kernel(size_t buckets, int combiner, const long long* __restrict__ row_offset,
                           const float* const* __restrict__ rows, OutT* __restrict__ out,
                           OutMap om) {
-  constexpr int D = LPR * 4;
-  constexpr int GPB = kBlock / LPR;
-  const int g = threadIdx.x / LPR;
-  const int l = threadIdx.x % LPR;
-  const size_t stride = (size_t)gridDim.x * GPB * BU;
-  for (size_t u0 = ((size_t)blockIdx.x * GPB + g) * BU; u0 < buckets; u0 += stride) {
-    long long off[BU];
-    int n[BU];
-    float4 acc[BU];
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      const size_t u = u0 + k;
-      off[k] = (u < buckets) ? row_offset[u] : 0;
-      n[k] = (u < buckets) ? (int)(row_offset[u + 1] - off[k]) : 0;
-      acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      for (int j = 0; j < n[k]; j++) {
-        const float* r = rows[off[k] + j];
-        if (r != nullptr) {
-          const float4 v = ld4(r + l * 4);
-          acc[k].x += v.x;
-          acc[k].y += v.y;
-          acc[k].z += v.z;
-          acc[k].w += v.w;
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < BU; k++) {
-      const size_t u = u0 + k;
-      if (u < buckets) {
-        float4 v = acc[k];
-        if (combiner == 1 && n[k] > 1) {
-          const float sc = 1.0f / (float)n[k];
-          v.x = mean_product<OutT>(v.x, sc);
-          v.y = mean_product<OutT>(v.y, sc);
-          v.z = mean_product<OutT>(v.z, sc);
-          v.w = mean_product<OutT>(v.w, sc);
-        }
-        Store4<OutT>::st(out + out_row(u, om) * (size_t)D + l * 4, v);
-      }
-    }
-  }
+  pool_vec4_body<LPR, BU>(buckets, combiner, row_offset, PointerRows{rows}, out, om);
 }
 
 template <typename OutT>
@@ -387,45 +327,38 @@ __global__ void __launch_bounds__(kBlock)
                              const long long* __restrict__ row_offset,
                              const float* const* __restrict__ rows, OutT* __restrict__ out,
                              OutMap om) {
-  const int lane = threadIdx.x & 63;
-  const size_t wave = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const size_t nwaves = ((size_t)gridDim.x * kBlock) >> 6;
-  for (size_t u = wave; u < buckets; u += nwaves) {
-    const long long off = row_offset[u];
-    const int n = (int)(row_offset[u + 1] - off);
-    const float sc = (combiner == 1 && n > 1) ? 1.0f / (float)n : 1.0f;
-    for (int v = lane; v < D; v += 64) {
-      float sum = 0.0f;
-      for (int j = 0; j < n; j++) {
-        const float* r = rows[off + j];
-        sum += (r != nullptr) ? r[v] : 0.0f;
-      }
-      const float m = (D % 2 == 0) ? mean_product<OutT>(sum, sc) : sum * sc;
-      Store4<OutT>::st1(out + out_row(u, om) * (size_t)D + v, (combiner == 1) ? m : sum);
-    }
+  pool_generic_body(buckets, D, combiner, row_offset, PointerRows{rows}, out, om);
+}
+
+// run-time vector size -> lanes per row (see with_dtype, common.h): f(std::integral_constant<int,
+// LPR>{}) for the seven vec4 sizes D = 4 * LPR of 16-byte aligned buffers; false = there is no vec4
+// case and the caller launches its generic kernel
+template <typename F>
+bool with_lpr(int D, bool aligned16, F&& f) {
+  if (!aligned16 || D % 4 != 0) return false;
+  switch (D / 4) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    case 16: f(std::integral_constant<int, 16>{}); return true;
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
   }
+  return false;
 }
 
 template <typename OutT>
 int launch_pool_ptrs(size_t buckets, int D, int combiner, const long long* ro,
                      const float* const* rows, OutT* out, hipStream_t s, OutMap om) {
   // row stores are hipMalloc'ed ([capacity][D] fp32): rows are 16-byte aligned iff D % 4 == 0
-  const bool aligned = reinterpret_cast<uintptr_t>(out) % 16 == 0;
-#define HCTR_PP(LPR_)                                                                          \
-  case LPR_:                                                                                    \
-    hipLaunchKernelGGL((pool_ptrs_vec4_kernel<LPR_, 4, OutT>),                                  \
-                       dim3(grid_for(ceil_div<size_t>(buckets, 4), kBlock / LPR_, 256 * 8)),    \
-                       dim3(kBlock), 0, s, buckets, combiner, ro, rows, out, om);               \
-    break;
-  bool done = aligned && D % 4 == 0;
-  if (done) {
-    switch (D / 4) {
-      HCTR_PP(1) HCTR_PP(2) HCTR_PP(4) HCTR_PP(8) HCTR_PP(16) HCTR_PP(32) HCTR_PP(64)
-      default: done = false;
-    }
-  }
-#undef HCTR_PP
-  if (!done)
+  const bool vec = with_lpr(D, reinterpret_cast<uintptr_t>(out) % 16 == 0, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value;
+    hipLaunchKernelGGL((pool_ptrs_vec4_kernel<LPR, 4, OutT>),
+                       dim3(grid_for(ceil_div<size_t>(buckets, 4), kBlock / LPR, 256 * 8)),
+                       dim3(kBlock), 0, s, buckets, combiner, ro, rows, out, om);
+  });
+  if (!vec)
     hipLaunchKernelGGL((pool_ptrs_generic_kernel<OutT>), dim3(grid_for(buckets * 64, kBlock)),
                        dim3(kBlock), 0, s, buckets, D, combiner, ro, rows, out, om);
   HCTR_LAUNCH_CHECK();
@@ -562,42 +495,23 @@ template <typename OffT, typename OutT>
 int launch_pool(size_t buckets, int D, int combiner, const OffT* ro, const uint64_t* vi,
                 const float* table, OutT* out, bool multi_hot, hipStream_t s,
                 const uint32_t* one_hot, OutMap om) {
-#define HCTR_POOL_CASE(LPR_, BU_)                                                              \
-  {                                                                                            \
-    constexpr int GPB = kBlock / LPR_;                                                         \
-    if (multi_hot) {                                                                           \
-      const int grid = grid_for(ceil_div<size_t>(buckets, (size_t)8), GPB, 256 * 8);          \
-      hipLaunchKernelGGL((pool_flat_kernel<LPR_, 8, 8, OffT, OutT>), dim3(grid), dim3(kBlock), \
-                         0, s, buckets, combiner, ro, vi, table, out, om);                     \
-    } else {                                                                                   \
-      const int grid = grid_for(ceil_div<size_t>(buckets, (size_t)BU_), GPB, 256 * 8);        \
-      hipLaunchKernelGGL((pool_vec4_kernel<LPR_, BU_, OffT, OutT>), dim3(grid), dim3(kBlock), \
-                         0, s, buckets, combiner, ro, vi, table, out, one_hot, om);            \
-    }                                                                                          \
-  }
   const bool aligned = (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
                        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-  if (aligned && D % 4 == 0) {
-    switch (D / 4) {
-      case 1: HCTR_POOL_CASE(1, 4) break;
-      case 2: HCTR_POOL_CASE(2, 4) break;
-      case 4: HCTR_POOL_CASE(4, 4) break;
-      case 8: HCTR_POOL_CASE(8, 4) break;
-      case 16: HCTR_POOL_CASE(16, 4) break;
-      case 32: HCTR_POOL_CASE(32, 4) break;
-      case 64: HCTR_POOL_CASE(64, 4) break;
-      default: {
-        const int grid = grid_for(buckets * 64, kBlock);
-        hipLaunchKernelGGL((pool_generic_kernel<OffT, OutT>), dim3(grid), dim3(kBlock), 0, s,
-                           buckets, D, combiner, ro, vi, table, out, om);
-      }
+  const bool vec = with_lpr(D, aligned, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value, GPB = kBlock / LPR;
+    if (multi_hot) {
+      const int grid = grid_for(ceil_div<size_t>(buckets, (size_t)8), GPB, 256 * 8);
+      hipLaunchKernelGGL((pool_flat_kernel<LPR, 8, 8, OffT, OutT>), dim3(grid), dim3(kBlock), 0, s,
+                         buckets, combiner, ro, vi, table, out, om);
+    } else {
+      const int grid = grid_for(ceil_div<size_t>(buckets, (size_t)4), GPB, 256 * 8);
+      hipLaunchKernelGGL((pool_vec4_kernel<LPR, 4, OffT, OutT>), dim3(grid), dim3(kBlock), 0, s,
+                         buckets, combiner, ro, vi, table, out, one_hot, om);
     }
-  } else {
-    const int grid = grid_for(buckets * 64, kBlock);
-    hipLaunchKernelGGL((pool_generic_kernel<OffT, OutT>), dim3(grid), dim3(kBlock), 0, s, buckets,
-                       D, combiner, ro, vi, table, out, om);
-  }
-#undef HCTR_POOL_CASE
+  });
+  if (!vec)
+    hipLaunchKernelGGL((pool_generic_kernel<OffT, OutT>), dim3(grid_for(buckets * 64, kBlock)),
+                       dim3(kBlock), 0, s, buckets, D, combiner, ro, vi, table, out, om);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -665,50 +579,35 @@ int forward_pool_dispatch(size_t buckets, int D, int combiner, const void* ro, i
     set_error("output map: inner * outer must equal the bucket count (< 2^32)");
     return HCTR_ERR_INVALID_ARG;
   }
-  // HCTR_POOL_KERNEL=bucket|flat pins the kernel (measurements); default: the caller's hint
-  static const int forced = [] {
-    const char* v = getenv("HCTR_POOL_KERNEL");
-    if (!v) return -1;
-    return v[0] == 'f' ? 1 : (v[0] == 'b' ? 0 : -1);
-  }();
-  if (forced >= 0) multi_hot = forced == 1;
-#define HCTR_POOL_OUT(OffT)                                                                       \
-  switch (out_dtype) {                                                                            \
-    case HCTR_EMB_F32:                                                                            \
-      return launch_pool<OffT, float>(buckets, D, combiner, (const OffT*)ro, vi, table,           \
-                                      (float*)out, multi_hot, s, one_hot, om);                      \
-    case HCTR_EMB_F16:                                                                            \
-      return launch_pool<OffT, __half>(buckets, D, combiner, (const OffT*)ro, vi, table,          \
-                                       (__half*)out, multi_hot, s, one_hot, om);                    \
-    case HCTR_EMB_BF16:                                                                           \
-      return launch_pool<OffT, __hip_bfloat16>(buckets, D, combiner, (const OffT*)ro, vi, table,  \
-                                               (__hip_bfloat16*)out, multi_hot, s, one_hot, om);   \
-    default:                                                                                      \
-      set_error("out_dtype");                                                                     \
-      return HCTR_ERR_INVALID_ARG;                                                                \
-  }
-  if (key_type == HCTR_KEY_U32) {
-    HCTR_POOL_OUT(uint32_t)
-  } else if (key_type == HCTR_KEY_I64) {
-    HCTR_POOL_OUT(long long)
-  }
-#undef HCTR_POOL_OUT
-  set_error("key_type");
-  return HCTR_ERR_INVALID_ARG;
+  return with_key_type(key_type, [&](auto* off) -> int {
+    using OffT = std::remove_pointer_t<decltype(off)>;
+    return with_dtype(out_dtype, [&](auto* t) -> int {
+      using OutT = std::remove_pointer_t<decltype(t)>;
+      return launch_pool(buckets, D, combiner, (const OffT*)ro, vi, table, (OutT*)out, multi_hot, s,
+                         one_hot, om);
+    });
+  });
 }
 
 }  // namespace hctr
 
 using namespace hctr;
 
+// what every pooling entry checks first; ptrs: none of the entry's buffers is null
+static int check_pool_args(size_t buckets, int vec_size, int combiner, bool ptrs) {
+  HCTR_REQUIRE(vec_size > 0, "vec_size");
+  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
+  HCTR_REQUIRE(buckets == 0 || ptrs, "null pointer");
+  return HCTR_OK;
+}
+
 extern "C" {
 
 int hctr_forward_pool(size_t buckets, int vec_size, int combiner, const void* row_offset,
                       int key_type, const uint64_t* value_index, const float* table, void* out,
                       int out_dtype, hctr_stream_t stream) {
-  HCTR_REQUIRE(vec_size > 0, "vec_size");
-  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
-  HCTR_REQUIRE(buckets == 0 || (row_offset && value_index && table && out), "null pointer");
+  HCTR_TRY(
+      check_pool_args(buckets, vec_size, combiner, row_offset && value_index && table && out));
   return forward_pool_dispatch(buckets, vec_size, combiner, row_offset, key_type, value_index,
                                table, out, out_dtype, false, as_stream(stream), nullptr);
 }
@@ -716,27 +615,16 @@ int hctr_forward_pool(size_t buckets, int vec_size, int combiner, const void* ro
 static int forward_pool_ptrs_impl(size_t buckets, int vec_size, int combiner,
                                   const int64_t* row_offset, const float* const* rows, void* out,
                                   int out_dtype, OutMap om, hctr_stream_t stream) {
-  HCTR_REQUIRE(vec_size > 0, "vec_size");
-  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
+  HCTR_TRY(check_pool_args(buckets, vec_size, combiner, row_offset && rows && out));
   if (buckets == 0) return HCTR_OK;
-  HCTR_REQUIRE(row_offset && rows && out, "null pointer");
   HCTR_REQUIRE(om.inner == 0u || ((size_t)om.inner * om.outer == buckets &&
                                   buckets <= (size_t)0xFFFFFFFFu),
                "output map: samples * lookups must equal the bucket count (< 2^32)");
-  hipStream_t s = as_stream(stream);
-  const long long* ro = (const long long*)row_offset;
-  switch (out_dtype) {
-    case HCTR_EMB_F32:
-      return launch_pool_ptrs<float>(buckets, vec_size, combiner, ro, rows, (float*)out, s, om);
-    case HCTR_EMB_F16:
-      return launch_pool_ptrs<__half>(buckets, vec_size, combiner, ro, rows, (__half*)out, s, om);
-    case HCTR_EMB_BF16:
-      return launch_pool_ptrs<__hip_bfloat16>(buckets, vec_size, combiner, ro, rows,
-                                              (__hip_bfloat16*)out, s, om);
-    default:
-      HCTR_REQUIRE(false, "out_dtype");
-  }
-  return HCTR_OK;
+  return with_dtype(out_dtype, [&](auto* t) -> int {
+    using OutT = std::remove_pointer_t<decltype(t)>;
+    return launch_pool_ptrs(buckets, vec_size, combiner, (const long long*)row_offset, rows,
+                            (OutT*)out, as_stream(stream), om);
+  });
 }
 
 int hctr_forward_pool_ptrs(size_t buckets, int vec_size, int combiner, const int64_t* row_offset,
@@ -760,29 +648,19 @@ int hctr_forward_pool_ptrs_mapped(size_t buckets, int vec_size, int combiner,
 int hctr_forward_pool_weighted(size_t buckets, int vec_size, int combiner, const int64_t* row_offset,
                                const uint64_t* value_index, const float* weights,
                                const float* table, float* out, hctr_stream_t stream) {
-  HCTR_REQUIRE(vec_size > 0, "vec_size");
-  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
+  HCTR_TRY(
+      check_pool_args(buckets, vec_size, combiner, row_offset && value_index && table && out));
   if (buckets == 0) return HCTR_OK;
-  HCTR_REQUIRE(row_offset && value_index && table && out, "null pointer");
   hipStream_t s = as_stream(stream);
-  const bool v4 = vec_size % 4 == 0 && reinterpret_cast<uintptr_t>(table) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(out) % 16 == 0;
-  bool done = false;
-#define HCTR_PW(LPR_)                                                                            \
-  case LPR_:                                                                                      \
-    hipLaunchKernelGGL(pool_weighted_vec4_kernel<LPR_>,                                           \
-                       dim3(grid_for(buckets, kBlock / LPR_, 8192)), dim3(kBlock), 0, s, buckets, \
-                       combiner, (const long long*)row_offset, value_index, weights, table, out); \
-    done = true;                                                                                  \
-    break;
-  if (v4) {
-    switch (vec_size / 4) {
-      HCTR_PW(1) HCTR_PW(2) HCTR_PW(4) HCTR_PW(8) HCTR_PW(16) HCTR_PW(32) HCTR_PW(64)
-      default: break;
-    }
-  }
-#undef HCTR_PW
-  if (!done)
+  const bool a16 = reinterpret_cast<uintptr_t>(table) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  const bool vec = with_lpr(vec_size, a16, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value;
+    hipLaunchKernelGGL(pool_weighted_vec4_kernel<LPR>, dim3(grid_for(buckets, kBlock / LPR, 8192)),
+                       dim3(kBlock), 0, s, buckets, combiner, (const long long*)row_offset,
+                       value_index, weights, table, out);
+  });
+  if (!vec)
     hipLaunchKernelGGL(pool_weighted_kernel, dim3(grid_for(buckets * 64, kBlock, 8192)),
                        dim3(kBlock), 0, s, buckets, vec_size, combiner,
                        (const long long*)row_offset, value_index, weights, table, out);
@@ -793,29 +671,18 @@ int hctr_forward_pool_weighted(size_t buckets, int vec_size, int combiner, const
 int hctr_expand_key_grads(size_t buckets, int vec_size, int combiner, const int64_t* row_offset,
                           const float* weights, const float* top_grad, float* key_grads,
                           hctr_stream_t stream) {
-  HCTR_REQUIRE(vec_size > 0, "vec_size");
-  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
+  HCTR_TRY(check_pool_args(buckets, vec_size, combiner, row_offset && top_grad && key_grads));
   if (buckets == 0) return HCTR_OK;
-  HCTR_REQUIRE(row_offset && top_grad && key_grads, "null pointer");
   hipStream_t s = as_stream(stream);
-  const bool v4 = vec_size % 4 == 0 && reinterpret_cast<uintptr_t>(top_grad) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(key_grads) % 16 == 0;
-  bool done = false;
-#define HCTR_EG(LPR_)                                                                            \
-  case LPR_:                                                                                      \
-    hipLaunchKernelGGL(expand_key_grads_vec4_kernel<LPR_>,                                        \
-                       dim3(grid_for(buckets, kBlock / LPR_, 8192)), dim3(kBlock), 0, s, buckets, \
-                       combiner, (const long long*)row_offset, weights, top_grad, key_grads);     \
-    done = true;                                                                                  \
-    break;
-  if (v4) {
-    switch (vec_size / 4) {
-      HCTR_EG(1) HCTR_EG(2) HCTR_EG(4) HCTR_EG(8) HCTR_EG(16) HCTR_EG(32) HCTR_EG(64)
-      default: break;
-    }
-  }
-#undef HCTR_EG
-  if (!done)
+  const bool a16 = reinterpret_cast<uintptr_t>(top_grad) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(key_grads) % 16 == 0;
+  const bool vec = with_lpr(vec_size, a16, [&](auto lpr) {
+    constexpr int LPR = decltype(lpr)::value;
+    hipLaunchKernelGGL(expand_key_grads_vec4_kernel<LPR>,
+                       dim3(grid_for(buckets, kBlock / LPR, 8192)), dim3(kBlock), 0, s, buckets,
+                       combiner, (const long long*)row_offset, weights, top_grad, key_grads);
+  });
+  if (!vec)
     hipLaunchKernelGGL(expand_key_grads_kernel, dim3(grid_for(buckets * 64, kBlock, 8192)),
                        dim3(kBlock), 0, s, buckets, vec_size, combiner,
                        (const long long*)row_offset, weights, top_grad, key_grads);
@@ -826,9 +693,8 @@ int hctr_expand_key_grads(size_t buckets, int vec_size, int combiner, const int6
 int hctr_forward_pool_multihot(size_t buckets, int vec_size, int combiner, const void* row_offset,
                                int key_type, const uint64_t* value_index, const float* table,
                                void* out, int out_dtype, hctr_stream_t stream) {
-  HCTR_REQUIRE(vec_size > 0, "vec_size");
-  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
-  HCTR_REQUIRE(buckets == 0 || (row_offset && value_index && table && out), "null pointer");
+  HCTR_TRY(
+      check_pool_args(buckets, vec_size, combiner, row_offset && value_index && table && out));
   return forward_pool_dispatch(buckets, vec_size, combiner, row_offset, key_type, value_index,
                                table, out, out_dtype, true, as_stream(stream), nullptr);
 }
@@ -837,9 +703,8 @@ int hctr_forward_pool_mapped(size_t buckets, int vec_size, int combiner, const v
                              int key_type, const uint64_t* value_index, const float* table,
                              void* out, int out_dtype, int multi_hot, size_t samples,
                              size_t lookups, const uint32_t* one_hot, hctr_stream_t stream) {
-  HCTR_REQUIRE(vec_size > 0, "vec_size");
-  HCTR_REQUIRE(combiner == 0 || combiner == 1, "combiner must be 0 (sum) or 1 (mean)");
-  HCTR_REQUIRE(buckets == 0 || (row_offset && value_index && table && out), "null pointer");
+  HCTR_TRY(
+      check_pool_args(buckets, vec_size, combiner, row_offset && value_index && table && out));
   HCTR_REQUIRE((samples == 0 && lookups == 0) || (samples > 0 && lookups > 0 &&
                                                   samples <= 0xFFFFFFFFull &&
                                                   lookups <= 0xFFFFFFFFull),

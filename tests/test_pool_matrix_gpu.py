@@ -473,6 +473,46 @@ def test_expand_grid(D):
     _expand_case(2 * 32768 + 37, D, 0, False, mean_len=1.5)
 
 
+# ---- 3b. the sign of zero ------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("comb", [0, 1])
+@pytest.mark.parametrize("D", [8, 6])
+def test_negative_zero_rows(oracle, D, comb, dt):
+    """a table of -0.0 only, 16 buckets of 0, 1 and 3 keys, vec4 (D = 8) and generic (D = 6) path:
+    the sum starts at +0.0f, so (+0.0) + (-0.0) = +0.0 is what every kernel stores (an accumulator
+    that started from the first row instead would store -0.0); the oracle's bits, sign included"""
+    from hugectr_amd import _lib
+    nb, rows = 16, 8
+    lens = np.array([0, 1, 3] * 6)[:nb]
+    ro_h = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    vi_h = (np.arange(ro_h[-1]) % rows).astype(np.uint64)
+    tab_h = np.full((rows, D), -0.0, dtype=np.float32)
+    assert np.signbit(tab_h).all()
+    if dt == "f32":
+        want = oracle.forward(ro_h, vi_h, tab_h, D, comb)
+    else:
+        want = oracle.forward_mixed(ro_h, vi_h, tab_h, D, comb, dt)
+    ro, vi, tab = _In(ro_h), _In(vi_h), _In(tab_h)
+    ptrs = _In((tab.t.data_ptr() + vi_h.astype(np.int64) * (D * 4)).astype(np.int64))
+    L, s = _lib.lib, _lib.stream_ptr()
+    calls = {
+        "pool": lambda o: L.hctr_forward_pool(nb, D, comb, ro.p, _lib.KEY_I64, vi.p, tab.p, o.p,
+                                              _code(dt), s),
+        "multihot": lambda o: L.hctr_forward_pool_multihot(nb, D, comb, ro.p, _lib.KEY_I64, vi.p,
+                                                           tab.p, o.p, _code(dt), s),
+        "ptrs": lambda o: L.hctr_forward_pool_ptrs(nb, D, comb, ro.p, ptrs.p, o.p, _code(dt), s),
+    }
+    if dt == "f32":  # the weighted entry's only output type
+        calls["weighted"] = lambda o: L.hctr_forward_pool_weighted(nb, D, comb, ro.p, vi.p, None,
+                                                                   tab.p, o.p, s)
+    for name, call in calls.items():
+        out = _Out(nb, D, dt)
+        _lib.check(call(out))
+        _assert_bits(out.result(), want, f"-0.0 rows, {name} D={D} comb={comb} {dt}")
+    for x, name in ((ro, "row_offset"), (vi, "value_index"), (tab, "table"), (ptrs, "rows")):
+        x.assert_unchanged(name)
+
+
 # ---- 4. reorder ----------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _perm(bpg, S, D, N):
