@@ -65,6 +65,29 @@ constexpr uint64_t kInvalidIndex = ~0ull;  // std::numeric_limits<size_t>::max()
                                    (__attribute__((address_space(3))) void*)(lds_wave_base), 16, 0, 0)
 #endif
 
+// four 16-bit LDS elements base[e0], base[e1], base[e2], base[e3] (element offsets) as two packed
+// words (a hctr_u32x2, e0 in the low half of word 0).  For the gfx950 device this is one transposed
+// read, ds_read_b64_tr_b16 at base + tr_off (elements; the lane address must be 8-byte aligned and
+// EXEC all ones): of each 16 consecutive lanes, lane 4q + p supplies the address of elements
+// 4p .. 4p+3 of row q of a 4 x 16 block, and lane i receives element i of rows 0 .. 3 -- the caller
+// passes BOTH descriptions of the same block and e0 .. e3 are not evaluated.  Everywhere else (the
+// host pass, the host interpreter of tests/emu) it is the four plain reads and tr_off is not
+// evaluated.
+typedef unsigned int hctr_u32x2 __attribute__((ext_vector_type(2)));
+#ifndef HCTR_LDS_READ_TR16_B64
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+typedef short hctr_s16x4 __attribute__((ext_vector_type(4)));
+#define HCTR_LDS_READ_TR16_B64(base, tr_off, e0, e1, e2, e3)                \
+  __builtin_bit_cast(hctr_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(   \
+                                     (__attribute__((address_space(3))) hctr_s16x4*)((base) + (tr_off))))
+#else
+#define HCTR_LDS_READ_TR16_B64(base, tr_off, e0, e1, e2, e3)                          \
+  hctr_u32x2 {                                                                        \
+    (unsigned)(base)[e0] | ((unsigned)(base)[e1] << 16), (unsigned)(base)[e2] | ((unsigned)(base)[e3] << 16) \
+  }
+#endif
+#endif
+
 // counted wait on this wave's vector-memory queue + a barrier that does not drain it (a plain
 // __syncthreads() waits for every outstanding LDS DMA: a ring of more than two staging buffers
 // would never have a tile in flight across it).  Macros: the host interpreter has no queues.

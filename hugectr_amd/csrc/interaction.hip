@@ -168,6 +168,10 @@ struct Mfma16;
 template <>
 struct Mfma16<true> : H16<true> {
   typedef bf16x8 vec8;
+  // two fp32 values rounded to the type, a in the low half of the word
+  __device__ __forceinline__ static unsigned pack2(float a, float b) {
+    return (unsigned)from_f32(a) | ((unsigned)from_f32(b) << 16);
+  }
   __device__ __forceinline__ static f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
@@ -175,6 +179,12 @@ struct Mfma16<true> : H16<true> {
 template <>
 struct Mfma16<false> : H16<false> {
   typedef f16x8 vec8;
+  __device__ __forceinline__ static unsigned pack2(float a, float b) {  // (one v_cvt_pk_f16_f32)
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    const f16x2 v = __builtin_convertvector((f32x2){a, b}, f16x2);
+    return __builtin_bit_cast(unsigned, v);
+  }
   __device__ __forceinline__ static f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
   }
@@ -182,9 +192,24 @@ struct Mfma16<false> : H16<false> {
 
 template <int W>
 struct InterCfg16 {
-  static constexpr int LD = W + 8;   // row stride in 16-bit elements (+16 B against conflicts)
-  static constexpr int XT = 32 * LD; // elements
+  static constexpr int LD = W + 8;   // forward: row stride in 16-bit elements (+16 B against conflicts)
+  static constexpr int XT = 32 * W;  // backward: the tile's elements (rows unpadded, chunks swizzled)
   static constexpr int GS = 40;      // G row stride (elements): 80 B -> 16 distinct 16-B slots
+  // The backward's tile is read three ways: by rows in 16-byte chunks (tile write, gradient rows
+  // out), by columns through the transposed read (4 rows x 32 columns per half wave) and written
+  // back 8 bytes per lane, lane = row, one half chunk for all.  Chunk ch of row `row` lies at chunk
+  // ch ^ bwd_swz(row) of that row: the 16 chunks of a transposed read then cover all 64 banks
+  // once, the 16 rows of an 8-byte write the 32 banks twice (2-way, hidden behind the store's
+  // register transfer), and a row's chunks stay a permutation of themselves.
+  __host__ __device__ static constexpr int bwd_swz(int row) {
+    return W == 128 ? (((row & 3) << 2) | ((row >> 2) & 3))
+           : W == 64 ? ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))
+                     : ((row >> 1) & 3);
+  }
+  // element offset of 16-byte chunk ch of row `row` in the backward's tile
+  __host__ __device__ static constexpr int bwd_off(int row, int ch) {
+    return row * W + ((ch ^ bwd_swz(row)) << 3);
+  }
   // the layouts of InterCfg<W>, in 16-bit elements
   static size_t fwd_lds(const InterShape& s) {
     return (size_t)((s.n_ins + 1) * LD + ((s.out_len + 7) & ~7)) * 2;
@@ -355,10 +380,13 @@ __device__ __forceinline__ void load_gather_rows(f32x4 (&lo)[NPRE], f32x4 (&hi)[
 
 // load_gather_rows for the backward, whose prefetch registers are scarcer: lane s < n_emb holds
 // the row number of embedding s (my_idx, loaded a sample ahead), each entry takes its own from that
-// lane; returns the entries' live bits (row number != kInvalidIndex), the row numbers die here
+// lane; returns the entries' live bits (row number != kInvalidIndex).  The lane's row number for the
+// sample after (*my_next) is asked for once the current one has been handed out and in front of the
+// rows: it takes my_idx's place without a copy that would have to wait for it.
 template <int W, int NPRE>
 __device__ __forceinline__ uint32_t load_gather_rows_lane(f32x4 (&lo)[NPRE], f32x4 (&hi)[NPRE],
-                                                          uint64_t my_idx,
+                                                          uint64_t& my_idx,
+                                                          const uint64_t* __restrict__ my_next,
                                                           const unsigned short* __restrict__ mlp,
                                                           const float* __restrict__ table, size_t b,
                                                           int n_vec, int lane) {
@@ -371,6 +399,7 @@ __device__ __forceinline__ uint32_t load_gather_rows_lane(f32x4 (&lo)[NPRE], f32
     const int row = i / W8;
     idx[q] = __shfl(my_idx, row > 0 ? row - 1 : 0);
   }
+  my_idx = *my_next;
   load_gather_rows<W, NPRE>(lo, hi, idx, mlp, table, b, n_vec, lane);
   uint32_t live = 0;
 #pragma unroll
@@ -465,14 +494,18 @@ __global__ void __launch_bounds__(64, 2)
   // grad_map[b * n_emb + s] of emb_grad (the all-to-all send layout: no reorder pass behind it)
   // GATHER: the tile is rebuilt from the fp32 table through value_index exactly as
   // interaction_fwd16_gather_kernel built it (emb / row_of unused) -- the pooled vectors are never
-  // stored; row numbers run one sample ahead of the rows, which are rounded when the tile is written
+  // stored; row numbers run one sample ahead of the rows, which are rounded when the tile is written.
+  // Everything a sample reads from global memory (rows, both parts of the top gradient, the row
+  // numbers of the sample after) is asked for by one unconditional prefetch a sample ahead, oldest
+  // first in the order it is needed: the vector-memory counter retires in order, so a load issued
+  // behind the prefetch, or a branch around it, would turn the next wait into a wait for all of it
   using C = InterCfg16<W>;
   using H = Mfma16<BF>;
   constexpr int GS = C::GS;
   HCTR_DYN_LDS16(unsigned short, smem16);
   const int lane = threadIdx.x;
   const int n_ins = n_emb + 1;
-  unsigned short* xt = smem16;            // [32][LD] X, reused for dX
+  unsigned short* xt = smem16;            // [32][W] X (chunks at C::bwd_off), reused for dX
   unsigned short* gm = smem16 + C::XT;    // [32][GS]
   unsigned short* pair_nm = gm + 32 * GS; // [n_pairs]
   constexpr int W8 = W / 8;
@@ -496,6 +529,7 @@ __global__ void __launch_bounds__(64, 2)
   uint32_t live = 0;
   uint64_t idx_nxt = 0;
   unsigned short gpre[NG];
+  u32x4 gt_nxt = {0u, 0u, 0u, 0u};  // the sample's pass-through gradient (row 0: lanes < W8)
   size_t b = blockIdx.x;
   const size_t last = batch - 1;
   const int my_s = lane < n_emb ? lane : 0;
@@ -503,10 +537,14 @@ __global__ void __launch_bounds__(64, 2)
   // the loader they share, interaction_fwd16_kernel's: profiles/interaction_refactor_resources.txt)
 #define HCTR_BWD16_PREFETCH(bb)                                                       \
   {                                                                                   \
-    if constexpr (GATHER)                                                             \
-      live = load_gather_rows_lane<W, NPRE>(lo, hi, idx_nxt, mlp, table, (bb), n_vec, lane); \
-    else                                                                              \
+    if constexpr (GATHER) {                                                           \
+      const size_t nx__ = (bb) + gridDim.x;                                           \
+      live = load_gather_rows_lane<W, NPRE>(                                          \
+          lo, hi, idx_nxt, value_index + (nx__ < batch ? nx__ : last) * (size_t)n_emb + my_s, \
+          mlp, table, (bb), n_vec, lane);                                             \
+    } else                                                                            \
       load_sample_tile16<W, NPRE>(pre, mlp, emb, row_of, (bb), n_emb, n_vec, lane);   \
+    gt_nxt = reinterpret_cast<const u32x4*>(top_grad + (bb) * (size_t)out_len)[lane < W8 ? lane : 0]; \
     const unsigned short* g__ = top_grad + (bb) * (size_t)out_len + W;                \
     _Pragma("unroll") for (int q = 0; q < NG; q++) {                                  \
       int p__ = lane + 64 * q;                                                        \
@@ -516,17 +554,14 @@ __global__ void __launch_bounds__(64, 2)
   }
   if constexpr (GATHER) idx_nxt = value_index[(b < batch ? b : last) * (size_t)n_emb + my_s];
   if (b < batch) HCTR_BWD16_PREFETCH(b)
-  if constexpr (GATHER) {
-    const size_t nb = b + gridDim.x;
-    idx_nxt = value_index[(nb < batch ? nb : last) * (size_t)n_emb + my_s];
-  }
   for (; b < batch; b += gridDim.x) {
+    const u32x4 gt = gt_nxt;
 #pragma unroll
     for (int q = 0; q < NPRE; q++) {
       const int i = lane + 64 * q;
       if (i < n_vec) {
         const int row = i / W8, c8 = i % W8;
-        *reinterpret_cast<u32x4*>(xt + row * C::LD + c8 * 8) =
+        *reinterpret_cast<u32x4*>(xt + C::bwd_off(row, c8)) =
             GATHER ? gather_tile_vec<H>(lo[q], hi[q], (live >> q) & 1u, row) : pre[q];
       }
     }
@@ -541,14 +576,18 @@ __global__ void __launch_bounds__(64, 2)
       }
     }
     __syncthreads();
-    const size_t nb = b + gridDim.x;
-    if (nb < batch) HCTR_BWD16_PREFETCH(nb)
-    if constexpr (GATHER) {
-      const size_t nb2 = nb + gridDim.x;
-      idx_nxt = value_index[(nb2 < batch ? nb2 : last) * (size_t)n_emb + my_s];
-    }
+    // the next sample's rows and gradients; behind the last one the last sample's again (legal
+    // reads nobody uses): a branch around the prefetch would make every wait behind it, for a load
+    // issued in front of it, a wait for everything
+    const size_t nb = b + gridDim.x < batch ? b + gridDim.x : last;
+    HCTR_BWD16_PREFETCH(nb)
 
+    // dX^T = X^T G on the MFMA (G is symmetric: its fragment is the same as either operand): lane
+    // (r, h) feeds column T*32 + r of X rows k0 .. k0+7 -- two transposed reads, lane 4q + p of each
+    // 16 supplying row q, columns 4p .. 4p+3 of its block -- and receives row r of dX, columns
+    // T*32 + 8g + 4h .. +3 in registers 4g .. 4g+3, which go back to the tile as one 8-byte store
     constexpr int HP = NT >= 2 ? 2 : 1;
+    const int tq = (lane >> 2) & 3, tp = lane & 3, tj = (lane >> 4) & 1;
 #pragma unroll
     for (int pn = 0; pn < NT / HP; pn++) {
       f32x16 acc[HP];
@@ -559,34 +598,40 @@ __global__ void __launch_bounds__(64, 2)
 #pragma unroll
       for (int s2 = 0; s2 < 2; s2++) {
         const int k0 = 16 * s2 + 8 * h;
-        const typename H::vec8 af = *reinterpret_cast<const typename H::vec8*>(gm + r * GS + k0);
+        const typename H::vec8 gf = *reinterpret_cast<const typename H::vec8*>(gm + r * GS + k0);
 #pragma unroll
         for (int t = 0; t < HP; t++) {
-          const int col = (pn * HP + t) * 32 + r;
-          unsigned int w4[4];
+          const int T = pn * HP + t;
+          const int col = T * 32 + r;
+          hctr_u32x2 x2[2];
 #pragma unroll
-          for (int e = 0; e < 4; e++) {
-            const unsigned lo = xt[(k0 + 2 * e) * C::LD + col];
-            const unsigned hi = xt[(k0 + 2 * e + 1) * C::LD + col];
-            w4[e] = lo | (hi << 16);
+          for (int j = 0; j < 2; j++) {
+            const int r0 = k0 + 4 * j;
+            x2[j] = HCTR_LDS_READ_TR16_B64(
+                xt, C::bwd_off(r0 + tq, 4 * T + 2 * tj + (tp >> 1)) + 4 * (tp & 1),
+                C::bwd_off(r0, col >> 3) + (col & 7), C::bwd_off(r0 + 1, col >> 3) + (col & 7),
+                C::bwd_off(r0 + 2, col >> 3) + (col & 7), C::bwd_off(r0 + 3, col >> 3) + (col & 7));
           }
-          const u32x4 packed = {w4[0], w4[1], w4[2], w4[3]};
-          const typename H::vec8 bfv = *reinterpret_cast<const typename H::vec8*>(&packed);
-          acc[t] = H::mfma(af, bfv, acc[t]);
+          const u32x4 packed = {x2[0][0], x2[0][1], x2[1][0], x2[1][1]};
+          const typename H::vec8 xf = *reinterpret_cast<const typename H::vec8*>(&packed);
+          acc[t] = H::mfma(xf, gf, acc[t]);
         }
       }
       __syncthreads();
+      if (r < n_ins) {
 #pragma unroll
-      for (int t = 0; t < HP; t++) {
+        for (int t = 0; t < HP; t++) {
 #pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-          const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-          if (row < n_ins) xt[row * C::LD + (pn * HP + t) * 32 + r] = H::from_f32(acc[t][reg]);
+          for (int g = 0; g < 4; g++) {
+            hctr_u32x2 w2;
+            w2[0] = H::pack2(acc[t][4 * g], acc[t][4 * g + 1]);
+            w2[1] = H::pack2(acc[t][4 * g + 2], acc[t][4 * g + 3]);
+            *reinterpret_cast<hctr_u32x2*>(xt + C::bwd_off(r, 4 * (pn * HP + t) + g) + 4 * h) = w2;
+          }
         }
       }
     }
     __syncthreads();
-    const unsigned short* gtop = top_grad + b * (size_t)out_len;
     u32x4* mg4 = reinterpret_cast<u32x4*>(mlp_grad + b * W);
     u32x4* eg4 = reinterpret_cast<u32x4*>(emb_grad + b * (size_t)n_emb * W);
 #pragma unroll
@@ -594,9 +639,8 @@ __global__ void __launch_bounds__(64, 2)
       const int i = lane + 64 * q;
       if (i < n_vec) {
         const int row = i / W8, c8 = i % W8;
-        u32x4 v = *reinterpret_cast<const u32x4*>(xt + row * C::LD + c8 * 8);
+        u32x4 v = *reinterpret_cast<const u32x4*>(xt + C::bwd_off(row, c8));
         if (row == 0) {
-          const u32x4 gt = reinterpret_cast<const u32x4*>(gtop)[c8];
           u32x4 o4;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
