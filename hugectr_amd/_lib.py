@@ -310,6 +310,8 @@ _SIGNATURES = {
     "hctr_metric_ndcg": (c_int, [_P, c_size_t, _P, _P, c_size_t, _P, _P]),
     "hctr_raw_decode_tile": (c_size_t, [c_size_t]),
     "hctr_raw_decode": (c_int, [_P, c_size_t, c_size_t, _P, c_int, _P, _P]),
+    "hctr_parquet_decode": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_size_t, c_size_t, c_size_t,
+                                    c_size_t, _P, _P, c_int, _P]),
 }
 METRIC_MAX_CLASSES = 256
 METRIC_COUNTER_WORDS = 264
@@ -319,6 +321,19 @@ RAW_DECODE_MAX_BLOCKS = 1024
 RAW_DECODE_MAX_SEGMENTS = 4096
 RAW_SEGMENT_FIELDS = [("col0", "<u4"), ("ncols", "<u4"), ("kind", "<u4"), ("reserved", "<u4"),
                       ("sample0", "<u8"), ("sample1", "<u8"), ("dst_offset", "<u8")]
+# hctr_parquet_decode: physical types, segment and output kinds, hctr_parquet_column /
+# hctr_parquet_segment as numpy records
+PQ_F32, PQ_F64, PQ_I32, PQ_I64 = range(4)
+PQ_SEG_TILE, PQ_SEG_RAGGED, PQ_SEG_GROUP = range(3)
+PQ_OUT_F32, PQ_OUT_F32_VIA_F64, PQ_OUT_KEY_I64, PQ_OUT_KEY_I32 = range(4)
+PQ_NO_OFFSETS = 0xFFFFFFFFFFFFFFFF
+PQ_NO_OUTPUT = 0xFFFFFFFF
+PQ_DECODE_MAX_BLOCKS = 1024
+PQ_DECODE_MAX_SEGMENTS = 4096
+PQ_TILE_SAMPLES, PQ_TILE_COLS, PQ_BLOCK = 64, 32, 256
+PQ_COLUMN_FIELDS = [("values", "<u8"), ("offsets", "<u8"), ("ptype", "<u4"), ("esize", "<u4")]
+PQ_SEGMENT_FIELDS = [(n, "<u4") for n in ("kind", "out_kind", "list0", "ncols", "sample0", "sample1",
+                                          "out0", "out1", "group", "lookup", "item0", "n_items")]
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 

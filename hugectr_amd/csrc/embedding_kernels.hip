@@ -735,3 +735,6 @@ int hctr_backward_reorder(size_t batch_per_gpu, int slot_num, int vec_size, int 
 
 // the Raw reader's batch split (hctr_raw_decode) shares this unit too
 #include "raw_decode.hip"
+
+// and so does the Parquet reader's batch decode (hctr_parquet_decode)
+#include "parquet_decode.hip"

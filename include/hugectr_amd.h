@@ -1307,6 +1307,81 @@ size_t hctr_raw_decode_tile(size_t width);
 int hctr_raw_decode(const uint32_t* raw, size_t batch, size_t width, const void* plan,
                     int n_segments, void* out_base, hctr_stream_t stream);
 
+/* ---- Parquet reader: one launch turns resident columns into one batch (csrc/parquet_decode.hip) ----
+ * The reference reads a Parquet file into device columns and converts them with
+ * dense_data_converter_kernel__, offset_kernel__ and value_kernel_without_shared_mem__ /
+ * value_kernel__ (R/HugeCTR/src/data_readers/parquet_data_converter.cu:55-260): one launch per
+ * kind, an inclusive scan between the offsets and the values.  Arrow's list offsets are prefix sums
+ * already, so here every output position has a closed form and one launch writes everything.
+ *
+ * slot      device, 8-byte aligned: one staged FILE.  Column c's values lie at slot +
+ *           columns[c].values at their physical width (the chunks of a file laid one behind the
+ *           other); a list column also has int64 offsets[rows + 1] at slot + columns[c].offsets,
+ *           rebased over the whole file (offsets[0] = 0); a scalar column has
+ *           offsets = HCTR_PQ_NO_OFFSETS and stands for offsets[i] = i
+ * columns   device: n_columns hctr_parquet_column entries
+ * plan      device, 8-byte aligned, built once per reader: n_segments hctr_parquet_segment entries,
+ *           then int64 addend[n_list], then uint32 column[n_list] (the column lists the segments
+ *           point into; addend = the slot offset of a key column)
+ * rows      rows of the staged file; the batch is its rows [first_row, first_row + batch)
+ * out_base  device, 8-byte aligned; out_offsets: device, one byte offset from out_base per output of
+ *           the plan (ragged outputs have data-dependent sizes, so the table is per batch)
+ *
+ * With off_s the offsets of slot s of a param with S slots (HCTR_PQ_SEG_RAGGED; a = first_row):
+ *   row_offsets[b*S + s] = sum_{s'<S} (off_s'[a+b] - off_s'[a]) + sum_{s'<s} (off_s'[a+b+1] - off_s'[a+b])
+ *   row_offsets[B*S]     = sum_{s'<S} (off_s'[a+B] - off_s'[a])
+ *   keys[row_offsets[b*S+s] + j] = values_s[off_s[a+b] + j] + addend_s
+ * and for lookup l of a collection (HCTR_PQ_SEG_GROUP, one segment per lookup):
+ *   bucket_range[l*B + b] = sum_{l'<l} (off_l'[a+B] - off_l'[a]) + off_l[a+b] - off_l[a]
+ *   keys of lookup l      = values_l[off_l[a] .. off_l[a+B]) as int64, behind lookup l-1's
+ * HCTR_PQ_SEG_TILE writes out[(b - sample0) * ncols + j] = convert(values_{col j}[a + b]) for the
+ * samples [sample0, sample1) of the batch: label, dense and params whose slots are all scalar.
+ * Plain stores, every position once, no atomics.  The caller guarantees that the column table and
+ * the offsets describe memory inside the slot and that every output lies inside its arena. */
+enum { HCTR_PQ_F32 = 0, HCTR_PQ_F64 = 1, HCTR_PQ_I32 = 2, HCTR_PQ_I64 = 3 }; /* physical types */
+enum { HCTR_PQ_SEG_TILE = 0, HCTR_PQ_SEG_RAGGED = 1, HCTR_PQ_SEG_GROUP = 2 };
+enum {
+  HCTR_PQ_OUT_F32 = 0,         /* (float)value, round to nearest even */
+  HCTR_PQ_OUT_F32_VIA_F64 = 1, /* (float)(double)value: what numpy's astype gives for a group of
+                                  columns it first promoted to float64 (differs for |int64| > 2^53) */
+  HCTR_PQ_OUT_KEY_I64 = 2,     /* int64: sign-extended value + addend; row offsets int64 */
+  HCTR_PQ_OUT_KEY_I32 = 3      /* int32: the low 32 bits of that sum; row offsets int32 */
+};
+#define HCTR_PQ_NO_OFFSETS (~0ull)
+#define HCTR_PQ_NO_OUTPUT 0xFFFFFFFFu
+typedef struct {
+  uint64_t values;  /* bytes from slot; a multiple of 8 */
+  uint64_t offsets; /* bytes from slot (int64 [rows + 1]), or HCTR_PQ_NO_OFFSETS */
+  uint32_t ptype;   /* HCTR_PQ_F32 .. HCTR_PQ_I64 */
+  uint32_t esize;   /* 4 or 8 */
+} hctr_parquet_column;
+typedef struct {
+  uint32_t kind;             /* HCTR_PQ_SEG_* */
+  uint32_t out_kind;         /* HCTR_PQ_OUT_* (GROUP: keys are int64 without addend) */
+  uint32_t list0, ncols;     /* the segment's columns: entries [list0, list0 + ncols) of the lists;
+                                GROUP: ALL lookups of the collection, in lookup order */
+  uint32_t sample0, sample1; /* TILE: samples of the batch */
+  uint32_t out0;             /* index into out_offsets: TILE data; RAGGED row offsets; GROUP bucket
+                                range (ncols * batch + 1 int64); HCTR_PQ_NO_OUTPUT = not written */
+  uint32_t out1;             /* RAGGED / GROUP: keys */
+  uint32_t group;            /* RAGGED: lanes per sample, a power of two 1..64 */
+  uint32_t lookup;           /* GROUP: which lookup of the collection this segment writes */
+  uint32_t item0, n_items;   /* work items (workgroup passes) of the launch taken by this segment:
+                                TILE ceil(samples / ts) * ceil(ncols / 32) with ts = 64 *
+                                min(16, 32 / min(ncols, 32)), RAGGED
+                                ceil(batch / (256 / group)), GROUP ceil(batch / 256); item0 counts
+                                up over the segments, n_items of the launch is their sum */
+} hctr_parquet_segment;
+#define HCTR_PQ_DECODE_MAX_BLOCKS 1024
+#define HCTR_PQ_DECODE_MAX_SEGMENTS 4096
+#define HCTR_PQ_TILE_SAMPLES 64
+#define HCTR_PQ_TILE_COLS 32
+/* at most HCTR_PQ_DECODE_MAX_BLOCKS workgroups are launched, further items are grid-strided */
+int hctr_parquet_decode(const void* slot, const void* columns, int n_columns, const void* plan,
+                        int n_segments, int n_list, size_t n_items, size_t rows, size_t first_row,
+                        size_t batch, void* out_base, const uint64_t* out_offsets, int n_outputs,
+                        hctr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

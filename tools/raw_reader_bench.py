@@ -151,16 +151,17 @@ def reader_level(path, B, nb, hot, sizes, ebc, i64):
     return res
 
 
-def build_model(path, B, nb, hot, sizes, kind):
+def build_model(path, B, nb, hot, sizes, kind, rp=None):
     """bench.py's model of the shape: DLRM (one-hot, concat lookups, Interaction) or the MLPerf
-    DCNv2 (multi-hot, sum, MultiCross), embedding_collection, mixed precision, SGD"""
+    DCNv2 (multi-hot, sum, MultiCross), embedding_collection, mixed precision, SGD.  rp: other
+    DataReaderParams than the Raw file's (tools/parquet_reader_bench.py)"""
     solver = hugectr.CreateSolver(max_eval_batches=1, batchsize_eval=B, batchsize=B, lr=0.005,
                                   vvgpu=[[0]], repeat_dataset=True, i64_input_key=False,
                                   use_mixed_precision=True, scaler=1024.0,
                                   use_embedding_collection=True)
     opt = hugectr.CreateOptimizer(optimizer_type=hugectr.Optimizer_t.SGD,
                                   update_type=hugectr.Update_t.Local, atomic_update=True)
-    rp = hugectr.DataReaderParams(
+    rp = rp or hugectr.DataReaderParams(
         data_reader_type=hugectr.DataReaderType_t.RawAsync, source=[path], eval_source="",
         check_type=hugectr.Check_t.Non, num_samples=B * nb, eval_num_samples=0,
         slot_size_array=sizes, async_param=async_param())
