@@ -1,5 +1,5 @@
-"""CPU: the host-side halves of the Parquet reader's device path (hugectr_amd/data.py) -- the plan
-hctr_parquet_decode gets, the staging of a chunked file into a file slot -- as pure numpy against
+"""CPU: the host-side halves of the Parquet reader's device path (hugectr_amd/reader_parquet.py) --
+the plan hctr_parquet_decode gets, the staging of a chunked file into a file slot -- as pure numpy against
 pq.read_table(...).combine_chunks(); and what the reader does on every device: decode="host",
 cache_batches, stats(), the schema check, close()."""
 import gc
@@ -88,7 +88,7 @@ def test_plan_lists_every_output_once():
 def test_staging_of_a_chunked_file(files):
     """rebased offsets, values and descriptor table against combine_chunks()"""
     import pyarrow.parquet as pq
-    from hugectr_amd import _lib, data
+    from hugectr_amd import _lib, data, reader_parquet
     path = open(files).read().split()[1]
     names = po.LABELS + po.CONTS + po.CATS
     offs = np.concatenate([[0], np.cumsum(po.SIZES)[:-1]])
@@ -97,7 +97,7 @@ def test_staging_of_a_chunked_file(files):
             "outputs": pl["outputs"]}
     t = pq.read_table(path, columns=names, use_threads=False)
     assert t.column("a1").num_chunks == 5, "the fixture must arrive in several chunks"
-    _, rows, nv = data._parquet_file_info(path)
+    _, rows, nv = reader_parquet._parquet_file_info(path)
     bound = data.parquet_slot_layout(_columns(), len(pl["outputs"]), B, rows,
                                      [nv[n] for n in names])[2]
     buf = np.full(bound, 0xAB, np.uint8)
@@ -110,7 +110,7 @@ def test_staging_of_a_chunked_file(files):
         arr = whole.column(n).chunk(0)
         assert (int(desc[i]["ptype"]), int(desc[i]["esize"])) == (pt, esz)
         assert int(desc[i]["values"]) % 8 == 0
-        dt = data._pq_numpy(pt)
+        dt = reader_parquet._pq_numpy(pt)
         if is_list:
             o = arr.offsets.to_numpy().astype(np.int64)
             want = arr.values.to_numpy()[o[0]:o[-1]]
@@ -183,7 +183,7 @@ def test_schema_check_chooses_the_host_path(files, tmp_path):
 
 
 def test_close_twice_and_dropped_readers_leave_no_threads(files):
-    from hugectr_amd import data
+    from hugectr_amd import reader_parquet, reader_prefetch
     r = _host(files)
     r.next_batch()
     r.close()
@@ -191,13 +191,15 @@ def test_close_twice_and_dropped_readers_leave_no_threads(files):
     with pytest.raises(RuntimeError):
         r.next_batch()
     # the staging workers hold no reference to their reader: they end with their queue
+    import functools
     import queue
     tasks = queue.Queue()
-    th = threading.Thread(target=data._stage_worker, args=(tasks,), daemon=True,
+    th = threading.Thread(target=reader_prefetch._worker, args=(tasks,), daemon=True,
                           name="hctr-parquet-stage-test")
     th.start()
-    latch = data._Latch(1)
-    tasks.put((None, np.zeros(16, np.uint8), "/nonexistent.parquet", {"names": []}, latch))
+    latch = reader_prefetch._Latch(1)
+    tasks.put((functools.partial(reader_parquet._stage_file, np.zeros(16, np.uint8),
+                                 "/nonexistent.parquet", {"names": []}), None, latch))
     latch.done.wait()
     assert latch.error is not None        # (handed to next_batch(), the worker lives on)
     tasks.put(None)

@@ -99,21 +99,17 @@ def reader_level(files, B, nb, hot, sizes, ebc, i64):
     res["wait_ms_per_batch"] = (r.stats()["wait_ms"] - w0) / n
     res["stats"] = r.stats()
     # ---- the stages alone, on the file the reader is in
-    fj, pl = r._fjobs[0], r._plan
-    st, slot = fj["res"], fj["slot"]
+    u, pl = r.head_unit(), r.plan
+    st, slot = u["latch"].result, u["slot"]
     n_out, raw, pin = len(pl["outputs"]), slot["dev"], slot["pin"]
     arena = torch.empty(int(st["tab"][0, n_out]), dtype=torch.uint8, device=dev)
-    tab = raw[st["tab_off"]:]
     used_in = sum(int(st["cnt"][0, k]) * o["esize"] for k, o in enumerate(pl["outputs"]))
     res["file_bytes_staged"], res["bytes_out"] = int(st["used"]), used_in
     res["bytes_in"] = int(st["used"]) * B // max(st["rows"], 1)
     res["segments"], res["work_items"] = len(pl["segments"]), pl["n_items"]
     res["lanes_per_sample"] = sorted({int(g) for g in pl["segments"]["group"] if g})
     torch.cuda.synchronize()
-    res["decode_kernel_ms"] = rrb.event_ms(lambda: _lib.check(_lib.lib.hctr_parquet_decode(
-        _lib.ptr(raw), _lib.ptr(raw), len(r._columns), _lib.ptr(pl["device"]), len(pl["segments"]),
-        len(pl["list"]), pl["n_items"], st["rows"], 0, B, _lib.ptr(arena), _lib.ptr(tab), n_out,
-        _lib.stream_ptr())))
+    res["decode_kernel_ms"] = rrb.event_ms(lambda: r.decode_into(arena, u, 0, _lib.stream_ptr()))
     src = torch.empty(res["bytes_in"], dtype=torch.uint8, device=dev)
     src2, arena2 = torch.empty_like(src), torch.empty_like(arena)
     res["d2d_copy_bytes_in_ms"] = rrb.event_ms(lambda: src2.copy_(src))

@@ -126,15 +126,14 @@ def reader_level(path, B, nb, hot, sizes, ebc, i64):
     res["unthrottled_ms_per_batch"] = (time.perf_counter() - t_begin) / n * 1e3
     res["wait_ms_per_batch"] = (r.stats()["wait_ms"] - w0) / n
     res["stats"] = r.stats()
-    pl = r._plan
-    pin, _, raw = r._slots[0]
+    # ---- the stages alone, on the buffers of the batch the reader is at
+    u, pl = r.head_unit(), r.plan
+    pin, raw = u["slot"]["pin"], u["slot"]["dev"]
     arena = torch.empty(pl["arena_bytes"], dtype=torch.uint8, device=dev)
     res["bytes_in"], res["bytes_out"] = raw.numel() * 4, int(pl["arena_bytes"])
     res["segments"] = len(pl["segments"])
     torch.cuda.synchronize()
-    res["decode_kernel_ms"] = event_ms(lambda: _lib.check(_lib.lib.hctr_raw_decode(
-        _lib.ptr(raw), B, r.width, _lib.ptr(pl["device"]), len(pl["segments"]), _lib.ptr(arena),
-        _lib.stream_ptr())))
+    res["decode_kernel_ms"] = event_ms(lambda: r.decode_into(arena, u, 0, _lib.stream_ptr()))
     raw2, arena2 = torch.empty_like(raw), torch.empty_like(arena)
     res["d2d_copy_bytes_in_ms"] = event_ms(lambda: raw2.copy_(raw))
     res["d2d_copy_bytes_out_ms"] = event_ms(lambda: arena2.copy_(arena))
@@ -144,7 +143,7 @@ def reader_level(path, B, nb, hot, sizes, ebc, i64):
     t = []
     for k in range(5):   # one worker's share of a fill is 1 / threads of this
         t0 = time.perf_counter()
-        np.copyto(r._slots[0][1], r.data[(k % nb) * B:(k % nb + 1) * B])
+        np.copyto(u["slot"]["np"], r.data[(k % nb) * B:(k % nb + 1) * B])
         t.append(time.perf_counter() - t0)
     res["memmap_to_pinned_one_thread_ms"] = med(t)
     r.close()
