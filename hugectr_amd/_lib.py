@@ -28,6 +28,7 @@ UPDATE_LOCAL, UPDATE_GLOBAL, UPDATE_LAZY_GLOBAL = range(3)
 EMB_DISTRIBUTED, EMB_LOCALIZED = 0, 1
 KEY_U32, KEY_I64 = 0, 1
 F32, F16, BF16 = 0, 1, 2
+FTRL_SEG_BLOCK_ELEMS = 1024  # HCTR_FTRL_SEG_BLOCK_ELEMS: elements per block of hctr_ftrl_segments
 
 
 class EmbeddingParams(Structure):
@@ -249,6 +250,10 @@ _SIGNATURES = {
     "hctr_dense_grad_finish": (c_int, [_P, c_int, c_size_t, c_int, c_float, c_float, _P, _P]),
     "hctr_sum_groups": (c_int, [c_int, c_size_t, _P, c_int, _P, _P]),
     "hctr_sgd_shadow": (c_int, [c_size_t, c_float, c_float, _P, _P, _P, c_int, _P]),
+    "hctr_ftrl_shadow": (c_int, [c_size_t, c_float, c_float, c_float, c_float, c_float, _P, _P, _P,
+                                 _P, _P, c_int, _P]),
+    "hctr_ftrl_segments": (c_int, [_P, c_int, c_size_t, c_float, c_float, c_float, c_float,
+                                   c_float, _P, _P, _P, _P]),
     "hctr_bce_loss_workspace_bytes": (c_size_t, []),
     "hctr_bce_loss": (c_int, [c_size_t, _P, _P, c_float, _P, _P, _P, c_int, _P]),
     "hctr_convert_transpose16": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, c_int, _P]),

@@ -1,6 +1,6 @@
 // dense_ops.hip -- the dense ops next to the GEMMs: the DCN cross layers' element-wise kernels and
-// the MLP edge kernels (ReLU backward + bias gradient, split-K group sums, SGD with the 16-bit shadow
-// copy, BCE loss, the logit head, the skinny first layer).  The dot interaction is interaction.hip,
+// the MLP edge kernels (ReLU backward + bias gradient, split-K group sums, SGD / Ftrl with the 16-bit
+// shadow copy, BCE loss, the logit head, the skinny first layer).  The dot interaction is interaction.hip,
 // the cross layers' GEMMs are cross_gemm.hip.
 //
 // MultiCrossLayer<T> (DCN v1): R/HugeCTR/src/layers/multi_cross_layer.cu:582-601 (fprop functor),
@@ -382,6 +382,112 @@ __global__ void __launch_bounds__(kBlock)
     const unsigned lo = (unsigned)H::from_f32(wv[0]) | ((unsigned)H::from_f32(wv[1]) << 16);
     const unsigned hi = (unsigned)H::from_f32(wv[2]) | ((unsigned)H::from_f32(wv[3]) << 16);
     reinterpret_cast<uint2*>(w16)[i] = make_uint2(lo, hi);
+  }
+}
+
+// ================================================================================================
+// Dense Ftrl (ftrl_update_kernel and its launch, R/HugeCTR/src/optimizers/ftrl_optimizer.cu:28-43,
+// 92-93).  Like sgd_apply, the step is ONE expression for every kernel that takes it (f32x4 or
+// float), so a parameter rounds the same whichever kernel updates it.
+//   g = grad * grad_scale;  n' = n + g*g;  z' = z + g + (sqrt(n + eps) - sqrt(n' + eps)) * w / lr
+//   w' = |z'| > lambda1 ? (lambda1 * sgn(z') - z') / (sqrt(n' + eps) / lr + l2) : 0
+// with eps = FLT_EPSILON, l2 = lambda2 + beta / lr (formed once on the host) and sgn = +1 for a
+// clear sign bit.  A parameter whose gradient is 0 on the first step becomes 0: z' stays 0.
+// ================================================================================================
+struct FtrlHp {
+  float lr, lambda1, l2, grad_scale;
+};
+
+__device__ __forceinline__ float ftrl_apply(float w, float& z, float& n, float grad, FtrlHp h) {
+  constexpr float eps = 1.1920928955078125e-7f;  // FLT_EPSILON
+  const float g = grad * h.grad_scale;
+  const float n_new = n + g * g;
+  const float root = sqrtf(n_new + eps);
+  const float z_new = z + g + (sqrtf(n + eps) - root) * w / h.lr;
+  const float x = (__builtin_signbitf(z_new) ? -h.lambda1 : h.lambda1) - z_new;
+  const float y = root / h.lr + h.l2;
+  n = n_new;
+  z = z_new;
+  return fabsf(z_new) > h.lambda1 ? x / y : 0.f;
+}
+
+__device__ __forceinline__ f32x4 ftrl_apply(f32x4 w, f32x4& z, f32x4& n, f32x4 grad, FtrlHp h) {
+  f32x4 out;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    float ze = z[e], ne = n[e];
+    out[e] = ftrl_apply(w[e], ze, ne, grad[e], h);
+    z[e] = ze;
+    n[e] = ne;
+  }
+  return out;
+}
+
+// the flat form: the twin of sgd_shadow_kernel (SHADOW 0: no 16-bit copy, 1: fp16, 2: bf16)
+template <int SHADOW>
+__global__ void __launch_bounds__(kBlock)
+    ftrl_shadow_kernel(size_t n4, FtrlHp h, float* __restrict__ w, float* __restrict__ z,
+                       float* __restrict__ nacc, const float* __restrict__ g,
+                       unsigned short* __restrict__ w16) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4;
+       i += (size_t)gridDim.x * kBlock) {
+    f32x4 zv = reinterpret_cast<f32x4*>(z)[i];
+    f32x4 nv = reinterpret_cast<f32x4*>(nacc)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    const f32x4 wv = ftrl_apply(reinterpret_cast<f32x4*>(w)[i], zv, nv, gv, h);
+    reinterpret_cast<f32x4*>(w)[i] = wv;
+    reinterpret_cast<f32x4*>(z)[i] = zv;
+    reinterpret_cast<f32x4*>(nacc)[i] = nv;
+    if (SHADOW) {
+      using H = H16<SHADOW == 2>;
+      const unsigned lo = (unsigned)H::from_f32(wv[0]) | ((unsigned)H::from_f32(wv[1]) << 16);
+      const unsigned hi = (unsigned)H::from_f32(wv[2]) | ((unsigned)H::from_f32(wv[3]) << 16);
+      reinterpret_cast<uint2*>(w16)[i] = make_uint2(lo, hi);
+    }
+  }
+}
+
+// the segmented form: parameter tensors that do not live in one buffer; their gradients and the
+// state do (flat g / z / n, a segment's elements at `off`).  A block takes kFtrlSegElems elements
+// of one segment and finds the segment like dense_grad_finish_kernel does.  Groups of 4 go through
+// the vector form when the segment allows it (w 16-byte aligned, off % 4 == 0), the tail and
+// everything else through the scalar form of the same expression.
+constexpr int kFtrlSegElems = HCTR_FTRL_SEG_BLOCK_ELEMS;
+static_assert(kFtrlSegElems == kBlock * 4, "a thread takes 4 elements");
+
+__global__ void __launch_bounds__(kBlock)
+    ftrl_segments_kernel(const hctr_ftrl_seg* __restrict__ segs, int nseg, FtrlHp h,
+                         float* __restrict__ z, float* __restrict__ nacc,
+                         const float* __restrict__ g) {
+  int si = -1;
+  for (int base = 0; base < nseg; base += 64) {
+    const int t = base + (int)(threadIdx.x & 63);
+    const bool in = t < nseg && segs[t].block0 <= (long long)blockIdx.x;
+    si += (int)__popcll(__ballot(in));
+  }
+  if (si < 0) return;  // (a table whose first segment does not start at block 0)
+  const hctr_ftrl_seg sg = segs[si];
+  const size_t cnt = (size_t)sg.n, off = (size_t)sg.off;
+  float* w = reinterpret_cast<float*>(sg.w);
+  const size_t e0 = ((size_t)((long long)blockIdx.x - sg.block0) * kBlock + threadIdx.x) * 4;
+  if (e0 >= cnt) return;
+  const bool vec = (sg.w & 15) == 0 && (off & 3) == 0 && e0 + 4 <= cnt;
+  if (vec) {
+    f32x4 zv = *reinterpret_cast<f32x4*>(z + off + e0);
+    f32x4 nv = *reinterpret_cast<f32x4*>(nacc + off + e0);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + off + e0);
+    const f32x4 wv = ftrl_apply(*reinterpret_cast<f32x4*>(w + e0), zv, nv, gv, h);
+    *reinterpret_cast<f32x4*>(w + e0) = wv;
+    *reinterpret_cast<f32x4*>(z + off + e0) = zv;
+    *reinterpret_cast<f32x4*>(nacc + off + e0) = nv;
+    return;
+  }
+  const size_t e1 = e0 + 4 < cnt ? e0 + 4 : cnt;
+  for (size_t e = e0; e < e1; e++) {
+    float zs = z[off + e], ns = nacc[off + e];
+    w[e] = ftrl_apply(w[e], zs, ns, g[off + e], h);
+    z[off + e] = zs;
+    nacc[off + e] = ns;
   }
 }
 
@@ -1242,6 +1348,59 @@ int hctr_sgd_shadow(size_t n, float lr, float grad_scale, float* w, const float*
   else
     hipLaunchKernelGGL(sgd_shadow_kernel<false>, grid, dim3(kBlock), 0, s, n / 4, lr, grad_scale,
                        w, g, (unsigned short*)w16);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+static int ftrl_check(float lr, float beta, float lambda1, float lambda2, float grad_scale) {
+  HCTR_REQUIRE(lr > 0.f && lr < INFINITY, "ftrl: lr must be positive and finite");
+  HCTR_REQUIRE(beta >= 0.f && lambda1 >= 0.f && lambda2 >= 0.f,
+               "ftrl: beta, lambda1 and lambda2 must not be negative");
+  HCTR_REQUIRE(grad_scale == grad_scale && fabsf(grad_scale) < INFINITY, "ftrl: grad_scale");
+  return HCTR_OK;
+}
+
+static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+int hctr_ftrl_shadow(size_t n, float lr, float beta, float lambda1, float lambda2, float grad_scale,
+                     float* w, float* z, float* nacc, const float* g, void* w16, int dtype,
+                     hctr_stream_t stream) {
+  HCTR_REQUIRE(n % 4 == 0, "n must be a multiple of 4");
+  HCTR_TRY(ftrl_check(lr, beta, lambda1, lambda2, grad_scale));
+  HCTR_REQUIRE(!w16 || dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16,
+               "16-bit shadow dtypes only");
+  if (n == 0) return HCTR_OK;
+  HCTR_REQUIRE(w && z && nacc && g, "null pointer");
+  HCTR_REQUIRE(aligned16(w) && aligned16(z) && aligned16(nacc) && aligned16(g) && aligned16(w16),
+               "16-byte aligned buffers");
+  hipStream_t s = as_stream(stream);
+  const FtrlHp h = {lr, lambda1, lambda2 + beta / lr, grad_scale};
+  const dim3 grid(grid_for(n / 4, kBlock, 4096));
+  if (!w16)
+    hipLaunchKernelGGL(ftrl_shadow_kernel<0>, grid, dim3(kBlock), 0, s, n / 4, h, w, z, nacc, g,
+                       (unsigned short*)nullptr);
+  else if (dtype == HCTR_EMB_F16)
+    hipLaunchKernelGGL(ftrl_shadow_kernel<1>, grid, dim3(kBlock), 0, s, n / 4, h, w, z, nacc, g,
+                       (unsigned short*)w16);
+  else
+    hipLaunchKernelGGL(ftrl_shadow_kernel<2>, grid, dim3(kBlock), 0, s, n / 4, h, w, z, nacc, g,
+                       (unsigned short*)w16);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_ftrl_segments(const hctr_ftrl_seg* segs, int nseg, size_t nblocks, float lr, float beta,
+                       float lambda1, float lambda2, float grad_scale, float* z, float* nacc,
+                       const float* g, hctr_stream_t stream) {
+  HCTR_REQUIRE(nseg >= 0 && nblocks <= 0x7FFFFFFFu, "ftrl segments: segment / block count");
+  HCTR_TRY(ftrl_check(lr, beta, lambda1, lambda2, grad_scale));
+  if (nseg == 0 || nblocks == 0) return HCTR_OK;
+  HCTR_REQUIRE(segs && z && nacc && g, "null pointer");
+  HCTR_REQUIRE(aligned16(z) && aligned16(nacc) && aligned16(g), "16-byte aligned buffers");
+  hipStream_t s = as_stream(stream);
+  const FtrlHp h = {lr, lambda1, lambda2 + beta / lr, grad_scale};
+  hipLaunchKernelGGL(ftrl_segments_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, s, segs, nseg,
+                     h, z, nacc, g);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }

@@ -19,6 +19,10 @@ kernels).  What this module fixes is how they are *issued* for the DLRM shapes
   sums, the launch adds them in the same order as the kernels it replaces and either writes
   `flat_g` or takes the SGD step and refreshes the 16-bit copy.  A module without a
   `DenseGradFinish` finishes layer by layer as before.
+* `Optimizer_t.Ftrl` for the dense layers (torch has none): `FusedMLP.ftrl_step` on the flat
+  buffers (`hctr_ftrl_shadow`, one launch per module, 16-bit copy included) and `DenseFtrl`, a
+  torch optimizer over parameters that do not live in one buffer (`hctr_ftrl_segments`, one launch
+  per step).
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ from typing import List, Sequence
 
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import FTRL_SEG_BLOCK_ELEMS, check, lib, ptr, stream_ptr
 
 _DT16 = {torch.float16: 1, torch.bfloat16: 2}  # hctr_emb_dtype_t
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
@@ -309,18 +313,20 @@ class FusedMLP(torch.nn.Module):
         self._w16: List[torch.Tensor] = []
         self._b16: List[torch.Tensor] = []
         self.flat_w = self.flat_g = self.flat_w16 = None
+        self.flat_z = self.flat_n = None  # Ftrl state, only after flatten(ftrl_state=True)
         self._gw: List[torch.Tensor] = []
         self._gb: List[torch.Tensor] = []
         self._lw: List[_LayerWS] = []
         self._finisher = None  # a DenseGradFinish: backward leaves partial sums for its launch
         self._loss_out = None
 
-    def flatten(self):
+    def flatten(self, ftrl_state: bool = False):
         """Move masters, gradients and 16-bit copies into three flat buffers (parameters become
         views).  Afterwards backward writes gradients straight into `flat_g`, `sgd_step` is one
         kernel (update + shadow refresh), and a data-parallel all-reduce runs on `flat_g` as is.
         The backward's workspaces (split-K partial products, bias tile partials) are allocated
-        here, once per layer."""
+        here, once per layer.  ftrl_state: also the Ftrl state `flat_z` / `flat_n` (fp32, zero) that
+        `ftrl_step` needs; nothing is allocated for them otherwise."""
         dev = self.weights[0].device
         sizes = [p.numel() for p in list(self.weights) + list(self.biases)]
         offs, tot = [], 0
@@ -330,6 +336,9 @@ class FusedMLP(torch.nn.Module):
         self.flat_w = torch.zeros(tot, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(tot, dtype=torch.float32, device=dev)
         self.flat_w16 = torch.zeros(tot, dtype=self.dtype, device=dev)
+        if ftrl_state:
+            self.flat_z = torch.zeros(tot, dtype=torch.float32, device=dev)
+            self.flat_n = torch.zeros(tot, dtype=torch.float32, device=dev)
         params = list(self.weights) + list(self.biases)
         views16 = []
         self._gw, self._gb = [], []
@@ -344,6 +353,7 @@ class FusedMLP(torch.nn.Module):
         self._gw, self._gb = gviews[:nl], gviews[nl:]
         self.flat_w16.copy_(self.flat_w)
         self._offs = (offs[:nl], offs[nl:])
+        self._spans = list(zip(offs, sizes))  # (offset, count) per parameter, parameters() order
         # split-K partial products [groups][out][in] of every layer, slices 512-byte aligned
         need = [self.wgrad_groups * w.numel() if min(w.shape) >= 8 else 0 for w in self.weights]
         starts, at = [], 0
@@ -359,6 +369,20 @@ class FusedMLP(torch.nn.Module):
         check(lib.hctr_sgd_shadow(self.flat_w.numel(), float(lr), float(grad_scale),
                                   ptr(self.flat_w), ptr(self.flat_g), ptr(self.flat_w16),
                                   _DT16[self.dtype], stream_ptr()))
+
+    def ftrl_step(self, lr: float, beta: float, lambda1: float, lambda2: float,
+                  grad_scale: float = 1.0):
+        """the Ftrl step on the flat buffers and the refresh of the 16-bit copy, one launch (after
+        flatten(ftrl_state=True))"""
+        assert self.flat_z is not None, "ftrl_step: flatten(ftrl_state=True) first"
+        check(lib.hctr_ftrl_shadow(self.flat_w.numel(), float(lr), float(beta), float(lambda1),
+                                   float(lambda2), float(grad_scale), ptr(self.flat_w),
+                                   ptr(self.flat_z), ptr(self.flat_n), ptr(self.flat_g),
+                                   ptr(self.flat_w16), _DT16[self.dtype], stream_ptr()))
+
+    def ftrl_state(self):
+        """[(z, n)] views per parameter, in parameters() order"""
+        return [(self.flat_z[o:o + c], self.flat_n[o:o + c]) for o, c in self._spans]
 
     def refresh_shadow(self):
         """call after every optimizer step (and once after .to(device))"""
@@ -498,3 +522,109 @@ class DenseGradFinish:
                 loss, m._loss_out = m._loss_out, None
         check(lib.hctr_dense_grad_finish(ptr(self._table), self._nseg, self._nblocks, int(sgd),
                                          float(lr), float(grad_scale), ptr(loss), stream_ptr()))
+
+
+class DenseFtrl(torch.optim.Optimizer):
+    """Ftrl for dense parameters that do not live in one buffer (fp32 models, InnerProduct,
+    MultiCross, WeightMultiply, FmOrder2 weights): FtrlOptimizer of the reference
+    (R/HugeCTR/src/optimizers/ftrl_optimizer.cu), the whole step as ONE launch
+    (`hctr_ftrl_segments`).
+
+    The optimizer owns three flat fp32 buffers over all its parameters -- gradients `g`, and the
+    state `z` / `n` (zero at the start) -- every parameter's span starting 16-byte aligned.  Each
+    parameter's `.grad` is, for good, a view into `g`: autograd accumulates into an existing
+    `.grad` in place, and `zero_grad` zeroes the buffer with one call whatever `set_to_none` says,
+    so the gradient addresses never change and the device-resident segment table is built once
+    (again only if a parameter's storage moved).  `step()` copies no table and never waits for
+    the device.  A `.grad` somebody replaced or dropped is copied back into its view and
+    re-attached by the next `step()` / `zero_grad()`.
+
+    `scaler`: the loss scaler the gradients carry; the step divides by it (grad_scale = 1 / scaler),
+    so the caller does not.  `lr` lives in `param_groups`.  The state dict holds `z` and `n` per
+    parameter, in parameter order, and no hyper-parameters."""
+
+    def __init__(self, params, lr: float, beta: float = 0.0, lambda1: float = 0.0,
+                 lambda2: float = 0.0, scaler: float = 1.0):
+        super().__init__(params, dict(lr=lr, beta=beta, lambda1=lambda1, lambda2=lambda2))
+        assert len(self.param_groups) == 1, "DenseFtrl: one parameter group"
+        self.scaler = float(scaler)
+        self._params = list(self.param_groups[0]["params"])
+        for p in self._params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError("DenseFtrl: contiguous fp32 parameters on the GPU only")
+        dev = self._params[0].device
+        self._spans, tot = [], 0
+        for p in self._params:
+            self._spans.append((tot, p.numel()))
+            tot += (p.numel() + 3) // 4 * 4  # every span starts 16-byte aligned
+        self.flat_g = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.flat_z = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.flat_n = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self._gviews = [self.flat_g[o:o + c].view_as(p) for p, (o, c) in zip(self._params, self._spans)]
+        self._attach()
+        self._sig = self._table = None
+        self._nblocks = 0
+
+    def _attach(self, keep: bool = True):
+        """every parameter's .grad is its view again; keep: what a foreign .grad held goes there"""
+        for p, v in zip(self._params, self._gviews):
+            if p.grad is not v:
+                if keep and p.grad is not None:
+                    v.copy_(p.grad)
+                p.grad = v
+
+    def _build(self, sig):
+        import numpy as np
+        per = FTRL_SEG_BLOCK_ELEMS
+        t = np.zeros((len(sig), 4), dtype=np.int64)
+        block0 = 0
+        for r, (w, (off, cnt)) in enumerate(zip(sig, self._spans)):
+            t[r] = (w, off, cnt, block0)
+            block0 += (cnt + per - 1) // per
+        self._table = torch.from_numpy(t).to(self.flat_g.device)
+        self._sig, self._nblocks = sig, block0
+
+    def ftrl_state(self):
+        """[(z, n)] views per parameter, in parameter order"""
+        return [(self.flat_z[o:o + c], self.flat_n[o:o + c]) for o, c in self._spans]
+
+    def zero_grad(self, set_to_none: bool = True):
+        self._attach(keep=False)
+        self.flat_g.zero_()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        assert closure is None, "DenseFtrl: no closure"
+        self._attach()
+        sig = tuple(p.data_ptr() for p in self._params)
+        if sig != self._sig:
+            self._build(sig)
+        h = self.param_groups[0]
+        check(lib.hctr_ftrl_segments(ptr(self._table), len(sig), self._nblocks, float(h["lr"]),
+                                     float(h["beta"]), float(h["lambda1"]), float(h["lambda2"]),
+                                     1.0 / self.scaler, ptr(self.flat_z), ptr(self.flat_n),
+                                     ptr(self.flat_g), stream_ptr()))
+
+    def state_dict(self):
+        return ftrl_state_dict(self.ftrl_state())
+
+    def load_state_dict(self, state_dict):
+        load_ftrl_state_dict(self.ftrl_state(), state_dict)
+
+
+def ftrl_state_dict(state):
+    """the dense Ftrl state as a checkpoint holds it: `z` and `n` per parameter, in parameter
+    order, flat fp32 on the host -- the same for `DenseFtrl` and for flattened FusedMLPs"""
+    return {"optimizer": "Ftrl", "z": [z.detach().cpu().clone() for z, _ in state],
+            "n": [n.detach().cpu().clone() for _, n in state]}
+
+
+def load_ftrl_state_dict(state, sd):
+    if sd.get("optimizer") != "Ftrl" or len(sd["z"]) != len(state) or len(sd["n"]) != len(state):
+        raise ValueError("dense Ftrl state: the file does not match the model's parameters")
+    for (z, n), zs, ns in zip(state, sd["z"], sd["n"]):
+        if zs.numel() != z.numel() or ns.numel() != n.numel():
+            raise ValueError("dense Ftrl state: the file does not match the model's parameters")
+    for (z, n), zs, ns in zip(state, sd["z"], sd["n"]):
+        z.copy_(zs.reshape(-1))
+        n.copy_(ns.reshape(-1))

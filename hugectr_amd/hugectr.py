@@ -26,7 +26,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .dense import DenseGradFinish, FusedMLP, bce_with_logits
+from .dense import (DenseFtrl, DenseGradFinish, FusedMLP, bce_with_logits, ftrl_state_dict,
+                    load_ftrl_state_dict)
 from .embedding import OptParams, SparseEmbeddingHash, backward_reorder, forward_reorder
 from .embedding_collection import (DataParallelCollection, EmbeddingCollection,  # noqa: F401
                                    EmbeddingCollectionConfig, EmbeddingTableConfig)
@@ -702,6 +703,10 @@ class Model:
                           ((not self.ebc_configs and len(self._loss_layers) == 1 and
                             (self.bpg <= 8192 or env == "1")) or
                            (ebc_graph and (self.bpg <= 32768 or env == "1"))))
+        # dense Ftrl stays out of the captured step: the capture drops every parameter's .grad,
+        # DenseFtrl's gradients live in persistent views (DESIGN.md "Dense-tower glue")
+        if Optimizer_t(self.opt.optimizer_type) == Optimizer_t.Ftrl and self._dense_params:
+            self._graph_ok = False
         self._graph, self._graph_wait = None, 0
         self._dense_opt = self._make_dense_opt()
         # Model.reader_override: anything with next_batch(train) / has_eval() handing out batches
@@ -728,8 +733,10 @@ class Model:
     def _plan_execution(self):
         """what the training step may fuse and overlap, decided once from the graph:
 
-        * dense SGD on flat buffers: when every trainable dense tensor lives in a 16-bit FusedMLP
-          and the optimizer is SGD (the reference's DLRM configurations), the backward's
+        * dense SGD / Ftrl on flat buffers: when every trainable dense tensor lives in a 16-bit
+          FusedMLP and the optimizer is SGD (the reference's DLRM configurations) or Ftrl (its
+          samples/ftrl; there the finish launch always writes `flat_g` and `hctr_ftrl_shadow`
+          takes the step per MLP, after the all-reduce on N > 1), the backward's
           kernels leave their partial sums and ONE launch per step (`hctr_dense_grad_finish`,
           `DenseGradFinish`) finishes every gradient of every MLP: on one GPU straight through the
           SGD step and the refresh of the 16-bit copies; on N > 1 into one flat gradient buffer
@@ -760,12 +767,15 @@ class Model:
         in_mlps = sum(sum(q.numel() for q in m.parameters()) for m in mlps)
         total = sum(q.numel() for q in self._dense_params)
         self._flat_mlps = []
+        self._flat_ftrl = Optimizer_t(self.opt.optimizer_type) == Optimizer_t.Ftrl
         if (fused_ok and mlps and in_mlps == total and s.use_mixed_precision and
-                Optimizer_t(self.opt.optimizer_type) == Optimizer_t.SGD):
+                Optimizer_t(self.opt.optimizer_type) in (Optimizer_t.SGD, Optimizer_t.Ftrl)):
             for m in mlps:
-                m.flatten()
+                m.flatten(ftrl_state=self._flat_ftrl)
             self._flat_mlps = mlps
             self._dense_opt = None
+            for q in self._dense_params:  # (a DenseFtrl made before the plan left its views there)
+                q.grad = None
             # every partial sum the backward's kernels leave is finished by one launch per step
             self._dense_finish = DenseGradFinish(mlps)
         # -- logit head -----------------------------------------------------------------------------
@@ -1233,6 +1243,9 @@ class Model:
         if t == Optimizer_t.Nesterov:
             return torch.optim.SGD(self._dense_params, lr=lr, momentum=max(o.momentum_factor, 1e-6),
                                    nesterov=True)
+        if t == Optimizer_t.Ftrl:  # torch has none: this library's own (dense.DenseFtrl)
+            return DenseFtrl(self._dense_params, lr=lr, beta=o.beta, lambda1=o.lambda1,
+                             lambda2=o.lambda2, scaler=self.solver.scaler)
         return torch.optim.SGD(self._dense_params, lr=lr)
 
     # -- execution ---------------------------------------------------------------------------------
@@ -1788,26 +1801,33 @@ class Model:
         if self._flat_mlps:
             # one GPU: the finish launch takes the partial sums through the SGD step; N > 1 (or no
             # step): it leaves the gradients in flat_g, the all-reduce and hctr_sgd_shadow follow
-            one = self.world == 1 and not frozen
+            # Ftrl: always gradients first, then (after the all-reduce: ONE step on the summed
+            # gradient) hctr_ftrl_shadow per MLP
+            one = self.world == 1 and not frozen and not self._flat_ftrl
             if reduced is None:
                 self._dense_finish.finish(one, self._lr, 1.0 / self.solver.scaler)
             if frozen or one:
                 return
             for m in self._flat_mlps:  # gradients are shares of the global-batch mean: plain sum
-                if reduced is None:
+                if reduced is None and self.world > 1:
                     _all_reduce(m.flat_g)
-                m.sgd_step(self._lr, 1.0 / self.solver.scaler)
+                if self._flat_ftrl:
+                    o = self.opt
+                    m.ftrl_step(self._lr, o.beta, o.lambda1, o.lambda2, 1.0 / self.solver.scaler)
+                else:
+                    m.sgd_step(self._lr, 1.0 / self.solver.scaler)
             return
         if self._dense_opt is None:
             return
         if frozen:
             self._dense_opt.zero_grad(set_to_none=True)
             return
+        ftrl = isinstance(self._dense_opt, DenseFtrl)  # (divides by the scaler in its own launch)
         if self.world > 1 and reduced is None:
             for q in self._dense_params:
                 if q.grad is not None:
                     _all_reduce(q.grad)
-        if self.solver.scaler != 1.0:  # one multi-tensor launch, not one per parameter
+        if self.solver.scaler != 1.0 and not ftrl:  # one multi-tensor launch, not one per parameter
             grads = [q.grad for q in self._dense_params if q.grad is not None]
             if grads:
                 torch._foreach_div_(grads, self.solver.scaler)
@@ -2092,6 +2112,10 @@ class Model:
                     os.path.join(d, f"emb_vector.rank{self.rank}"))
         if self.rank == 0 and self._dense_opt is not None:
             torch.save(self._dense_opt.state_dict(), f"{prefix}_opt_dense_{iteration}.model")
+        elif self.rank == 0 and self._flat_mlps and self._flat_ftrl:
+            # the flat path has no optimizer object: z / n of the MLPs in DenseFtrl's layout
+            torch.save(ftrl_state_dict(self._flat_ftrl_state()),
+                       f"{prefix}_opt_dense_{iteration}.model")
         if self.rank == 0 and self._dense_params:
             blobs = [b.detach().float().contiguous().flatten() for b, _ in self._dense_blobs()]
             torch.cat(blobs).cpu().numpy().astype("<f4").tofile(f"{prefix}_dense_{iteration}.model")
@@ -2267,8 +2291,21 @@ class Model:
     def load_dense_optimizer_states(self, path: str):
         """state of the dense optimizer as save_params_to_files wrote it (<prefix>_opt_dense_<iter>
         .model, model.cpp:1238)"""
-        if self._dense_opt is not None:
+        if isinstance(self._dense_opt, DenseFtrl):
+            self._dense_opt.load_state_dict(torch.load(path, map_location="cpu"))
+        elif self._dense_opt is not None:
             self._dense_opt.load_state_dict(torch.load(path, map_location=self.device))
+        elif self._flat_mlps and self._flat_ftrl:  # the same file, whichever path wrote it
+            load_ftrl_state_dict(self._flat_ftrl_state(), torch.load(path, map_location="cpu"))
+
+    def _flat_ftrl_state(self):
+        """[(z, n)] per dense parameter of the flat Ftrl path, in the order of _dense_params (the
+        order DenseFtrl holds them in when the same model runs unfused)"""
+        by_param = {}
+        for m in self._flat_mlps:
+            for q, zn in zip(m.parameters(), m.ftrl_state()):
+                by_param[id(q)] = zn
+        return [by_param[id(q)] for q in self._dense_params]
 
     def load_sparse_optimizer_states(self, paths: Sequence[str]):
         for path, (name, (se, p, h, _, _)) in zip(paths, self._emb.items()):

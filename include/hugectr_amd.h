@@ -724,6 +724,36 @@ int hctr_sum_groups(int groups, size_t n, const void* in, int dtype, float* out,
 int hctr_sgd_shadow(size_t n, float lr, float grad_scale, float* w, const float* g, void* w16,
                     int dtype, hctr_stream_t stream);
 
+/* Dense Ftrl (FtrlOptimizer<T>::update and ftrl_update_kernel,
+ * R/HugeCTR/src/optimizers/ftrl_optimizer.cu:28-43, 92-93), per element, eps = FLT_EPSILON:
+ *   g  = grad * grad_scale                               (grad_scale = 1 / solver.scaler)
+ *   n' = n + g*g
+ *   z' = z + g + (sqrt(n + eps) - sqrt(n' + eps)) * w / lr
+ *   w' = |z'| > lambda1 ? (lambda1 * sgn(z') - z') / (sqrt(n' + eps) / lr + lambda2 + beta / lr) : 0
+ * sgn = +1 for a clear sign bit; |z'| == lambda1 gives 0.  z and n are fp32 and start at 0
+ * (FtrlOptimizer::initialize); a parameter whose gradient is 0 on the first step therefore
+ * becomes 0 whatever it was (z' stays 0), as in the reference.  lr > 0; beta, lambda1, lambda2 >= 0.
+ *
+ * hctr_ftrl_shadow: the twin of hctr_sgd_shadow on flat buffers, n % 4 == 0, 16-byte aligned;
+ * the 16-bit compute copy w16 (dtype F16 or BF16) is refreshed in the same pass, or not written
+ * when w16 is NULL (dtype is ignored then).
+ *
+ * hctr_ftrl_segments: ONE launch over parameter tensors that do not live in one buffer.  The
+ * table (device memory) holds per segment the address of w, the element offset `off` of that
+ * parameter inside the flat g / z / n buffers, the count n >= 1 (any value) and block0 = the sum
+ * of ceil(n / HCTR_FTRL_SEG_BLOCK_ELEMS) over the segments in front; nblocks = that sum over all
+ * segments.  Both entries take the same step expression: an element rounds the same in either. */
+#define HCTR_FTRL_SEG_BLOCK_ELEMS 1024
+typedef struct {
+  int64_t w, off, n, block0;
+} hctr_ftrl_seg;
+int hctr_ftrl_shadow(size_t n, float lr, float beta, float lambda1, float lambda2, float grad_scale,
+                     float* w, float* z, float* nacc, const float* g, void* w16, int dtype,
+                     hctr_stream_t stream);
+int hctr_ftrl_segments(const hctr_ftrl_seg* segs, int nseg, size_t nblocks, float lr, float beta,
+                       float lambda1, float lambda2, float grad_scale, float* z, float* nacc,
+                       const float* g, hctr_stream_t stream);
+
 /* BinaryCrossEntropyLoss (R/HugeCTR/src/loss.cu:231-262): *loss = mean_i bce(logit_i, label_i);
  * dlogit_i = (sigmoid(logit_i) - label_i) * grad_scale (grad_scale = scaler / batch / total_gpu_count
  * in the reference); dlogit may be NULL (evaluation).  dtype of logit/dlogit: hctr_emb_dtype_t.
