@@ -99,6 +99,15 @@ class DevOut:
         from hugectr_amd import _lib
         return _lib.ptr(self.t)
 
+    def fill(self, a):
+        """an in/out buffer (an accumulator, a master weight): the rows start as the host array a,
+        whose element type is the buffer's"""
+        import torch
+        raw = np.ascontiguousarray(a).reshape(-1)
+        assert raw.size == self.rows * self.D
+        self.t[:raw.size].copy_(torch.from_numpy(raw))
+        return self
+
     def result(self):
         """the rows as fp32 (or raw integers); asserts that everything around them is untouched"""
         b = self.base if self.int_bits else self.base.float()
