@@ -263,12 +263,12 @@ __global__ void __launch_bounds__(kGemmThreads)
       }
       cg_u32x4 hv;
 #pragma unroll
-      for (int e = 0; e < 4; e++) hv[e] = (uint32_t)h[2 * e] | ((uint32_t)h[2 * e + 1] << 16);
+      for (int e = 0; e < 4; e++) hv[e] = pack16(h[2 * e], h[2 * e + 1]);
       if (gm < g.M) *reinterpret_cast<cg_u32x4*>(g.H + off) = hv;
     }
     cg_u32x4 ov;
 #pragma unroll
-    for (int e = 0; e < 4; e++) ov[e] = (uint32_t)o[2 * e] | ((uint32_t)o[2 * e + 1] << 16);
+    for (int e = 0; e < 4; e++) ov[e] = pack16(o[2 * e], o[2 * e + 1]);
     if (gm < g.M) *reinterpret_cast<cg_u32x4*>(g.C + off) = ov;
   }
 }
@@ -377,8 +377,7 @@ __global__ void __launch_bounds__(kBigThreads)
       const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
       cg_u32x4 ov;
 #pragma unroll
-      for (int e = 0; e < 4; e++)
-        ov[e] = (uint32_t)H16::from_f32(v[2 * e]) | ((uint32_t)H16::from_f32(v[2 * e + 1]) << 16);
+      for (int e = 0; e < 4; e++) ov[e] = H16::pack2(v[2 * e], v[2 * e + 1]);
       if (gm < g.M) *reinterpret_cast<cg_u32x4*>(g.C + (size_t)gm * g.ldc + gn) = ov;
     }
   }

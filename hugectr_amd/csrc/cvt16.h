@@ -69,9 +69,9 @@ __device__ __forceinline__ void st4_from_f32<float>(float* p, float4 v) {
 
 // ---- raw: kernels that move 16-bit data as unsigned short / packed words ---------------------------
 template <bool BF>
-struct H16;
+struct H16Bits;
 template <>
-struct H16<true> {
+struct H16Bits<true> {
   __device__ __forceinline__ static unsigned short from_f32(float v) {
     __bf16 h = (__bf16)v;
     return *reinterpret_cast<unsigned short*>(&h);
@@ -81,7 +81,7 @@ struct H16<true> {
   }
 };
 template <>
-struct H16<false> {
+struct H16Bits<false> {
   __device__ __forceinline__ static unsigned short from_f32(float v) {
     _Float16 h = (_Float16)v;
     return *reinterpret_cast<unsigned short*>(&h);
@@ -89,6 +89,27 @@ struct H16<false> {
   __device__ __forceinline__ static float to_f32(unsigned short u) {
     _Float16 h = *reinterpret_cast<_Float16*>(&u);
     return (float)h;
+  }
+};
+
+// a 32-bit word of two 16-bit values: the first one in the low half
+__device__ __forceinline__ unsigned short lo16(unsigned v) { return (unsigned short)(v & 0xFFFFu); }
+__device__ __forceinline__ unsigned short hi16(unsigned v) { return (unsigned short)(v >> 16); }
+__device__ __forceinline__ unsigned pack16(unsigned short a, unsigned short b) {
+  return (unsigned)a | ((unsigned)b << 16);
+}
+
+template <bool BF>
+struct H16 : H16Bits<BF> {
+  using H16Bits<BF>::from_f32;
+  using H16Bits<BF>::to_f32;
+  __device__ __forceinline__ static float lo(unsigned v) { return to_f32(lo16(v)); }
+  __device__ __forceinline__ static float hi(unsigned v) { return to_f32(hi16(v)); }
+  __device__ __forceinline__ static unsigned pack2(float a, float b) {
+    return pack16(from_f32(a), from_f32(b));
+  }
+  __device__ __forceinline__ static uint2 pack4(float a, float b, float c, float d) {
+    return make_uint2(pack2(a, b), pack2(c, d));
   }
 };
 

@@ -1,7 +1,9 @@
 // dense_ops.hip -- the dense ops next to the GEMMs: the DCN cross layers' element-wise kernels and
 // the MLP edge kernels (ReLU backward + bias gradient, split-K group sums, SGD / Ftrl with the 16-bit
 // shadow copy, BCE loss, the logit head, the skinny first layer).  The dot interaction is interaction.hip,
-// the cross layers' GEMMs are cross_gemm.hip.
+// the cross layers' GEMMs are cross_gemm.hip.  By family: cross v1, column-tile producers, loss and
+// logit head, skinny first layer, optimizers, fixed-order sums and the finish launch; then the
+// host entries in the same order.
 //
 // MultiCrossLayer<T> (DCN v1): R/HugeCTR/src/layers/multi_cross_layer.cu:582-601 (fprop functor),
 //   :671-812 (bprop) -- 4 element-wise kernels + a gemv per layer in the reference; here all layers
@@ -76,6 +78,8 @@ __global__ void __launch_bounds__(kBlock)
 // LDS = true: one wavefront per workgroup keeps its dW/db partial rows in LDS (2*layers*w floats)
 // instead of read-modify-writing them in global memory for every row -- the per-row RMW chain
 // through L2 made the backward 12x slower than the forward at the DCN shape.
+constexpr int kCrossBwdWaves = 256 * 4;  // waves used by the cross backward (deterministic reduce)
+
 template <int NPL, bool LDS>
 __global__ void __launch_bounds__(kBlock)
     cross_v1_bwd_kernel(size_t batch, int w, int layers, const float* __restrict__ x0,
@@ -162,13 +166,91 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ================================================================================================
+// Column-tile producers: an elementwise pass over 16-bit rows that also leaves the column sums of
+// what it wrote, as one fp32 partial row per row tile (the tiles are added in fixed order by the
+// COLSUM finish below: deterministic).  A workgroup owns a tile of rows x cw 16-byte column
+// vectors: thread t owns column vector c8 = t % cw and walks the rows g = t / cw, + rg, ...;
+// cw = min(n / 8, 256), rg = 256 / cw row groups, whose sums meet in LDS in group order.
+// ================================================================================================
+struct Terms8 {
+  float v[8];
+};
+
+// one column block of one tile: term(at) handles the vector at element offset `at` of row r and
+// returns its eight fp32 terms; their sums over the tile's rows go to partial[blockIdx.x][...].
+// Every thread of the workgroup calls this (two barriers), whether it owns a vector or not.
+template <typename F>
+__device__ __forceinline__ void col_tile_sum(float* red, size_t rows, int n, int cw, int rg, int rpt,
+                                             int col0, float* __restrict__ partial, F&& term) {
+  const int c8 = threadIdx.x % cw, g = threadIdx.x / cw;
+  const int cc = col0 + c8;
+  const bool live = g < rg && cc < n / 8;
+  const size_t r0 = (size_t)blockIdx.x * (size_t)rpt;
+  const size_t r1 = r0 + (size_t)rpt < rows ? r0 + (size_t)rpt : rows;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (live) {
+#pragma unroll 4
+    for (size_t r = r0 + g; r < r1; r += rg) {
+      const Terms8 t = term(r * n + cc * 8);
+#pragma unroll
+      for (int e = 0; e < 8; e++) acc[e] += t.v[e];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; e++) red[e * kBlock + threadIdx.x] = acc[e];
+  __syncthreads();
+  if (g == 0 && cc < n / 8) {
+    float* p = partial + (size_t)blockIdx.x * n + cc * 8;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      float sum = 0.f;
+      for (int k = 0; k < rg; k++) sum += red[e * kBlock + k * cw + c8];
+      p[e] = sum;
+    }
+  }
+  __syncthreads();
+}
+
 // Fused ReLU backward + bias gradient for the MLP layers around the path:
 //   dz[b][n] = dy[b][n] * (y[b][n] > 0),   db[n] = sum_b dz[b][n]
 // PyTorch issues threshold_backward (read dy,y / write dz) and a column-sum reduction (read dz)
-// as two launches; fused, dz is consumed from registers.  Two-stage, fixed-order column sums
-// (deterministic): stage 1 writes partial[row_tile][n], stage 2 adds the tiles in order.
-// ================================================================================================
+// as two launches; fused, dz is consumed from registers.
 constexpr int kRbRows = 128;  // rows per workgroup
+
+template <bool BF>
+__global__ void __launch_bounds__(kBlock)
+    relu_bwd_bias_kernel(size_t rows, int n, int cw, int rg, const unsigned short* __restrict__ dy,
+                         const unsigned short* __restrict__ y, unsigned short* __restrict__ dz,
+                         float* __restrict__ partial) {
+  using H = H16<BF>;
+  __shared__ float red[kBlock * 8];
+  // a workgroup takes the column blocks one after the other: uniform trip count
+  for (int col0 = 0; col0 < n / 8; col0 += cw)
+    col_tile_sum(red, rows, n, cw, rg, kRbRows, col0, partial, [&](size_t at) {
+      const u32x4 gv = *reinterpret_cast<const u32x4*>(dy + at);
+      const u32x4 av = *reinterpret_cast<const u32x4*>(y + at);
+      u32x4 o;
+      Terms8 t;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const unsigned short z0 = H::lo(av[e]) > 0.f ? lo16(gv[e]) : (unsigned short)0;
+        const unsigned short z1 = H::hi(av[e]) > 0.f ? hi16(gv[e]) : (unsigned short)0;
+        t.v[2 * e] = H::to_f32(z0);
+        t.v[2 * e + 1] = H::to_f32(z1);
+        o[e] = pack16(z0, z1);
+      }
+      *reinterpret_cast<u32x4*>(dz + at) = o;
+      return t;
+    });
+}
+
+// DCN-v2 cross layer, the elementwise step of one layer's backward in the activations' 16-bit type
+// (MultiCrossBackwardFunctorv2: fused_mul_fma3, R/HugeCTR/src/layers/multi_cross_layer.cu:391-424,
+// 127-165 -- S0 = dY .* X0, dX += dY .* H, one rounding per element as its paired-half kernel
+// rounds -- and the bias gradient db = column sums of S0, which the reference takes in the
+// epilogue of the dV GEMM, :770-776): dY is read once for both products, S0 is summed from
+// registers.  FIRST (the last layer, visited first): dX = dY .* H, the accumulator is not read (nor
+// cleared beforehand).
 
 // rows per workgroup of cross_v2_bwd_step_kernel: 128 at most, fewer (a power of two >= 16) while
 // the grid would stay below ~2 k workgroups -- 64 tiles of 128 rows at batch 8192 left three
@@ -182,69 +264,7 @@ inline int cross_step_rows_per_tile(size_t batch, int width) {
   return rpt;
 }
 
-// thread t of a workgroup owns 16-byte column vector (t % cw) and walks rows (t / cw), +rg, ...;
-// cw = min(n/8, 256), rg = 256 / cw row groups; the rg partial sums meet in LDS in fixed order.
-template <bool BF>
-__global__ void __launch_bounds__(kBlock)
-    relu_bwd_bias_kernel(size_t rows, int n, int cw, int rg, const unsigned short* __restrict__ dy,
-                         const unsigned short* __restrict__ y, unsigned short* __restrict__ dz,
-                         float* __restrict__ partial) {
-  using H = H16<BF>;
-  __shared__ float red[kBlock * 8];
-  const int n8 = n / 8;
-  const int c8 = threadIdx.x % cw, g = threadIdx.x / cw;
-  const bool live = g < rg;
-  const size_t r0 = (size_t)blockIdx.x * kRbRows;
-  const size_t r1 = r0 + kRbRows < rows ? r0 + kRbRows : rows;
-  for (int cc = c8; cc - c8 < n8; cc += cw) {  // uniform trip count: every thread reaches the barriers
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (live && cc < n8) {
-#pragma unroll 4
-      for (size_t r = r0 + g; r < r1; r += rg) {
-        const u32x4 gv = *reinterpret_cast<const u32x4*>(dy + r * n + cc * 8);
-        const u32x4 av = *reinterpret_cast<const u32x4*>(y + r * n + cc * 8);
-        u32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const unsigned short g0 = (unsigned short)(gv[e] & 0xFFFFu);
-          const unsigned short g1 = (unsigned short)(gv[e] >> 16);
-          const float y0 = H::to_f32((unsigned short)(av[e] & 0xFFFFu));
-          const float y1 = H::to_f32((unsigned short)(av[e] >> 16));
-          const unsigned short z0 = y0 > 0.f ? g0 : (unsigned short)0;
-          const unsigned short z1 = y1 > 0.f ? g1 : (unsigned short)0;
-          acc[2 * e] += H::to_f32(z0);
-          acc[2 * e + 1] += H::to_f32(z1);
-          o[e] = (unsigned)z0 | ((unsigned)z1 << 16);
-        }
-        *reinterpret_cast<u32x4*>(dz + r * n + cc * 8) = o;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) red[e * kBlock + threadIdx.x] = acc[e];
-    __syncthreads();
-    if (g == 0 && cc < n8) {
-      float* p = partial + (size_t)blockIdx.x * n + cc * 8;
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        float sum = 0.f;
-        for (int k = 0; k < rg; k++) sum += red[e * kBlock + k * cw + c8];
-        p[e] = sum;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ================================================================================================
-// DCN-v2 cross layer, the elementwise step of one layer's backward in the activations' 16-bit type
-// (MultiCrossBackwardFunctorv2: fused_mul_fma3, R/HugeCTR/src/layers/multi_cross_layer.cu:391-424,
-// 127-165 -- S0 = dY .* X0, dX += dY .* H, one rounding per element as its paired-half kernel
-// rounds -- and the bias gradient db = column sums of S0, which the reference takes in the
-// epilogue of the dV GEMM, :770-776): dY is read once for both products, S0 is summed from
-// registers.  Thread layout and the two-stage fixed-order column sums are relu_bwd_bias_kernel's.
-// FIRST (the last layer, visited first): dX = dY .* H, the accumulator is not read (nor cleared
-// beforehand).
-// ================================================================================================
+// the grid is (row tiles of rpt rows, column blocks): blockIdx.y picks the column block
 template <bool BF, bool FIRST>
 __global__ void __launch_bounds__(kBlock)
     cross_v2_bwd_step_kernel(size_t rows, int n, int cw, int rg, int rpt,
@@ -254,241 +274,35 @@ __global__ void __launch_bounds__(kBlock)
                              unsigned short* __restrict__ s0, float* __restrict__ partial) {
   using H = H16<BF>;
   __shared__ float red[kBlock * 8];
-  const int n8 = n / 8;
-  const int c8 = threadIdx.x % cw, g = threadIdx.x / cw;
-  const bool live = g < rg;
-  // a workgroup = rpt rows x cw 16-byte column vectors (blockIdx.y picks the column block): the
-  // grid is (row tiles, column blocks), sized by the host for >= ~1 k workgroups at any batch
-  const size_t r0 = (size_t)blockIdx.x * (size_t)rpt;
-  const size_t r1 = r0 + (size_t)rpt < rows ? r0 + (size_t)rpt : rows;
-  const int cc = (int)blockIdx.y * cw + c8;
-  {
-    float sum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (live && cc < n8) {
-#pragma unroll 4
-      for (size_t r = r0 + g; r < r1; r += rg) {
-        const size_t at = r * n + cc * 8;
-        const u32x4 gv = *reinterpret_cast<const u32x4*>(dy + at);
-        const u32x4 xv = *reinterpret_cast<const u32x4*>(x0 + at);
-        const u32x4 hv = *reinterpret_cast<const u32x4*>(hm + at);
-        u32x4 av = {0u, 0u, 0u, 0u};
-        if (!FIRST) av = *reinterpret_cast<const u32x4*>(acc_io + at);
-        u32x4 so, ao;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const float g0 = H::to_f32((unsigned short)(gv[e] & 0xFFFFu));
-          const float g1 = H::to_f32((unsigned short)(gv[e] >> 16));
-          // (the product of two 16-bit values is exact in fp32: one rounding, to the 16-bit type)
-          const unsigned short p0 = H::from_f32(g0 * H::to_f32((unsigned short)(xv[e] & 0xFFFFu)));
-          const unsigned short p1 = H::from_f32(g1 * H::to_f32((unsigned short)(xv[e] >> 16)));
-          sum[2 * e] += H::to_f32(p0);
-          sum[2 * e + 1] += H::to_f32(p1);
-          so[e] = (unsigned)p0 | ((unsigned)p1 << 16);
-          float a0 = g0 * H::to_f32((unsigned short)(hv[e] & 0xFFFFu));
-          float a1 = g1 * H::to_f32((unsigned short)(hv[e] >> 16));
-          if (!FIRST) {
-            a0 += H::to_f32((unsigned short)(av[e] & 0xFFFFu));
-            a1 += H::to_f32((unsigned short)(av[e] >> 16));
-          }
-          ao[e] = (unsigned)H::from_f32(a0) | ((unsigned)H::from_f32(a1) << 16);
-        }
-        *reinterpret_cast<u32x4*>(s0 + at) = so;
-        *reinterpret_cast<u32x4*>(acc_io + at) = ao;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) red[e * kBlock + threadIdx.x] = sum[e];
-    __syncthreads();
-    if (g == 0 && cc < n8) {
-      float* p = partial + (size_t)blockIdx.x * n + cc * 8;
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        float t = 0.f;
-        for (int k = 0; k < rg; k++) t += red[e * kBlock + k * cw + c8];
-        p[e] = t;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// db[c..c+3] = sum over tiles of partial[tile][c..c+3]: a workgroup owns 8 float4 column groups x 32
-// tile groups; the 32 group sums are added in fixed order through LDS.
-__global__ void __launch_bounds__(kBlock)
-    colsum_partials_kernel(size_t tiles, int n, const float* __restrict__ partial,
-                           float* __restrict__ db) {
-  __shared__ f32x4 red[kBlock];
-  const int c4 = blockIdx.x * 8 + (threadIdx.x & 7), tg = threadIdx.x >> 3;
-  const bool live = c4 * 4 < n;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (live) {
-#pragma unroll 8
-    for (size_t t = tg; t < tiles; t += 32)
-      s += *reinterpret_cast<const f32x4*>(partial + t * n + c4 * 4);
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (tg == 0 && live) {
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 32; k++) sum += red[k * 8 + threadIdx.x];
-    *reinterpret_cast<f32x4*>(db + c4 * 4) = sum;
-  }
-}
-
-// out[i] = sum_g in[g][i] (fixed order), 16-bit partial products of a split-K GEMM -> fp32
-template <bool BF>
-__global__ void __launch_bounds__(kBlock)
-    sum_groups_kernel(int groups, size_t n8, const unsigned short* __restrict__ in,
-                      float* __restrict__ out) {
-  using H = H16<BF>;
-  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n8) return;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int g = 0; g < groups; g++) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(in + ((size_t)g * n8 + i) * 8);
+  col_tile_sum(red, rows, n, cw, rg, rpt, (int)blockIdx.y * cw, partial, [&](size_t at) {
+    const u32x4 gv = *reinterpret_cast<const u32x4*>(dy + at);
+    const u32x4 xv = *reinterpret_cast<const u32x4*>(x0 + at);
+    const u32x4 hv = *reinterpret_cast<const u32x4*>(hm + at);
+    u32x4 av = {0u, 0u, 0u, 0u};
+    if (!FIRST) av = *reinterpret_cast<const u32x4*>(acc_io + at);
+    u32x4 so, ao;
+    Terms8 t;
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      acc[2 * e] += H::to_f32((unsigned short)(v[e] & 0xFFFFu));
-      acc[2 * e + 1] += H::to_f32((unsigned short)(v[e] >> 16));
+      const float g0 = H::lo(gv[e]), g1 = H::hi(gv[e]);
+      // (the product of two 16-bit values is exact in fp32: one rounding, to the 16-bit type)
+      const unsigned short p0 = H::from_f32(g0 * H::lo(xv[e]));
+      const unsigned short p1 = H::from_f32(g1 * H::hi(xv[e]));
+      t.v[2 * e] = H::to_f32(p0);
+      t.v[2 * e + 1] = H::to_f32(p1);
+      so[e] = pack16(p0, p1);
+      float a0 = g0 * H::lo(hv[e]);
+      float a1 = g1 * H::hi(hv[e]);
+      if (!FIRST) {
+        a0 += H::lo(av[e]);
+        a1 += H::hi(av[e]);
+      }
+      ao[e] = H::pack2(a0, a1);
     }
-  }
-  f32x4* o = reinterpret_cast<f32x4*>(out + i * 8);
-  o[0] = f32x4{acc[0], acc[1], acc[2], acc[3]};
-  o[1] = f32x4{acc[4], acc[5], acc[6], acc[7]};
-}
-
-// the dense SGD step as ONE expression for every kernel that takes it (f32x4 or float): a parameter
-// rounds the same (contraction included) whichever kernel updates it
-template <typename V>
-__device__ __forceinline__ V sgd_apply(V w, V g, float lr, float grad_scale) {
-  w -= lr * grad_scale * g;
-  return w;
-}
-
-// dense SGD step fused with the refresh of the 16-bit compute copy: w -= lr * g; w16 = (T16)w
-template <bool BF>
-__global__ void __launch_bounds__(kBlock)
-    sgd_shadow_kernel(size_t n4, float lr, float grad_scale, float* __restrict__ w,
-                      const float* __restrict__ g, unsigned short* __restrict__ w16) {
-  using H = H16<BF>;
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4;
-       i += (size_t)gridDim.x * kBlock) {
-    f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    wv = sgd_apply(wv, gv, lr, grad_scale);
-    reinterpret_cast<f32x4*>(w)[i] = wv;
-    const unsigned lo = (unsigned)H::from_f32(wv[0]) | ((unsigned)H::from_f32(wv[1]) << 16);
-    const unsigned hi = (unsigned)H::from_f32(wv[2]) | ((unsigned)H::from_f32(wv[3]) << 16);
-    reinterpret_cast<uint2*>(w16)[i] = make_uint2(lo, hi);
-  }
-}
-
-// ================================================================================================
-// Dense Ftrl (ftrl_update_kernel and its launch, R/HugeCTR/src/optimizers/ftrl_optimizer.cu:28-43,
-// 92-93).  Like sgd_apply, the step is ONE expression for every kernel that takes it (f32x4 or
-// float), so a parameter rounds the same whichever kernel updates it.
-//   g = grad * grad_scale;  n' = n + g*g;  z' = z + g + (sqrt(n + eps) - sqrt(n' + eps)) * w / lr
-//   w' = |z'| > lambda1 ? (lambda1 * sgn(z') - z') / (sqrt(n' + eps) / lr + l2) : 0
-// with eps = FLT_EPSILON, l2 = lambda2 + beta / lr (formed once on the host) and sgn = +1 for a
-// clear sign bit.  A parameter whose gradient is 0 on the first step becomes 0: z' stays 0.
-// ================================================================================================
-struct FtrlHp {
-  float lr, lambda1, l2, grad_scale;
-};
-
-__device__ __forceinline__ float ftrl_apply(float w, float& z, float& n, float grad, FtrlHp h) {
-  constexpr float eps = 1.1920928955078125e-7f;  // FLT_EPSILON
-  const float g = grad * h.grad_scale;
-  const float n_new = n + g * g;
-  const float root = sqrtf(n_new + eps);
-  const float z_new = z + g + (sqrtf(n + eps) - root) * w / h.lr;
-  const float x = (__builtin_signbitf(z_new) ? -h.lambda1 : h.lambda1) - z_new;
-  const float y = root / h.lr + h.l2;
-  n = n_new;
-  z = z_new;
-  return fabsf(z_new) > h.lambda1 ? x / y : 0.f;
-}
-
-__device__ __forceinline__ f32x4 ftrl_apply(f32x4 w, f32x4& z, f32x4& n, f32x4 grad, FtrlHp h) {
-  f32x4 out;
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    float ze = z[e], ne = n[e];
-    out[e] = ftrl_apply(w[e], ze, ne, grad[e], h);
-    z[e] = ze;
-    n[e] = ne;
-  }
-  return out;
-}
-
-// the flat form: the twin of sgd_shadow_kernel (SHADOW 0: no 16-bit copy, 1: fp16, 2: bf16)
-template <int SHADOW>
-__global__ void __launch_bounds__(kBlock)
-    ftrl_shadow_kernel(size_t n4, FtrlHp h, float* __restrict__ w, float* __restrict__ z,
-                       float* __restrict__ nacc, const float* __restrict__ g,
-                       unsigned short* __restrict__ w16) {
-  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4;
-       i += (size_t)gridDim.x * kBlock) {
-    f32x4 zv = reinterpret_cast<f32x4*>(z)[i];
-    f32x4 nv = reinterpret_cast<f32x4*>(nacc)[i];
-    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    const f32x4 wv = ftrl_apply(reinterpret_cast<f32x4*>(w)[i], zv, nv, gv, h);
-    reinterpret_cast<f32x4*>(w)[i] = wv;
-    reinterpret_cast<f32x4*>(z)[i] = zv;
-    reinterpret_cast<f32x4*>(nacc)[i] = nv;
-    if (SHADOW) {
-      using H = H16<SHADOW == 2>;
-      const unsigned lo = (unsigned)H::from_f32(wv[0]) | ((unsigned)H::from_f32(wv[1]) << 16);
-      const unsigned hi = (unsigned)H::from_f32(wv[2]) | ((unsigned)H::from_f32(wv[3]) << 16);
-      reinterpret_cast<uint2*>(w16)[i] = make_uint2(lo, hi);
-    }
-  }
-}
-
-// the segmented form: parameter tensors that do not live in one buffer; their gradients and the
-// state do (flat g / z / n, a segment's elements at `off`).  A block takes kFtrlSegElems elements
-// of one segment and finds the segment like dense_grad_finish_kernel does.  Groups of 4 go through
-// the vector form when the segment allows it (w 16-byte aligned, off % 4 == 0), the tail and
-// everything else through the scalar form of the same expression.
-constexpr int kFtrlSegElems = HCTR_FTRL_SEG_BLOCK_ELEMS;
-static_assert(kFtrlSegElems == kBlock * 4, "a thread takes 4 elements");
-
-__global__ void __launch_bounds__(kBlock)
-    ftrl_segments_kernel(const hctr_ftrl_seg* __restrict__ segs, int nseg, FtrlHp h,
-                         float* __restrict__ z, float* __restrict__ nacc,
-                         const float* __restrict__ g) {
-  int si = -1;
-  for (int base = 0; base < nseg; base += 64) {
-    const int t = base + (int)(threadIdx.x & 63);
-    const bool in = t < nseg && segs[t].block0 <= (long long)blockIdx.x;
-    si += (int)__popcll(__ballot(in));
-  }
-  if (si < 0) return;  // (a table whose first segment does not start at block 0)
-  const hctr_ftrl_seg sg = segs[si];
-  const size_t cnt = (size_t)sg.n, off = (size_t)sg.off;
-  float* w = reinterpret_cast<float*>(sg.w);
-  const size_t e0 = ((size_t)((long long)blockIdx.x - sg.block0) * kBlock + threadIdx.x) * 4;
-  if (e0 >= cnt) return;
-  const bool vec = (sg.w & 15) == 0 && (off & 3) == 0 && e0 + 4 <= cnt;
-  if (vec) {
-    f32x4 zv = *reinterpret_cast<f32x4*>(z + off + e0);
-    f32x4 nv = *reinterpret_cast<f32x4*>(nacc + off + e0);
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + off + e0);
-    const f32x4 wv = ftrl_apply(*reinterpret_cast<f32x4*>(w + e0), zv, nv, gv, h);
-    *reinterpret_cast<f32x4*>(w + e0) = wv;
-    *reinterpret_cast<f32x4*>(z + off + e0) = zv;
-    *reinterpret_cast<f32x4*>(nacc + off + e0) = nv;
-    return;
-  }
-  const size_t e1 = e0 + 4 < cnt ? e0 + 4 : cnt;
-  for (size_t e = e0; e < e1; e++) {
-    float zs = z[off + e], ns = nacc[off + e];
-    w[e] = ftrl_apply(w[e], zs, ns, g[off + e], h);
-    z[off + e] = zs;
-    nacc[off + e] = ns;
-  }
+    *reinterpret_cast<u32x4*>(s0 + at) = so;
+    *reinterpret_cast<u32x4*>(acc_io + at) = ao;
+    return t;
+  });
 }
 
 // ================================================================================================
@@ -498,6 +312,19 @@ __global__ void __launch_bounds__(kBlock)
 // partials are added in fixed order by the last launch (deterministic).
 // ================================================================================================
 constexpr int kBceBlocks = 256;
+
+// one sample: *loss = bce(z, y), *grad = sigmoid(z) - y, both through exp(-|z|)
+__device__ __forceinline__ void bce_term(float z, float y, float* grad, float* loss) {
+  if (z >= 0.f) {
+    const float e = expf(-z);
+    *grad = (1.f - y) - e / (1.f + e);
+    *loss = z * (1.f - y) + logf(1.f + e);
+  } else {
+    const float e = expf(z);
+    *grad = -y + e / (1.f + e);
+    *loss = -z * y + logf(1.f + e);
+  }
+}
 
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
@@ -509,16 +336,9 @@ __global__ void __launch_bounds__(kBlock)
        i += (size_t)gridDim.x * kBlock) {
     const float x = ld_as_f32(logit + i);
     const float y = label[i];
-    float g;
-    if (x >= 0.f) {
-      const float e = expf(-x);
-      g = (1.f - y) - e / (1.f + e);
-      val += x * (1.f - y) + logf(1.f + e);
-    } else {
-      const float e = expf(x);
-      g = -y + e / (1.f + e);
-      val += -x * y + logf(1.f + e);
-    }
+    float g, l;
+    bce_term(x, y, &g, &l);
+    val += l;
     if (dlogit) st_from_f32(dlogit + i, g * grad_scale);
   }
   const float tot = block_reduce_sum<float, kBlock>(val, smem);
@@ -589,6 +409,8 @@ __global__ void __launch_bounds__(kBlock)
       if (r >= batch) break;  // wave-uniform
       const float z = dot[i] + b0;
       const float y = label[r];
+      // bce_term written out: through the function this kernel's <T, 1, 8> form schedules 24
+      // instructions differently and measured 1 - 3 % slower (profiles/dense_refactor_ab.txt)
       float g, l;
       if (z >= 0.f) {
         const float e = expf(-z);
@@ -642,48 +464,15 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-// fixed-order sum of the block partials: a 1024-thread workgroup owns 64 columns; 16 row groups sum
-// consecutive chunks of the partial blocks (coalesced 256-byte reads), then the group sums are
-// added in group order
-__global__ void __launch_bounds__(1024)
-    logit_head_finish_kernel(int blocks, int K, size_t batch, const float* __restrict__ partial,
-                             float* __restrict__ dw, float* __restrict__ db,
-                             float* __restrict__ loss) {
-  __shared__ float part[16][64];
-  const int c = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int k = blockIdx.x * 64 + c;
-  const int chunk = (blocks + 15) / 16;
-  const int b0 = grp * chunk, b1 = min(blocks, b0 + chunk);
-  float t = 0.f;
-  if (k < K + 2) {
-    int b = b0;
-    for (; b + 8 <= b1; b += 8) {  // 8 independent loads in flight, added in order
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = partial[(size_t)(b + u) * (K + 2) + k];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t += v[u];
-    }
-    for (; b < b1; b++) t += partial[(size_t)b * (K + 2) + k];
-  }
-  part[grp][c] = t;
-  __syncthreads();
-  if (grp == 0 && k < K + 2) {
-    float tot = 0.f;
-#pragma unroll
-    for (int g = 0; g < 16; g++) tot += part[g][c];
-    if (k < K) dw[k] = tot;
-    else if (k == K) *db = tot;
-    else *loss = tot / (float)batch;
-  }
-}
 
-// ---- first layer of the bottom MLP: y = relu(x W^T + b) with a handful of input features (K <= 16,
-//      DLRM: 13 dense features -> 512).  As a GEMM it is all output traffic and no arithmetic
-//      (library kernel: 30 us forward; ReLU backward + bias + a K = batch weight-gradient GEMM with
-//      13 columns: 72 us).  Here 128 lanes own one row at a time, a lane 4 consecutive outputs
-//      with their K weights in registers; the backward folds dz = dy * (y > 0) into the
-//      weight-gradient sum, so dz is never written (the layer has no data gradient).
+// ================================================================================================
+// Skinny first layer of the bottom MLP: y = relu(x W^T + b) with a handful of input features
+// (K <= 16, DLRM: 13 dense features -> 512).  As a GEMM it is all output traffic and no arithmetic
+// (library kernel: 30 us forward; ReLU backward + bias + a K = batch weight-gradient GEMM with
+// 13 columns: 72 us).  Here 128 lanes own one row at a time, a lane 4 consecutive outputs
+// with their K weights in registers; the backward folds dz = dy * (y > 0) into the
+// weight-gradient sum, so dz is never written (the layer has no data gradient).
+// ================================================================================================
 constexpr int kSkinnyK = 16;       // padded K
 constexpr int kSkinnyBlocks = 256;
 constexpr int kSkinnyLanes = 128;  // lanes per row, 4 outputs each (N <= 512)
@@ -933,77 +722,190 @@ __global__ void __launch_bounds__(kSkinnyBwdBlock)
   for (int i = threadIdx.x; i < N * stride; i += kSkinnyBwdBlock) out[i] = lds[i];
 }
 
-// dw [N][K] and db [N] from the block partials: 64 elements per block, 16 groups of lanes each sum
-// a consecutive chunk of the partial blocks (8 loads in flight), group sums added in group order
-__global__ void __launch_bounds__(1024)
-    skinny_fc_finish_kernel(int blocks, int K, int N, const float* __restrict__ partial,
-                            float* __restrict__ dw, float* __restrict__ db) {
-  __shared__ float part[16][64];
-  const int stride = kSkinnyK + 1;
-  const int total = N * stride;
-  const int c = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + c;
-  const int chunk = (blocks + 15) / 16;
-  const int b0 = grp * chunk, b1 = min(blocks, b0 + chunk);
-  float t = 0.f;
-  if (i < total) {
-    int b = b0;
-    for (; b + 8 <= b1; b += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = partial[(size_t)(b + u) * total + i];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t += v[u];
-    }
-    for (; b < b1; b++) t += partial[(size_t)b * total + i];
-  }
-  part[grp][c] = t;
-  __syncthreads();
-  if (grp == 0 && i < total) {
-    float tot = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; q++) tot += part[q][c];
-    const int n = i / stride, k = i % stride;
-    if (k == kSkinnyK) db[n] = tot;
-    else if (k < K) dw[(size_t)n * K + k] = tot;
+// ================================================================================================
+// Optimizers of the dense layers: SGD and Ftrl on the fp32 masters, with the refresh of the 16-bit
+// compute copy.  The dense SGD step is ONE expression for every kernel that takes it (f32x4 or
+// float): a parameter rounds the same (contraction included) whichever kernel updates it.
+// ================================================================================================
+template <typename V>
+__device__ __forceinline__ V sgd_apply(V w, V g, float lr, float grad_scale) {
+  w -= lr * grad_scale * g;
+  return w;
+}
+
+// dense SGD step fused with the refresh of the 16-bit compute copy: w -= lr * g; w16 = (T16)w
+template <bool BF>
+__global__ void __launch_bounds__(kBlock)
+    sgd_shadow_kernel(size_t n4, float lr, float grad_scale, float* __restrict__ w,
+                      const float* __restrict__ g, unsigned short* __restrict__ w16) {
+  using H = H16<BF>;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4;
+       i += (size_t)gridDim.x * kBlock) {
+    f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    wv = sgd_apply(wv, gv, lr, grad_scale);
+    reinterpret_cast<f32x4*>(w)[i] = wv;
+    reinterpret_cast<uint2*>(w16)[i] = H::pack4(wv[0], wv[1], wv[2], wv[3]);
   }
 }
 
 // ================================================================================================
-// Gradient finish: ONE launch per step takes every fixed-order partial sum the backward's producers
-// left (split-K weight-gradient products, bias tile partials, the logit head's and the skinny first
-// layer's block partials) to its place in the flat gradient buffer -- or, SGD = true, straight
-// through the optimizer step into the fp32 masters and their 16-bit copy.  A workgroup finds its
-// segment in the table by its block number; each segment kind adds in the order of the kernel it
-// stands in for (sum_groups / colsum_partials / logit_head_finish / skinny_fc_finish), term for
-// term, so every gradient keeps its bits.
+// Dense Ftrl (ftrl_update_kernel and its launch, R/HugeCTR/src/optimizers/ftrl_optimizer.cu:28-43,
+// 92-93).  Like sgd_apply, the step is ONE expression for every kernel that takes it (f32x4 or
+// float), so a parameter rounds the same whichever kernel updates it.
+//   g = grad * grad_scale;  n' = n + g*g;  z' = z + g + (sqrt(n + eps) - sqrt(n' + eps)) * w / lr
+//   w' = |z'| > lambda1 ? (lambda1 * sgn(z') - z') / (sqrt(n' + eps) / lr + l2) : 0
+// with eps = FLT_EPSILON, l2 = lambda2 + beta / lr (formed once on the host) and sgn = +1 for a
+// clear sign bit.  A parameter whose gradient is 0 on the first step becomes 0: z' stays 0.
 // ================================================================================================
+struct FtrlHp {
+  float lr, lambda1, l2, grad_scale;
+};
+
+__device__ __forceinline__ float ftrl_apply(float w, float& z, float& n, float grad, FtrlHp h) {
+  constexpr float eps = 1.1920928955078125e-7f;  // FLT_EPSILON
+  const float g = grad * h.grad_scale;
+  const float n_new = n + g * g;
+  const float root = sqrtf(n_new + eps);
+  const float z_new = z + g + (sqrtf(n + eps) - root) * w / h.lr;
+  const float x = (__builtin_signbitf(z_new) ? -h.lambda1 : h.lambda1) - z_new;
+  const float y = root / h.lr + h.l2;
+  n = n_new;
+  z = z_new;
+  return fabsf(z_new) > h.lambda1 ? x / y : 0.f;
+}
+
+__device__ __forceinline__ f32x4 ftrl_apply(f32x4 w, f32x4& z, f32x4& n, f32x4 grad, FtrlHp h) {
+  f32x4 out;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    float ze = z[e], ne = n[e];
+    out[e] = ftrl_apply(w[e], ze, ne, grad[e], h);
+    z[e] = ze;
+    n[e] = ne;
+  }
+  return out;
+}
+
+// the flat form: the twin of sgd_shadow_kernel (SHADOW 0: no 16-bit copy, 1: fp16, 2: bf16)
+template <int SHADOW>
+__global__ void __launch_bounds__(kBlock)
+    ftrl_shadow_kernel(size_t n4, FtrlHp h, float* __restrict__ w, float* __restrict__ z,
+                       float* __restrict__ nacc, const float* __restrict__ g,
+                       unsigned short* __restrict__ w16) {
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4;
+       i += (size_t)gridDim.x * kBlock) {
+    f32x4 zv = reinterpret_cast<f32x4*>(z)[i];
+    f32x4 nv = reinterpret_cast<f32x4*>(nacc)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    const f32x4 wv = ftrl_apply(reinterpret_cast<f32x4*>(w)[i], zv, nv, gv, h);
+    reinterpret_cast<f32x4*>(w)[i] = wv;
+    reinterpret_cast<f32x4*>(z)[i] = zv;
+    reinterpret_cast<f32x4*>(nacc)[i] = nv;
+    if (SHADOW) {
+      using H = H16<SHADOW == 2>;
+      reinterpret_cast<uint2*>(w16)[i] = H::pack4(wv[0], wv[1], wv[2], wv[3]);
+    }
+  }
+}
+
+// a workgroup's entry in a table of segments (hctr_ftrl_seg, hctr_dense_seg): the last one whose
+// first block is not past it, -1 if there is none.  Every wavefront looks at 64 table entries per
+// step (one load latency, not one per segment).
+template <typename Seg>
+__device__ __forceinline__ int find_segment(const Seg* __restrict__ segs, int nseg) {
+  int si = -1;
+  for (int base = 0; base < nseg; base += 64) {
+    const int t = base + (int)(threadIdx.x & 63);
+    const bool in = t < nseg && segs[t].block0 <= (long long)blockIdx.x;
+    si += (int)__popcll(__ballot(in));
+  }
+  return si;
+}
+
+// the segmented form: parameter tensors that do not live in one buffer; their gradients and the
+// state do (flat g / z / n, a segment's elements at `off`).  A block takes kFtrlSegElems elements
+// of one segment.  Groups of 4 go through the vector form when the segment allows it (w 16-byte
+// aligned, off % 4 == 0), the tail and everything else through the scalar form of the same
+// expression.
+constexpr int kFtrlSegElems = HCTR_FTRL_SEG_BLOCK_ELEMS;
+static_assert(kFtrlSegElems == kBlock * 4, "a thread takes 4 elements");
+
+__global__ void __launch_bounds__(kBlock)
+    ftrl_segments_kernel(const hctr_ftrl_seg* __restrict__ segs, int nseg, FtrlHp h,
+                         float* __restrict__ z, float* __restrict__ nacc,
+                         const float* __restrict__ g) {
+  const int si = find_segment(segs, nseg);
+  if (si < 0) return;  // (a table whose first segment does not start at block 0)
+  const hctr_ftrl_seg sg = segs[si];
+  const size_t cnt = (size_t)sg.n, off = (size_t)sg.off;
+  float* w = reinterpret_cast<float*>(sg.w);
+  const size_t e0 = ((size_t)((long long)blockIdx.x - sg.block0) * kBlock + threadIdx.x) * 4;
+  if (e0 >= cnt) return;
+  const bool vec = (sg.w & 15) == 0 && (off & 3) == 0 && e0 + 4 <= cnt;
+  if (vec) {
+    f32x4 zv = *reinterpret_cast<f32x4*>(z + off + e0);
+    f32x4 nv = *reinterpret_cast<f32x4*>(nacc + off + e0);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + off + e0);
+    const f32x4 wv = ftrl_apply(*reinterpret_cast<f32x4*>(w + e0), zv, nv, gv, h);
+    *reinterpret_cast<f32x4*>(w + e0) = wv;
+    *reinterpret_cast<f32x4*>(z + off + e0) = zv;
+    *reinterpret_cast<f32x4*>(nacc + off + e0) = nv;
+    return;
+  }
+  const size_t e1 = e0 + 4 < cnt ? e0 + 4 : cnt;
+  for (size_t e = e0; e < e1; e++) {
+    float zs = z[off + e], ns = nacc[off + e];
+    w[e] = ftrl_apply(w[e], zs, ns, g[off + e], h);
+    z[off + e] = zs;
+    nacc[off + e] = ns;
+  }
+}
+
+// ================================================================================================
+// Fixed-order sums and the gradient finish.  Every partial sum the backward's producers leave
+// (split-K weight-gradient products, bias tile partials, the logit head's and the skinny first
+// layer's block partials) is described by one hctr_dense_seg and added by ONE body per kind, a
+// function of (segment, block number within the segment, store policy).  Two kernels call them:
+// dense_grad_finish_kernel, ONE launch per step over a table of segments, which stores into the
+// flat gradient buffer or, SGD = true, straight through the optimizer step into the fp32 masters
+// and their 16-bit copy; and dense_seg_finish_kernel, one segment for the stand-alone entries
+// (hctr_sum_groups, the db of hctr_relu_bwd_bias / hctr_cross_v2_bwd_step, hctr_logit_head,
+// hctr_skinny_fc_bwd).  The order of additions is the body's, so a gradient has the same bits
+// whichever way it was finished.
+// ================================================================================================
+// a segment's source or gradient address as a pointer.  The table holds integers, and a pointer
+// made from an integer is a flat one (flat_load / flat_store); these addresses are global memory,
+// and saying so gives the global instructions a kernel's pointer arguments get.
+template <typename T>
+__device__ __forceinline__ T* seg_ptr(int64_t addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (T*)reinterpret_cast<__attribute__((address_space(1))) T*>(addr);
+#else
+  return reinterpret_cast<T*>(addr);
+#endif
+}
+
 template <bool SGD>
 __device__ __forceinline__ void finish_store4(const hctr_dense_seg& sg, size_t at, f32x4 gv,
                                               float lr, float grad_scale) {
   if (!SGD) {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(sg.g) + at) = gv;
+    *reinterpret_cast<f32x4*>(seg_ptr<float>(sg.g) + at) = gv;
     return;
   }
   f32x4* wp = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(sg.w) + at);
   const f32x4 wv = sgd_apply(*wp, gv, lr, grad_scale);
   *wp = wv;
-  unsigned lo, hi;
-  if (sg.bf16) {
-    lo = (unsigned)H16<true>::from_f32(wv[0]) | ((unsigned)H16<true>::from_f32(wv[1]) << 16);
-    hi = (unsigned)H16<true>::from_f32(wv[2]) | ((unsigned)H16<true>::from_f32(wv[3]) << 16);
-  } else {
-    lo = (unsigned)H16<false>::from_f32(wv[0]) | ((unsigned)H16<false>::from_f32(wv[1]) << 16);
-    hi = (unsigned)H16<false>::from_f32(wv[2]) | ((unsigned)H16<false>::from_f32(wv[3]) << 16);
-  }
-  *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(sg.w16) + at) = make_uint2(lo, hi);
+  *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(sg.w16) + at) =
+      sg.bf16 ? H16<true>::pack4(wv[0], wv[1], wv[2], wv[3])
+              : H16<false>::pack4(wv[0], wv[1], wv[2], wv[3]);
 }
 
 template <bool SGD>
 __device__ __forceinline__ void finish_store1(const hctr_dense_seg& sg, size_t at, float gv,
                                               float lr, float grad_scale) {
   if (!SGD) {
-    reinterpret_cast<float*>(sg.g)[at] = gv;
+    seg_ptr<float>(sg.g)[at] = gv;
     return;
   }
   float* wp = reinterpret_cast<float*>(sg.w) + at;
@@ -1013,36 +915,84 @@ __device__ __forceinline__ void finish_store1(const hctr_dense_seg& sg, size_t a
       sg.bf16 ? H16<true>::from_f32(wv) : H16<false>::from_f32(wv);
 }
 
-// sum_groups_kernel's sum for element group i
-template <bool BF>
-__device__ __forceinline__ void finish_sum_groups(int groups, size_t n8, size_t i,
-                                                  const unsigned short* __restrict__ in,
-                                                  f32x4& lo, f32x4& hi) {
+// SUM_GROUPS: out[i] = sum_g in[g][i], g = 0 .. count - 1 in order; 16-bit partial products of a
+// split-K GEMM -> fp32.  A thread owns 8 consecutive elements, a block 256 * 8.
+// UNROLL loads in flight, added in group order whatever UNROLL is.
+template <bool BF, int UNROLL>
+__device__ __forceinline__ void sum_groups8(int groups, size_t n8, size_t i,
+                                            const unsigned short* __restrict__ in, f32x4& lo,
+                                            f32x4& hi) {
   using H = H16<BF>;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  // (the usual 16 groups: all 16 loads in flight, added in group order)
-#pragma unroll 16
+#pragma unroll UNROLL
   for (int g = 0; g < groups; g++) {
     const u32x4 v = *reinterpret_cast<const u32x4*>(in + ((size_t)g * n8 + i) * 8);
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      acc[2 * e] += H::to_f32((unsigned short)(v[e] & 0xFFFFu));
-      acc[2 * e + 1] += H::to_f32((unsigned short)(v[e] >> 16));
+      acc[2 * e] += H::lo(v[e]);
+      acc[2 * e + 1] += H::hi(v[e]);
     }
   }
   lo = f32x4{acc[0], acc[1], acc[2], acc[3]};
   hi = f32x4{acc[4], acc[5], acc[6], acc[7]};
 }
 
-// the chunked block sum of logit_head_finish_kernel / skinny_fc_finish_kernel for 64 consecutive
-// columns: 16 chunk groups, each added in block order, then the groups in order.  Here a wavefront
-// takes four of the groups, one after the other (256 threads instead of 1024): the same sums.
+// SRC: the products' type, 1 bf16, 0 fp16, -1 as the segment says (a table mixes both)
+template <bool SGD, int UNROLL, int SRC = -1>
+__device__ __forceinline__ void finish_sum_groups(const hctr_dense_seg& sg, int blk, float lr,
+                                                  float grad_scale) {
+  const size_t n8 = (size_t)sg.n / 8;
+  const size_t i = (size_t)blk * kBlock + threadIdx.x;
+  if (i >= n8) return;
+  const unsigned short* in = seg_ptr<const unsigned short>(sg.src);
+  f32x4 lo, hi;
+  if (SRC < 0 ? sg.src_bf16 != 0 : SRC == 1) sum_groups8<true, UNROLL>((int)sg.count, n8, i, in, lo, hi);
+  else sum_groups8<false, UNROLL>((int)sg.count, n8, i, in, lo, hi);
+  finish_store4<SGD>(sg, (size_t)sg.dst + i * 8, lo, lr, grad_scale);
+  finish_store4<SGD>(sg, (size_t)sg.dst + i * 8 + 4, hi, lr, grad_scale);
+}
+
+// COLSUM: db[c .. c + 3] = sum over tiles of partial[tile][c .. c + 3].  A block of 256 threads
+// owns 8 float4 column groups x 32 tile groups: tile group tg adds tiles tg, tg + 32, ... in order,
+// then the 32 group sums are added in group order through LDS (red: 256 f32x4).
+template <bool SGD>
+__device__ __forceinline__ void finish_colsum(const hctr_dense_seg& sg, int blk, f32x4* red,
+                                              float lr, float grad_scale) {
+  const float* partial = seg_ptr<const float>(sg.src);
+  const size_t tiles = (size_t)sg.count;
+  const int n = (int)sg.n;
+  const int c4 = blk * 8 + (threadIdx.x & 7), tg = threadIdx.x >> 3;
+  const bool live = c4 * 4 < n;
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (live) {
+#pragma unroll 8
+    for (size_t t = tg; t < tiles; t += 32)
+      s += *reinterpret_cast<const f32x4*>(partial + t * n + c4 * 4);
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (tg == 0 && live) {
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 32; k++) sum += red[k * 8 + threadIdx.x];
+    finish_store4<SGD>(sg, (size_t)sg.dst + (size_t)c4 * 4, sum, lr, grad_scale);
+  }
+}
+
+// The chunked block sum of the logit head's and the skinny first layer's block partials
+// (partial[block][stride], this block's 64 consecutive columns, `col` the thread's): 16 chunk
+// groups of ceil(blocks / 16) consecutive blocks, each added in block order with 8 loads in flight,
+// then the 16 group sums in group order through LDS (part: float [16][64]).  The groups are dealt
+// to the block's WAVES wavefronts -- a template argument, which the caller keeps equal to
+// blockDim.x / 64: one each at 1024 threads (straight-line code), four each, one after the other,
+// at 256 -- the same sums.  The total is valid in the first wavefront.
+template <int WAVES>
 __device__ __forceinline__ float finish_block_chunks(float (*part)[64], int blocks, size_t stride,
                                                      size_t col, bool live,
                                                      const float* __restrict__ partial) {
   const int c = threadIdx.x & 63;
   const int chunk = (blocks + 15) / 16;
-  for (int grp = threadIdx.x >> 6; grp < 16; grp += kBlock / 64) {
+  for (int grp = threadIdx.x >> 6; grp < 16; grp += WAVES) {
     const int b0 = grp * chunk, b1 = min(blocks, b0 + chunk);
     float t = 0.f;
     if (live) {
@@ -1067,115 +1017,165 @@ __device__ __forceinline__ float finish_block_chunks(float (*part)[64], int bloc
   return tot;
 }
 
+// LOGIT_HEAD: partial [count blocks][K + 2] = dw, db, loss; *loss = sum / batch (sg.k)
+template <bool SGD, int WAVES>
+__device__ __forceinline__ void finish_logit_head(const hctr_dense_seg& sg, int blk,
+                                                  float (*part)[64], float lr, float grad_scale,
+                                                  float* __restrict__ loss) {
+  const int K = (int)sg.n;
+  const int k = blk * 64 + (int)(threadIdx.x & 63);
+  const bool live = k < K + 2;
+  const float tot = finish_block_chunks<WAVES>(part, (int)sg.count, (size_t)(K + 2), (size_t)k, live,
+                                        seg_ptr<const float>(sg.src));
+  if (threadIdx.x < 64 && live) {
+    if (k < K) finish_store1<SGD>(sg, (size_t)sg.dst + k, tot, lr, grad_scale);
+    else if (k == K) finish_store1<SGD>(sg, (size_t)sg.dst2, tot, lr, grad_scale);
+    else if (loss) *loss = tot / (float)(size_t)sg.k;
+  }
+}
+
+// SKINNY: partial [count blocks][N][kSkinnyK + 1] -> dw [N][K] and db [N]
+template <bool SGD, int WAVES>
+__device__ __forceinline__ void finish_skinny(const hctr_dense_seg& sg, int blk, float (*part)[64],
+                                              float lr, float grad_scale) {
+  const int stride = kSkinnyK + 1;
+  const int K = (int)sg.k, total = (int)sg.n * stride;
+  const int i = blk * 64 + (int)(threadIdx.x & 63);
+  const bool live = i < total;
+  const float tot = finish_block_chunks<WAVES>(part, (int)sg.count, (size_t)total, (size_t)i, live,
+                                        seg_ptr<const float>(sg.src));
+  if (threadIdx.x < 64 && live) {
+    const int n = i / stride, kk = i % stride;
+    if (kk == kSkinnyK) finish_store1<SGD>(sg, (size_t)sg.dst2 + n, tot, lr, grad_scale);
+    else if (kk < K) finish_store1<SGD>(sg, (size_t)sg.dst + (size_t)n * K + kk, tot, lr, grad_scale);
+  }
+}
+
 template <bool SGD>
 __global__ void __launch_bounds__(kBlock)
     dense_grad_finish_kernel(const hctr_dense_seg* __restrict__ segs, int nseg, float lr,
                              float grad_scale, float* __restrict__ loss) {
   __shared__ f32x4 red[kBlock];  // colsum: [32 tile groups][8]; head / skinny: float [16][64]
-  // the block's segment = the last one whose first block is not past it: every wavefront looks at
-  // 64 table entries per step (one load latency, not one per segment)
-  int si = -1;
-  for (int base = 0; base < nseg; base += 64) {
-    const int t = base + (int)(threadIdx.x & 63);
-    const bool in = t < nseg && segs[t].block0 <= (long long)blockIdx.x;
-    si += (int)__popcll(__ballot(in));
-  }
-  const hctr_dense_seg sg = segs[si];
+  const hctr_dense_seg sg = segs[find_segment(segs, nseg)];
   const int blk = (int)((long long)blockIdx.x - sg.block0);
-  const size_t dst = (size_t)sg.dst, dst2 = (size_t)sg.dst2;
   switch ((int)sg.kind) {
-    case HCTR_DENSE_SEG_SUM_GROUPS: {
-      const size_t n8 = (size_t)sg.n / 8;
-      const size_t i = (size_t)blk * kBlock + threadIdx.x;
-      if (i >= n8) return;
-      const unsigned short* in = reinterpret_cast<const unsigned short*>(sg.src);
-      f32x4 lo, hi;
-      if (sg.src_bf16) finish_sum_groups<true>((int)sg.count, n8, i, in, lo, hi);
-      else finish_sum_groups<false>((int)sg.count, n8, i, in, lo, hi);
-      finish_store4<SGD>(sg, dst + i * 8, lo, lr, grad_scale);
-      finish_store4<SGD>(sg, dst + i * 8 + 4, hi, lr, grad_scale);
-      return;
-    }
-    case HCTR_DENSE_SEG_COLSUM: {  // colsum_partials_kernel
-      const float* partial = reinterpret_cast<const float*>(sg.src);
-      const size_t tiles = (size_t)sg.count;
-      const int n = (int)sg.n;
-      const int c4 = blk * 8 + (threadIdx.x & 7), tg = threadIdx.x >> 3;
-      const bool live = c4 * 4 < n;
-      f32x4 s = {0.f, 0.f, 0.f, 0.f};
-      if (live) {
-#pragma unroll 8
-        for (size_t t = tg; t < tiles; t += 32)
-          s += *reinterpret_cast<const f32x4*>(partial + t * n + c4 * 4);
-      }
-      red[threadIdx.x] = s;
-      __syncthreads();
-      if (tg == 0 && live) {
-        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 32; k++) sum += red[k * 8 + threadIdx.x];
-        finish_store4<SGD>(sg, dst + (size_t)c4 * 4, sum, lr, grad_scale);
-      }
-      return;
-    }
-    case HCTR_DENSE_SEG_LOGIT_HEAD: {  // logit_head_finish_kernel; partial [blocks][K + 2]
-      const int K = (int)sg.n;
-      const int k = blk * 64 + (int)(threadIdx.x & 63);
-      const bool live = k < K + 2;
-      const float tot = finish_block_chunks(reinterpret_cast<float(*)[64]>(red), (int)sg.count,
-                                            (size_t)(K + 2), (size_t)k, live,
-                                            reinterpret_cast<const float*>(sg.src));
-      if (threadIdx.x < 64 && live) {
-        if (k < K) finish_store1<SGD>(sg, dst + k, tot, lr, grad_scale);
-        else if (k == K) finish_store1<SGD>(sg, dst2, tot, lr, grad_scale);
-        else if (loss) *loss = tot / (float)(size_t)sg.k;
-      }
-      return;
-    }
-    case HCTR_DENSE_SEG_SKINNY: {  // skinny_fc_finish_kernel; partial [blocks][N][kSkinnyK + 1]
-      const int stride = kSkinnyK + 1;
-      const int K = (int)sg.k, total = (int)sg.n * stride;
-      const int i = blk * 64 + (int)(threadIdx.x & 63);
-      const bool live = i < total;
-      const float tot = finish_block_chunks(reinterpret_cast<float(*)[64]>(red), (int)sg.count,
-                                            (size_t)total, (size_t)i, live,
-                                            reinterpret_cast<const float*>(sg.src));
-      if (threadIdx.x < 64 && live) {
-        const int n = i / stride, kk = i % stride;
-        if (kk == kSkinnyK) finish_store1<SGD>(sg, dst2 + n, tot, lr, grad_scale);
-        else if (kk < K) finish_store1<SGD>(sg, dst + (size_t)n * K + kk, tot, lr, grad_scale);
-      }
-      return;
-    }
+    // (the usual 16 groups: all 16 loads in flight)
+    case HCTR_DENSE_SEG_SUM_GROUPS: return finish_sum_groups<SGD, 16>(sg, blk, lr, grad_scale);
+    case HCTR_DENSE_SEG_COLSUM: return finish_colsum<SGD>(sg, blk, red, lr, grad_scale);
+    case HCTR_DENSE_SEG_LOGIT_HEAD:
+      return finish_logit_head<SGD, kWavesPerBlock>(sg, blk, reinterpret_cast<float(*)[64]>(red), lr,
+                                                    grad_scale, loss);
+    case HCTR_DENSE_SEG_SKINNY:
+      return finish_skinny<SGD, kWavesPerBlock>(sg, blk, reinterpret_cast<float(*)[64]>(red), lr,
+                                                grad_scale);
     default: {  // HCTR_DENSE_SEG_DIRECT: the gradient is in g already; only the step is left
       if (!SGD) return;
       const size_t i = (size_t)blk * kBlock + threadIdx.x;
       if (i >= (size_t)sg.n / 4) return;
-      const f32x4 gv = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(sg.g) + dst + i * 4);
-      finish_store4<SGD>(sg, dst + i * 4, gv, lr, grad_scale);
+      const size_t at = (size_t)sg.dst + i * 4;
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(sg.g) + at);
+      finish_store4<SGD>(sg, at, gv, lr, grad_scale);
       return;
     }
   }
 }
 
-constexpr int kCrossBwdWaves = 256 * 4;  // waves used by the cross backward (deterministic reduce)
+// one segment of kind KIND, gradients only: the finish of a stand-alone entry.  256 threads for the
+// group and column sums, 1024 for the chunked block sums (one chunk group per wavefront).  KIND is a
+// template argument, like the wavefront count of the chunked sums, and the group sum keeps 4 loads
+// in flight here: as measured, a switch on the kind inside one kernel, blockDim.x for the wavefront
+// count and 16 loads in flight were each slower (profiles/dense_refactor_ab.txt).
+constexpr int seg_finish_threads(int kind) {
+  return kind == HCTR_DENSE_SEG_LOGIT_HEAD || kind == HCTR_DENSE_SEG_SKINNY ? 1024 : kBlock;
+}
+
+template <int KIND, int SRC>
+__global__ void __launch_bounds__(seg_finish_threads(KIND))
+    dense_seg_finish_kernel(const hctr_dense_seg sg, float* __restrict__ loss) {
+  __shared__ f32x4 red[kBlock];
+  const int blk = (int)blockIdx.x;
+  constexpr int WAVES = seg_finish_threads(KIND) / 64;
+  float(*part)[64] = reinterpret_cast<float(*)[64]>(red);
+  if (KIND == HCTR_DENSE_SEG_SUM_GROUPS) finish_sum_groups<false, 4, SRC>(sg, blk, 0.f, 0.f);
+  if (KIND == HCTR_DENSE_SEG_COLSUM) finish_colsum<false>(sg, blk, red, 0.f, 0.f);
+  if (KIND == HCTR_DENSE_SEG_LOGIT_HEAD)
+    finish_logit_head<false, WAVES>(sg, blk, part, 0.f, 0.f, loss);
+  if (KIND == HCTR_DENSE_SEG_SKINNY)
+    finish_skinny<false, WAVES>(sg, blk, part, 0.f, 0.f);
+}
 
 }  // namespace
 }  // namespace hctr
 
 using namespace hctr;
 
+// ================================================================================================
+// Host entries, in the order of the kernels above.  Run-time value -> template argument as in
+// common.h (with_bool / with_dtype).
+// ================================================================================================
+namespace {
+
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
+// the 16-bit element type of a dtype the caller has required to be HCTR_EMB_BF16 or HCTR_EMB_F16
+template <bool BF>
+using T16 = std::conditional_t<BF, __hip_bfloat16, __half>;
+
+inline bool is16(int dtype) { return dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16; }
+inline bool aligned(const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+
+// f(int_c<NPL>{}): the 64-lane column slots per lane of the cross v1 kernels, a power of two
+template <typename F>
+void with_npl(int npl, F&& f) {
+  if (npl <= 1) f(int_c<1>{});
+  else if (npl <= 2) f(int_c<2>{});
+  else if (npl <= 4) f(int_c<4>{});
+  else if (npl <= 8) f(int_c<8>{});
+  else if (npl <= 16) f(int_c<16>{});
+  else if (npl <= 32) f(int_c<32>{});
+  else f(int_c<64>{});
+}
+
+// f(int_c<NSEG>{}, int_c<ROWS>{}) of the logit head: NSEG 256-element segments cover K, a
+// wavefront then takes ROWS = 8 / NSEG rows per iteration
+template <typename F>
+void with_head_shape(int k, F&& f) {
+  const int nseg = (k + 255) / 256;
+  if (nseg <= 1) f(int_c<1>{}, int_c<8>{});
+  else if (nseg <= 2) f(int_c<2>{}, int_c<4>{});
+  else if (nseg <= 4) f(int_c<4>{}, int_c<2>{});
+  else f(int_c<8>{}, int_c<1>{});
+}
+
+// The finish of a stand-alone entry: the entry's partial sums as ONE gradients-only segment of kind
+// KIND, handed to dense_seg_finish_kernel<KIND> by value.  out stands for the flat buffer (dst = 0;
+// 16-byte aligned where the kind stores float4, as the entries always required).  out2 is addressed
+// from it: dst2 is its signed distance in elements (both are float arrays), which the device adds to
+// out as a 64-bit offset, so out2 may lie below out.
+template <int KIND, int SRC = -1>
+int finish_one(const void* src, size_t count, size_t n, size_t k, float* out, float* out2,
+               float* loss, hipStream_t s) {
+  hctr_dense_seg sg = {};
+  sg.kind = KIND;
+  sg.src = (int64_t)reinterpret_cast<uintptr_t>(src);
+  sg.count = (int64_t)count;
+  sg.n = (int64_t)n;
+  sg.k = (int64_t)k;
+  sg.g = (int64_t)reinterpret_cast<uintptr_t>(out);
+  if (out2) sg.dst2 = ((int64_t)reinterpret_cast<uintptr_t>(out2) - sg.g) / (int64_t)sizeof(float);
+  sg.src_bf16 = SRC == 1;
+  hipLaunchKernelGGL((dense_seg_finish_kernel<KIND, SRC>), dim3(hctr_dense_seg_blocks(KIND, n)),
+                     dim3(seg_finish_threads(KIND)), 0, s, sg, loss);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
-#define HCTR_CROSS_DISPATCH(MACRO)       \
-  if (npl <= 1) MACRO(1)                 \
-  else if (npl <= 2) MACRO(2)            \
-  else if (npl <= 4) MACRO(4)            \
-  else if (npl <= 8) MACRO(8)            \
-  else if (npl <= 16) MACRO(16)          \
-  else if (npl <= 32) MACRO(32)          \
-  else MACRO(64)
-
+// ---- cross v1 --------------------------------------------------------------------------------------
 int hctr_cross_v1_fwd(size_t batch, int width, int layers, const float* x0, const float* kernels,
                       const float* biases, float* outputs, float* hiddens, hctr_stream_t stream) {
   HCTR_REQUIRE(width >= 1 && layers >= 1, "shape");
@@ -1183,13 +1183,11 @@ int hctr_cross_v1_fwd(size_t batch, int width, int layers, const float* x0, cons
   if (batch == 0) return HCTR_OK;
   HCTR_REQUIRE(x0 && kernels && biases && outputs && hiddens, "null pointer");
   hipStream_t s = as_stream(stream);
-  const int npl = (width + 63) / 64;
-  const int grid = grid_for(batch * 64, kBlock);
-#define HCTR_CF(N_)                                                                            \
-  hipLaunchKernelGGL(cross_v1_fwd_kernel<N_>, dim3(grid), dim3(kBlock), 0, s, batch, width,    \
-                     layers, x0, kernels, biases, outputs, hiddens);
-  HCTR_CROSS_DISPATCH(HCTR_CF)
-#undef HCTR_CF
+  with_npl((width + 63) / 64, [&](auto npl) {
+    hipLaunchKernelGGL(cross_v1_fwd_kernel<decltype(npl)::value>, dim3(grid_for(batch * 64, kBlock)),
+                       dim3(kBlock), 0, s, batch, width, layers, x0, kernels, biases, outputs,
+                       hiddens);
+  });
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -1209,23 +1207,17 @@ int hctr_cross_v1_bwd(size_t batch, int width, int layers, const float* x0, cons
                    bias_grads && workspace,
                "null pointer");
   hipStream_t s = as_stream(stream);
-  const int npl = (width + 63) / 64;
-  const int grid = kCrossBwdWaves / kWavesPerBlock;
+  // one wavefront per workgroup with its partial rows in LDS while they fit, else in the workspace
   const size_t lds_bytes = (size_t)layers * 2 * width * sizeof(float);
-  if (lds_bytes <= 60 * 1024) {
-#define HCTR_CB(N_)                                                                           \
-  hipLaunchKernelGGL((cross_v1_bwd_kernel<N_, true>), dim3(kCrossBwdWaves), dim3(64), lds_bytes, \
-                     s, batch, width, layers, x0, kernels, outputs, hiddens, out_grad, in_grad,  \
-                     workspace);
-    HCTR_CROSS_DISPATCH(HCTR_CB)
-#undef HCTR_CB
-  } else {
-#define HCTR_CB(N_)                                                                           \
-  hipLaunchKernelGGL((cross_v1_bwd_kernel<N_, false>), dim3(grid), dim3(kBlock), 0, s, batch, \
-                     width, layers, x0, kernels, outputs, hiddens, out_grad, in_grad, workspace);
-    HCTR_CROSS_DISPATCH(HCTR_CB)
-#undef HCTR_CB
-  }
+  with_npl((width + 63) / 64, [&](auto npl) {
+    with_bool(lds_bytes <= 60 * 1024, [&](auto lds) {
+      constexpr bool LDS = decltype(lds)::value;
+      hipLaunchKernelGGL((cross_v1_bwd_kernel<decltype(npl)::value, LDS>),
+                         dim3(LDS ? kCrossBwdWaves : kCrossBwdWaves / kWavesPerBlock),
+                         dim3(LDS ? 64 : kBlock), LDS ? lds_bytes : 0, s, batch, width, layers, x0,
+                         kernels, outputs, hiddens, out_grad, in_grad, workspace);
+    });
+  });
   HCTR_LAUNCH_CHECK();
   hipLaunchKernelGGL(cross_v1_reduce_kernel,
                      dim3((unsigned)ceil_div<size_t>((size_t)layers * 2 * width, 32)),
@@ -1235,6 +1227,7 @@ int hctr_cross_v1_bwd(size_t batch, int width, int layers, const float* x0, cons
   return HCTR_OK;
 }
 
+// ---- column-tile producers -------------------------------------------------------------------------
 size_t hctr_relu_bwd_bias_workspace_bytes(size_t rows, int n) {
   return ceil_div<size_t>(rows, (size_t)kRbRows) * (size_t)n * sizeof(float);
 }
@@ -1243,27 +1236,21 @@ size_t hctr_relu_bwd_bias_workspace_bytes(size_t rows, int n) {
 static int relu_bwd_bias_impl(size_t rows, int n, const void* dy, const void* y, void* dz, float* db,
                               float* workspace, int dtype, bool finish, hctr_stream_t stream) {
   HCTR_REQUIRE(n > 0 && n % 8 == 0, "n must be a multiple of 8");
-  HCTR_REQUIRE(dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16, "16-bit dtypes only");
+  HCTR_REQUIRE(is16(dtype), "16-bit dtypes only");
   if (rows == 0) return HCTR_OK;
   HCTR_REQUIRE(dy && y && dz && (db || !finish) && workspace, "null pointer");
   hipStream_t s = as_stream(stream);
   const size_t tiles = ceil_div<size_t>(rows, (size_t)kRbRows);
   const int cw = n / 8 < kBlock ? n / 8 : kBlock;
-  const int rg = kBlock / cw;
-  if (dtype == HCTR_EMB_BF16)
-    hipLaunchKernelGGL(relu_bwd_bias_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), 0, s, rows,
-                       n, cw, rg, (const unsigned short*)dy, (const unsigned short*)y,
-                       (unsigned short*)dz, workspace);
-  else
-    hipLaunchKernelGGL(relu_bwd_bias_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0, s,
-                       rows, n, cw, rg, (const unsigned short*)dy, (const unsigned short*)y,
-                       (unsigned short*)dz, workspace);
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    hipLaunchKernelGGL(relu_bwd_bias_kernel<decltype(bf)::value>, dim3((unsigned)tiles),
+                       dim3(kBlock), 0, s, rows, n, cw, kBlock / cw, (const unsigned short*)dy,
+                       (const unsigned short*)y, (unsigned short*)dz, workspace);
+  });
   HCTR_LAUNCH_CHECK();
   if (!finish) return HCTR_OK;
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3(ceil_div<int>(n, 32)), dim3(kBlock), 0, s,
-                     tiles, n, workspace, db);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
+  return finish_one<HCTR_DENSE_SEG_COLSUM>(workspace, tiles, (size_t)n, 0, db, nullptr, nullptr,
+                                           s);
 }
 
 int hctr_relu_bwd_bias(size_t rows, int n, const void* dy, const void* y, void* dz, float* db,
@@ -1286,152 +1273,44 @@ int hctr_cross_v2_bwd_step(size_t batch, int width, const void* dy, const void* 
                            void* acc, void* s0, float* db, float* workspace, int first, int dtype,
                            hctr_stream_t stream) {
   HCTR_REQUIRE(width > 0 && width % 8 == 0, "width must be a multiple of 8");
-  HCTR_REQUIRE(dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16, "16-bit dtypes only");
+  HCTR_REQUIRE(is16(dtype), "16-bit dtypes only");
   if (batch == 0) return HCTR_OK;
   HCTR_REQUIRE(dy && x0 && h && acc && s0 && db && workspace, "null pointer");
   hipStream_t s = as_stream(stream);
   const int cw = width / 8 < kBlock ? width / 8 : kBlock;
-  const int rg = kBlock / cw;
   const int rpt = cross_step_rows_per_tile(batch, width);
   const size_t tiles = ceil_div<size_t>(batch, (size_t)rpt);
   const unsigned col_blocks = (unsigned)ceil_div<int>(width / 8, cw);
-#define HCTR_CROSS_STEP(BF_, FIRST_)                                                              \
-  hipLaunchKernelGGL((cross_v2_bwd_step_kernel<BF_, FIRST_>), dim3((unsigned)tiles, col_blocks),   \
-                     dim3(kBlock), 0, s, batch, width, cw, rg, rpt, (const unsigned short*)dy,     \
-                     (const unsigned short*)x0, (const unsigned short*)h, (unsigned short*)acc,    \
-                     (unsigned short*)s0, workspace)
-  if (dtype == HCTR_EMB_BF16) {
-    if (first) HCTR_CROSS_STEP(true, true);
-    else HCTR_CROSS_STEP(true, false);
-  } else {
-    if (first) HCTR_CROSS_STEP(false, true);
-    else HCTR_CROSS_STEP(false, false);
-  }
-#undef HCTR_CROSS_STEP
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    with_bool(first != 0, [&](auto f) {
+      hipLaunchKernelGGL((cross_v2_bwd_step_kernel<decltype(bf)::value, decltype(f)::value>),
+                         dim3((unsigned)tiles, col_blocks), dim3(kBlock), 0, s, batch, width, cw,
+                         kBlock / cw, rpt, (const unsigned short*)dy, (const unsigned short*)x0,
+                         (const unsigned short*)h, (unsigned short*)acc, (unsigned short*)s0,
+                         workspace);
+    });
+  });
   HCTR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3(ceil_div<int>(width, 32)), dim3(kBlock), 0, s,
-                     tiles, width, workspace, db);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
+  return finish_one<HCTR_DENSE_SEG_COLSUM>(workspace, tiles, (size_t)width, 0, db, nullptr,
+                                           nullptr, s);
 }
 
-int hctr_sum_groups(int groups, size_t n, const void* in, int dtype, float* out,
-                    hctr_stream_t stream) {
-  HCTR_REQUIRE(groups > 0 && n % 8 == 0, "n must be a multiple of 8");
-  HCTR_REQUIRE(dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16, "16-bit dtypes only");
-  if (n == 0) return HCTR_OK;
-  HCTR_REQUIRE(in && out, "null pointer");
-  hipStream_t s = as_stream(stream);
-  const size_t n8 = n / 8;
-  const dim3 grid((unsigned)ceil_div<size_t>(n8, (size_t)kBlock));
-  if (dtype == HCTR_EMB_BF16)
-    hipLaunchKernelGGL(sum_groups_kernel<true>, grid, dim3(kBlock), 0, s, groups, n8,
-                       (const unsigned short*)in, out);
-  else
-    hipLaunchKernelGGL(sum_groups_kernel<false>, grid, dim3(kBlock), 0, s, groups, n8,
-                       (const unsigned short*)in, out);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
-}
-
-int hctr_sgd_shadow(size_t n, float lr, float grad_scale, float* w, const float* g, void* w16,
-                    int dtype, hctr_stream_t stream) {
-  HCTR_REQUIRE(n % 4 == 0, "n must be a multiple of 4");
-  HCTR_REQUIRE(dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16, "16-bit shadow dtypes only");
-  if (n == 0) return HCTR_OK;
-  HCTR_REQUIRE(w && g && w16, "null pointer");
-  hipStream_t s = as_stream(stream);
-  const dim3 grid(grid_for(n / 4, kBlock, 4096));
-  if (dtype == HCTR_EMB_BF16)
-    hipLaunchKernelGGL(sgd_shadow_kernel<true>, grid, dim3(kBlock), 0, s, n / 4, lr, grad_scale, w,
-                       g, (unsigned short*)w16);
-  else
-    hipLaunchKernelGGL(sgd_shadow_kernel<false>, grid, dim3(kBlock), 0, s, n / 4, lr, grad_scale,
-                       w, g, (unsigned short*)w16);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
-}
-
-static int ftrl_check(float lr, float beta, float lambda1, float lambda2, float grad_scale) {
-  HCTR_REQUIRE(lr > 0.f && lr < INFINITY, "ftrl: lr must be positive and finite");
-  HCTR_REQUIRE(beta >= 0.f && lambda1 >= 0.f && lambda2 >= 0.f,
-               "ftrl: beta, lambda1 and lambda2 must not be negative");
-  HCTR_REQUIRE(grad_scale == grad_scale && fabsf(grad_scale) < INFINITY, "ftrl: grad_scale");
-  return HCTR_OK;
-}
-
-static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-int hctr_ftrl_shadow(size_t n, float lr, float beta, float lambda1, float lambda2, float grad_scale,
-                     float* w, float* z, float* nacc, const float* g, void* w16, int dtype,
-                     hctr_stream_t stream) {
-  HCTR_REQUIRE(n % 4 == 0, "n must be a multiple of 4");
-  HCTR_TRY(ftrl_check(lr, beta, lambda1, lambda2, grad_scale));
-  HCTR_REQUIRE(!w16 || dtype == HCTR_EMB_BF16 || dtype == HCTR_EMB_F16,
-               "16-bit shadow dtypes only");
-  if (n == 0) return HCTR_OK;
-  HCTR_REQUIRE(w && z && nacc && g, "null pointer");
-  HCTR_REQUIRE(aligned16(w) && aligned16(z) && aligned16(nacc) && aligned16(g) && aligned16(w16),
-               "16-byte aligned buffers");
-  hipStream_t s = as_stream(stream);
-  const FtrlHp h = {lr, lambda1, lambda2 + beta / lr, grad_scale};
-  const dim3 grid(grid_for(n / 4, kBlock, 4096));
-  if (!w16)
-    hipLaunchKernelGGL(ftrl_shadow_kernel<0>, grid, dim3(kBlock), 0, s, n / 4, h, w, z, nacc, g,
-                       (unsigned short*)nullptr);
-  else if (dtype == HCTR_EMB_F16)
-    hipLaunchKernelGGL(ftrl_shadow_kernel<1>, grid, dim3(kBlock), 0, s, n / 4, h, w, z, nacc, g,
-                       (unsigned short*)w16);
-  else
-    hipLaunchKernelGGL(ftrl_shadow_kernel<2>, grid, dim3(kBlock), 0, s, n / 4, h, w, z, nacc, g,
-                       (unsigned short*)w16);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
-}
-
-int hctr_ftrl_segments(const hctr_ftrl_seg* segs, int nseg, size_t nblocks, float lr, float beta,
-                       float lambda1, float lambda2, float grad_scale, float* z, float* nacc,
-                       const float* g, hctr_stream_t stream) {
-  HCTR_REQUIRE(nseg >= 0 && nblocks <= 0x7FFFFFFFu, "ftrl segments: segment / block count");
-  HCTR_TRY(ftrl_check(lr, beta, lambda1, lambda2, grad_scale));
-  if (nseg == 0 || nblocks == 0) return HCTR_OK;
-  HCTR_REQUIRE(segs && z && nacc && g, "null pointer");
-  HCTR_REQUIRE(aligned16(z) && aligned16(nacc) && aligned16(g), "16-byte aligned buffers");
-  hipStream_t s = as_stream(stream);
-  const FtrlHp h = {lr, lambda1, lambda2 + beta / lr, grad_scale};
-  hipLaunchKernelGGL(ftrl_segments_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, s, segs, nseg,
-                     h, z, nacc, g);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
-}
-
+// ---- loss and logit head ---------------------------------------------------------------------------
 size_t hctr_bce_loss_workspace_bytes(void) { return kBceBlocks * sizeof(float); }
 
 int hctr_bce_loss(size_t batch, const void* logit, const float* label, float grad_scale,
                   void* dlogit, float* loss, float* workspace, int dtype, hctr_stream_t stream) {
   HCTR_REQUIRE(batch > 0, "empty batch");
   HCTR_REQUIRE(logit && label && loss && workspace, "null pointer");
+  HCTR_REQUIRE(dtype == HCTR_EMB_F32 || is16(dtype), "bad dtype");
   hipStream_t s = as_stream(stream);
-  const int blocks = (int)(ceil_div<size_t>(batch, (size_t)kBlock) < (size_t)kBceBlocks
-                               ? ceil_div<size_t>(batch, (size_t)kBlock)
-                               : (size_t)kBceBlocks);
-  switch (dtype) {
-    case HCTR_EMB_F32:
-      hipLaunchKernelGGL(bce_kernel<float>, dim3(blocks), dim3(kBlock), 0, s, batch,
-                         (const float*)logit, label, grad_scale, (float*)dlogit, workspace);
-      break;
-    case HCTR_EMB_F16:
-      hipLaunchKernelGGL(bce_kernel<__half>, dim3(blocks), dim3(kBlock), 0, s, batch,
-                         (const __half*)logit, label, grad_scale, (__half*)dlogit, workspace);
-      break;
-    case HCTR_EMB_BF16:
-      hipLaunchKernelGGL(bce_kernel<__hip_bfloat16>, dim3(blocks), dim3(kBlock), 0, s, batch,
-                         (const __hip_bfloat16*)logit, label, grad_scale, (__hip_bfloat16*)dlogit,
-                         workspace);
-      break;
-    default:
-      HCTR_REQUIRE(false, "bad dtype");
-  }
+  const int blocks = (int)std::min<size_t>(ceil_div<size_t>(batch, (size_t)kBlock), (size_t)kBceBlocks);
+  HCTR_TRY(with_dtype(dtype, [&](auto* t) -> int {
+    using T = std::remove_pointer_t<decltype(t)>;
+    hipLaunchKernelGGL(bce_kernel<T>, dim3(blocks), dim3(kBlock), 0, s, batch, (const T*)logit, label,
+                       grad_scale, (T*)dlogit, workspace);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(kBlock), 0, s, blocks, batch, workspace, loss);
   HCTR_LAUNCH_CHECK();
@@ -1440,16 +1319,18 @@ int hctr_bce_loss(size_t batch, const void* logit, const float* label, float gra
 
 size_t hctr_logit_head_workspace_bytes(int k) { return (size_t)kHeadBlocks * (k + 2) * sizeof(float); }
 
-static int logit_head_rows(int k) {
-  const int nseg = (k + 255) / 256;
-  return nseg <= 1 ? 8 : (nseg <= 2 ? 4 : (nseg <= 4 ? 2 : 1));
+static int logit_head_check(size_t batch, int k) {
+  HCTR_REQUIRE(batch > 0 && k >= 4 && k % 4 == 0 && k <= 256 * kHeadMaxSeg,
+               "logit head: K must be a multiple of 4 and <= 2048");
+  return HCTR_OK;
 }
 
 int hctr_logit_head_blocks(size_t batch, int k) {
-  HCTR_REQUIRE(batch > 0 && k >= 4 && k % 4 == 0 && k <= 256 * kHeadMaxSeg,
-               "logit head: K must be a multiple of 4 and <= 2048");
+  HCTR_TRY(logit_head_check(batch, k));
+  int rows = 0;
+  with_head_shape(k, [&](auto, auto r) { rows = decltype(r)::value; });
   return (int)std::min<size_t>((size_t)kHeadBlocks,
-                               ceil_div<size_t>(batch, (size_t)(kBlock / 64) * logit_head_rows(k)));
+                               ceil_div<size_t>(batch, (size_t)(kBlock / 64) * rows));
 }
 
 // finish = false: the block partials stay in the workspace (hctr_dense_grad_finish adds them)
@@ -1457,40 +1338,26 @@ static int logit_head_impl(size_t batch, int k, const void* x, const void* w, co
                            const float* label, float grad_scale, void* dx, float* dw, float* db,
                            float* loss, float* workspace, int dtype, bool finish,
                            hctr_stream_t stream) {
-  HCTR_REQUIRE(batch > 0 && k >= 4 && k % 4 == 0 && k <= 256 * kHeadMaxSeg,
-               "logit head: K must be a multiple of 4 and <= 2048");
+  HCTR_TRY(logit_head_check(batch, k));
   HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "16-bit activations");
   HCTR_REQUIRE(x && w && bias && label && ((dw && db && loss) || !finish) && workspace,
                "null pointer");
-  HCTR_REQUIRE(reinterpret_cast<uintptr_t>(x) % 8 == 0 && reinterpret_cast<uintptr_t>(w) % 8 == 0 &&
-                   (dx == nullptr || reinterpret_cast<uintptr_t>(dx) % 8 == 0),
-               "8-byte aligned buffers");
+  HCTR_REQUIRE(aligned(x, 8) && aligned(w, 8) && aligned(dx, 8), "8-byte aligned buffers");
   hipStream_t s = as_stream(stream);
-  const int nseg = (k + 255) / 256;
   const int blocks = hctr_logit_head_blocks(batch, k);
   const size_t lds = (size_t)(kBlock / 64) * (k + 2) * sizeof(float);
-#define HCTR_HEAD(T_, NSEG_, ROWS_)                                                               \
-  hipLaunchKernelGGL((logit_head_kernel<T_, NSEG_, ROWS_>), dim3(blocks), dim3(kBlock), lds, s,   \
-                     batch, k, (const T_*)x, (const T_*)w, (const T_*)bias, label, grad_scale,    \
-                     (T_*)dx, workspace)
-#define HCTR_HEAD_T(T_)                       \
-  if (nseg <= 1) HCTR_HEAD(T_, 1, 8);         \
-  else if (nseg <= 2) HCTR_HEAD(T_, 2, 4);    \
-  else if (nseg <= 4) HCTR_HEAD(T_, 4, 2);    \
-  else HCTR_HEAD(T_, 8, 1);
-  if (dtype == HCTR_EMB_BF16) {
-    HCTR_HEAD_T(__hip_bfloat16)
-  } else {
-    HCTR_HEAD_T(__half)
-  }
-#undef HCTR_HEAD_T
-#undef HCTR_HEAD
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    using T = T16<decltype(bf)::value>;
+    with_head_shape(k, [&](auto nseg, auto rows) {
+      hipLaunchKernelGGL((logit_head_kernel<T, decltype(nseg)::value, decltype(rows)::value>),
+                         dim3(blocks), dim3(kBlock), lds, s, batch, k, (const T*)x, (const T*)w,
+                         (const T*)bias, label, grad_scale, (T*)dx, workspace);
+    });
+  });
   HCTR_LAUNCH_CHECK();
   if (!finish) return HCTR_OK;
-  hipLaunchKernelGGL(logit_head_finish_kernel, dim3(ceil_div<int>(k + 2, 64)), dim3(1024), 0, s,
-                     blocks, k, batch, workspace, dw, db, loss);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
+  return finish_one<HCTR_DENSE_SEG_LOGIT_HEAD>(workspace, (size_t)blocks, (size_t)k, batch, dw,
+                                               db, loss, s);
 }
 
 int hctr_logit_head(size_t batch, int k, const void* x, const void* w, const void* bias,
@@ -1507,31 +1374,30 @@ int hctr_logit_head_partials(size_t batch, int k, const void* x, const void* w, 
                          workspace, dtype, false, stream);
 }
 
-static int skinny_check(size_t batch, int k, int n, int dtype) {
+// ---- skinny first layer ----------------------------------------------------------------------------
+static int skinny_check(size_t batch, int k, int n) {
   HCTR_REQUIRE(batch > 0 && k >= 1 && k <= kSkinnyK, "skinny fc: 1 <= K <= 16");
   HCTR_REQUIRE(n >= 4 && n % 4 == 0 && n <= 512, "skinny fc: N a multiple of 4, <= 512");
-  HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "16-bit weights / activations");
   return HCTR_OK;
 }
 
 int hctr_skinny_fc_fwd(size_t batch, int k, int n, const float* x, const void* w, const void* bias,
                        void* y, int dtype, hctr_stream_t stream) {
-  HCTR_TRY(skinny_check(batch, k, n, dtype));
+  HCTR_TRY(skinny_check(batch, k, n));
+  HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "16-bit weights / activations");
   HCTR_REQUIRE(x && w && bias && y, "null pointer");
-  HCTR_REQUIRE(reinterpret_cast<uintptr_t>(y) % 8 == 0, "8-byte aligned output");
+  HCTR_REQUIRE(aligned(y, 8), "8-byte aligned output");
   hipStream_t s = as_stream(stream);
   // R consecutive rows per block (even, <= 256: 16 KB of LDS), about 4 blocks per CU
   size_t rows = ceil_div<size_t>(batch, 1024);
   rows = std::min<size_t>(256, (rows + 1) / 2 * 2);
   const int blocks = (int)ceil_div<size_t>(batch, rows);
   const size_t lds = rows * kSkinnyK * sizeof(float);
-  if (dtype == HCTR_EMB_BF16)
-    hipLaunchKernelGGL(skinny_fc_fwd_kernel<__hip_bfloat16>, dim3(blocks), dim3(kBlock), lds, s,
-                       batch, k, n, (int)rows, x, (const __hip_bfloat16*)w,
-                       (const __hip_bfloat16*)bias, (__hip_bfloat16*)y);
-  else
-    hipLaunchKernelGGL(skinny_fc_fwd_kernel<__half>, dim3(blocks), dim3(kBlock), lds, s, batch, k, n,
-                       (int)rows, x, (const __half*)w, (const __half*)bias, (__half*)y);
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    using T = T16<decltype(bf)::value>;
+    hipLaunchKernelGGL(skinny_fc_fwd_kernel<T>, dim3(blocks), dim3(kBlock), lds, s, batch, k, n,
+                       (int)rows, x, (const T*)w, (const T*)bias, (T*)y);
+  });
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -1545,19 +1411,14 @@ static int skinny_bwd_blocks(size_t batch, int k, int n, const void* dy, const v
   // matrix-core form: needs a spare input column for db and 16-byte rows (HCTR_SKINNY_BWD=valu|mfma)
   const char* mode = getenv("HCTR_SKINNY_BWD");
   const bool want_mfma = mode ? strcmp(mode, "valu") != 0 : kSkinnyBwdMfmaDefault;
-  *mfma = want_mfma && k < kSkinnyK && n % 8 == 0 && reinterpret_cast<uintptr_t>(dy) % 16 == 0 &&
-          reinterpret_cast<uintptr_t>(y) % 16 == 0;
-  if (*mfma) {
-    const int rsets = (kSkinnyBwdBlock / 64) / ceil_div<int>(n, 128);
-    return (int)std::min<size_t>((size_t)kSkinnyBlocks, ceil_div<size_t>(batch, (size_t)rsets * 16));
-  }
-  return (int)std::min<size_t>((size_t)kSkinnyBlocks,
-                               ceil_div<size_t>(batch, kSkinnyBwdBlock / kSkinnyLanes));
+  *mfma = want_mfma && k < kSkinnyK && n % 8 == 0 && aligned(dy, 16) && aligned(y, 16);
+  const int rows = *mfma ? (kSkinnyBwdBlock / 64) / ceil_div<int>(n, 128) * 16
+                         : kSkinnyBwdBlock / kSkinnyLanes;
+  return (int)std::min<size_t>((size_t)kSkinnyBlocks, ceil_div<size_t>(batch, (size_t)rows));
 }
 
 int hctr_skinny_fc_bwd_blocks(size_t batch, int k, int n, const void* dy, const void* y) {
-  HCTR_REQUIRE(batch > 0 && k >= 1 && k <= kSkinnyK, "skinny fc: 1 <= K <= 16");
-  HCTR_REQUIRE(n >= 4 && n % 4 == 0 && n <= 512, "skinny fc: N a multiple of 4, <= 512");
+  HCTR_TRY(skinny_check(batch, k, n));
   bool mfma;
   return skinny_bwd_blocks(batch, k, n, dy, y, &mfma);
 }
@@ -1566,42 +1427,27 @@ int hctr_skinny_fc_bwd_blocks(size_t batch, int k, int n, const void* dy, const 
 static int skinny_fc_bwd_impl(size_t batch, int k, int n, const float* x, const void* dy,
                               const void* y, float* dw, float* db, float* workspace, int dtype,
                               bool finish, hctr_stream_t stream) {
-  HCTR_TRY(skinny_check(batch, k, n, dtype));
+  HCTR_TRY(skinny_check(batch, k, n));
+  HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "16-bit weights / activations");
   HCTR_REQUIRE(x && dy && y && ((dw && db) || !finish) && workspace, "null pointer");
-  HCTR_REQUIRE(reinterpret_cast<uintptr_t>(dy) % 8 == 0 && reinterpret_cast<uintptr_t>(y) % 8 == 0,
-               "8-byte aligned activations");
+  HCTR_REQUIRE(aligned(dy, 8) && aligned(y, 8), "8-byte aligned activations");
   hipStream_t s = as_stream(stream);
   const size_t lds = (size_t)n * (kSkinnyK + 1) * sizeof(float);
   bool mfma;
   const int blocks = skinny_bwd_blocks(batch, k, n, dy, y, &mfma);
-  if (mfma) {
-    if (dtype == HCTR_EMB_BF16)
-      hipLaunchKernelGGL(skinny_fc_bwd_mfma_kernel<__hip_bfloat16>, dim3(blocks),
-                         dim3(kSkinnyBwdBlock), lds, s, batch, k, n, x, (const __hip_bfloat16*)dy,
-                         (const __hip_bfloat16*)y, workspace);
-    else
-      hipLaunchKernelGGL(skinny_fc_bwd_mfma_kernel<__half>, dim3(blocks), dim3(kSkinnyBwdBlock), lds,
-                         s, batch, k, n, x, (const __half*)dy, (const __half*)y, workspace);
-    HCTR_LAUNCH_CHECK();
-    if (!finish) return HCTR_OK;
-    hipLaunchKernelGGL(skinny_fc_finish_kernel, dim3(ceil_div<int>(n * (kSkinnyK + 1), 64)),
-                       dim3(1024), 0, s, blocks, k, n, workspace, dw, db);
-    HCTR_LAUNCH_CHECK();
-    return HCTR_OK;
-  }
-  if (dtype == HCTR_EMB_BF16)
-    hipLaunchKernelGGL(skinny_fc_bwd_kernel<__hip_bfloat16>, dim3(blocks), dim3(kSkinnyBwdBlock), lds, s,
-                       batch, k, n, x, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)y,
-                       workspace);
-  else
-    hipLaunchKernelGGL(skinny_fc_bwd_kernel<__half>, dim3(blocks), dim3(kSkinnyBwdBlock), lds, s, batch, k, n,
-                       x, (const __half*)dy, (const __half*)y, workspace);
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    using T = T16<decltype(bf)::value>;
+    with_bool(mfma, [&](auto m) {
+      constexpr auto kernel =
+          decltype(m)::value ? skinny_fc_bwd_mfma_kernel<T> : skinny_fc_bwd_kernel<T>;
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSkinnyBwdBlock), lds, s, batch, k, n, x,
+                         (const T*)dy, (const T*)y, workspace);
+    });
+  });
   HCTR_LAUNCH_CHECK();
   if (!finish) return HCTR_OK;
-  hipLaunchKernelGGL(skinny_fc_finish_kernel, dim3(ceil_div<int>(n * (kSkinnyK + 1), 64)),
-                     dim3(1024), 0, s, blocks, k, n, workspace, dw, db);
-  HCTR_LAUNCH_CHECK();
-  return HCTR_OK;
+  return finish_one<HCTR_DENSE_SEG_SKINNY>(workspace, (size_t)blocks, (size_t)n, (size_t)k, dw,
+                                           db, nullptr, s);
 }
 
 int hctr_skinny_fc_bwd(size_t batch, int k, int n, const float* x, const void* dy, const void* y,
@@ -1613,6 +1459,87 @@ int hctr_skinny_fc_bwd_partials(size_t batch, int k, int n, const float* x, cons
                                 const void* y, float* workspace, int dtype, hctr_stream_t stream) {
   return skinny_fc_bwd_impl(batch, k, n, x, dy, y, nullptr, nullptr, workspace, dtype, false,
                             stream);
+}
+
+// ---- optimizers ------------------------------------------------------------------------------------
+int hctr_sgd_shadow(size_t n, float lr, float grad_scale, float* w, const float* g, void* w16,
+                    int dtype, hctr_stream_t stream) {
+  HCTR_REQUIRE(n % 4 == 0, "n must be a multiple of 4");
+  HCTR_REQUIRE(is16(dtype), "16-bit shadow dtypes only");
+  if (n == 0) return HCTR_OK;
+  HCTR_REQUIRE(w && g && w16, "null pointer");
+  hipStream_t s = as_stream(stream);
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    hipLaunchKernelGGL(sgd_shadow_kernel<decltype(bf)::value>, dim3(grid_for(n / 4, kBlock, 4096)),
+                       dim3(kBlock), 0, s, n / 4, lr, grad_scale, w, g, (unsigned short*)w16);
+  });
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+static int ftrl_check(float lr, float beta, float lambda1, float lambda2, float grad_scale) {
+  HCTR_REQUIRE(lr > 0.f && lr < INFINITY, "ftrl: lr must be positive and finite");
+  HCTR_REQUIRE(beta >= 0.f && lambda1 >= 0.f && lambda2 >= 0.f,
+               "ftrl: beta, lambda1 and lambda2 must not be negative");
+  HCTR_REQUIRE(grad_scale == grad_scale && fabsf(grad_scale) < INFINITY, "ftrl: grad_scale");
+  return HCTR_OK;
+}
+
+int hctr_ftrl_shadow(size_t n, float lr, float beta, float lambda1, float lambda2, float grad_scale,
+                     float* w, float* z, float* nacc, const float* g, void* w16, int dtype,
+                     hctr_stream_t stream) {
+  HCTR_REQUIRE(n % 4 == 0, "n must be a multiple of 4");
+  HCTR_TRY(ftrl_check(lr, beta, lambda1, lambda2, grad_scale));
+  HCTR_REQUIRE(!w16 || is16(dtype), "16-bit shadow dtypes only");
+  if (n == 0) return HCTR_OK;
+  HCTR_REQUIRE(w && z && nacc && g, "null pointer");
+  HCTR_REQUIRE(aligned(w, 16) && aligned(z, 16) && aligned(nacc, 16) && aligned(g, 16) &&
+                   aligned(w16, 16),
+               "16-byte aligned buffers");
+  hipStream_t s = as_stream(stream);
+  const FtrlHp h = {lr, lambda1, lambda2 + beta / lr, grad_scale};
+  const dim3 grid(grid_for(n / 4, kBlock, 4096));
+  // SHADOW 0: no 16-bit copy, 1: fp16, 2: bf16
+  auto launch = [&](auto shadow) {
+    hipLaunchKernelGGL(ftrl_shadow_kernel<decltype(shadow)::value>, grid, dim3(kBlock), 0, s, n / 4,
+                       h, w, z, nacc, g, (unsigned short*)w16);
+  };
+  if (!w16) launch(int_c<0>{});
+  else if (dtype == HCTR_EMB_F16) launch(int_c<1>{});
+  else launch(int_c<2>{});
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_ftrl_segments(const hctr_ftrl_seg* segs, int nseg, size_t nblocks, float lr, float beta,
+                       float lambda1, float lambda2, float grad_scale, float* z, float* nacc,
+                       const float* g, hctr_stream_t stream) {
+  HCTR_REQUIRE(nseg >= 0 && nblocks <= 0x7FFFFFFFu, "ftrl segments: segment / block count");
+  HCTR_TRY(ftrl_check(lr, beta, lambda1, lambda2, grad_scale));
+  if (nseg == 0 || nblocks == 0) return HCTR_OK;
+  HCTR_REQUIRE(segs && z && nacc && g, "null pointer");
+  HCTR_REQUIRE(aligned(z, 16) && aligned(nacc, 16) && aligned(g, 16), "16-byte aligned buffers");
+  hipStream_t s = as_stream(stream);
+  const FtrlHp h = {lr, lambda1, lambda2 + beta / lr, grad_scale};
+  hipLaunchKernelGGL(ftrl_segments_kernel, dim3((unsigned)nblocks), dim3(kBlock), 0, s, segs, nseg,
+                     h, z, nacc, g);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+// ---- fixed-order sums and the finish launch --------------------------------------------------------
+int hctr_sum_groups(int groups, size_t n, const void* in, int dtype, float* out,
+                    hctr_stream_t stream) {
+  HCTR_REQUIRE(groups > 0 && n % 8 == 0, "n must be a multiple of 8");
+  HCTR_REQUIRE(is16(dtype), "16-bit dtypes only");
+  if (n == 0) return HCTR_OK;
+  HCTR_REQUIRE(in && out, "null pointer");
+  int rc = HCTR_OK;
+  with_bool(dtype == HCTR_EMB_BF16, [&](auto bf) {
+    rc = finish_one<HCTR_DENSE_SEG_SUM_GROUPS, decltype(bf)::value ? 1 : 0>(
+        in, (size_t)groups, n, 0, out, nullptr, nullptr, as_stream(stream));
+  });
+  return rc;
 }
 
 int hctr_dense_seg_blocks(int kind, size_t n) {
@@ -1632,12 +1559,10 @@ int hctr_dense_grad_finish(const hctr_dense_seg* segs, int nseg, size_t nblocks,
   if (nseg == 0 || nblocks == 0) return HCTR_OK;
   HCTR_REQUIRE(segs, "null pointer");
   hipStream_t s = as_stream(stream);
-  if (sgd)
-    hipLaunchKernelGGL(dense_grad_finish_kernel<true>, dim3((unsigned)nblocks), dim3(kBlock), 0, s,
-                       segs, nseg, lr, grad_scale, loss);
-  else
-    hipLaunchKernelGGL(dense_grad_finish_kernel<false>, dim3((unsigned)nblocks), dim3(kBlock), 0, s,
-                       segs, nseg, lr, grad_scale, loss);
+  with_bool(sgd != 0, [&](auto sg) {
+    hipLaunchKernelGGL(dense_grad_finish_kernel<decltype(sg)::value>, dim3((unsigned)nblocks),
+                       dim3(kBlock), 0, s, segs, nseg, lr, grad_scale, loss);
+  });
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }

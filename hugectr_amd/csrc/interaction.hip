@@ -168,7 +168,9 @@ struct Mfma16;
 template <>
 struct Mfma16<true> : H16<true> {
   typedef bf16x8 vec8;
-  // two fp32 values rounded to the type, a in the low half of the word
+  // two fp32 values rounded to the type, a in the low half of the word.  Both Mfma16<BF>::pack2 hide
+  // H16<BF>::pack2 of cvt16.h (the fp16 one is another instruction choice, this one its twin): call
+  // them through Mfma16 only -- the inherited pack4 goes through the base's.
   __device__ __forceinline__ static unsigned pack2(float a, float b) {
     return (unsigned)from_f32(a) | ((unsigned)from_f32(b) << 16);
   }

@@ -1,7 +1,10 @@
-"""hctr_dense_grad_finish: one launch finishes every partial sum of the dense backward.  Every
-segment kind is held, bit for bit, against the entry point it stands in for (hctr_sum_groups, the db
-of hctr_relu_bwd_bias, hctr_logit_head, hctr_skinny_fc_bwd: the code before this kernel, not under
-test here) and against fp64; SGD mode against gradients-only + hctr_sgd_shadow."""
+"""hctr_dense_grad_finish: one launch finishes every partial sum of the dense backward.  The
+stand-alone entries (hctr_sum_groups, the db of hctr_relu_bwd_bias, hctr_logit_head,
+hctr_skinny_fc_bwd) and the finish launch run the same device bodies, so their agreeing proves no
+order.  The witness of every segment kind is a float32 restatement of the documented order of
+additions, computed here on the CPU from the partials read back from the workspace: the
+stand-alone entry AND the finish launch must match it bit for bit (and each other, and fp64
+within a tolerance); SGD mode is held against gradients-only + hctr_sgd_shadow."""
 import numpy as np
 import pytest
 
@@ -9,6 +12,55 @@ pytestmark = pytest.mark.gpu
 
 SUM, COLSUM, HEAD, SKINNY, DIRECT = range(5)
 LR, GS = 0.01, 1.0 / 1024   # not powers of two: the update's rounding is visible
+
+
+def _np32(t):
+    return t.detach().float().cpu().contiguous().numpy()
+
+
+def _same_bits(t, want):
+    """a float32 tensor against a float32 array, as bit patterns (-0.0 != 0.0, NaN == the same NaN)"""
+    got = _np32(t).reshape(-1)
+    want = np.ascontiguousarray(want, dtype=np.float32).reshape(-1)
+    return got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def _f32_group_sum(parts):
+    """[groups][n] float32: acc = 0; for g in range(groups): acc += in[g]"""
+    acc = np.zeros(parts.shape[1], dtype=np.float32)
+    for g in range(parts.shape[0]):
+        acc = acc + parts[g]
+    return acc
+
+
+def _f32_colsum(partial):
+    """[tiles][n] float32: tile group tg = 0..31 adds tiles tg, tg + 32, ... in order, then the 32
+    group sums are added in group order"""
+    tiles, n = partial.shape
+    s = np.zeros((32, n), dtype=np.float32)
+    for tg in range(32):
+        for t in range(tg, tiles, 32):
+            s[tg] = s[tg] + partial[t]
+    total = np.zeros(n, dtype=np.float32)
+    for k in range(32):
+        total = total + s[k]
+    return total
+
+
+def _f32_chunk_sum(partial):
+    """[blocks][cols] float32: 16 groups of chunk = ceil(blocks / 16) consecutive blocks, each added
+    in block order, then the 16 group sums in group order"""
+    blocks, cols = partial.shape
+    chunk = (blocks + 15) // 16
+    t = np.zeros((16, cols), dtype=np.float32)
+    tot = np.zeros(cols, dtype=np.float32)
+    with np.errstate(all="ignore"):  # (columns no producer defines may hold anything)
+        for g in range(16):
+            for b in range(g * chunk, min(blocks, (g + 1) * chunk)):
+                t[g] = t[g] + partial[b]
+        for g in range(16):
+            tot = tot + t[g]
+    return tot
 
 
 def _dt(name):
@@ -47,8 +99,7 @@ def _flat(n, tdt, seed=0):
     return g, w, w.to(tdt)
 
 
-@pytest.mark.parametrize("n", [8, 40, 256, 1024])
-@pytest.mark.parametrize("groups", [1, 16])
+@pytest.mark.parametrize("groups,n", [(g, n) for n in (8, 40, 256, 1024) for g in (1, 16)] + [(3, 8)])
 @pytest.mark.parametrize("dtype", ["bf16", "f16"])
 def test_finish_sum_groups_segment(n, groups, dtype):
     """split-K partial products -> fp32, g = 0..G-1 in order; the segment starts 16-byte (not 32-byte)
@@ -64,6 +115,8 @@ def test_finish_sum_groups_segment(n, groups, dtype):
     _finish([dict(kind=SUM, src=p, count=groups, n=n, dst=4)], [flat], sgd=False)
     got = flat[0][4:4 + n]
     assert torch.equal(got, want)
+    order = _f32_group_sum(_np32(p))
+    assert _same_bits(want, order) and _same_bits(got, order)
     assert torch.isnan(flat[0][:4]).all() and torch.isnan(flat[0][4 + n:]).all()
     ref = p.double().sum(0)
     assert (got.double() - ref).norm() <= 1e-2 * ref.norm()
@@ -97,6 +150,8 @@ def test_finish_colsum_segment(rows, n, dtype):
     got = flat[0][4:4 + n]
     assert torch.equal(dz0, dz1)
     assert torch.equal(got, want)
+    for ws, out in ((ws0, want), (ws1, got)):
+        assert _same_bits(out, _f32_colsum(_np32(ws[:tiles * n]).reshape(tiles, n)))
     ref = (dy.double() * (y > 0)).sum(0)
     assert torch.allclose(got.double(), ref, rtol=1e-5, atol=1e-4)
 
@@ -135,6 +190,11 @@ def test_finish_logit_head_segment(B, K, dtype):
     assert torch.equal(flat[0][:K], dw)
     assert torch.equal(flat[0][K + 4:K + 5], db)
     assert torch.equal(loss1, loss)
+    for wsx, got_dw, got_db, got_loss in ((ws, dw, db, loss),
+                                          (ws1, flat[0][:K], flat[0][K + 4:K + 5], loss1)):
+        order = _f32_chunk_sum(_np32(wsx[:blocks * (K + 2)]).reshape(blocks, K + 2))
+        assert _same_bits(got_dw, order[:K]) and _same_bits(got_db, order[K:K + 1])
+        assert _same_bits(got_loss, order[K + 1:] / np.float32(B))
     z = x.double() @ w.double().t() + b.double()
     dz = (torch.sigmoid(z) - y.double()) * scale
     assert torch.allclose(flat[0][:K].double(), (dz.t() @ x.double())[0], rtol=1e-4, atol=1e-7)
@@ -142,10 +202,11 @@ def test_finish_logit_head_segment(B, K, dtype):
 
 
 @pytest.mark.parametrize("B,K,N", [(1000, 13, 256), (777, 16, 128), (300, 7, 136), (3, 13, 512),
-                                   (9000, 7, 508)])
+                                   (9000, 7, 508), (9300, 13, 64)])
 @pytest.mark.parametrize("dtype", ["bf16", "f16"])
 def test_finish_skinny_segment(B, K, N, dtype):
-    """block partials of the skinny first layer's backward (matrix-core and vector forms)"""
+    """block partials of the skinny first layer's backward (matrix-core and vector forms);
+    B = 9300 at N = 64 leaves 37 blocks: chunks of 3, a last chunk of 1 and three empty groups"""
     import torch
     from hugectr_amd._lib import check, lib, ptr, stream_ptr
     tdt, code = _dt(dtype)
@@ -169,6 +230,11 @@ def test_finish_skinny_segment(B, K, N, dtype):
     _finish([dict(kind=SKINNY, src=ws1, count=blocks, n=N, k=K, dst=0, dst2=nw)], [flat], sgd=False)
     assert torch.equal(flat[0][:N * K].view(N, K), dw)
     assert torch.equal(flat[0][nw:nw + N], db)
+    # (each side from its own workspace: the columns K .. 15 of a partial row are not defined)
+    for ws, got_dw, got_db in ((ws0, dw, db), (ws1, flat[0][:N * K], flat[0][nw:nw + N])):
+        part = _np32(ws[:blocks * N * 17]).reshape(blocks, N * 17)
+        order = _f32_chunk_sum(part).reshape(N, 17)
+        assert _same_bits(got_dw, order[:, :K]) and _same_bits(got_db, order[:, 16])
     dz = dy.double() * (y > 0)
     x16 = x.to(tdt).double()
     assert torch.allclose(flat[0][nw:nw + N].double(), dz.sum(0), rtol=1e-5, atol=1e-4)

@@ -15,7 +15,7 @@ covers.
 
 Dispatch, as the host code decides it (a case below names the branch it is there for):
 
-  hctr_cross_v1_fwd / _bwd   one wavefront per row, NPL columns per lane: HCTR_CROSS_DISPATCH takes
+  hctr_cross_v1_fwd / _bwd   one wavefront per row, NPL columns per lane: with_npl takes
         NPL from {1, 2, 4, 8, 16, 32, 64} by ceil(w / 64) (w <= 4096).  Forward: min(ceil(B / 4),
         2048) blocks of 4 wavefronts, a second row per wavefront from B > 8192.  Backward: always
         1024 wavefronts (a second row from B > 1024, a third from B > 2048) with their dW / db
@@ -25,7 +25,7 @@ Dispatch, as the host code decides it (a case below names the branch it is there
         rows in a fixed order.
   hctr_relu_bwd_bias(_partials)   128 rows per workgroup; cw = min(n / 8, 256) column threads,
         rg = 256 / cw row groups (threads >= cw * rg idle); n / 8 > 256 walks the columns in
-        several passes (the last one ragged); colsum_partials_kernel adds the tiles in 32 groups.
+        several passes (the last one ragged); the COLSUM finish adds the tiles in 32 groups.
   hctr_cross_v2_bwd_step     the same thread layout on a (row tiles, column blocks) grid; rows per
         tile = 128, halved down to 16 while ceil(B / rows) * column blocks < 2048:
         at width 8   B <= 65504 -> 16,  <= 131008 -> 32,  <= 262016 -> 64,  above -> 128.
