@@ -29,6 +29,7 @@ EMB_DISTRIBUTED, EMB_LOCALIZED = 0, 1
 KEY_U32, KEY_I64 = 0, 1
 F32, F16, BF16 = 0, 1, 2
 FTRL_SEG_BLOCK_ELEMS = 1024  # HCTR_FTRL_SEG_BLOCK_ELEMS: elements per block of hctr_ftrl_segments
+TRANSPOSE16_TILE = 32  # HCTR_TRANSPOSE16_TILE: rows and columns per block of hctr_transpose16_segments
 
 
 class EmbeddingParams(Structure):
@@ -259,6 +260,10 @@ _SIGNATURES = {
     "hctr_convert_transpose16": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, c_int, _P]),
     "hctr_gemm_nt16": (c_int, [c_size_t, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, _P, _P,
                                _P, _P, c_int, _P]),
+    "hctr_gemm_nt16_drelu_tiles": (c_int, [c_size_t, c_int]),
+    "hctr_gemm_nt16_drelu": (c_int, [c_size_t, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P,
+                                     c_int, _P]),
+    "hctr_transpose16_segments": (c_int, [_P, c_int, c_size_t, _P]),
     "hctr_cross_v2_bwd_step_workspace_bytes": (c_size_t, [c_size_t, c_int]),
     "hctr_cross_v2_bwd_step": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "hctr_lru_create": (c_int, [c_size_t, c_size_t, c_int, c_int, c_char_p, c_uint64, POINTER(_P)]),

@@ -32,6 +32,13 @@
 //       EPI_PLAIN     C = (T)acc
 //       EPI_CROSS     H = (T)(acc + b[n]);  C = (T)(X_l + X_0 * H)      (H is stored too: backward)
 //       EPI_RESIDUAL  C = (T)(acc + R)
+//       EPI_DRELU     C = y > 0 ? (T)acc : 0, and the column sums of what the tile stored as one
+//                     fp32 row per row tile (the data gradient of a Linear layer with the ReLU
+//                     mask and the bias gradient of the layer below: hctr_gemm_nt16_drelu)
+//     EPI_DRELU (hctr_gemm_nt16_drelu) is the data gradient of an MLP layer: A = dz of the layer
+//     above, Bt = W^T (FusedMLP keeps it, transpose16_segments_kernel below), y = the ReLU output of
+//     the layer below; its column sums are added per thread over its rows and then over the 16 row
+//     groups in group order through the same LDS image: deterministic, no atomics;
 //   * block id -> tile: column tiles of one row panel are consecutive on ONE XCD (block b runs on
 //     XCD b % 8), so the panel of A is fetched from HBM once per XCD L2.
 #include "common.h"
@@ -49,7 +56,7 @@ typedef unsigned int cg_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kGemmThreads = 256;
 constexpr int kGemmBN = 128;
 constexpr int kGemmBK = 64;  // 16-bit elements: 128 bytes per LDS row
-constexpr int kEpiPlain = 0, kEpiCross = 1, kEpiResidual = 2;
+constexpr int kEpiPlain = 0, kEpiCross = 1, kEpiResidual = 2, kEpiDrelu = 3;
 
 // H16<BF> (cvt16.h) with the type's MFMA on packed words
 template <bool BF>
@@ -82,8 +89,8 @@ struct GemmArgs {
   int lda, ldb, ldc;
   const unsigned short* bias;  // EPI_CROSS: [N] (16-bit)
   const unsigned short* X0;    // EPI_CROSS: [M][ldc]
-  const unsigned short* XL;    // EPI_CROSS: [M][ldc]; EPI_RESIDUAL: R [M][ldc]
-  unsigned short* H;           // EPI_CROSS: [M][ldc]
+  const unsigned short* XL;    // EPI_CROSS: [M][ldc]; EPI_RESIDUAL: R [M][ldc]; EPI_DRELU: y [M][ldc]
+  unsigned short* H;           // EPI_CROSS: [M][ldc]; EPI_DRELU: the partial rows, fp32 [tiles_m][N]
   int tiles_n;                 // N / 128
   int tiles_m;                 // ceil(M / BM)
 };
@@ -233,6 +240,7 @@ __global__ void __launch_bounds__(kGemmThreads)
         ct[row * kGemmBN + col] = acc[i][j][r];
       }
   HCTR_RAW_BARRIER();
+  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // EPI_DRELU: this thread's column sums
 #pragma unroll
   for (int i = 0; i < NCH; i++) {
     const int row = (i * kGemmThreads + tid) >> 4;
@@ -250,6 +258,13 @@ __global__ void __launch_bounds__(kGemmThreads)
       for (int e = 0; e < 8; e++) {
         const unsigned short ru = (unsigned short)(exl[i][e >> 1] >> ((e & 1) * 16));
         o[e] = H16::from_f32(v[e] + H16::to_f32(ru));
+      }
+    } else if constexpr (EPI == kEpiDrelu) {
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const unsigned short yu = (unsigned short)(exl[i][e >> 1] >> ((e & 1) * 16));
+        o[e] = H16::to_f32(yu) > 0.f ? H16::from_f32(v[e]) : (unsigned short)0;  // (a NaN y masks)
+        if (gm < g.M) cs[e] += H16::to_f32(o[e]);  // (as stored; rows past M add nothing)
       }
     } else {
       unsigned short h[8];
@@ -271,9 +286,25 @@ __global__ void __launch_bounds__(kGemmThreads)
     for (int e = 0; e < 4; e++) ov[e] = pack16(o[2 * e], o[2 * e + 1]);
     if (gm < g.M) *reinterpret_cast<cg_u32x4*>(g.C + off) = ov;
   }
+  if constexpr (EPI == kEpiDrelu) {
+    // column sums of the tile: thread t summed rows t / 16, + 16, ... of column chunk t % 16 (in
+    // that order); the 16 row groups meet in LDS ([16][128] fp32, the image above is read out) and
+    // are added in group order
+    HCTR_RAW_BARRIER();
+    const cg_f32x4 s0 = {cs[0], cs[1], cs[2], cs[3]}, s1 = {cs[4], cs[5], cs[6], cs[7]};
+    *reinterpret_cast<cg_f32x4*>(ct + (tid >> 4) * kGemmBN + cc * 8) = s0;
+    *reinterpret_cast<cg_f32x4*>(ct + (tid >> 4) * kGemmBN + cc * 8 + 4) = s1;
+    HCTR_RAW_BARRIER();
+    if (tid < kGemmBN) {
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < kGemmThreads / 16; k++) sum += ct[k * kGemmBN + tid];
+      reinterpret_cast<float*>(g.H)[(size_t)tile_m * g.N + n0 + tid] = sum;
+    }
+  }
 }
 
-// The same product on 256 x 256 tiles (plain epilogue): 512 threads = 8 wavefronts as 2 x 4, a
+// The same product on 256 x 256 tiles (EPI_PLAIN or EPI_DRELU): 512 threads = 8 wavefronts as 2 x 4, a
 // wavefront owns 128 x 64 of C (4 x 2 MFMA tiles: 6 fragment reads per 8 MFMAs instead of 4 per 4),
 // two staging buffers of 64 KB.  What it is for: the K = 3456 -> N = 512 products at batch 65536
 // are bound by what the L2 can feed the LDS, not by the matrix pipe -- 2048 tiles of 128 x 128 move
@@ -282,7 +313,7 @@ __global__ void __launch_bounds__(kGemmThreads)
 // least as many tiles as CUs.  The accumulators leave through LDS in two passes of 128 rows.
 constexpr int kBigBM = 256, kBigBN = 256, kBigThreads = 512;
 
-template <bool BF>
+template <bool BF, int EPI>
 __global__ void __launch_bounds__(kBigThreads)
     cross_gemm_nt16_big_kernel(GemmArgs g) {
   using H16 = Cg16<BF>;
@@ -352,8 +383,20 @@ __global__ void __launch_bounds__(kBigThreads)
   float* ct = reinterpret_cast<float*>(lds_raw);
   constexpr int NCH = 128 * kBigBN / 8 / kBigThreads;  // 8 chunks of 8 columns per thread and pass
   const int cc = tid & 31;
+  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // EPI_DRELU: this thread's column sums
 #pragma unroll 1
   for (int p = 0; p < 2; p++) {
+    // EPI_DRELU: the pass's y is requested first, all chunks of this thread at once (one trip that
+    // overlaps the accumulators' way through LDS, as in the kernel above)
+    cg_u32x4 yv[NCH];
+    if constexpr (EPI == kEpiDrelu) {
+#pragma unroll
+      for (int i = 0; i < NCH; i++) {
+        int gm = m0 + p * 128 + ((i * kBigThreads + tid) >> 5);
+        gm = gm < g.M ? gm : g.M - 1;  // (clamped: a legal read; the store below is predicated)
+        yv[i] = *reinterpret_cast<const cg_u32x4*>(g.XL + (size_t)gm * g.ldc + n0 + cc * 8);
+      }
+    }
     HCTR_RAW_BARRIER();  // (the K loop's / the previous pass's reads of the buffer are done)
     if (wm == p) {
 #pragma unroll
@@ -376,21 +419,55 @@ __global__ void __launch_bounds__(kBigThreads)
       const cg_f32x4 v1 = *reinterpret_cast<const cg_f32x4*>(ct + row * kBigBN + cc * 8 + 4);
       const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
       cg_u32x4 ov;
+      if constexpr (EPI == kEpiDrelu) {
+        unsigned short o[8];
 #pragma unroll
-      for (int e = 0; e < 4; e++) ov[e] = H16::pack2(v[2 * e], v[2 * e + 1]);
+        for (int e = 0; e < 8; e++) {
+          const unsigned short yu = (unsigned short)(yv[i][e >> 1] >> ((e & 1) * 16));
+          o[e] = H16::to_f32(yu) > 0.f ? H16::from_f32(v[e]) : (unsigned short)0;  // (a NaN y masks)
+          if (gm < g.M) cs[e] += H16::to_f32(o[e]);  // (as stored; rows past M add nothing)
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) ov[e] = pack16(o[2 * e], o[2 * e + 1]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++) ov[e] = H16::pack2(v[2 * e], v[2 * e + 1]);
+      }
       if (gm < g.M) *reinterpret_cast<cg_u32x4*>(g.C + (size_t)gm * g.ldc + gn) = ov;
+    }
+  }
+  if constexpr (EPI == kEpiDrelu) {
+    // column sums of the tile: thread t summed rows t / 32, + 16, ... of both passes for column
+    // chunk t % 32 (in that order); the 16 row groups meet in LDS ([16][256] fp32) and are added in
+    // group order
+    HCTR_RAW_BARRIER();
+    const cg_f32x4 s0 = {cs[0], cs[1], cs[2], cs[3]}, s1 = {cs[4], cs[5], cs[6], cs[7]};
+    *reinterpret_cast<cg_f32x4*>(ct + (tid >> 5) * kBigBN + cc * 8) = s0;
+    *reinterpret_cast<cg_f32x4*>(ct + (tid >> 5) * kBigBN + cc * 8 + 4) = s1;
+    HCTR_RAW_BARRIER();
+    if (tid < kBigBN) {
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < kBigThreads / 32; k++) sum += ct[k * kBigBN + tid];
+      reinterpret_cast<float*>(g.H)[(size_t)tile_m * g.N + n0 + tid] = sum;
     }
   }
 }
 
 template <bool BF>
-int launch_big(const GemmArgs& g, hipStream_t s) {
+int launch_big(const GemmArgs& g, int epi, hipStream_t s) {
   constexpr int lds = 2 * (kBigBM + kBigBN) * kGemmBK * 2;  // 128 KB
-  // (per device and cheap: asked on every launch rather than remembered per process)
-  HCTR_HIP(hipFuncSetAttribute((const void*)cross_gemm_nt16_big_kernel<BF>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL((cross_gemm_nt16_big_kernel<BF>), dim3((unsigned)(g.tiles_m * g.tiles_n)),
-                     dim3(kBigThreads), lds, s, g);
+  const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
+  // (the attribute is per device and cheap: asked on every launch rather than remembered per process)
+  if (epi == kEpiDrelu) {
+    HCTR_HIP(hipFuncSetAttribute((const void*)cross_gemm_nt16_big_kernel<BF, kEpiDrelu>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((cross_gemm_nt16_big_kernel<BF, kEpiDrelu>), grid, dim3(kBigThreads), lds, s, g);
+  } else {
+    HCTR_HIP(hipFuncSetAttribute((const void*)cross_gemm_nt16_big_kernel<BF, kEpiPlain>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((cross_gemm_nt16_big_kernel<BF, kEpiPlain>), grid, dim3(kBigThreads), lds, s, g);
+  }
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -425,6 +502,34 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// The 16-bit weights W [rows][cols] of several layers -> their transposes [cols][rows], one launch:
+// a block of 256 threads moves one tile of 32 x 32 of the segment it falls into (the table is a
+// handful of segments: a linear search)
+__global__ void __launch_bounds__(256)
+    transpose16_segments_kernel(const hctr_transpose16_seg* __restrict__ segs, int nseg) {
+  __shared__ unsigned short tile[32][33];
+  int si = 0;
+  while (si + 1 < nseg && (int64_t)blockIdx.x >= segs[si + 1].block0) si++;
+  const hctr_transpose16_seg sg = segs[si];
+  const unsigned short* __restrict__ src = reinterpret_cast<const unsigned short*>(sg.src);
+  unsigned short* __restrict__ dst = reinterpret_cast<unsigned short*>(sg.dst);
+  const int rows = (int)sg.rows, cols = (int)sg.cols;
+  const int blk = (int)((int64_t)blockIdx.x - sg.block0), tiles_c = (cols + 31) / 32;
+  const int r0 = blk / tiles_c * 32, c0 = blk % tiles_c * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int r = r0 + ty + 8 * k, c = c0 + tx;
+    if (r < rows && c < cols) tile[ty + 8 * k][tx] = src[(size_t)r * cols + c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int c = c0 + ty + 8 * k, r = r0 + tx;
+    if (r < rows && c < cols) dst[(size_t)c * rows + r] = tile[tx][ty + 8 * k];
+  }
+}
+
 template <int BM, int STAGES>
 constexpr int gemm_lds_bytes() {
   constexpr int ring = STAGES * (BM + kGemmBN) * kGemmBK * 2, epi = BM * kGemmBN * 4;
@@ -448,6 +553,7 @@ int launch_epi(const GemmArgs& g, int epi, hipStream_t s) {
   switch (epi) {
     case kEpiPlain: return launch_one<BM, BF, kEpiPlain, STAGES>(g, s);
     case kEpiCross: return launch_one<BM, BF, kEpiCross, STAGES>(g, s);
+    case kEpiDrelu: return launch_one<BM, BF, kEpiDrelu, STAGES>(g, s);
     default: return launch_one<BM, BF, kEpiResidual, STAGES>(g, s);
   }
 }
@@ -464,13 +570,28 @@ int launch_stages(const GemmArgs& g, int epi, int stages, hipStream_t s) {
 
 using namespace hctr;
 
-extern "C" {
+// tile height a product is launched with: 256 = the 256 x 256 kernel (plain and dReLU epilogues).
+// HCTR_GEMM_BM = 64 / 128 / 256 forces one (measurements; 256 only where that kernel is legal)
+static int gemm_tile_height(size_t m, int n, int epilogue) {
+  const char* bm_env = getenv("HCTR_GEMM_BM");
+  // products with at least a tile of 256 x 256 per CU: half the L2 -> LDS traffic per flop
+  const size_t tiles256 = ceil_div<size_t>(m, 256) * (size_t)(n / 256);
+  // (dReLU at N = 256: 128-row tiles measured 16.5 us against 19.0 at M = 65536, K = 128 -- the
+  //  epilogue's y read and dz store are most of that kernel; from N = 512 on the 256-row kernel
+  //  ties or wins, profiles/dgrad_relu_shapes.txt)
+  const bool big_auto = tiles256 >= 256 && (epilogue != kEpiDrelu || n >= 512);
+  if ((epilogue == kEpiPlain || epilogue == kEpiDrelu) && n % 256 == 0 &&
+      (bm_env ? atoi(bm_env) == 256 : big_auto))
+    return 256;
+  // 128-row tiles while they give every CU two workgroups, 64-row tiles for the small products
+  // (B = 8192 x N = 512: 256 tiles of 128 rows = one per CU, nothing to overlap a barrier with)
+  const size_t tiles128 = ceil_div<size_t>(m, 128) * (size_t)(n / kGemmBN);
+  return (bm_env ? atoi(bm_env) == 64 : tiles128 < 512) ? 64 : 128;
+}
 
-int hctr_gemm_nt16(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb, void* c,
-                   int ldc, int epilogue, const void* bias, const void* x0, const void* xl,
-                   void* h_out, int dtype, hctr_stream_t stream) {
+static int gemm_nt16_check(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb,
+                           const void* c, int ldc, int dtype) {
   HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "gemm_nt16: 16-bit types only");
-  HCTR_REQUIRE(epilogue >= kEpiPlain && epilogue <= kEpiResidual, "gemm_nt16: epilogue");
   if (m == 0) return HCTR_OK;
   HCTR_REQUIRE(a && bt && c, "null pointer");
   HCTR_REQUIRE(n > 0 && k > 0 && n % kGemmBN == 0 && k % kGemmBK == 0,
@@ -478,11 +599,13 @@ int hctr_gemm_nt16(size_t m, int n, int k, const void* a, int lda, const void* b
   HCTR_REQUIRE(lda >= k && ldb >= k && ldc >= n && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0,
                "gemm_nt16: leading dimensions (multiples of 8 elements)");
   HCTR_REQUIRE(m <= (size_t)0x7FFFFF00, "gemm_nt16: M");
-  auto al16 = [](const void* p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  HCTR_REQUIRE(al16(a) && al16(bt) && al16(c) && al16(bias) && al16(x0) && al16(xl) && al16(h_out),
-               "gemm_nt16: 16-byte aligned buffers");
-  if (epilogue == kEpiCross) HCTR_REQUIRE(bias && x0 && xl && h_out, "gemm_nt16: cross epilogue operands");
-  if (epilogue == kEpiResidual) HCTR_REQUIRE(xl, "gemm_nt16: residual operand");
+  return HCTR_OK;
+}
+
+// (arguments checked; h_out: H of the cross epilogue, the partial rows of the dReLU epilogue)
+static int gemm_nt16_launch(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb,
+                            void* c, int ldc, int epilogue, const void* bias, const void* x0,
+                            const void* xl, void* h_out, int dtype, hctr_stream_t stream) {
   GemmArgs g;
   g.M = (int)m;
   g.N = n;
@@ -498,38 +621,62 @@ int hctr_gemm_nt16(size_t m, int n, int k, const void* a, int lda, const void* b
   g.XL = (const unsigned short*)xl;
   g.H = (unsigned short*)h_out;
   g.tiles_n = n / kGemmBN;
-  // 128-row tiles while they give every CU two workgroups, 64-row tiles for the small products
-  // (B = 8192 x N = 512: 256 tiles of 128 rows = one per CU, nothing to overlap a barrier with)
-  const size_t tiles128 = ceil_div<size_t>(m, 128) * (size_t)g.tiles_n;
-  const char* bm_env = getenv("HCTR_GEMM_BM");
-  const bool bm64 = bm_env ? atoi(bm_env) == 64 : tiles128 < 512;
   hipStream_t s = as_stream(stream);
   const bool bf = dtype == HCTR_EMB_BF16;
-  // plain products with at least a tile of 256 x 256 per CU: half the L2 -> LDS traffic per flop
-  // (HCTR_GEMM_BM=256 forces, any other value keeps the 128-wide tiles)
-  {
-    const size_t tiles256 = ceil_div<size_t>(m, 256) * (size_t)(n / 256);
-    const bool big = epilogue == kEpiPlain && n % 256 == 0 &&
-                     (bm_env ? atoi(bm_env) == 256 : tiles256 >= 256);
-    if (big) {
-      g.tiles_n = n / 256;
-      g.tiles_m = (int)ceil_div<size_t>(m, 256);
-      return bf ? launch_big<true>(g, s) : launch_big<false>(g, s);
-    }
+  const int bm = gemm_tile_height(m, n, epilogue);
+  g.tiles_m = (int)ceil_div<size_t>(m, (size_t)bm);
+  if (bm == 256) {
+    g.tiles_n = n / 256;
+    return bf ? launch_big<true>(g, epilogue, s) : launch_big<false>(g, epilogue, s);
   }
   // depth of the staging ring (HCTR_GEMM_STAGES: 2 / 3 / 4, measurements)
   const char* st_env = getenv("HCTR_GEMM_STAGES");
   int stages = st_env ? atoi(st_env) : 2;
   if (stages != 3 && stages != 4) stages = 2;
-  if (bm64) {
-    g.tiles_m = (int)ceil_div<size_t>(m, 64);
+  if (bm == 64)
     return bf ? launch_stages<64, true>(g, epilogue, stages, s)
               : launch_stages<64, false>(g, epilogue, stages, s);
-  }
-  g.tiles_m = (int)ceil_div<size_t>(m, 128);
   if (stages == 4) stages = 3;  // (4 x 32 KB + nothing else: 128 KB of the CU's 160 -- not built)
   return bf ? launch_stages<128, true>(g, epilogue, stages, s)
             : launch_stages<128, false>(g, epilogue, stages, s);
+}
+
+extern "C" {
+
+int hctr_gemm_nt16(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb, void* c,
+                   int ldc, int epilogue, const void* bias, const void* x0, const void* xl,
+                   void* h_out, int dtype, hctr_stream_t stream) {
+  HCTR_REQUIRE(dtype == HCTR_EMB_F16 || dtype == HCTR_EMB_BF16, "gemm_nt16: 16-bit types only");
+  HCTR_REQUIRE(epilogue >= kEpiPlain && epilogue <= kEpiResidual, "gemm_nt16: epilogue");
+  HCTR_TRY(gemm_nt16_check(m, n, k, a, lda, bt, ldb, c, ldc, dtype));
+  if (m == 0) return HCTR_OK;
+  auto al16 = [](const void* p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  HCTR_REQUIRE(al16(a) && al16(bt) && al16(c) && al16(bias) && al16(x0) && al16(xl) && al16(h_out),
+               "gemm_nt16: 16-byte aligned buffers");
+  if (epilogue == kEpiCross) HCTR_REQUIRE(bias && x0 && xl && h_out, "gemm_nt16: cross epilogue operands");
+  if (epilogue == kEpiResidual) HCTR_REQUIRE(xl, "gemm_nt16: residual operand");
+  return gemm_nt16_launch(m, n, k, a, lda, bt, ldb, c, ldc, epilogue, bias, x0, xl, h_out, dtype,
+                          stream);
+}
+
+int hctr_gemm_nt16_drelu_tiles(size_t m, int n) {
+  HCTR_REQUIRE(n > 0 && n % kGemmBN == 0, "gemm_nt16: N % 128 == 0 and K % 64 == 0");
+  HCTR_REQUIRE(m <= (size_t)0x7FFFFF00, "gemm_nt16: M");
+  if (m == 0) return 0;
+  return (int)ceil_div<size_t>(m, (size_t)gemm_tile_height(m, n, kEpiDrelu));
+}
+
+int hctr_gemm_nt16_drelu(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb,
+                         const void* y, void* dz, int ldc, float* partials, int dtype,
+                         hctr_stream_t stream) {
+  HCTR_TRY(gemm_nt16_check(m, n, k, a, lda, bt, ldb, dz, ldc, dtype));
+  if (m == 0) return HCTR_OK;
+  HCTR_REQUIRE(y && partials, "null pointer");
+  auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  HCTR_REQUIRE(al16(a) && al16(bt) && al16(y) && al16(dz) && al16(partials),
+               "gemm_nt16: 16-byte aligned buffers");
+  return gemm_nt16_launch(m, n, k, a, lda, bt, ldb, dz, ldc, kEpiDrelu, nullptr, nullptr, y, partials,
+                          dtype, stream);
 }
 
 int hctr_convert_transpose16(size_t batch, int rows, int cols, const float* src, void* dst,
@@ -545,6 +692,17 @@ int hctr_convert_transpose16(size_t batch, int rows, int cols, const float* src,
   else
     hipLaunchKernelGGL(convert_transpose16_kernel<false>, grid, dim3(256), 0, as_stream(stream), rows,
                        cols, src, (unsigned short*)dst, (unsigned short*)dst_t);
+  HCTR_LAUNCH_CHECK();
+  return HCTR_OK;
+}
+
+int hctr_transpose16_segments(const hctr_transpose16_seg* segs, int nseg, size_t nblocks,
+                               hctr_stream_t stream) {
+  if (nseg == 0 || nblocks == 0) return HCTR_OK;
+  HCTR_REQUIRE(segs && nseg > 0, "transpose16_segments: segment table");
+  HCTR_REQUIRE(nblocks <= (size_t)0x7FFFFFFF, "transpose16_segments: blocks");
+  hipLaunchKernelGGL(transpose16_segments_kernel, dim3((unsigned)nblocks), dim3(256), 0,
+                     as_stream(stream), segs, nseg);
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }

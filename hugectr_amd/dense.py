@@ -19,6 +19,14 @@ kernels).  What this module fixes is how they are *issued* for the DLRM shapes
   sums, the launch adds them in the same order as the kernels it replaces and either writes
   `flat_g` or takes the SGD step and refreshes the 16-bit copy.  A module without a
   `DenseGradFinish` finishes layer by layer as before.
+* in a flattened module the data gradient of layer i + 1, the ReLU mask of layer i and layer i's
+  bias partials are ONE kernel, `hctr_gemm_nt16_drelu` (the library's own MFMA GEMM with a dReLU
+  epilogue), where layer i is a ReLU layer through `_LinearFn`, the type is 16-bit, in % 128 == 0
+  and out % 64 == 0: layer i + 1's backward leaves dz and the partial rows with layer i's
+  `_LayerWS`, layer i's backward skips `hctr_relu_bwd_bias`.  The kernel reads W^T, kept in
+  `flat_w16t` and refreshed by one launch wherever `flat_w16` is.  HCTR_DGRAD_FUSED = auto (where
+  it was measured faster, `_dgrad_fused_wins`) | 0 (never; read by `flatten()` too, which then keeps
+  no `flat_w16t`) | 1 (wherever legal).
 * `Optimizer_t.Ftrl` for the dense layers (torch has none): `FusedMLP.ftrl_step` on the flat
   buffers (`hctr_ftrl_shadow`, one launch per module, 16-bit copy included) and `DenseFtrl`, a
   torch optimizer over parameters that do not live in one buffer (`hctr_ftrl_segments`, one launch
@@ -26,13 +34,14 @@ kernels).  What this module fixes is how they are *issued* for the DLRM shapes
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 from typing import List, Sequence
 
 import torch
 
-from ._lib import FTRL_SEG_BLOCK_ELEMS, check, lib, ptr, stream_ptr
+from ._lib import FTRL_SEG_BLOCK_ELEMS, TRANSPOSE16_TILE, check, lib, ptr, stream_ptr
 
 _DT16 = {torch.float16: 1, torch.bfloat16: 2}  # hctr_emb_dtype_t
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
@@ -113,6 +122,36 @@ def bce_with_logits(logit: torch.Tensor, label: torch.Tensor, grad_scale: float)
 _SEG_SUM, _SEG_COLSUM, _SEG_HEAD, _SEG_SKINNY, _SEG_DIRECT = range(5)
 
 
+def _dgrad_mode() -> str:
+    """HCTR_DGRAD_FUSED = auto (the measured rule below) | 0 (never) | 1 (wherever the shape is legal)"""
+    v = os.environ.get("HCTR_DGRAD_FUSED", "auto")
+    return v if v in ("0", "1") else "auto"
+
+
+def _dgrad_fused_wins(m: int, n: int, k: int) -> bool:
+    """`auto`: is hctr_gemm_nt16_drelu faster than the library's data-gradient GEMM [m, k] x [k, n]
+    plus hctr_relu_bwd_bias_partials?  Measured per shape, median of the fused call below the
+    pair's fastest repeat (profiles/dgrad_relu_shapes.txt; DESIGN.md "Dense-tower glue")."""
+    # the four (n, k) that were measured, each at m = 2048 .. 65536, all won (by 13 .. 51 us a
+    # call); any other shape stays on the library until it is measured
+    # (tools/microbench_dgrad_relu.py)
+    return 2048 <= m <= 65536 and (n, k) in _DGRAD_MEASURED_WINS
+
+
+_DGRAD_MEASURED_WINS = frozenset([(512, 256), (1024, 512), (1024, 1024), (256, 128)])
+
+
+def _transpose_table(segs, device):
+    """hctr_transpose16_seg table of (src, dst, rows, cols) on the device -> (table, nseg, nblocks)"""
+    import numpy as np
+    t = np.zeros((len(segs), 8), dtype=np.int64)
+    block0, per = 0, TRANSPOSE16_TILE
+    for r, (src, dst, rows, cols) in enumerate(segs):
+        t[r, :5] = (src, dst, rows, cols, block0)
+        block0 += ((rows + per - 1) // per) * ((cols + per - 1) // per)
+    return torch.from_numpy(t).to(device), len(segs), block0
+
+
 class _LayerWS:
     """Workspaces of one layer of a flattened FusedMLP (allocated once, stable addresses: nothing is
     allocated per call, a captured graph replays on them) and what the last backward left in them:
@@ -123,6 +162,38 @@ class _LayerWS:
         self.mlp, self.idx, self.wpart = mlp, idx, wpart
         self._ws = None
         self.w_seg = self.b_seg = None
+        # (dz, partial rows, tiles) the layer above left with hctr_gemm_nt16_drelu: this layer's
+        # masked gradient and its bias partials exist already
+        self.pre = None
+        self._colsum = None
+
+    def take_pre(self, dy):
+        """(partial rows, tiles) when dy IS the dz the layer above left (the same storage: a
+        gradient autograd summed with another consumer's is masked here as usual), else None.
+        `pre` holds dz itself, not its address: while it does, autograd cannot add another
+        consumer's gradient into dz in place, nor can the allocator hand its storage to another
+        tensor -- the address test relies on both.  (A backward that never reaches this layer
+        leaves dz alive until the next one does.)"""
+        pre, self.pre = self.pre, None
+        if pre is not None and pre[0].data_ptr() == dy.data_ptr() and pre[0].shape == dy.shape:
+            return pre[1], pre[2]
+        return None
+
+    def finish_colsum(self, partials: torch.Tensor, tiles: int, n: int):
+        """the bias gradient from the partial rows into its place in flat_g (no DenseGradFinish):
+        a one-segment table, rebuilt only when the workspace moved or the batch changed"""
+        import numpy as np
+        m = self.mlp
+        sig = (partials.data_ptr(), tiles, n, m.flat_g.data_ptr())
+        if self._colsum is None or self._colsum[0] != sig:
+            t = np.zeros((1, DenseGradFinish._FIELDS), dtype=np.int64)
+            t[0, :13] = (_SEG_COLSUM, sig[0], tiles, n, 0, 0, sig[3], m.flat_w.data_ptr(),
+                         m.flat_w16.data_ptr(), m._offs[1][self.idx], 0,
+                         int(m.dtype == torch.bfloat16), 0)
+            self._colsum = (sig, torch.from_numpy(t).to(partials.device),
+                            _count(lib.hctr_dense_seg_blocks(_SEG_COLSUM, n)))
+        check(lib.hctr_dense_grad_finish(ptr(self._colsum[1]), 1, self._colsum[2], 0, 0.0, 1.0, None,
+                                         stream_ptr()))
 
     @property
     def defer(self) -> bool:
@@ -139,12 +210,15 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_master, b_master, w16, b16, relu: bool, groups: int, gw=None, gb=None,
-                lw=None):
+                lw=None, w16t=None, below=None):
         """gw / gb: views of the module's flat gradient buffer; when given, backward writes the
         weight / bias gradients there and returns no gradient for the masters.  lw: the layer's
-        _LayerWS (flattened module)"""
+        _LayerWS (flattened module).  w16t / below: W^T [in, out] and the _LayerWS of the ReLU
+        layer that produced x -- backward then computes that layer's masked gradient and bias
+        partials with the data gradient, in one kernel (hctr_gemm_nt16_drelu)"""
         x = x.contiguous()
         ctx.gw, ctx.gb, ctx.lw = gw, gb, lw
+        ctx.w16t, ctx.below = w16t, below
         if relu:
             y = torch._addmm_activation(b16, x, w16.t(), use_gelu=False)
         else:
@@ -160,9 +234,17 @@ class _LinearFn(torch.autograd.Function):
         n = dy.shape[1]
         lw = ctx.lw
         defer = lw is not None and lw.defer
+        pre = None
         if lw is not None:
             lw.w_seg = lw.b_seg = None
-        if ctx.relu and n % 8 == 0 and dy.dtype in _DT16 and dy.is_cuda:
+            pre = lw.take_pre(dy)
+        if pre is not None:  # dy is dz already, the layer above left it with the bias partials
+            if defer:
+                lw.b_seg = (_SEG_COLSUM, pre[0], pre[1], 0)
+            else:
+                lw.finish_colsum(pre[0], pre[1], n)
+            db = None
+        elif ctx.relu and n % 8 == 0 and dy.dtype in _DT16 and dy.is_cuda:
             # fused ReLU backward + bias gradient (HIP): one pass instead of two
             dz = torch.empty_like(dy)
             nbytes = lib.hctr_relu_bwd_bias_workspace_bytes(dy.shape[0], n)
@@ -185,14 +267,28 @@ class _LinearFn(torch.autograd.Function):
             db = dy.sum(0, dtype=torch.float32)
             if ctx.gb is not None:
                 ctx.gb.copy_(db)
-        dx = dy @ w16 if ctx.needs_input_grad[0] else None
+        if not ctx.needs_input_grad[0]:
+            dx = None
+        elif ctx.below is not None:
+            # x is the ReLU output of the layer below: its dz = (x > 0) ? dy @ W : 0 and the column
+            # sums of dz leave the GEMM's epilogue; that layer's backward finds them in `pre`
+            rows, k = dy.shape
+            dx = torch.empty_like(x)
+            tiles = _count(lib.hctr_gemm_nt16_drelu_tiles(rows, x.shape[1]))
+            part = ctx.below.ws(tiles * x.shape[1] * 4)
+            check(lib.hctr_gemm_nt16_drelu(rows, x.shape[1], k, ptr(dy), k, ptr(ctx.w16t), k, ptr(x),
+                                           ptr(dx), x.shape[1], ptr(part), _DT16[dy.dtype],
+                                           stream_ptr()))
+            ctx.below.pre = (dx, part, tiles)
+        else:
+            dx = dy @ w16
         dw = split_k_wgrad(dy, x, ctx.groups, out=ctx.gw, part=lw.wpart if lw is not None else None,
                            finish=not defer)
         if defer and isinstance(dw, int):
             lw.w_seg = (_SEG_SUM, lw.wpart, dw, 0)
         if ctx.gw is not None:  # gradients live in the flat buffer; nothing for autograd to keep
-            return dx, None, None, None, None, None, None, None, None, None
-        return dx, dw.float(), db, None, None, None, None, None, None, None
+            return (dx,) + (None,) * 11
+        return (dx, dw.float(), db) + (None,) * 9
 
 
 class _SkinnyFirstFn(torch.autograd.Function):
@@ -313,6 +409,11 @@ class FusedMLP(torch.nn.Module):
         self._w16: List[torch.Tensor] = []
         self._b16: List[torch.Tensor] = []
         self.flat_w = self.flat_g = self.flat_w16 = None
+        self.flat_w16t = None  # W^T of the layers whose data gradient may take the fused kernel
+        self._w16t: List[torch.Tensor] = []
+        self._t_segs = []      # (src, dst, rows, cols) per transposed layer
+        self._t_table = None   # (device table, nseg, nblocks) of hctr_transpose16_segments
+        self._t_hold = False
         self.flat_z = self.flat_n = None  # Ftrl state, only after flatten(ftrl_state=True)
         self._gw: List[torch.Tensor] = []
         self._gb: List[torch.Tensor] = []
@@ -362,13 +463,42 @@ class FusedMLP(torch.nn.Module):
             at += (n + 255) // 256 * 256
         part = torch.empty(max(at, 1), dtype=self.dtype, device=dev)
         self._lw = [_LayerWS(self, i, part[starts[i]:starts[i] + need[i]]) for i in range(nl)]
+        # W^T [in][out] of every layer whose data gradient can go through hctr_gemm_nt16_drelu (it
+        # reads both operands K-contiguous), one flat buffer, every view 16-byte aligned
+        fus = [i for i in range(nl) if self._dgrad_fusable(i)] if _dgrad_mode() != "0" else []
+        self._w16t, self._t_segs, self._t_table, self.flat_w16t = [None] * nl, [], None, None
+        if fus:
+            self.flat_w16t = torch.zeros(sum(self.weights[i].numel() for i in fus), dtype=self.dtype,
+                                         device=dev)
+            at = 0
+            for i in fus:
+                o, k = self.weights[i].shape  # (out * in is a multiple of 64 * 128)
+                self._w16t[i] = self.flat_w16t[at:at + o * k].view(k, o)
+                self._t_segs.append((self._w16[i].data_ptr(), self._w16t[i].data_ptr(), o, k))
+                at += o * k
+            self._t_table = _transpose_table(self._t_segs, dev)
+            self.refresh_transposed()
         return self
+
+    def _dgrad_fusable(self, i: int) -> bool:
+        """can layer i's data gradient carry the ReLU mask and the bias sums of layer i - 1?  (the
+        shapes hctr_gemm_nt16_drelu takes: N = in, K = out)"""
+        return (i >= 1 and self.relu[i - 1] and self.dtype in _DT16 and
+                self.dims[i] % 128 == 0 and self.dims[i + 1] % 64 == 0)
+
+    def refresh_transposed(self):
+        """flat_w16t from flat_w16, one launch; called wherever flat_w16 is refreshed (inside
+        DenseGradFinish.one_transpose() its one launch covers all modules instead)"""
+        if self._t_table is not None and not self._t_hold:
+            t, nseg, nblocks = self._t_table
+            check(lib.hctr_transpose16_segments(ptr(t), nseg, nblocks, stream_ptr()))
 
     def sgd_step(self, lr: float, grad_scale: float = 1.0):
         """w -= lr * grad_scale * g and refresh of the 16-bit copy, one launch (after flatten())"""
         check(lib.hctr_sgd_shadow(self.flat_w.numel(), float(lr), float(grad_scale),
                                   ptr(self.flat_w), ptr(self.flat_g), ptr(self.flat_w16),
                                   _DT16[self.dtype], stream_ptr()))
+        self.refresh_transposed()
 
     def ftrl_step(self, lr: float, beta: float, lambda1: float, lambda2: float,
                   grad_scale: float = 1.0):
@@ -379,6 +509,7 @@ class FusedMLP(torch.nn.Module):
                                    float(lambda2), float(grad_scale), ptr(self.flat_w),
                                    ptr(self.flat_z), ptr(self.flat_n), ptr(self.flat_g),
                                    ptr(self.flat_w16), _DT16[self.dtype], stream_ptr()))
+        self.refresh_transposed()
 
     def ftrl_state(self):
         """[(z, n)] views per parameter, in parameters() order"""
@@ -388,6 +519,7 @@ class FusedMLP(torch.nn.Module):
         """call after every optimizer step (and once after .to(device))"""
         if self.flat_w is not None:
             self.flat_w16.copy_(self.flat_w)
+            self.refresh_transposed()
             return
         if not self._w16:
             self._w16 = [w.detach().to(self.dtype) for w in self.weights]
@@ -411,10 +543,22 @@ class FusedMLP(torch.nn.Module):
         if i == 0 and self._skinny_first(x):
             return _SkinnyFirstFn.apply(x, self.weights[0], self.biases[0], self._w16[0],
                                         self._b16[0], gw, gb, lw)
+        # x is the output of layer i - 1, a ReLU layer (flatten() kept W^T only then), and it came
+        # straight out of _LinearFn (the skinny first layer folds its own mask): its mask and bias
+        # sums ride in this layer's data-gradient GEMM (HCTR_DGRAD_FUSED)
+        w16t = self._w16t[i] if lw is not None and i >= 1 and self._w16t else None
+        below = None
+        if w16t is not None and x.is_cuda and x.dtype == self.dtype and \
+                x.grad_fn is not None and x.grad_fn.name() == "_LinearFnBackward":
+            mode = _dgrad_mode()
+            if mode == "1" or (mode == "auto" and
+                               _dgrad_fused_wins(x.shape[0], self.dims[i], self.dims[i + 1])):
+                below = self._lw[i - 1]
         if x.dtype != self.dtype:
             x = x.to(self.dtype)
         return _LinearFn.apply(x, self.weights[i], self.biases[i], self._w16[i], self._b16[i],
-                               self.relu[i], self.wgrad_groups, gw, gb, lw)
+                               self.relu[i], self.wgrad_groups, gw, gb, lw,
+                               w16t if below is not None else None, below)
 
     def can_fuse_bce_head(self) -> bool:
         k = self.dims[-2]
@@ -468,6 +612,28 @@ class DenseGradFinish:
         self._sig = None
         self._table = None
         self._nseg = self._nblocks = 0
+        # the transposed 16-bit weights of all modules: one table, one launch
+        segs = [sg for m in self.mlps for sg in m._t_segs]
+        self._t_table = _transpose_table(segs, self.mlps[0].flat_w.device) if segs else None
+
+    def refresh_transposed(self):
+        """flat_w16t of every module from its flat_w16, one launch"""
+        if self._t_table is not None:
+            t, nseg, nblocks = self._t_table
+            check(lib.hctr_transpose16_segments(ptr(t), nseg, nblocks, stream_ptr()))
+
+    @contextlib.contextmanager
+    def one_transpose(self):
+        """around the per-module steps (sgd_step / ftrl_step / refresh_shadow) of one optimizer
+        step: their transposes are left to ONE launch for all modules at the end"""
+        for m in self.mlps:
+            m._t_hold = True
+        try:
+            yield
+        finally:
+            for m in self.mlps:
+                m._t_hold = False
+        self.refresh_transposed()
 
     def release(self):
         for m in self.mlps:
@@ -522,6 +688,8 @@ class DenseGradFinish:
                 loss, m._loss_out = m._loss_out, None
         check(lib.hctr_dense_grad_finish(ptr(self._table), self._nseg, self._nblocks, int(sgd),
                                          float(lr), float(grad_scale), ptr(loss), stream_ptr()))
+        if sgd:  # (the 16-bit copies were refreshed)
+            self.refresh_transposed()
 
 
 class DenseFtrl(torch.optim.Optimizer):

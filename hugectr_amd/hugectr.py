@@ -1808,14 +1808,15 @@ class Model:
                 self._dense_finish.finish(one, self._lr, 1.0 / self.solver.scaler)
             if frozen or one:
                 return
-            for m in self._flat_mlps:  # gradients are shares of the global-batch mean: plain sum
-                if reduced is None and self.world > 1:
-                    _all_reduce(m.flat_g)
-                if self._flat_ftrl:
-                    o = self.opt
-                    m.ftrl_step(self._lr, o.beta, o.lambda1, o.lambda2, 1.0 / self.solver.scaler)
-                else:
-                    m.sgd_step(self._lr, 1.0 / self.solver.scaler)
+            with self._dense_finish.one_transpose():  # (W^T of all modules: one launch)
+                for m in self._flat_mlps:  # gradients are shares of the global-batch mean: plain sum
+                    if reduced is None and self.world > 1:
+                        _all_reduce(m.flat_g)
+                    if self._flat_ftrl:
+                        o = self.opt
+                        m.ftrl_step(self._lr, o.beta, o.lambda1, o.lambda2, 1.0 / self.solver.scaler)
+                    else:
+                        m.sgd_step(self._lr, 1.0 / self.solver.scaler)
             return
         if self._dense_opt is None:
             return

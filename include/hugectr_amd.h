@@ -849,6 +849,20 @@ int hctr_dense_grad_finish(const hctr_dense_seg* segs, int nseg, size_t nblocks,
 int hctr_gemm_nt16(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb, void* c,
                    int ldc, int epilogue, const void* bias, const void* x0, const void* xl,
                    void* h_out, int dtype, hctr_stream_t stream);
+/* The data gradient of a Linear layer with the ReLU mask and the bias gradient of the layer below
+ * in the epilogue of the same kernel (no library GEMM has one):
+ *   dz[m][n] = y[m][n] > 0 ? (T)(sum_k a[m][k] * bt[n][k]) : +0    (a NaN y masks, as
+ *                                                                  hctr_relu_bwd_bias does)
+ *   partials[t][n] = sum over the rows of row tile t of (float)dz[m][n]  (the values as stored;
+ *                    added in a fixed order, no atomics)
+ * a = dz of the layer above [m][lda], bt = W^T [n][ldb] (K-contiguous), y / dz [m][ldc], partials
+ * fp32 [hctr_gemm_nt16_drelu_tiles(m, n)][n]: the layout of a COLSUM segment of
+ * hctr_dense_grad_finish, count = that number of tiles (it follows the tile height the launch
+ * takes for (m, n), HCTR_GEMM_BM included).  Shapes and alignment as for hctr_gemm_nt16. */
+int hctr_gemm_nt16_drelu_tiles(size_t m, int n);
+int hctr_gemm_nt16_drelu(size_t m, int n, int k, const void* a, int lda, const void* bt, int ldb,
+                         const void* y, void* dz, int ldc, float* partials, int dtype,
+                         hctr_stream_t stream);
 /* fp32 master weights [batch][rows][cols] -> their 16-bit copy dst [batch][rows][cols] and its
  * transpose dst_t [batch][cols][rows] in one pass (either may be NULL): the operands of
  * hctr_gemm_nt16 for MultiCrossLayer v2 (the reference converts its master weights per step too,
@@ -856,6 +870,19 @@ int hctr_gemm_nt16(size_t m, int n, int k, const void* a, int lda, const void* b
  * operands are read K-contiguous here). */
 int hctr_convert_transpose16(size_t batch, int rows, int cols, const float* src, void* dst,
                              void* dst_t, int dtype, hctr_stream_t stream);
+/* The transposes of 16-bit matrices as ONE launch: segment i copies src [rows][cols] to dst
+ * [cols][rows] (device addresses of 16-bit elements; the bits are moved, so either 16-bit type).
+ * FusedMLP keeps W^T of its layers this way, refreshed wherever the 16-bit copy of the weights is:
+ * hctr_gemm_nt16_drelu reads both operands K-contiguous.  block0 = the sum of
+ * ceil(rows / HCTR_TRANSPOSE16_TILE) * ceil(cols / HCTR_TRANSPOSE16_TILE) over the segments in
+ * front, nblocks that sum over all of them.  The table lives in device memory. */
+#define HCTR_TRANSPOSE16_TILE 32
+typedef struct {
+  int64_t src, dst, rows, cols, block0;
+  int64_t reserved[3];
+} hctr_transpose16_seg;
+int hctr_transpose16_segments(const hctr_transpose16_seg* segs, int nseg, size_t nblocks,
+                              hctr_stream_t stream);
 /* One layer's elementwise step of MultiCrossBackwardFunctorv2 in the activations' 16-bit type
  * (fused_mul_fma3, R/HugeCTR/src/layers/multi_cross_layer.cu:391-424 / 127-165, + the bias gradient
  * the reference takes in the dV GEMM's epilogue, :770-776): s0 = dy .* x0, acc = (first ? 0 : acc)
