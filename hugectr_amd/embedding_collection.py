@@ -73,6 +73,168 @@ _HYBRID_STEP = {_lib.OPT_SGD: "SGD", _lib.OPT_ADAGRAD: "AdaGrad", _lib.OPT_ADAM:
 _OPT_NAMES = {**_HYBRID_STEP, _lib.OPT_FTRL: "Ftrl", _lib.OPT_RMSPROP: "RMSProp"}
 HYBRID_MAX_KEYS_PER_CALL = 1 << 24  # hctr_lru_lookup_index
 
+# -- per-table optimizers (EmbeddingTableConfig.opt_params) ------------------------------------------
+# the hyper-parameters (fields of hugectr.OptParamsPy) each optimizer's step reads: two tables whose
+# optimizers agree in type and in THESE fields run in one collection, whatever their other fields
+_OPT_READS = {_lib.OPT_ADAGRAD: ("epsilon", "initial_accu_value"),
+              _lib.OPT_FTRL: ("beta", "lambda1", "lambda2"),
+              _lib.OPT_ADAM: ("beta1", "beta2", "epsilon"),
+              _lib.OPT_RMSPROP: ("beta2", "epsilon"),  # (beta2 is passed as RMSProp's beta)
+              _lib.OPT_MOMENTUM_SGD: ("momentum_factor",),
+              _lib.OPT_NESTEROV: ("momentum_factor",),
+              _lib.OPT_SGD: ()}
+# what each kind of table accepts (the update kernels behind it), in the order the messages list
+_STATIC_STEP = {_lib.OPT_SGD: "SGD", _lib.OPT_ADAGRAD: "AdaGrad", _lib.OPT_FTRL: "Ftrl"}
+_KIND_STEP = {"static": _STATIC_STEP, "dp": _STATIC_STEP, "hybrid": _HYBRID_STEP,
+              "dynamic": _OPT_NAMES}
+
+
+def optimizer_key(opt) -> tuple:
+    """(type code, the hyper-parameters that type reads): equal keys = one runtime collection
+    (None: no optimizer known, as when a config is split outside a model)"""
+    if opt is None:
+        return None
+    code = int(opt.optimizer_type)
+    return (code,) + tuple(float(getattr(opt, f)) for f in _OPT_READS[code])
+
+
+def resolve_table_optimizer(table, model_opt):
+    """-> (optimizer, "table" | "model"): the table's opt_params when given and initialized, else
+    the model's optimizer (the rule of Model._emb_opt for SparseEmbedding(optimizer=...))"""
+    o = getattr(table, "opt_params", None)
+    if o is not None and getattr(o, "initialized", False):
+        return o, "table"
+    return model_opt, "model"
+
+
+def group_lookups_by_optimizer(lookups, model_opt):
+    """lookups [(table_config, bottom, top, combiner)] -> [(lookup ids, optimizer)]: one group per
+    distinct optimizer_key of the tables' resolved optimizers.  The ids of a group ascend and the
+    groups come in the order of their first lookup, so the user's lookup order decides the
+    output.  Every table resolving alike gives one group of all lookups.  No device is touched."""
+    groups, where = [], {}
+    for l, (t, _, _, _) in enumerate(lookups):
+        opt, _ = resolve_table_optimizer(t, model_opt)
+        k = optimizer_key(opt)
+        if k not in where:
+            where[k] = len(groups)
+            groups.append(([], opt))
+        groups[where[k]][0].append(l)
+    return groups
+
+
+def table_kind(table, dp: bool = False) -> str:
+    """"hybrid" | "dynamic" | "dp" (a replicated static table) | "static\""""
+    if getattr(table, "var_type", None) == "hybrid":
+        return "hybrid"
+    if table.max_vocabulary_size < 0:
+        return "dynamic"
+    return "dp" if dp else "static"
+
+
+def check_table_optimizer(table, kind: str, opt, source: str):
+    """raises RuntimeError when a table of this kind cannot step with `opt`; source: "table" (its
+    own opt_params) or "model".  Pure: called by Model.compile before any device call."""
+    code = int(opt.optimizer_type)
+    ok = _KIND_STEP[kind]
+    if code in ok:
+        return
+    name = _OPT_NAMES.get(code, code)
+    whose = (f"EmbeddingTableConfig {table.name!r} opt_params" if source == "table"
+             else "the model's optimizer")
+    if kind == "hybrid":
+        raise RuntimeError(
+            f"hybrid embedding_collection tables ['{table.name}'] do not support {name} "
+            f"({whose}); supported: {', '.join(ok.values())}")
+    what = "replicated (\"dp\") static" if kind == "dp" else kind
+    raise RuntimeError(
+        f"static embedding_collection tables support SGD, AdaGrad and Ftrl "
+        f"(R/HugeCTR/embedding_storage/ragged_static_embedding.cu:593-700): {what} table "
+        f"{table.name!r} resolves to {name} ({whose}); supported: {', '.join(ok.values())}")
+
+
+def _one_optimizer(config, optimizer, epsilon, initial_accu_value, ftrl, beta1, beta2,
+                   momentum_factor, rmsprop_beta):
+    """EmbeddingCollection / DataParallelCollection are one-optimizer objects.  -> None when no
+    table of the config carries opt_params (the `optimizer=` arguments hold), else the one
+    optimizer every table resolves to, a table without opt_params resolving to the arguments.
+    Tables that disagree are the reference's refusal
+    (R/HugeCTR/embedding_storage/embedding_table.cpp:40-45)."""
+    if all(resolve_table_optimizer(t, None)[1] == "model" for t, _, _, _ in config.lookups):
+        return None
+    from types import SimpleNamespace
+    args = SimpleNamespace(optimizer_type=int(optimizer), epsilon=epsilon,
+                           initial_accu_value=initial_accu_value, lambda1=ftrl[0], lambda2=ftrl[1],
+                           beta=ftrl[2], beta1=beta1, momentum_factor=momentum_factor,
+                           beta2=rmsprop_beta if optimizer == _lib.OPT_RMSPROP else beta2)
+    groups = group_lookups_by_optimizer(config.lookups, args)
+    if len(groups) > 1:
+        names = [sorted({config.lookups[l][0].name for l in ids}) for ids, _ in groups]
+        raise RuntimeError(
+            f"embedding_collection: tables {names} resolve to different optimizers: HugeCTR does "
+            "not support grouping embedding table with different optimizer; hugectr.Model splits "
+            "such a config into one collection per optimizer")
+    return groups[0][1]
+
+
+def sinusoidal_table(max_sequence_len: int, ev_size: int):
+    """InitParams(Sinusoidal): row r, column c -> sin(r f) for even c, cos(r f) for odd c with
+    f = exp(-(c - c % 2) ln(10000) / ev_size) (R/HugeCTR/src/data_simulator.cu:39-49), computed in
+    fp64 and rounded once -> numpy fp32 [max_sequence_len, ev_size]"""
+    import numpy as np
+    r = np.arange(int(max_sequence_len), dtype=np.float64)[:, None]
+    c = np.arange(int(ev_size), dtype=np.int64)[None, :]
+    f = np.exp(-(c - c % 2).astype(np.float64) * np.log(10000.0) / float(ev_size))
+    return np.where(c % 2 == 0, np.sin(r * f), np.cos(r * f)).astype(np.float32)
+
+
+def check_init_param(table, storage: str = "static"):
+    """the table-dependent checks of EmbeddingTableConfig.init_param; storage: of the collection
+    the table runs in (a static table beside a dynamic one is held by the dynamic table).
+    -> "default" | "uniform" | "sinusoidal".  Raises RuntimeError naming the table."""
+    ip = getattr(table, "init_param", None)
+    kind = "default" if ip is None else ip.initializer_type.name.lower()
+    if kind == "default":
+        return kind
+    if table_kind(table) in ("dynamic", "hybrid"):
+        storage = table_kind(table)
+    if storage != "static":
+        raise RuntimeError(
+            f"EmbeddingTableConfig {table.name!r}: init_param {ip.initializer_type.name} is "
+            f"honoured on static tables; a table held in {storage} storage takes the storage's "
+            "`initializer`")
+    if kind == "sinusoidal":
+        have = int(table.max_vocabulary_size) * int(table.ev_size)
+        if int(ip.max_sequence_len) * int(ip.ev_size) != have:
+            raise RuntimeError(
+                f"EmbeddingTableConfig {table.name!r}: Sinusoidal init_param of max_sequence_len "
+                f"{ip.max_sequence_len} x ev_size {ip.ev_size} does not match the table's "
+                f"{table.max_vocabulary_size} x {table.ev_size} elements")
+    elif kind != "uniform":
+        raise RuntimeError(f"EmbeddingTableConfig {table.name!r}: init_param "
+                           f"{ip.initializer_type.name} is not available; Default, Uniform and "
+                           "Sinusoidal are")
+    return kind
+
+
+def fill_static_table(rows: torch.Tensor, table, num_shards: int, shard_id: int, generator):
+    """first values of one static table shard (`rows`: its slice of the flat table, local row j
+    holds key j * num_shards + shard_id): Default U(+-sqrt(1/vocab))
+    (ragged_static_embedding.cu:499-509), Uniform(up_bound) the same draw with another bound;
+    Sinusoidal is computed on the host and written over the Default draw -- whatever a table's
+    init_param, the generator moves on as for Default, so the tables behind it keep their bits."""
+    kind = check_init_param(table)
+    b = float(table.init_param.up_bound) if kind == "uniform" else \
+        (1.0 / table.max_vocabulary_size) ** 0.5
+    rows.uniform_(-b, b, generator=generator)
+    if kind == "sinusoidal":
+        ip = table.init_param
+        whole = sinusoidal_table(ip.max_sequence_len, ip.ev_size).reshape(
+            int(table.max_vocabulary_size), int(table.ev_size))
+        part = torch.from_numpy(whole[shard_id::num_shards].copy())
+        # (the last shards of a vocabulary that does not divide keep one spare row)
+        rows[:part.shape[0]].copy_(part.to(rows.device))
+
 
 @dataclass
 class EmbeddingTableConfig:
@@ -88,7 +250,10 @@ class EmbeddingTableConfig:
     initializer ("ones" | "zeros" | a float literal | anything else = uniform (0, 1], a function of
     (seed, key, element)).  max_capacity, init_capacity and max_hbm_for_vectors are PER OWNING GPU,
     exactly as for a SOK variable: every shard of a row-sharded table has max_capacity slots and
-    its own HBM budget.  A violation raises RuntimeError when the object is made."""
+    its own HBM budget.  A violation raises RuntimeError when the object is made.
+    opt_params (what hugectr.CreateOptimizer returns): this table's optimizer; not given, the
+    model's (or the collection's `optimizer=`).  The learning rate is never part of it.  init_param
+    (hugectr.InitParams): Default, Uniform(up_bound) or Sinusoidal first values of a static table."""
     name: str
     max_vocabulary_size: int
     ev_size: int
@@ -109,6 +274,13 @@ class EmbeddingTableConfig:
 
         if self.var_type not in (None, "hbm", "hybrid"):
             bad(f'var_type must be None, "hbm" or "hybrid", not {self.var_type!r}')
+        if self.opt_params is not None or self.init_param is not None:
+            from .hugectr import InitParams, OptParamsPy  # (that module imports this one)
+            if self.opt_params is not None and not isinstance(self.opt_params, OptParamsPy):
+                bad("opt_params must be what hugectr.CreateOptimizer returns (an OptParamsPy), "
+                    f"not {self.opt_params!r}")
+            if self.init_param is not None and not isinstance(self.init_param, InitParams):
+                bad(f"init_param must be a hugectr.InitParams, not {self.init_param!r}")
         if self.var_type != "hybrid":
             given = [k for k, d in (("max_capacity", None), ("init_capacity", None),
                                     ("max_load_factor", 0.5), ("max_bucket_size", 128),
@@ -308,6 +480,16 @@ class EmbeddingCollection(TableIO):
         # optimizer state this one uses -- the evaluation runtime of a model owns per-batch
         # scratch only (a second copy of 100+ GB tables would not even fit for a moment)
         assert global_batch % self.world == 0
+        # one collection runs one optimizer: tables that carry opt_params replace the arguments
+        # when every table of the config then resolves alike (a table without follows the
+        # arguments); hugectr.Model hands over one such group per collection
+        o = _one_optimizer(config, optimizer, epsilon, initial_accu_value, ftrl, beta1, beta2,
+                           momentum_factor, rmsprop_beta)
+        if o is not None:
+            optimizer, epsilon, initial_accu_value = int(o.optimizer_type), o.epsilon, \
+                o.initial_accu_value
+            ftrl, beta1, beta2 = (o.lambda1, o.lambda2, o.beta), o.beta1, o.beta2
+            momentum_factor, rmsprop_beta = o.momentum_factor, o.beta2
         # CompressionStrategy.Unique selects the reference's unique-compressed model-parallel
         # operator (distinct rows travel, the receiver pools;
         # R/HugeCTR/embedding/dense_model_parallel_embedding.cpp:1-279): `_setup_unique` and the
@@ -349,6 +531,11 @@ class EmbeddingCollection(TableIO):
             storage = "dynamic" if any(t.max_vocabulary_size < 0 for t, _, _, _ in config.lookups) \
                 else "static"
         assert storage in ("static", "dynamic", "hybrid")
+        for t, _, _, _ in config.lookups:  # (before any device call)
+            check_init_param(t, storage)
+        if storage == "static" and optimizer not in _STATIC_STEP:
+            # static EBC tables: SGD / AdaGrad / Ftrl only (SURVEY q9)
+            raise _lib.HugeCTRAmdError("EBC static tables support SGD, AdaGrad and Ftrl")
         self.dynamic = storage == "dynamic"
         # storage="hybrid": one bounded LRU table (hybrid_table.HybridTable) per local table shard,
         # `_setup_hybrid` and the *_hybrid stages below
@@ -359,11 +546,7 @@ class EmbeddingCollection(TableIO):
         self.lr, self.optimizer, self.scaler, self.epsilon = lr, optimizer, scaler, epsilon
         self.beta1, self.beta2, self.momentum_factor = beta1, beta2, momentum_factor
         self.out_dtype, self.batch_major, self.key_dtype = out_dtype, batch_major, key_dtype
-        if not (self.dynamic or self.hybrid) and \
-                optimizer not in (_lib.OPT_SGD, _lib.OPT_ADAGRAD, _lib.OPT_FTRL):
-            # static EBC tables: SGD / AdaGrad / Ftrl only (SURVEY q9)
-            raise _lib.HugeCTRAmdError("EBC static tables support SGD, AdaGrad and Ftrl")
-        self.ftrl = tuple(float(x) for x in ftrl)  # (lambda1, lambda2, beta)
+        self.ftrl =tuple(float(x) for x in ftrl)  # (lambda1, lambda2, beta)
         tables: List[EmbeddingTableConfig] = []
         for t, _, _, _ in config.lookups:
             if t not in tables:
@@ -435,9 +618,9 @@ class EmbeddingCollection(TableIO):
             for t in self.local_tables:  # U(+-sqrt(1/vocab)) per table (ragged_static_embedding.cu:499-509)
                 ns = len(self.owners[t])
                 n = -(-tables[t].max_vocabulary_size // ns)
-                b = (1.0 / tables[t].max_vocabulary_size) ** 0.5
                 s0 = self.row_start_of_table[t]
-                self.table[s0:s0 + n].uniform_(-b, b, generator=g)
+                fill_static_table(self.table[s0:s0 + n], tables[t], ns,
+                                  self.owners[t].index(self.rank), g)
             if optimizer == _lib.OPT_ADAGRAD:
                 self.accum = torch.full_like(self.table, initial_accu_value)
             if optimizer == _lib.OPT_FTRL:  # n and z start at zero (ragged_static_embedding.cu:484-496)
@@ -967,8 +1150,9 @@ class EmbeddingCollection(TableIO):
         return d
 
     def table_stats(self):
-        """{table name: dict(size, capacity_now, max_capacity, hbm_slots, rejected, doublings)} of
-        the hybrid tables this rank holds a shard of (host synchronisations: a reporting call)"""
+        """{table name: dict(size, capacity_now, max_capacity, hbm_slots, rejected, doublings,
+        optimizer)} of the hybrid tables this rank holds a shard of (host synchronisations: a
+        reporting call)"""
         if not self.hybrid:
             raise _lib.HugeCTRAmdError("table_stats: this collection has no hybrid tables")
         out = {}
@@ -976,7 +1160,8 @@ class EmbeddingCollection(TableIO):
             h = self.hyb[t]
             out[self.tables[t].name] = dict(
                 size=h.size(), capacity_now=h.current_capacity, max_capacity=h.capacity,
-                hbm_slots=h.hbm_slots, rejected=h.rejected_count(), doublings=h.doublings)
+                hbm_slots=h.hbm_slots, rejected=h.rejected_count(), doublings=h.doublings,
+                optimizer=_OPT_NAMES.get(self.optimizer, self.optimizer))
         return out
 
     def _hybrid_pool(self, send: torch.Tensor, direct: bool = False) -> torch.Tensor:
@@ -1381,8 +1566,17 @@ class DataParallelCollection(TableIO):
             dist.get_world_size(group) if dist.is_initialized() else 1)
         self.rank = rank if rank is not None else (dist.get_rank(group) if dist.is_initialized() else 0)
         assert global_batch % self.world == 0
+        # (tables that carry opt_params: as in EmbeddingCollection._setup)
+        o = _one_optimizer(config, optimizer, epsilon, initial_accu_value, ftrl, 0.9, 0.999, 0.0,
+                           0.9)
+        if o is not None:
+            optimizer, epsilon, initial_accu_value = int(o.optimizer_type), o.epsilon, \
+                o.initial_accu_value
+            ftrl = (o.lambda1, o.lambda2, o.beta)
         if optimizer not in (_lib.OPT_SGD, _lib.OPT_ADAGRAD, _lib.OPT_FTRL):
             raise _lib.HugeCTRAmdError("EBC static tables support SGD, AdaGrad and Ftrl")
+        for t, _, _, _ in config.lookups:
+            check_init_param(t)
         self.dev = torch.device("cuda", torch.cuda.current_device())
         self.B, self.bpg = global_batch, global_batch // self.world
         self.lr, self.optimizer, self.scaler, self.epsilon = lr, optimizer, scaler, epsilon
@@ -1406,8 +1600,7 @@ class DataParallelCollection(TableIO):
         g = torch.Generator(device=self.dev)
         g.manual_seed(seed * 1000003 + 99991)  # replica-uniform: the SAME stream on every rank
         for t, s0 in zip(tables, starts):
-            b = (1.0 / t.max_vocabulary_size) ** 0.5
-            self.table[s0:s0 + t.max_vocabulary_size].uniform_(-b, b, generator=g)
+            fill_static_table(self.table[s0:s0 + t.max_vocabulary_size], t, 1, 0, g)
         self.accum = self.ftrl_z = None
         if optimizer == _lib.OPT_ADAGRAD:
             self.accum = torch.full_like(self.table, initial_accu_value)

@@ -134,7 +134,9 @@ def create_collection(path: str, c: int, meta: MetaData, opt_state=None) -> str:
     """Removes and rewrites <path>/embedding_collection_<c> ONLY (the reference deletes the whole
     <path> per collection, :185, and so loses the collections written before): meta_data and, per
     table, key<i> / weight<i> (/ opt_state<i> when opt_state = (number of arrays, Optimizer_t
-    value)) with their heads, at full size -- every owner then writes its portion at its offset."""
+    value), or {table id: (number of arrays, Optimizer_t value)} where the tables of the collection
+    run different optimizers) with their heads, at full size -- every owner then writes its portion
+    at its offset."""
     d = collection_dir(path, c)
     os.makedirs(path, exist_ok=True)
     if os.path.isdir(d):
@@ -148,8 +150,12 @@ def create_collection(path: str, c: int, meta: MetaData, opt_state=None) -> str:
         files = [(f"key{i}", file_head(KIND_KEY, i), kn * meta.key_dtype.itemsize),
                  (f"weight{i}", file_head(KIND_WEIGHT, i), kn * ev * 4)]
         if opt_state is not None:
-            files.append((f"opt_state{i}", file_head(KIND_OPT, i, int(opt_state[0]), int(opt_state[1])),
-                          int(opt_state[0]) * kn * ev * 4))
+            if isinstance(opt_state, dict) and t not in opt_state:
+                raise EmbeddingIOError(f"create_collection: no optimizer state entry for table id "
+                                       f"{t} (given for {sorted(opt_state)})")
+            ns, opt = opt_state[t] if isinstance(opt_state, dict) else opt_state
+            files.append((f"opt_state{i}", file_head(KIND_OPT, i, int(ns), int(opt)),
+                          int(ns) * kn * ev * 4))
         for name, head, body in files:
             with open(os.path.join(d, name), "wb") as f:
                 f.write(head)

@@ -30,7 +30,9 @@ from .dense import (DenseFtrl, DenseGradFinish, FusedMLP, bce_with_logits, ftrl_
                     load_ftrl_state_dict)
 from .embedding import OptParams, SparseEmbeddingHash, backward_reorder, forward_reorder
 from .embedding_collection import (DataParallelCollection, EmbeddingCollection,  # noqa: F401
-                                   EmbeddingCollectionConfig, EmbeddingTableConfig)
+                                   EmbeddingCollectionConfig, EmbeddingTableConfig,
+                                   check_init_param, check_table_optimizer,
+                                   group_lookups_by_optimizer, resolve_table_optimizer, table_kind)
 from .metrics import EvalMetrics
 from .layers import (MultiCrossLayer, interaction, interaction_gather, interaction_indexed,
                      regather_supported)
@@ -307,6 +309,55 @@ def CreateOptimizer(optimizer_type=Optimizer_t.Adam, update_type=Update_t.Global
                     initial_accu_value=0.0, momentum_factor=0.0, atomic_update=True) -> OptParamsPy:
     return OptParamsPy(optimizer_type, update_type, beta, lambda1, lambda2, beta1, beta2, epsilon,
                        initial_accu_value, momentum_factor, atomic_update)
+
+
+class InitParams:
+    """EmbeddingTableConfig(init_param=...): how a static embedding_collection table is first
+    filled.  The reference's module has the argument but no constructor for it; this holder has
+    the arguments and checks of embedding::InitParams
+    (R/HugeCTR/embedding_storage/common.hpp:54-73).  Default: U(+-sqrt(1/vocabulary));
+    Uniform: U(-up_bound, up_bound); Sinusoidal: the position table of max_sequence_len rows
+    (embedding_collection.sinusoidal_table), max_sequence_len * ev_size being the table's size."""
+
+    def __init__(self, ev_size, initializer_type=Initializer_t.Default, up_bound=-1,
+                 max_sequence_len=-1):
+        if not isinstance(initializer_type, Initializer_t):
+            raise RuntimeError(f"InitParams: initializer_type must be an Initializer_t, not "
+                               f"{initializer_type!r}")
+        self.ev_size, self.initializer_type = int(ev_size), initializer_type
+        self.up_bound, self.max_sequence_len = 0.0, 0
+        if initializer_type == Initializer_t.Uniform:
+            if not up_bound > 0:
+                raise RuntimeError("InitParams: initialize type uniform should specify up_bound")
+            self.up_bound = float(up_bound)
+        if initializer_type == Initializer_t.Sinusoidal:
+            if not max_sequence_len > 0:
+                raise RuntimeError("InitParams: initialize type sinusoidal should specify "
+                                   "max_sequence_len")
+            self.max_sequence_len = int(max_sequence_len)
+
+    def __repr__(self):
+        return (f"InitParams(ev_size={self.ev_size}, initializer_type={self.initializer_type}, "
+                f"up_bound={self.up_bound}, max_sequence_len={self.max_sequence_len})")
+
+
+def check_embedding_collection_config(cfg: EmbeddingCollectionConfig, model_opt, world: int = 1):
+    """what Model.compile checks of a config's per-table options before any device call: every
+    table's resolved optimizer (its opt_params, else the model's) is one its kind of table runs,
+    and its init_param is one its storage honours.  Raises RuntimeError naming the table."""
+    from types import SimpleNamespace
+    for sub, _ in Model._split_by_ev_size(SimpleNamespace(world=world, opt=model_opt), cfg):
+        kinds = {table_kind(t) for t, _, _, _ in sub.lookups}
+        # (a static table beside a dynamic one is held by the dynamic table, all seven optimizers)
+        kind = "dp" if sub.shard_strategy == "dp" else "hybrid" if "hybrid" in kinds else \
+            "dynamic" if "dynamic" in kinds else "static"
+        tables = []
+        for t, _, _, _ in sub.lookups:
+            if t not in tables:
+                tables.append(t)
+        for t in tables:
+            check_table_optimizer(t, kind, *resolve_table_optimizer(t, model_opt))
+            check_init_param(t, "static" if kind == "dp" else kind)
 
 
 @dataclass
@@ -612,6 +663,8 @@ class Model:
         """loss_names / loss_weights: the multi-task form (model_wrapper.hpp compile overload);
         one BinaryCrossEntropyLoss is what this surface trains, so they must name that loss"""
         assert self.input is not None, "Model.add(Input(...)) first"
+        for cfg in self.ebc_configs:  # per-table opt_params / init_param: before any device call
+            check_embedding_collection_config(cfg, self.opt, self.world)
         # multi-task models (R/samples/mmoe): one BinaryCrossEntropyLoss per label, the training
         # loss is their weighted sum (Model::compile(loss_names, loss_weights), model.cpp)
         # Input(label_weights=...) seeds the weights, compile(loss_names, loss_weights) replaces
@@ -663,6 +716,7 @@ class Model:
             self._emb[se.sparse_embedding_name] = (se, p, h, ex, localized)
             self._shapes[se.sparse_embedding_name] = (p.slot_num, se.embedding_vec_size)
         self._ebc = []
+        self._ebc_stacked = {}  # id(config) -> ev of a list-form config that only optimizers split
         for cfg in self.ebc_configs:
             subs = self._split_by_ev_size(cfg)
             if len(subs) == 1:
@@ -675,7 +729,14 @@ class Model:
                 def width(t, bottom, c):  # a multi-hot concat lookup is max_hotness vectors wide
                     h = sp[bottom].max_nnz() if str(c).lower().endswith("concat") else 1
                     return t.ev_size * max(h, 1)
-                if cfg.top_name:
+                if cfg.top_name and len(self._split_by_ev_size(cfg, by_optimizer=False)) == 1:
+                    # only the tables' optimizers split this config: its output keeps the shape
+                    # and type of the unsplit collection's, [batch, lookups, ev] in lookup order
+                    ev = cfg.lookups[0][0].ev_size
+                    self._ebc_stacked[id(cfg)] = ev
+                    self._shapes[cfg.top_name] = (
+                        sum(width(t, b, c) for t, b, _, c in cfg.lookups) // ev, ev)
+                elif cfg.top_name:
                     self._shapes[cfg.top_name] = (sum(width(t, b, c) for t, b, _, c in cfg.lookups),)
                 else:
                     for t, b, top, c in cfg.lookups:
@@ -933,9 +994,16 @@ class Model:
                 out[f"embedding_collection{i}"] = r
         return out
 
-    def _split_by_ev_size(self, cfg: EmbeddingCollectionConfig):
+    def _split_by_ev_size(self, cfg: EmbeddingCollectionConfig, by_optimizer: bool = True):
         """the runtime keeps one vector size per collection: lookups of a config that mixes sizes
-        (wide 1 + deep 16 ...) run as one collection per size, each with the parent's placement"""
+        (wide 1 + deep 16 ...) run as one collection per size, each with the parent's placement.
+        Likewise one optimizer per collection: tables whose resolved optimizers (their opt_params,
+        else the model's) differ in type or in a hyper-parameter that type reads run as separate
+        collections (embedding_collection.group_lookups_by_optimizer; the reference refuses such a
+        group, embedding_table.cpp:40-45)."""
+        opt_groups = group_lookups_by_optimizer(cfg.lookups, getattr(self, "opt", None)) \
+            if by_optimizer else [(list(range(len(cfg.lookups))), None)]
+        opt_of = {l: g for g, (ids, _) in enumerate(opt_groups) for l in ids}
         dp_names = set()
         if isinstance(cfg.shard_strategy, (list, tuple)):
             for kind, names in cfg.shard_strategy:
@@ -959,7 +1027,8 @@ class Model:
         def kind(t):
             return "hybrid" if getattr(t, "var_type", None) == "hybrid" else "plain"
         kinds = sorted({kind(t) for t, _, _, _ in cfg.lookups if t.name not in dp_names})
-        if len(sizes) == 1 and not dp_names and len(strategies) <= 1 and len(kinds) <= 1:
+        if len(sizes) == 1 and not dp_names and len(strategies) <= 1 and len(kinds) <= 1 and \
+                len(opt_groups) == 1:
             return [(cfg, list(range(len(cfg.lookups))))]
         tables = []
         for t, _, _, _ in cfg.lookups:
@@ -967,17 +1036,20 @@ class Model:
                 tables.append(t)
         own = cfg.ownership(tables, self.world)
         out = []
-        for ev in sizes:  # replicated ("dp") tables: one data-parallel collection per vector size
+        groups = range(len(opt_groups))
+        # replicated ("dp") tables: one data-parallel collection per vector size (and optimizer)
+        for ev, og in [(e, g) for e in sizes for g in groups]:
             ids = [l for l, (t, _, _, _) in enumerate(cfg.lookups)
-                   if t.ev_size == ev and t.name in dp_names]
+                   if t.ev_size == ev and t.name in dp_names and opt_of[l] == og]
             if ids:
                 sub = EmbeddingCollectionConfig()
                 sub.lookups = [cfg.lookups[l] for l in ids]
                 sub.shard_strategy = "dp"
                 out.append((sub, ids))
-        for ev, strategy, knd in [(e, k, q) for e in sizes for k in strategies for q in kinds]:
+        for ev, strategy, knd, og in [(e, k, q, g) for e in sizes for k in strategies
+                                      for q in kinds for g in groups]:
             ids = [l for l, (t, _, _, _) in enumerate(cfg.lookups)
-                   if t.ev_size == ev and t.name not in dp_names and
+                   if t.ev_size == ev and t.name not in dp_names and opt_of[l] == og and
                    comp.get(t.name, "reduction") == strategy and kind(t) == knd]
             if not ids:
                 continue
@@ -999,31 +1071,15 @@ class Model:
     def _compile_ebc(self, cfg: EmbeddingCollectionConfig, sp, B, Be, declare_shapes=True):
         """embedding_collection of the model (R/HugeCTR/src/pybind/add_embedding_collection.cpp):
         one runtime for the training batch, one for the evaluation batch, sharing the tables"""
-        o = self.opt
-        t = Optimizer_t(o.optimizer_type)
+        # (_split_by_ev_size: the tables of a sub-config resolve to one optimizer, checked by
+        #  check_embedding_collection_config; the learning rate stays the model's)
+        o, _ = resolve_table_optimizer(cfg.lookups[0][0], self.opt)
+        # (the optimizer is one this kind of table runs: check_embedding_collection_config;
+        #  Optimizer_t's values are the library's codes)
+        code = int(o.optimizer_type)
         dynamic = any(tc.max_vocabulary_size < 0 for tc, _, _, _ in cfg.lookups)
         # (_split_by_ev_size: a sub-config is hybrid as a whole or not at all)
         hybrid = any(getattr(tc, "var_type", None) == "hybrid" for tc, _, _, _ in cfg.lookups)
-        codes = {Optimizer_t.SGD: _lib.OPT_SGD, Optimizer_t.AdaGrad: _lib.OPT_ADAGRAD,
-                 Optimizer_t.Ftrl: _lib.OPT_FTRL}
-        if hybrid:  # what hctr_lru_apply_update serves
-            codes = {Optimizer_t.SGD: _lib.OPT_SGD, Optimizer_t.AdaGrad: _lib.OPT_ADAGRAD,
-                     Optimizer_t.Adam: _lib.OPT_ADAM,
-                     Optimizer_t.MomentumSGD: _lib.OPT_MOMENTUM_SGD,
-                     Optimizer_t.Nesterov: _lib.OPT_NESTEROV}
-            if t not in codes:
-                raise RuntimeError(
-                    f"hybrid embedding_collection tables "
-                    f"{sorted({tc.name for tc, _, _, _ in cfg.lookups})} do not support "
-                    f"{t.name}; supported: SGD, AdaGrad, Adam, MomentumSGD, Nesterov")
-        elif dynamic:  # the dynamic table has all seven (embedding_storage/optimizers.cuh:29-233)
-            codes.update({Optimizer_t.Adam: _lib.OPT_ADAM, Optimizer_t.RMSProp: _lib.OPT_RMSPROP,
-                          Optimizer_t.MomentumSGD: _lib.OPT_MOMENTUM_SGD,
-                          Optimizer_t.Nesterov: _lib.OPT_NESTEROV})
-        code = codes.get(t)
-        if code is None:
-            raise RuntimeError("static embedding_collection tables support SGD, AdaGrad and Ftrl "
-                               "(R/HugeCTR/embedding_storage/ragged_static_embedding.cu:593-700)")
         params, offsets = [], []
         slot0, slot_of_param = 0, {}
         for p in self.input.sparse_params:
@@ -1046,11 +1102,10 @@ class Model:
                   batch_major=True, max_hotness=hot, seed=self.solver.seed,
                   ftrl=(o.lambda1, o.lambda2, o.beta))
         ekw = dict(kw, hotness=[p.max_nnz() for p in params])  # multi-hot concat lookups
-        if hybrid:  # (capacity, tier and initializer travel in the table configs)
-            ekw.update(beta1=o.beta1, beta2=o.beta2, momentum_factor=o.momentum_factor)
-        if dynamic:
-            kw.update(beta1=o.beta1, beta2=o.beta2, momentum_factor=o.momentum_factor,
-                      init_capacity=1 << 16)
+        if hybrid or dynamic:  # (capacity, tier and initializer travel in the table configs)
+            # (CreateOptimizer has no argument of its own for RMSProp's beta: beta2 is passed)
+            ekw.update(beta1=o.beta1, beta2=o.beta2, momentum_factor=o.momentum_factor,
+                       rmsprop_beta=o.beta2)
         if cfg.shard_strategy == "dp":  # replicated tables: no all-to-all, gradient all-reduce
             dkw = {k: v for k, v in kw.items() if k != "batch_major"}
             train = DataParallelCollection(cfg, B, **dkw)
@@ -1589,7 +1644,8 @@ class Model:
             for j, l in enumerate(rt["ids"]):
                 v0, reps = span[j] if span else (j, 1)
                 if cfg.top_name:
-                    tensors[(id(cfg), l)] = piece(v0, reps, as_float=True)
+                    tensors[(id(cfg), l)] = piece(v0, reps,
+                                                  as_float=id(cfg) not in self._ebc_stacked)
                 else:
                     tensors[cfg.lookups[l][2]] = piece(v0, reps)
 
@@ -1597,8 +1653,12 @@ class Model:
         for cfg in self.ebc_configs:
             if cfg.top_name and dict.__contains__(tensors, (id(cfg), 0)):
                 n = len(cfg.lookups)
-                tensors[cfg.top_name] = _Pending(
-                    lambda cfg=cfg, n=n: torch.cat([tensors[(id(cfg), l)] for l in range(n)], dim=1))
+                ev = self._ebc_stacked.get(id(cfg))
+
+                def resolve(cfg=cfg, n=n, ev=ev):
+                    x = torch.cat([tensors[(id(cfg), l)] for l in range(n)], dim=1)
+                    return x if ev is None else x.view(x.shape[0], -1, ev)
+                tensors[cfg.top_name] = _Pending(resolve)
 
     def _multi_task_loss(self, tensors):
         """weighted sum of the tasks' losses + every task's scores side by side"""
@@ -1960,6 +2020,11 @@ class Model:
             print(f"{'EmbeddingCollection':<40}{','.join(b for _, b, _, _ in cfg.lookups)[:28]:<30}"
                   f"{(cfg.top_name or ','.join(t for _, _, t, _ in cfg.lookups))[:28]:<30}"
                   f"({self.bpg},{e.L},{e.ev})")
+            for t in e.tables:  # each table's optimizer: its opt_params, else the model's
+                src = "opt_params" if resolve_table_optimizer(t, self.opt)[1] == "table" \
+                    else "model"
+                print(f"{'  table ' + t.name:<40}{'optimizer':<30}"
+                      f"{Optimizer_t(int(e.optimizer)).name + ' (' + src + ')':<30}")
         for L in self.layers:
             tops = ",".join(L.top_names)
             shp = self._shapes.get(L.top_names[0], ()) if L.top_names else ()
@@ -2185,7 +2250,9 @@ class Model:
             meta = embedding_io.MetaData(
                 ids, {i: sum(r[j] for r in counts) for j, i in enumerate(ids)},
                 {i: entries[i][1].ev for i in ids}, np.dtype(kd))
-            opt = (e0.io_state_count(), int(e0.optimizer)) if optimizer_states else None
+            # (per table: the config's tables may run different optimizers, opt_params)
+            opt = {i: (entries[i][1].io_state_count(), int(entries[i][1].optimizer))
+                   for i in ids} if optimizer_states else None
             if self.rank == 0:
                 embedding_io.create_collection(path, c, meta, opt)
             if self.world > 1:
@@ -2204,7 +2271,9 @@ class Model:
         """Model::embedding_load: every rank keeps the keys it owns (key % num_shards ==
         shard_id; a replicated table loads whole on every rank).  The tables are written in place
         -- a captured graph stays valid -- and only after every table asked for has been
-        validated.  Optimizer state is loaded where the dump holds it for the model's optimizer."""
+        validated.  Optimizer state is loaded where the dump holds it for that table's optimizer
+        (its opt_params, else the model's); a state file of another optimizer is refused in the
+        validation, before anything is written."""
         from . import embedding_io
         self._drain_prefetch()
         self.check_overflow()
@@ -2292,10 +2361,8 @@ class Model:
     def load_dense_optimizer_states(self, path: str):
         """state of the dense optimizer as save_params_to_files wrote it (<prefix>_opt_dense_<iter>
         .model, model.cpp:1238)"""
-        if isinstance(self._dense_opt, DenseFtrl):
+        if self._dense_opt is not None:  # (load_state_dict moves the state to the parameters)
             self._dense_opt.load_state_dict(torch.load(path, map_location="cpu"))
-        elif self._dense_opt is not None:
-            self._dense_opt.load_state_dict(torch.load(path, map_location=self.device))
         elif self._flat_mlps and self._flat_ftrl:  # the same file, whichever path wrote it
             load_ftrl_state_dict(self._flat_ftrl_state(), torch.load(path, map_location="cpu"))
 
