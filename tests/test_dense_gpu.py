@@ -211,6 +211,30 @@ def test_convert_transpose16(dtype_name, L, R, C):
     assert torch.equal(b, src.to(dt).transpose(1, 2))
 
 
+def test_transpose16_segments():
+    """hctr_transpose16_segments through the C ABI, three segments in one launch: 33 x 70 (a ragged
+    edge in both directions), 1 x 1 (a tile with one element) and 64 x 32 (exact tiles).  The same
+    bits as torch's transpose, and the sentinel around every segment survives."""
+    import torch
+    from hugectr_amd._lib import check, lib, ptr
+    shapes, gap, sentinel = [(33, 70), (1, 1), (64, 32)], 40, 0x7E7E
+    gen = torch.Generator().manual_seed(16)
+    srcs = [torch.randint(-32768, 32768, s, dtype=torch.int16, generator=gen).cuda() for s in shapes]
+    out = torch.full((gap + sum(r * c + gap for r, c in shapes),), sentinel, dtype=torch.int16,
+                     device="cuda")
+    # hctr_transpose16_seg as include/hugectr_amd.h lays it out: {src, dst, rows, cols, block0} and
+    # three reserved words, all int64; block0 = the 32 x 32 tiles of the segments in front
+    want, table, at = out.clone(), np.zeros((3, 8), dtype=np.int64), gap
+    for i, (src, (r, c), block0) in enumerate(zip(srcs, shapes, (0, 2 * 3, 2 * 3 + 1))):
+        table[i, :5] = (src.data_ptr(), out.data_ptr() + 2 * at, r, c, block0)
+        want[at:at + r * c] = src.t().reshape(-1)
+        at += r * c + gap
+    table = torch.from_numpy(table).cuda()
+    check(lib.hctr_transpose16_segments(ptr(table), 3, 2 * 3 + 1 + 2, None))
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+
+
 @pytest.mark.parametrize("dtype_name,rt,at", [("float16", 2e-2, 2e-2), ("bfloat16", 6e-2, 6e-2)])
 @pytest.mark.parametrize("B,w,p,L", [(200, 256, 128, 2), (1024, 3456, 512, 3)])
 def test_cross_v2_on_the_own_gemm_matches_oracle(oracle, monkeypatch, dtype_name, rt, at, B, w, p, L):
