@@ -152,7 +152,8 @@ __global__ void __launch_bounds__(kBlock)
     for (uint64_t probes = 0; probes <= size; ++probes) {
       const long long cur = tab[slot].key;
       if (cur == k64) {
-        res = tab[slot].val;
+        const uint64_t v = tab[slot].val;
+        res = v < kNoRow ? v : kInvalidIndex;  // (an erased key keeps its entry and owns no row)
         break;
       }
       if (cur == empty) break;
@@ -195,10 +196,13 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// Erasure by value: the entry keeps its key and its slot, its value becomes "no row" -- what the
+// index resolves as a miss and hands a new row at the key's next inserting lookup (hashtable.hip).
+// No key is overwritten with a mark: every key but the reserved `empty` stays an ordinary key.
 template <typename K>
 __global__ void __launch_bounds__(kBlock)
     det_erase_kernel(HtEntry* __restrict__ tab, uint64_t size, const K* __restrict__ keys,
-                     size_t n, long long tomb, unsigned long long* __restrict__ d_erased) {
+                     size_t n, unsigned long long* __restrict__ d_erased) {
   const long long empty = KeyTraits<K>::empty;
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
        i += (size_t)gridDim.x * kBlock) {
@@ -209,14 +213,10 @@ __global__ void __launch_bounds__(kBlock)
     for (uint64_t probes = 0; probes <= size; ++probes) {
       const long long cur = tab[slot].key;
       if (cur == k64) {
-        // duplicates of one key in the batch race for the slot; one of them wins the CAS
-        const unsigned long long old =
-            atomicCAS(reinterpret_cast<unsigned long long*>(&tab[slot].key),
-                      (unsigned long long)k64, (unsigned long long)tomb);
-        if (old == (unsigned long long)k64) {
-          tab[slot].val = kInvalidIndex;
+        // duplicates of one key in the batch race for the row; one of them wins the CAS
+        const unsigned long long v = tab[slot].val;
+        if (v < kNoRow && atomicCAS(&tab[slot].val, v, (unsigned long long)kInvalidIndex) == v)
           atomicAdd(d_erased, 1ull);
-        }
         break;
       }
       if (cur == empty) break;
@@ -236,7 +236,9 @@ struct DetOpt {
 // One thread per element of one unique key's vector.  Formulas: optimizers.cuh:29-233 -- the
 // reference turns wgrad into the weight delta in place and then scatter_adds it; here the delta is
 // applied to the row directly (same arithmetic, one pass).
-// one element of one row: state update + weight delta (optimizers.cuh:29-233)
+// one element of one row: state update + weight delta (optimizers.cuh:29-233).  w == nullptr: the
+// key is not in the weight table -- the reference's *_update_grad_kernel still moves its state, and
+// only the scatter_add of the delta skips the key
 __device__ __forceinline__ void det_apply(const DetOpt& o, int dim, int e, float gi, float* w,
                                           float* st) {
   float delta;
@@ -279,7 +281,7 @@ __device__ __forceinline__ void det_apply(const DetOpt& o, int dim, int e, float
       st[e] = ni;
       const float ni_sqrt = sqrtf(ni + 1.1920929e-07f);
       const float sigma = (ni_sqrt - ni_prev_sqrt) / o.lr;
-      const float wi = *w;
+      const float wi = w != nullptr ? *w : 0.f;  // (Ftrl looks its weights up inserting: never null)
       const float zi = st[dim + e] + gi - sigma * wi;
       st[dim + e] = zi;
       const float p = (1.f - 2.f * (float)signbit(zi)) * o.lambda1 - zi;
@@ -287,7 +289,7 @@ __device__ __forceinline__ void det_apply(const DetOpt& o, int dim, int e, float
       delta = (p / q) * (float)signbit(o.lambda1 - fabsf(zi)) - wi;
     } break;
   }
-  *w += delta;
+  if (w != nullptr) *w += delta;
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -301,12 +303,14 @@ __global__ void __launch_bounds__(kBlock)
     const size_t k = (size_t)(i / dim);
     const int e = (int)(i % dim);
     const uint64_t rw = idx_w[k];
-    if (rw == kInvalidIndex) continue;  // scatter_add skips keys that are not in the table
-    const float gi = wgrad[ev_start[k] + e] / o.scaler;
     const int sdim = dim * (o.optimizer == HCTR_OPT_ADAM || o.optimizer == HCTR_OPT_FTRL ? 2 : 1);
     float* st = (rows_s != nullptr && idx_s != nullptr) ? rows_s + idx_s[k] * (uint64_t)sdim
                                                          : nullptr;
-    det_apply(o, dim, e, gi, rows_w + rw * dim + e, st);
+    // scatter_add skips keys that are not in the table: their state moves, their weights do not
+    float* w = rw != kInvalidIndex ? rows_w + rw * dim + e : nullptr;
+    if (w == nullptr && st == nullptr) continue;
+    const float gi = wgrad[ev_start[k] + e] / o.scaler;
+    det_apply(o, dim, e, gi, w, st);
   }
 }
 
@@ -322,10 +326,12 @@ __global__ void __launch_bounds__(kBlock)
        i += (uint64_t)gridDim.x * kBlock) {
     const size_t k = (size_t)(i / dim);
     const int e = (int)(i % dim);
+    // scatter_add skips keys that are not in the table: their state moves, their weights do not
     float* w = wptr[k];
-    if (w == nullptr) continue;  // scatter_add skips keys that are not in the table
+    float* st = sptr ? sptr[k] : nullptr;
+    if (w == nullptr && st == nullptr) continue;
     const float gi = wgrad[ev_start[k] + e] / o.scaler;
-    det_apply(o, dim, e, gi, w + e, sptr ? sptr[k] : nullptr);
+    det_apply(o, dim, e, gi, w ? w + e : nullptr, st);
   }
 }
 
@@ -556,7 +562,7 @@ int class_map(hctr_det* h, size_t ci, size_t rows, hipStream_t s) {
 }
 
 // make room for n more rows (cuco::dynamic_map::reserve): the index is re-built at twice the
-// capacity (tombstones are dropped); the rows stay where they are and get more memory behind them
+// capacity (entries of erased keys are dropped); the rows stay where they are and get more memory behind them
 int class_reserve(hctr_det* h, DetClass& c, size_t n, int key_type, hipStream_t s) {
   if (c.head_bound + n <= c.cap) return HCTR_OK;
   size_t head = 0;
@@ -1095,12 +1101,10 @@ int hctr_det_remove(hctr_det* h, const void* keys, size_t num_keys, const size_t
     const dim3 grid(grid_for(r.n, kBlock, 2048));
     if (h->key_type == HCTR_KEY_U32)
       hipLaunchKernelGGL(det_erase_kernel<uint32_t>, grid, dim3(kBlock), 0, s, c.ht.entries,
-                         c.ht.size, (const uint32_t*)key_at(h, keys, r.off), r.n,
-                         KeyTraits<uint32_t>::empty - 1, c.d_erased);
+                         c.ht.size, (const uint32_t*)key_at(h, keys, r.off), r.n, c.d_erased);
     else
       hipLaunchKernelGGL(det_erase_kernel<long long>, grid, dim3(kBlock), 0, s, c.ht.entries,
-                         c.ht.size, (const long long*)key_at(h, keys, r.off), r.n,
-                         KeyTraits<long long>::empty - 1, c.d_erased);
+                         c.ht.size, (const long long*)key_at(h, keys, r.off), r.n, c.d_erased);
     HCTR_LAUNCH_CHECK();
   }
   return HCTR_OK;

@@ -830,7 +830,7 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
     for (int r = 0; r < kHtTile / kBlock; r++) {
       uint64_t i = tile * (uint64_t)kHtTile + r * kBlock + threadIdx.x;
-      // erased entries (dynamic tables) keep a tombstone key with an invalid value
+      // erased entries (dynamic tables) keep their key with an invalid value
       if (i < size)
         c += (tab[i].key != empty && tab[i].val != kInvalidIndex && tab[i].val != kNoRow) ? 1u : 0u;
     }

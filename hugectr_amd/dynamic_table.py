@@ -27,7 +27,12 @@ class DynamicEmbeddingTable:
     """num_classes maps key -> fp32[dim_c]; grows on demand.  Method names follow the reference:
     lookup / lookup_unsafe / scatter_add / scatter_update / remove / export / clear / size /
     capacity.  Keys of one call are grouped by class: `id_spaces[i]` owns
-    keys[id_space_offsets[i]:id_space_offsets[i+1]] (host lists, as in the reference)."""
+    keys[id_space_offsets[i]:id_space_offsets[i+1]] (host lists, as in the reference).
+
+    One key value is reserved, as in the reference's map: the index's `empty` sentinel, 0xFFFFFFFF
+    for 32-bit and INT64_MAX for 64-bit keys, must not be presented.  Every other value is an
+    ordinary key: remove() erases by value (the entry keeps its key and owns no row until the key's
+    next inserting lookup), so no second value is taken out of the key domain."""
 
     def __init__(self, dimension_per_class: Sequence[int], initializer: str = "",
                  initial_capacity: int = 1048576, key_dtype=torch.int64, seed: int = 0):

@@ -16,8 +16,13 @@ FTRL, ADAM, RMSPROP, ADAGRAD, NESTEROV, MOMENTUM, SGD = range(7)  # Optimizer_t 
 
 
 class DetOracle:
-    def __init__(self, dims, init_value):
+    """dtype: the type the vectors are kept and summed in.  float32 (the default) is the reference's
+    arithmetic; float64 evaluates the same operations on the same fp32 inputs without the rounding of
+    the intermediate results (what the parity tests measure the fp32 evaluation's own error with)."""
+
+    def __init__(self, dims, init_value, dtype=f32):
         self.dims = list(dims)
+        self.dt = np.dtype(dtype).type
         self.init = f32(init_value)
         self.maps = [dict() for _ in dims]
 
@@ -30,9 +35,9 @@ class DetOracle:
         out = []
         for c, k in self._each(keys, id_spaces, offsets):
             if k not in self.maps[c]:  # insert-if-missing with the initializer (lookup kernel)
-                self.maps[c][k] = np.full(self.dims[c], self.init, dtype=f32)
+                self.maps[c][k] = np.full(self.dims[c], self.init, dtype=self.dt)
             out.append(self.maps[c][k].copy())
-        return np.concatenate(out) if out else np.zeros(0, dtype=f32)
+        return np.concatenate(out) if out else np.zeros(0, dtype=self.dt)
 
     def scatter(self, keys, elements, id_spaces, offsets, add):
         off = 0
@@ -40,9 +45,9 @@ class DetOracle:
             d = self.dims[c]
             if k in self.maps[c]:  # missing keys are skipped
                 if add:
-                    self.maps[c][k] = (self.maps[c][k] + elements[off:off + d]).astype(f32)
+                    self.maps[c][k] = (self.maps[c][k] + elements[off:off + d]).astype(self.dt)
                 else:
-                    self.maps[c][k] = elements[off:off + d].astype(f32).copy()
+                    self.maps[c][k] = elements[off:off + d].astype(self.dt).copy()
             off += d
 
     def remove(self, keys, id_spaces, offsets):
@@ -55,59 +60,64 @@ class DetOracle:
 
 def update(weights: DetOracle, states: DetOracle, opt, keys, id_spaces, offsets, ev_start, wgrad,
            lr, scaler=1.0, beta1=0.9, beta2=0.999, eps=1e-7, momentum=0.9, rms_beta=0.9,
-           lambda1=0.0, lambda2=0.0, ftrl_beta=0.0, times=1):
-    """dynamic_embedding.cu:176-330: state lookup (zeros), per-element formula, scatter_add"""
-    lr, scaler = f32(lr), f32(scaler)
-    b1, b2, eps, mom, rb = f32(beta1), f32(beta2), f32(eps), f32(momentum), f32(rms_beta)
+           lambda1=0.0, lambda2=0.0, ftrl_beta=0.0, times=1, dtype=None):
+    """dynamic_embedding.cu:176-330: state lookup (zeros), per-element formula, scatter_add.
+    dtype (default: the weights oracle's, float32 unless it was created otherwise): the type of
+    every intermediate result.  The inputs -- hyperparameters, gradients, initial values -- are the
+    fp32 numbers the device gets in either case."""
+    T = weights.dt if dtype is None else np.dtype(dtype).type
+    lr, scaler = T(f32(lr)), T(f32(scaler))
+    b1, b2, eps, mom, rb = (T(f32(x)) for x in (beta1, beta2, eps, momentum, rms_beta))
+    lambda1, eps_ftrl, one, two = T(f32(lambda1)), T(FLT_EPSILON), T(1), T(2)
     # AdamOptHyperParams::bias() (optimizer.hpp:58-60): std::pow(float beta, uint64 times) promotes
     # the FLOAT beta to double -- 0.999f, not 0.999 (found by pinning against the reference build)
-    bias = f32(np.sqrt(1.0 - float(b2) ** times) / (1.0 - float(b1) ** times))
+    bias = T(np.sqrt(1.0 - float(b2) ** times) / (1.0 - float(b1) ** times))
     lr_scaled_bias = lr * bias
-    l2b = f32(lambda2) + f32(ftrl_beta) / lr
+    l2b = T(f32(lambda2)) + T(f32(ftrl_beta)) / lr
     pos = 0
     for i, c in enumerate(id_spaces):
         d = weights.dims[c]
         for j in range(offsets[i], offsets[i + 1]):
             k = int(keys[j])
-            g = (wgrad[ev_start[pos]:ev_start[pos] + d].astype(f32) / scaler).astype(f32)
+            g = (wgrad[ev_start[pos]:ev_start[pos] + d].astype(T) / scaler).astype(T)
             pos += 1
             if opt != SGD:
                 sd = states.dims[c]
                 if k not in states.maps[c]:
-                    states.maps[c][k] = np.zeros(sd, dtype=f32)
+                    states.maps[c][k] = np.zeros(sd, dtype=T)
                 st = states.maps[c][k]
             if opt == FTRL and k not in weights.maps[c]:
-                weights.maps[c][k] = np.full(d, weights.init, dtype=f32)
+                weights.maps[c][k] = np.full(d, weights.init, dtype=T)
             if opt == SGD:
-                delta = (-lr * g).astype(f32)
+                delta = (-lr * g).astype(T)
             elif opt == MOMENTUM:
-                st[:] = (mom * st - lr * g).astype(f32)
+                st[:] = (mom * st - lr * g).astype(T)
                 delta = st.copy()
             elif opt == NESTEROV:
                 prev = st.copy()
-                st[:] = (mom * prev - lr * g).astype(f32)
-                delta = (st + mom * st - mom * prev).astype(f32)
+                st[:] = (mom * prev - lr * g).astype(T)
+                delta = (st + mom * st - mom * prev).astype(T)
             elif opt == ADAGRAD:
-                st[:] = (st + g * g).astype(f32)
-                delta = (-lr * g / (np.sqrt(st).astype(f32) + eps)).astype(f32)
+                st[:] = (st + g * g).astype(T)
+                delta = (-lr * g / (np.sqrt(st).astype(T) + eps)).astype(T)
             elif opt == RMSPROP:
-                st[:] = (rb * st + (f32(1) - rb) * g * g).astype(f32)
-                delta = (-lr * g / (np.sqrt(st).astype(f32) + eps)).astype(f32)
+                st[:] = (rb * st + (one - rb) * g * g).astype(T)
+                delta = (-lr * g / (np.sqrt(st).astype(T) + eps)).astype(T)
             elif opt == ADAM:
                 m, v = st[:d], st[d:]
-                m[:] = (b1 * m + (f32(1) - b1) * g).astype(f32)
-                v[:] = (b2 * v + (f32(1) - b2) * g * g).astype(f32)
-                delta = (-lr_scaled_bias * m / (np.sqrt(v).astype(f32) + eps)).astype(f32)
+                m[:] = (b1 * m + (one - b1) * g).astype(T)
+                v[:] = (b2 * v + (one - b2) * g * g).astype(T)
+                delta = (-lr_scaled_bias * m / (np.sqrt(v).astype(T) + eps)).astype(T)
             else:  # FTRL
                 n, z = st[:d], st[d:]
                 w = weights.maps[c][k]
-                n_prev_sqrt = np.sqrt(n + FLT_EPSILON).astype(f32)
-                n[:] = (n + g * g).astype(f32)
-                n_sqrt = np.sqrt(n + FLT_EPSILON).astype(f32)
-                sigma = ((n_sqrt - n_prev_sqrt) / lr).astype(f32)
-                z[:] = (z + g - sigma * w).astype(f32)
-                p = ((f32(1) - f32(2) * np.signbit(z).astype(f32)) * f32(lambda1) - z).astype(f32)
-                q = (n_sqrt / lr + l2b).astype(f32)
-                delta = ((p / q) * np.signbit(f32(lambda1) - np.abs(z)).astype(f32) - w).astype(f32)
+                n_prev_sqrt = np.sqrt(n + eps_ftrl).astype(T)
+                n[:] = (n + g * g).astype(T)
+                n_sqrt = np.sqrt(n + eps_ftrl).astype(T)
+                sigma = ((n_sqrt - n_prev_sqrt) / lr).astype(T)
+                z[:] = (z + g - sigma * w).astype(T)
+                p = ((one - two * np.signbit(z).astype(T)) * lambda1 - z).astype(T)
+                q = (n_sqrt / lr + l2b).astype(T)
+                delta = ((p / q) * np.signbit(lambda1 - np.abs(z)).astype(T) - w).astype(T)
             if k in weights.maps[c]:  # scatter_add skips missing keys
-                weights.maps[c][k] = (weights.maps[c][k] + delta).astype(f32)
+                weights.maps[c][k] = (weights.maps[c][k] + delta).astype(T)
