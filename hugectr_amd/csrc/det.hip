@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -64,49 +63,32 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// one V (float, or float4) of a row per thread; dv = V per row; a key without a row reads as zeros
+template <typename V>
 __global__ void __launch_bounds__(kBlock)
-    det_gather_kernel(const uint64_t* __restrict__ idx, size_t n, const float* __restrict__ rows,
-                      int dim, float* __restrict__ out) {
-  const uint64_t total = (uint64_t)n * dim;
+    det_gather_kernel(const uint64_t* __restrict__ idx, size_t n, const V* __restrict__ rows,
+                      int dv, V* __restrict__ out) {
+  const uint64_t total = (uint64_t)n * dv;
   for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < total;
        i += (uint64_t)gridDim.x * kBlock) {
-    const uint64_t r = idx[i / dim];
-    out[i] = r != kInvalidIndex ? rows[r * dim + (i % dim)] : 0.0f;
+    const uint64_t k = i / (uint32_t)dv;
+    const uint32_t c = (uint32_t)(i - k * (uint32_t)dv);
+    const uint64_t r = idx[k];
+    out[i] = r != kInvalidIndex ? rows[r * (uint32_t)dv + c] : V{};
   }
 }
 
 // dim % 4 == 0 and 16-byte aligned buffers: one float4 per thread (the common case)
-__global__ void __launch_bounds__(kBlock)
-    det_gather4_kernel(const uint64_t* __restrict__ idx, size_t n, const float4* __restrict__ rows,
-                       int d4, float4* __restrict__ out) {
-  const uint64_t total = (uint64_t)n * d4;
-  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < total;
-       i += (uint64_t)gridDim.x * kBlock) {
-    const uint64_t k = i / (uint32_t)d4;
-    const uint32_t c = (uint32_t)(i - k * (uint32_t)d4);
-    const uint64_t r = idx[k];
-    out[i] = r != kInvalidIndex ? rows[r * (uint32_t)d4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
 static void launch_det_gather(const uint64_t* idx, size_t n, const float* rows, int dim, float* out,
                               hipStream_t s) {
   const bool v4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(out) % 16 == 0;
-  if (v4)
-    hipLaunchKernelGGL(det_gather4_kernel, dim3(grid_for(n * (size_t)(dim / 4), kBlock, 8192)),
-                       dim3(kBlock), 0, s, idx, n, (const float4*)rows, dim / 4, (float4*)out);
-  else
-    hipLaunchKernelGGL(det_gather_kernel, dim3(grid_for(n * (size_t)dim, kBlock, 8192)),
-                       dim3(kBlock), 0, s, idx, n, rows, dim, out);
-}
-
-__global__ void __launch_bounds__(kBlock)
-    det_ptr_kernel(const uint64_t* __restrict__ idx, size_t n, float* rows, int dim,
-                   float** __restrict__ out) {
-  for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * kBlock)
-    out[i] = idx[i] != kInvalidIndex ? rows + idx[i] * (uint64_t)dim : nullptr;
+  with_bool(v4, [&](auto vec) {
+    using V = std::conditional_t<decltype(vec)::value, float4, float>;
+    const int dv = dim / (int)(sizeof(V) / sizeof(float));
+    hipLaunchKernelGGL(det_gather_kernel<V>, dim3(grid_for(n * (size_t)dv, kBlock, 8192)),
+                       dim3(kBlock), 0, s, idx, n, (const V*)rows, dv, (V*)out);
+  });
 }
 
 // ---- one launch over all id spaces of a call (instead of one hash pass per id space) -------------
@@ -138,27 +120,15 @@ __global__ void __launch_bounds__(kBlock)
                           const uint64_t* __restrict__ seg_off, int n_seg,
                           const K* __restrict__ keys, size_t n, uint64_t* __restrict__ idx,
                           uint32_t* __restrict__ miss, uint64_t* __restrict__ out_row) {
-  const long long empty = KeyTraits<K>::empty;
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
        i += (size_t)gridDim.x * kBlock) {
     const uint32_t c = seg_class[det_segment_of(seg_off, n_seg, i)];
     const HtEntry* __restrict__ tab = cls[c].tab;
     const uint64_t size = cls[c].size;
     const K key = keys[i];
-    const long long k64 = (long long)(sizeof(K) == 4 ? (unsigned long long)(uint32_t)key
-                                                     : (unsigned long long)key);
-    uint64_t slot = (uint64_t)murmur3_key(key) % size;
-    uint64_t res = kInvalidIndex;
-    for (uint64_t probes = 0; probes <= size; ++probes) {
-      const long long cur = tab[slot].key;
-      if (cur == k64) {
-        const uint64_t v = tab[slot].val;
-        res = v < kNoRow ? v : kInvalidIndex;  // (an erased key keeps its entry and owns no row)
-        break;
-      }
-      if (cur == empty) break;
-      slot = (slot + 1 == size) ? 0 : slot + 1;
-    }
+    const uint64_t slot = ht_walk_find(tab, size, widen_key<K>(key), KeyTraits<K>::empty,
+                                       (uint64_t)murmur3_key(key) % size);
+    const uint64_t res = slot != kHtAbsent ? live_row_of(tab[slot].val) : kInvalidIndex;
     idx[i] = res;
     if (res == kInvalidIndex) miss[c] = 1u;
     // (the table-wide row number right away: final unless a class has to insert and may grow)
@@ -166,14 +136,17 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// row address and / or table-wide row number of every key from its row index.  The class of a
+// position comes from the call's id-space table, or (n_seg == 0: keys of ONE class, nothing of the
+// call on the device) is `one`.
 __global__ void __launch_bounds__(kBlock)
     det_rows_multi_kernel(const DetClassDesc* __restrict__ cls, const uint32_t* __restrict__ seg_class,
-                          const uint64_t* __restrict__ seg_off, int n_seg,
+                          const uint64_t* __restrict__ seg_off, int n_seg, DetClassDesc one,
                           const uint64_t* __restrict__ idx, size_t n, float** __restrict__ out_ptr,
                           uint64_t* __restrict__ out_row) {
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
        i += (size_t)gridDim.x * kBlock) {
-    const DetClassDesc d = cls[seg_class[det_segment_of(seg_off, n_seg, i)]];
+    const DetClassDesc d = n_seg > 0 ? cls[seg_class[det_segment_of(seg_off, n_seg, i)]] : one;
     const uint64_t r = idx[i];
     if (out_ptr) out_ptr[i] = r != kInvalidIndex ? d.rows + r * (uint64_t)d.dim : nullptr;
     if (out_row) out_row[i] = r != kInvalidIndex ? d.row_base + r : kInvalidIndex;
@@ -203,25 +176,17 @@ template <typename K>
 __global__ void __launch_bounds__(kBlock)
     det_erase_kernel(HtEntry* __restrict__ tab, uint64_t size, const K* __restrict__ keys,
                      size_t n, unsigned long long* __restrict__ d_erased) {
-  const long long empty = KeyTraits<K>::empty;
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
        i += (size_t)gridDim.x * kBlock) {
     const K key = keys[i];
-    const long long k64 = (long long)(sizeof(K) == 4 ? (unsigned long long)(uint32_t)key
-                                                     : (unsigned long long)key);
-    uint64_t slot = (uint64_t)murmur3_key(key) % size;
-    for (uint64_t probes = 0; probes <= size; ++probes) {
-      const long long cur = tab[slot].key;
-      if (cur == k64) {
-        // duplicates of one key in the batch race for the row; one of them wins the CAS
-        const unsigned long long v = tab[slot].val;
-        if (v < kNoRow && atomicCAS(&tab[slot].val, v, (unsigned long long)kInvalidIndex) == v)
-          atomicAdd(d_erased, 1ull);
-        break;
-      }
-      if (cur == empty) break;
-      slot = (slot + 1 == size) ? 0 : slot + 1;
-    }
+    const uint64_t slot = ht_walk_find(tab, size, widen_key<K>(key), KeyTraits<K>::empty,
+                                       (uint64_t)murmur3_key(key) % size);
+    if (slot == kHtAbsent) continue;
+    // duplicates of one key in the batch race for the row; one of them wins the CAS
+    const unsigned long long v = tab[slot].val;
+    if (live_row_of(v) != kInvalidIndex &&
+        atomicCAS(&tab[slot].val, v, (unsigned long long)kInvalidIndex) == v)
+      atomicAdd(d_erased, 1ull);
   }
 }
 
@@ -292,69 +257,50 @@ __device__ __forceinline__ void det_apply(const DetOpt& o, int dim, int e, float
   if (w != nullptr) *w += delta;
 }
 
+// Where key k's weight row (w) and state row (st) are; nullptr: none.  By row
+// index into the arrays of one class; or by per-key row addresses: one launch for keys of any number
+// of classes (dynamic_embedding.cu:227-317: *_update_grad_kernel(ev_start_indices, ..., float**
+// state, float** weight)).
+struct RowsByIndex {
+  const uint64_t* __restrict__ idx_w;
+  const uint64_t* __restrict__ idx_s;  // nullptr (or rows_s == nullptr): no state
+  float* __restrict__ rows_w;
+  float* __restrict__ rows_s;
+  __device__ __forceinline__ void at(size_t k, int dim, int sdim, float*& w, float*& st) const {
+    // (the weight index is loaded first and looked at last: the two index loads are in flight
+    //  together -- one after the other was measured 8 % slower on the Adam step)
+    const uint64_t rw = idx_w[k];
+    st = (rows_s != nullptr && idx_s != nullptr) ? rows_s + idx_s[k] * (uint64_t)sdim : nullptr;
+    w = rw != kInvalidIndex ? rows_w + rw * dim : nullptr;
+  }
+};
+struct RowsByPointer {
+  float* const* __restrict__ wptr;
+  float* const* __restrict__ sptr;  // nullptr: no state
+  __device__ __forceinline__ void at(size_t k, int, int, float*& w, float*& st) const {
+    w = wptr[k];
+    st = sptr ? sptr[k] : nullptr;
+  }
+};
+
+template <typename Rows>
 __global__ void __launch_bounds__(kBlock)
-    det_update_kernel(DetOpt o, size_t n, int dim, const uint64_t* __restrict__ idx_w,
-                      const uint64_t* __restrict__ idx_s, float* __restrict__ rows_w,
-                      float* __restrict__ rows_s, const uint32_t* __restrict__ ev_start,
+    det_update_kernel(DetOpt o, size_t n, int dim, Rows rows, const uint32_t* __restrict__ ev_start,
                       const float* __restrict__ wgrad) {
   const uint64_t total = (uint64_t)n * dim;
-  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < total;
-       i += (uint64_t)gridDim.x * kBlock) {
-    const size_t k = (size_t)(i / dim);
-    const int e = (int)(i % dim);
-    const uint64_t rw = idx_w[k];
-    const int sdim = dim * (o.optimizer == HCTR_OPT_ADAM || o.optimizer == HCTR_OPT_FTRL ? 2 : 1);
-    float* st = (rows_s != nullptr && idx_s != nullptr) ? rows_s + idx_s[k] * (uint64_t)sdim
-                                                         : nullptr;
-    // scatter_add skips keys that are not in the table: their state moves, their weights do not
-    float* w = rw != kInvalidIndex ? rows_w + rw * dim + e : nullptr;
-    if (w == nullptr && st == nullptr) continue;
-    const float gi = wgrad[ev_start[k] + e] / o.scaler;
-    det_apply(o, dim, e, gi, w, st);
-  }
-}
-
-// the same step through per-key row addresses: one launch for keys of any number of classes
-// (dynamic_embedding.cu:227-317: *_update_grad_kernel(ev_start_indices, ..., float** state,
-// float** weight))
-__global__ void __launch_bounds__(kBlock)
-    det_update_ptr_kernel(DetOpt o, size_t n, int dim, float* const* __restrict__ wptr,
-                          float* const* __restrict__ sptr, const uint32_t* __restrict__ ev_start,
-                          const float* __restrict__ wgrad) {
-  const uint64_t total = (uint64_t)n * dim;
+  const int sdim = dim * (o.optimizer == HCTR_OPT_ADAM || o.optimizer == HCTR_OPT_FTRL ? 2 : 1);
   for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < total;
        i += (uint64_t)gridDim.x * kBlock) {
     const size_t k = (size_t)(i / dim);
     const int e = (int)(i % dim);
     // scatter_add skips keys that are not in the table: their state moves, their weights do not
-    float* w = wptr[k];
-    float* st = sptr ? sptr[k] : nullptr;
+    float *w, *st;
+    rows.at(k, dim, sdim, w, st);
     if (w == nullptr && st == nullptr) continue;
     const float gi = wgrad[ev_start[k] + e] / o.scaler;
     det_apply(o, dim, e, gi, w ? w + e : nullptr, st);
   }
 }
-
-// HCTR_DET_TRACE=1: wall time of the pieces of a growth step, to stderr
-struct GrowTrace {
-  bool on;
-  double t0;
-  const char* what;
-  static double now() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  }
-  explicit GrowTrace(const char* w) : what(w) {
-    static const bool e = [] { const char* v = getenv("HCTR_DET_TRACE"); return v && v[0] == '1'; }();
-    on = e;
-    t0 = on ? now() : 0.0;
-  }
-  void lap(const char* piece) {
-    if (!on) return;
-    const double t = now();
-    fprintf(stderr, "[det] %s: %s %.3f ms\n", what, piece, (t - t0) * 1e3);
-    t0 = t;
-  }
-};
 
 // ---- growing arrays --------------------------------------------------------------------------
 // A table's rows (and, for the flat row store's users, its optimizer state) live in ONE reserved
@@ -368,17 +314,7 @@ struct GrowTrace {
 // (ROCm 7.2, tools/vmm_probe.hip): the pieces of a range must all have ONE size (hipMemSetAccess
 // fails with "invalid argument" at the first piece larger than its predecessors), so the piece
 // size is a process-wide constant; reserving, freeing and reserving again is fine.
-inline size_t vm_piece_bytes() {
-  static const size_t v = [] {
-    const char* e = getenv("HCTR_DET_PIECE_MB");  // (a power of two; experiments only)
-    size_t mb = e ? (size_t)atol(e) : 64;
-    if (mb < 2) mb = 2;
-    size_t p = 2;
-    while (p < mb) p *= 2;
-    return p << 20;
-  }();
-  return v;
-}
+constexpr size_t kVmPieceBytes = (size_t)64 << 20;
 
 struct VmArray {
   char* base = nullptr;
@@ -404,7 +340,7 @@ int vm_reserve(VmArray& a, size_t bytes) {
 
 // physical pieces behind [off, off + bytes) (both multiples of the piece size, nothing mapped there yet)
 int vm_map(VmArray& a, size_t off, size_t bytes, bool zero, hipStream_t s) {
-  const size_t piece = vm_piece_bytes();
+  const size_t piece = kVmPieceBytes;
   int dev = 0;
   HCTR_HIP(hipGetDevice(&dev));
   hipMemAllocationProp prop = {};
@@ -437,7 +373,7 @@ int vm_map(VmArray& a, size_t off, size_t bytes, bool zero, hipStream_t s) {
 }
 
 void vm_release(VmArray& a) {
-  const size_t piece = vm_piece_bytes();
+  const size_t piece = kVmPieceBytes;
   for (const VmArray::Piece& p : a.pieces) {
     (void)hipMemUnmap(a.base + p.off, piece);
     (void)hipMemRelease(p.h);
@@ -512,18 +448,60 @@ struct hctr_det {
 
 namespace {
 
-int det_scratch(hctr_det* h, size_t n) {
-  if (n <= h->idx_cap) return HCTR_OK;
-  if (h->idx) (void)hipFree(h->idx);
-  if (h->idx2) (void)hipFree(h->idx2);
-  h->idx = h->idx2 = nullptr;
-  size_t c = h->idx_cap ? h->idx_cap : 1024;
+// a pair of scratch buffers that only grows: room for n elements in each, at `first` elements
+// times a power of two (freed and allocated again: what they held is not kept)
+template <typename A, typename B>
+int grow_device_buffers(A** a, B** b, size_t* cap, size_t n, size_t first) {
+  if (n <= *cap) return HCTR_OK;
+  if (*a) (void)hipFree(*a);
+  if (*b) (void)hipFree(*b);
+  *a = nullptr;
+  *b = nullptr;
+  size_t c = *cap ? *cap : first;
+  *cap = 0;
   while (c < n) c *= 2;
-  HCTR_HIP(hipMalloc(&h->idx, c * sizeof(uint64_t)));
-  HCTR_HIP(hipMalloc(&h->idx2, c * sizeof(uint64_t)));
-  h->idx_cap = c;
+  HCTR_HIP(hipMalloc(a, c * sizeof(A)));
+  HCTR_HIP(hipMalloc(b, c * sizeof(B)));
+  *cap = c;
   return HCTR_OK;
 }
+
+int det_scratch(hctr_det* h, size_t n) {
+  return grow_device_buffers(&h->idx, &h->idx2, &h->idx_cap, n, 1024);
+}
+
+// The live (key, row) pairs of a class's index, in device buffers that go with the holder.
+struct LivePairs {
+  int64_t* keys = nullptr;  // as HashTable::dump writes them: widened to 64 bits
+  uint64_t* rows = nullptr;
+  size_t n = 0;
+  LivePairs() = default;
+  LivePairs(const LivePairs&) = delete;
+  LivePairs& operator=(const LivePairs&) = delete;
+  ~LivePairs() {
+    if (keys) (void)hipFree(keys);
+    if (rows) (void)hipFree(rows);
+  }
+  int dump(HashTable& ht, hipStream_t s) {  // (synchronises)
+    HCTR_HIP(hipMalloc(&keys, (size_t)ht.size * sizeof(int64_t)));
+    HCTR_HIP(hipMalloc(&rows, (size_t)ht.size * sizeof(uint64_t)));
+    return ht.dump(keys, rows, &n, s);
+  }
+  // the first `count` keys in the table's own key type to device memory at dst (dst == keys: in
+  // place).  u32 keys are narrowed on the host; i64 keys are copied on the stream.
+  int keys_to(void* dst, size_t count, int key_type, hipStream_t s) const {
+    if (key_type == HCTR_KEY_U32) {
+      std::vector<int64_t> hk(count);
+      std::vector<uint32_t> hk32(count);
+      HCTR_HIP(hipMemcpy(hk.data(), keys, count * sizeof(int64_t), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < count; i++) hk32[i] = (uint32_t)hk[i];
+      HCTR_HIP(hipMemcpy(dst, hk32.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice));
+    } else if (dst != keys) {
+      HCTR_HIP(hipMemcpyAsync(dst, keys, count * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    }
+    return HCTR_OK;
+  }
+};
 
 int class_create(DetClass& c, size_t cap, int dim, int key_type) {
   c.dim = dim;
@@ -551,7 +529,7 @@ int class_map(hctr_det* h, size_t ci, size_t rows, hipStream_t s) {
               " (2^32 row numbers shared by " + std::to_string(h->cls.size()) + " classes)");
     return HCTR_ERR_INVALID_ARG;
   }
-  const size_t piece = vm_piece_bytes();
+  const size_t piece = kVmPieceBytes;
   const size_t need = ceil_div<size_t>(rows * (size_t)c.dim * sizeof(float), piece) * piece;
   if (need <= c.mapped) return HCTR_OK;
   HCTR_TRY(vm_map(h->rows_va, h->region_off[ci] + c.mapped, need - c.mapped, false, s));
@@ -566,46 +544,27 @@ int class_map(hctr_det* h, size_t ci, size_t rows, hipStream_t s) {
 int class_reserve(hctr_det* h, DetClass& c, size_t n, int key_type, hipStream_t s) {
   if (c.head_bound + n <= c.cap) return HCTR_OK;
   size_t head = 0;
-  GrowTrace tr("class_reserve");
   HCTR_TRY(c.ht.value_head(s, &head));  // synchronises: the exact row counter
   c.head_bound = head;
-  tr.lap("value_head (stream drained)");
   if (head + n <= c.cap) return HCTR_OK;
   size_t ncap = c.cap * 2;
   while (ncap < head + n) ncap *= 2;
   if (ncap > h->stride_rows && head + n <= h->stride_rows) ncap = h->stride_rows;
   const size_t ci = (size_t)(&c - h->cls.data());
   HCTR_TRY(class_map(h, ci, ncap, s));
-  tr.lap("pieces mapped");
-  // live (key, row) pairs of the old index
-  int64_t* d_keys = nullptr;
-  uint64_t* d_vals = nullptr;
-  const size_t slots = (size_t)c.ht.size;
-  HCTR_HIP(hipMalloc(&d_keys, slots * sizeof(int64_t)));
-  HCTR_HIP(hipMalloc(&d_vals, slots * sizeof(uint64_t)));
-  size_t live = 0;
-  HCTR_TRY(c.ht.dump(d_keys, d_vals, &live, s));
+  LivePairs live;  // of the old index
+  HCTR_TRY(live.dump(c.ht, s));
   HashTable nht;
   HCTR_TRY(nht.create(ncap, key_type));
-  if (live > 0) {
-    if (key_type == HCTR_KEY_U32) {
-      // dump widens keys to int64; the u32 insert path wants 32-bit keys
-      std::vector<int64_t> hk(live);
-      HCTR_HIP(hipMemcpy(hk.data(), d_keys, live * sizeof(int64_t), hipMemcpyDeviceToHost));
-      std::vector<uint32_t> hk32(live);
-      for (size_t i = 0; i < live; i++) hk32[i] = (uint32_t)hk[i];
-      HCTR_HIP(hipMemcpy(d_keys, hk32.data(), live * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    HCTR_TRY(nht.insert(d_keys, d_vals, live, s));
+  if (live.n > 0) {
+    // dump widens keys to int64; the u32 insert path wants 32-bit keys
+    HCTR_TRY(live.keys_to(live.keys, live.n, key_type, s));
+    HCTR_TRY(nht.insert(live.keys, live.rows, live.n, s));
   }
-  HCTR_TRY(nht.set_value_head(head, s));
-  tr.lap("re-index");
-  (void)hipFree(d_keys);
-  (void)hipFree(d_vals);
+  HCTR_TRY(nht.set_value_head(head, s));  // (synchronises: the pairs are free to go)
   c.ht.destroy();
   c.ht = nht;
   c.cap = ncap;
-  tr.lap("old index freed");
   // rows of erased keys stay allocated (indices are never reused); only the index forgets them
   return HCTR_OK;
 }
@@ -627,11 +586,29 @@ int ranges_of(const hctr_det* h, size_t num_keys, const size_t* id_spaces,
   return HCTR_OK;
 }
 
-inline const void* key_at(const hctr_det* h, const void* keys, size_t off) {
-  return (const char*)keys + off * (h->key_type == HCTR_KEY_U32 ? 4 : 8);
+// What the entry points over (keys, id spaces) start with: the handle, nothing to do for no keys
+// (*rs stays empty, and a caller's loops over it do nothing), the caller's pointers, the id spaces
+// as ranges, and (if asked) the scratch row indices.
+int det_enter(hctr_det* h, size_t num_keys, bool pointers_ok, const size_t* id_spaces,
+              const size_t* id_space_offsets, size_t num_id_spaces, bool scratch,
+              std::vector<Range>* rs) {
+  HCTR_REQUIRE(h, "null handle");
+  if (num_keys == 0) return HCTR_OK;
+  HCTR_REQUIRE(pointers_ok, "null pointer");
+  HCTR_TRY(ranges_of(h, num_keys, id_spaces, id_space_offsets, num_id_spaces, rs));
+  return scratch ? det_scratch(h, num_keys) : HCTR_OK;
 }
 
-// an inserting lookup that was queued and is not verified yet (det_verify_inserts)
+inline const void* key_at(const hctr_det* h, const void* keys, size_t off) {
+  size_t bytes = 0;
+  (void)with_key_type(h->key_type, [&](auto* k) -> int {
+    bytes = sizeof(std::remove_pointer_t<decltype(k)>);
+    return HCTR_OK;
+  });
+  return (const char*)keys + off * bytes;
+}
+
+// an inserting lookup: n keys of class cls, row indices to idx[0..n)
 struct Inserted {
   size_t cls;
   const void* keys;
@@ -639,17 +616,27 @@ struct Inserted {
   uint64_t* idx;
 };
 
-// lookup with insertion of unseen keys; leaves row indices in idx[0..n).  `log`: the call is noted
-// for det_verify_inserts, which every caller runs before it reads idx.
-int class_lookup_insert(hctr_det* h, DetClass& c, size_t cls_index, const void* keys, size_t n,
-                        uint64_t* idx, hipStream_t s, std::vector<Inserted>* log,
-                        bool two_launches = false) {
+// the non-empty ranges (of the classes flagged in `only`, if given) as inserting lookups that
+// leave the row index of keys[i] in idx[i]
+std::vector<Inserted> inserts_of(const hctr_det* h, const void* keys, const std::vector<Range>& rs,
+                                 uint64_t* idx, const std::vector<uint32_t>* only = nullptr) {
+  std::vector<Inserted> ins;
+  for (const Range& r : rs)
+    if (r.n && (only == nullptr || (*only)[r.cls]))
+      ins.push_back({r.cls, key_at(h, keys, r.off), r.n, idx + r.off});
+  return ins;
+}
+
+// lookup with insertion of unseen keys; queued only: det_insert_verify is what callers use
+int class_lookup_insert(hctr_det* h, const Inserted& it, hipStream_t s, bool two_launches = false) {
+  DetClass& c = h->cls[it.cls];
+  const size_t cls_index = it.cls, n = it.n;
+  uint64_t* const idx = it.idx;
   HCTR_TRY(class_reserve(h, c, n, h->key_type, s));
   IndexExtras ex;
   ex.host_error = h->h_err + cls_index;
   ex.two_launches = two_launches;
-  HCTR_TRY(c.ht.get_insert(keys, n, nullptr, idx, s, nullptr, &ex));
-  if (log != nullptr) log->push_back({cls_index, keys, n, idx});
+  HCTR_TRY(c.ht.get_insert(it.keys, n, nullptr, idx, s, nullptr, &ex));
   c.head_bound += n;
   hipLaunchKernelGGL(det_init_rows_kernel, dim3(grid_for(n * (size_t)c.dim, kBlock, 2048)),
                      dim3(kBlock), 0, s, c.ht.new_positions, c.ht.d_new_count, idx, c.rows, c.dim,
@@ -692,7 +679,7 @@ int det_verify_inserts(hctr_det* h, std::vector<Inserted>& ins, hipStream_t s) {
       DetClass& c = h->cls[it.cls];
       c.head_bound -= it.n < c.head_bound ? it.n : c.head_bound;  // (counted again below)
       h->repairs++;
-      HCTR_TRY(class_lookup_insert(h, c, it.cls, it.keys, it.n, it.idx, s, nullptr, true));
+      HCTR_TRY(class_lookup_insert(h, it, s, true));
     }
   HCTR_HIP(hipStreamSynchronize(s));
   for (size_t ci = 0; ci < redo.size(); ci++)
@@ -704,6 +691,21 @@ int det_verify_inserts(hctr_det* h, std::vector<Inserted>& ins, hipStream_t s) {
     }
   ins.clear();
   return HCTR_OK;
+}
+
+// Every insertion of a call, and the check that it handed out rows, before a row is read or a
+// pointer or a row base is taken.  reserve_sums: room for ALL of a class's keys first (a class may
+// own several lookups: a later one could otherwise grow the class after an earlier one's rows were
+// numbered against the smaller store).
+int det_insert_verify(hctr_det* h, std::vector<Inserted> ins, bool reserve_sums, hipStream_t s) {
+  if (reserve_sums) {
+    std::vector<size_t> need(h->cls.size(), 0);
+    for (const Inserted& it : ins) need[it.cls] += it.n;
+    for (size_t ci = 0; ci < need.size(); ci++)
+      if (need[ci]) HCTR_TRY(class_reserve(h, h->cls[ci], need[ci], h->key_type, s));
+  }
+  for (const Inserted& it : ins) HCTR_TRY(class_lookup_insert(h, it, s));
+  return det_verify_inserts(h, ins, s);
 }
 
 }  // namespace
@@ -779,7 +781,7 @@ int hctr_det_create(size_t num_classes, const size_t* dimension_per_class, const
   while (stride * max_row_bytes > ((size_t)1 << 40)) stride >>= 1;
   while (stride > ((size_t)1 << 24) && stride * max_row_bytes * num_classes > ((size_t)16 << 40)) stride >>= 1;
   if (stride < ((size_t)1 << 24) || stride * max_row_bytes * num_classes > ((size_t)16 << 40) ||
-      (stride * sizeof(float)) % vm_piece_bytes() != 0) {
+      (stride * sizeof(float)) % kVmPieceBytes != 0) {
     set_error("dynamic table: too many classes for one table (at most 255, fewer for very long vectors)");
     return fail(HCTR_ERR_INVALID_ARG);
   }
@@ -833,20 +835,11 @@ int hctr_det_destroy(hctr_det* h) {
 int hctr_det_lookup(hctr_det* h, const void* keys, float* elements, size_t num_keys,
                     const size_t* id_spaces, const size_t* id_space_offsets, size_t num_id_spaces,
                     hctr_stream_t stream) {
-  HCTR_REQUIRE(h, "null handle");
-  if (num_keys == 0) return HCTR_OK;
-  HCTR_REQUIRE(keys && elements, "null pointer");
   hipStream_t s = as_stream(stream);
   std::vector<Range> rs;
-  HCTR_TRY(ranges_of(h, num_keys, id_spaces, id_space_offsets, num_id_spaces, &rs));
-  HCTR_TRY(det_scratch(h, num_keys));
-  // every insertion (and the check that it handed out rows) before a row is read
-  std::vector<Inserted> ins;
-  for (const Range& r : rs)
-    if (r.n)
-      HCTR_TRY(class_lookup_insert(h, h->cls[r.cls], r.cls, key_at(h, keys, r.off), r.n,
-                                   h->idx + r.off, s, &ins));
-  HCTR_TRY(det_verify_inserts(h, ins, s));
+  HCTR_TRY(det_enter(h, num_keys, keys && elements, id_spaces, id_space_offsets, num_id_spaces,
+                     true, &rs));
+  HCTR_TRY(det_insert_verify(h, inserts_of(h, keys, rs, h->idx), false, s));
   size_t out_off = 0;
   for (const Range& r : rs) {
     DetClass& c = h->cls[r.cls];
@@ -861,30 +854,20 @@ int hctr_det_lookup(hctr_det* h, const void* keys, float* elements, size_t num_k
 int hctr_det_lookup_unsafe(hctr_det* h, const void* keys, float** elements, size_t num_keys,
                            const size_t* id_spaces, const size_t* id_space_offsets,
                            size_t num_id_spaces, hctr_stream_t stream) {
-  HCTR_REQUIRE(h, "null handle");
-  if (num_keys == 0) return HCTR_OK;
-  HCTR_REQUIRE(keys && elements, "null pointer");
   hipStream_t s = as_stream(stream);
   std::vector<Range> rs;
-  HCTR_TRY(ranges_of(h, num_keys, id_spaces, id_space_offsets, num_id_spaces, &rs));
-  HCTR_TRY(det_scratch(h, num_keys));
-  // two passes: every insertion (and so every re-allocation) happens before a pointer is taken
-  // (a class may own several ranges: reserve their sum, or a later range could move the store)
-  std::vector<size_t> need(h->cls.size(), 0);
-  for (const Range& r : rs) need[r.cls] += r.n;
-  for (size_t ci = 0; ci < need.size(); ci++)
-    if (need[ci]) HCTR_TRY(class_reserve(h, h->cls[ci], need[ci], h->key_type, s));
-  std::vector<Inserted> ins;
-  for (const Range& r : rs)
-    if (r.n)
-      HCTR_TRY(class_lookup_insert(h, h->cls[r.cls], r.cls, key_at(h, keys, r.off), r.n,
-                                   h->idx + r.off, s, &ins));
-  HCTR_TRY(det_verify_inserts(h, ins, s));
+  HCTR_TRY(det_enter(h, num_keys, keys && elements, id_spaces, id_space_offsets, num_id_spaces,
+                     true, &rs));
+  // two passes: every insertion (and so every growth) happens before a pointer is taken
+  HCTR_TRY(det_insert_verify(h, inserts_of(h, keys, rs, h->idx), true, s));
   for (const Range& r : rs) {
-    DetClass& c = h->cls[r.cls];
+    const DetClass& c = h->cls[r.cls];
     if (r.n == 0) continue;
-    hipLaunchKernelGGL(det_ptr_kernel, dim3(grid_for(r.n, kBlock, 1024)), dim3(kBlock), 0, s,
-                       h->idx + r.off, r.n, c.rows, c.dim, elements + r.off);
+    // (one class per launch: nothing of the call has to be on the device)
+    const DetClassDesc one = {nullptr, 0, c.rows, 0, c.dim};
+    hipLaunchKernelGGL(det_rows_multi_kernel, dim3(grid_for(r.n, kBlock, 1024)), dim3(kBlock), 0,
+                       s, nullptr, nullptr, nullptr, 0, one, h->idx + r.off, r.n,
+                       elements + r.off, nullptr);
     HCTR_LAUNCH_CHECK();
   }
   return HCTR_OK;
@@ -899,17 +882,9 @@ static int det_upload_spaces(hctr_det* h, const std::vector<Range>& rs,
     HCTR_HIP(hipMalloc(&h->d_miss, ncls * sizeof(uint32_t)));
   }
   if (rs.size() > h->seg_cap) {
-    if (h->d_seg_class) (void)hipFree(h->d_seg_class);
-    if (h->d_seg_off) (void)hipFree(h->d_seg_off);
-    h->d_seg_class = nullptr;
-    h->d_seg_off = nullptr;
-    size_t c = 64;
-    while (c < rs.size()) c *= 2;
-    HCTR_HIP(hipMalloc(&h->d_seg_class, c * sizeof(uint32_t)));
-    HCTR_HIP(hipMalloc(&h->d_seg_off, c * sizeof(uint64_t)));
-    h->seg_cap = c;
     h->up_seg_class.clear();
     h->up_seg_off.clear();
+    HCTR_TRY(grow_device_buffers(&h->d_seg_class, &h->d_seg_off, &h->seg_cap, rs.size(), 64));
   }
   std::vector<DetClassDesc> desc(ncls);
   memset((void*)desc.data(), 0, ncls * sizeof(DetClassDesc));
@@ -996,14 +971,13 @@ int hctr_det_lookup_rows(hctr_det* h, const void* keys, size_t num_keys, const s
     // class's base, are then different ones)
     uint64_t* early_rows = elements == nullptr ? row_index : nullptr;
     bool rows_done = early_rows != nullptr;
-    if (h->key_type == HCTR_KEY_U32)
-      hipLaunchKernelGGL(det_find_multi_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, h->d_desc,
-                         h->d_seg_class, h->d_seg_off, (int)rs.size(), (const uint32_t*)keys,
-                         num_keys, h->idx, h->d_miss, early_rows);
-    else
-      hipLaunchKernelGGL(det_find_multi_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, h->d_desc,
-                         h->d_seg_class, h->d_seg_off, (int)rs.size(), (const long long*)keys,
-                         num_keys, h->idx, h->d_miss, early_rows);
+    HCTR_TRY(with_key_type(h->key_type, [&](auto* k) -> int {
+      using K = std::remove_pointer_t<decltype(k)>;
+      hipLaunchKernelGGL(det_find_multi_kernel<K>, dim3(grid), dim3(kBlock), 0, s, h->d_desc,
+                         h->d_seg_class, h->d_seg_off, (int)rs.size(), (const K*)keys, num_keys,
+                         h->idx, h->d_miss, early_rows);
+      return HCTR_OK;
+    }));
     HCTR_LAUNCH_CHECK();
     if (insert) {
       // 2. only those classes take the inserting path (and may grow: every insertion happens
@@ -1012,22 +986,9 @@ int hctr_det_lookup_rows(hctr_det* h, const void* keys, size_t num_keys, const s
       HCTR_HIP(hipMemcpyAsync(miss.data(), h->d_miss, ncls * sizeof(uint32_t),
                               hipMemcpyDeviceToHost, s));
       HCTR_HIP(hipStreamSynchronize(s));
-      std::vector<size_t> need(ncls, 0);
-      bool any = false;
-      for (const Range& r : rs)
-        if (miss[r.cls]) {
-          need[r.cls] += r.n;
-          any = true;
-        }
-      if (any) {
-        for (size_t ci = 0; ci < ncls; ci++)
-          if (need[ci]) HCTR_TRY(class_reserve(h, h->cls[ci], need[ci], h->key_type, s));
-        std::vector<Inserted> ins;
-        for (const Range& r : rs)
-          if (miss[r.cls])
-            HCTR_TRY(class_lookup_insert(h, h->cls[r.cls], r.cls, key_at(h, keys, r.off), r.n,
-                                         h->idx + r.off, s, &ins));
-        HCTR_TRY(det_verify_inserts(h, ins, s));
+      std::vector<Inserted> ins = inserts_of(h, keys, rs, h->idx, &miss);
+      if (!ins.empty()) {
+        HCTR_TRY(det_insert_verify(h, std::move(ins), true, s));
         rebase();
         HCTR_TRY(det_upload_spaces(h, rs, base, s));
         rows_done = false;
@@ -1036,8 +997,8 @@ int hctr_det_lookup_rows(hctr_det* h, const void* keys, size_t num_keys, const s
     // 3. addresses / table-wide row numbers of all keys
     if (!rows_done) {
       hipLaunchKernelGGL(det_rows_multi_kernel, dim3(grid_for(num_keys, kBlock, 8192)), dim3(kBlock),
-                         0, s, h->d_desc, h->d_seg_class, h->d_seg_off, (int)rs.size(), h->idx,
-                         num_keys, elements, row_index);
+                         0, s, h->d_desc, h->d_seg_class, h->d_seg_off, (int)rs.size(),
+                         DetClassDesc{}, h->idx, num_keys, elements, row_index);
       HCTR_LAUNCH_CHECK();
     }
   }
@@ -1049,24 +1010,19 @@ int hctr_det_lookup_rows(hctr_det* h, const void* keys, size_t num_keys, const s
 static int det_scatter(hctr_det* h, const void* keys, const float* elements, size_t num_keys,
                        const size_t* id_spaces, const size_t* id_space_offsets,
                        size_t num_id_spaces, bool add, hipStream_t s) {
-  HCTR_REQUIRE(h, "null handle");
-  if (num_keys == 0) return HCTR_OK;
-  HCTR_REQUIRE(keys && elements, "null pointer");
   std::vector<Range> rs;
-  HCTR_TRY(ranges_of(h, num_keys, id_spaces, id_space_offsets, num_id_spaces, &rs));
-  HCTR_TRY(det_scratch(h, num_keys));
+  HCTR_TRY(det_enter(h, num_keys, keys && elements, id_spaces, id_space_offsets, num_id_spaces,
+                     true, &rs));
   size_t off = 0;
   for (const Range& r : rs) {
     DetClass& c = h->cls[r.cls];
     if (r.n == 0) continue;
     HCTR_TRY(c.ht.get_mark(key_at(h, keys, r.off), r.n, nullptr, h->idx, s));
     const dim3 grid(grid_for(r.n * (size_t)c.dim, kBlock, 4096));
-    if (add)
-      hipLaunchKernelGGL(det_scatter_kernel<true>, grid, dim3(kBlock), 0, s, h->idx, r.n, c.rows,
-                         c.dim, elements + off);
-    else
-      hipLaunchKernelGGL(det_scatter_kernel<false>, grid, dim3(kBlock), 0, s, h->idx, r.n, c.rows,
-                         c.dim, elements + off);
+    with_bool(add, [&](auto a) {
+      hipLaunchKernelGGL(det_scatter_kernel<decltype(a)::value>, grid, dim3(kBlock), 0, s, h->idx,
+                         r.n, c.rows, c.dim, elements + off);
+    });
     HCTR_LAUNCH_CHECK();
     off += r.n * (size_t)c.dim;
   }
@@ -1089,22 +1045,20 @@ int hctr_det_scatter_update(hctr_det* h, const void* keys, const float* elements
 
 int hctr_det_remove(hctr_det* h, const void* keys, size_t num_keys, const size_t* id_spaces,
                     const size_t* id_space_offsets, size_t num_id_spaces, hctr_stream_t stream) {
-  HCTR_REQUIRE(h, "null handle");
-  if (num_keys == 0) return HCTR_OK;
-  HCTR_REQUIRE(keys, "null pointer");
   hipStream_t s = as_stream(stream);
   std::vector<Range> rs;
-  HCTR_TRY(ranges_of(h, num_keys, id_spaces, id_space_offsets, num_id_spaces, &rs));
+  HCTR_TRY(det_enter(h, num_keys, keys != nullptr, id_spaces, id_space_offsets, num_id_spaces,
+                     false, &rs));
   for (const Range& r : rs) {
     DetClass& c = h->cls[r.cls];
     if (r.n == 0) continue;
     const dim3 grid(grid_for(r.n, kBlock, 2048));
-    if (h->key_type == HCTR_KEY_U32)
-      hipLaunchKernelGGL(det_erase_kernel<uint32_t>, grid, dim3(kBlock), 0, s, c.ht.entries,
-                         c.ht.size, (const uint32_t*)key_at(h, keys, r.off), r.n, c.d_erased);
-    else
-      hipLaunchKernelGGL(det_erase_kernel<long long>, grid, dim3(kBlock), 0, s, c.ht.entries,
-                         c.ht.size, (const long long*)key_at(h, keys, r.off), r.n, c.d_erased);
+    HCTR_TRY(with_key_type(h->key_type, [&](auto* k) -> int {
+      using K = std::remove_pointer_t<decltype(k)>;
+      hipLaunchKernelGGL(det_erase_kernel<K>, grid, dim3(kBlock), 0, s, c.ht.entries, c.ht.size,
+                         (const K*)key_at(h, keys, r.off), r.n, c.d_erased);
+      return HCTR_OK;
+    }));
     HCTR_LAUNCH_CHECK();
   }
   return HCTR_OK;
@@ -1115,34 +1069,18 @@ int hctr_det_export(hctr_det* h, size_t class_index, void* keys, float* values, 
   HCTR_REQUIRE(h && class_index < h->cls.size(), "class_index");
   hipStream_t s = as_stream(stream);
   DetClass& c = h->cls[class_index];
-  int64_t* d_keys = nullptr;
-  uint64_t* d_vals = nullptr;
-  const size_t slots = (size_t)c.ht.size;
-  HCTR_HIP(hipMalloc(&d_keys, slots * sizeof(int64_t)));
-  HCTR_HIP(hipMalloc(&d_vals, slots * sizeof(uint64_t)));
-  size_t live = 0;
-  int rc = c.ht.dump(d_keys, d_vals, &live, s);
-  if (rc == HCTR_OK) {
-    const size_t n = live < num_keys ? live : num_keys;
-    if (exported) *exported = n;
-    if (n > 0) {
-      HCTR_REQUIRE(keys && values, "null pointer");
-      if (h->key_type == HCTR_KEY_U32) {
-        std::vector<int64_t> hk(n);
-        std::vector<uint32_t> hk32(n);
-        (void)hipMemcpy(hk.data(), d_keys, n * sizeof(int64_t), hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < n; i++) hk32[i] = (uint32_t)hk[i];
-        (void)hipMemcpy(keys, hk32.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
-      } else {
-        (void)hipMemcpyAsync(keys, d_keys, n * sizeof(int64_t), hipMemcpyDeviceToDevice, s);
-      }
-      launch_det_gather(d_vals, n, c.rows, c.dim, values, s);
-      (void)hipStreamSynchronize(s);
-    }
+  LivePairs live;
+  HCTR_TRY(live.dump(c.ht, s));
+  const size_t n = live.n < num_keys ? live.n : num_keys;
+  if (exported) *exported = n;
+  if (n > 0) {
+    HCTR_REQUIRE(keys && values, "null pointer");
+    HCTR_TRY(live.keys_to(keys, n, h->key_type, s));
+    launch_det_gather(live.rows, n, c.rows, c.dim, values, s);
+    HCTR_LAUNCH_CHECK();
+    HCTR_HIP(hipStreamSynchronize(s));
   }
-  (void)hipFree(d_keys);
-  (void)hipFree(d_vals);
-  return rc;
+  return HCTR_OK;
 }
 
 int hctr_det_lookup_index(hctr_det* h, size_t class_index, const void* keys, size_t num_keys,
@@ -1151,11 +1089,9 @@ int hctr_det_lookup_index(hctr_det* h, size_t class_index, const void* keys, siz
   if (num_keys == 0) return HCTR_OK;
   HCTR_REQUIRE(keys && row_index, "null pointer");
   DetClass& c = h->cls[class_index];
-  if (insert) {
-    std::vector<Inserted> ins;
-    HCTR_TRY(class_lookup_insert(h, c, class_index, keys, num_keys, row_index, as_stream(stream), &ins));
-    return det_verify_inserts(h, ins, as_stream(stream));
-  }
+  if (insert)
+    return det_insert_verify(h, {{class_index, keys, num_keys, row_index}}, false,
+                             as_stream(stream));
   return c.ht.get_mark(keys, num_keys, nullptr, row_index, as_stream(stream));
 }
 
@@ -1239,8 +1175,12 @@ int hctr_det_update(hctr_det* weights, hctr_det* states, const hctr_det_opt_para
                     const size_t* id_space_offsets, size_t num_id_spaces,
                     const uint32_t* ev_start_indices, const float* wgrad, hctr_stream_t stream) {
   HCTR_REQUIRE(weights && p, "null pointer");
+  hipStream_t s = as_stream(stream);
+  hctr_det* h = weights;
+  std::vector<Range> rs;
+  HCTR_TRY(det_enter(h, num_unique_keys, unique_keys && ev_start_indices && wgrad, id_spaces,
+                     id_space_offsets, num_id_spaces, true, &rs));
   if (num_unique_keys == 0) return HCTR_OK;
-  HCTR_REQUIRE(unique_keys && ev_start_indices && wgrad, "null pointer");
   const int opt = p->optimizer;
   HCTR_REQUIRE(opt == HCTR_OPT_SGD || opt == HCTR_OPT_ADAM || opt == HCTR_OPT_ADAGRAD ||
                    opt == HCTR_OPT_MOMENTUM_SGD || opt == HCTR_OPT_NESTEROV ||
@@ -1248,11 +1188,6 @@ int hctr_det_update(hctr_det* weights, hctr_det* states, const hctr_det_opt_para
                "optimizer");
   const bool needs_state = opt != HCTR_OPT_SGD;
   HCTR_REQUIRE(!needs_state || states, "this optimizer needs a state table");
-  hipStream_t s = as_stream(stream);
-  hctr_det* h = weights;
-  std::vector<Range> rs;
-  HCTR_TRY(ranges_of(h, num_unique_keys, id_spaces, id_space_offsets, num_id_spaces, &rs));
-  HCTR_TRY(det_scratch(h, num_unique_keys));
   DetOpt o{};
   o.optimizer = opt;
   o.lr = p->lr;
@@ -1283,16 +1218,7 @@ int hctr_det_update(hctr_det* weights, hctr_det* states, const hctr_det_opt_para
     covered += r.n;
   }
   if (tiled && covered == num_unique_keys) {
-    if (num_unique_keys > h->ptr_cap) {
-      if (h->ptr_w) (void)hipFree(h->ptr_w);
-      if (h->ptr_s) (void)hipFree(h->ptr_s);
-      h->ptr_w = h->ptr_s = nullptr;
-      size_t c = h->ptr_cap ? h->ptr_cap : 1024;
-      while (c < num_unique_keys) c *= 2;
-      HCTR_HIP(hipMalloc(&h->ptr_w, c * sizeof(float*)));
-      HCTR_HIP(hipMalloc(&h->ptr_s, c * sizeof(float*)));
-      h->ptr_cap = c;
-    }
+    HCTR_TRY(grow_device_buffers(&h->ptr_w, &h->ptr_s, &h->ptr_cap, num_unique_keys, 1024));
     // (the reference looks the weights up with insertion only for Ftrl)
     HCTR_TRY(hctr_det_lookup_rows(h, unique_keys, num_unique_keys, id_spaces, id_space_offsets,
                                   num_id_spaces, opt == HCTR_OPT_FTRL ? 1 : 0, h->ptr_w, nullptr,
@@ -1302,10 +1228,10 @@ int hctr_det_update(hctr_det* weights, hctr_det* states, const hctr_det_opt_para
                                     id_space_offsets, num_id_spaces, 1, h->ptr_s, nullptr, nullptr,
                                     stream));
     const int dim = h->cls[rs[0].cls].dim;
-    hipLaunchKernelGGL(det_update_ptr_kernel,
+    const RowsByPointer rows = {h->ptr_w, needs_state ? h->ptr_s : nullptr};
+    hipLaunchKernelGGL(det_update_kernel<RowsByPointer>,
                        dim3(grid_for(num_unique_keys * (size_t)dim, kBlock, 8192)), dim3(kBlock), 0,
-                       s, o, num_unique_keys, dim, h->ptr_w, needs_state ? h->ptr_s : nullptr,
-                       ev_start_indices, wgrad);
+                       s, o, num_unique_keys, dim, rows, ev_start_indices, wgrad);
     HCTR_LAUNCH_CHECK();
     return HCTR_OK;
   }
@@ -1317,21 +1243,17 @@ int hctr_det_update(hctr_det* weights, hctr_det* states, const hctr_det_opt_para
     if (needs_state) {
       HCTR_REQUIRE(r.cls < states->cls.size() && states->cls[r.cls].dim == cw.dim * smul,
                    "state table: dimension must be ev_size * num_parameters_per_weight");
-      DetClass& cs = states->cls[r.cls];
-      std::vector<Inserted> ins;
-      HCTR_TRY(class_lookup_insert(states, cs, r.cls, kp, r.n, h->idx2, s, &ins));
-      HCTR_TRY(det_verify_inserts(states, ins, s));
-      rows_s = cs.rows;
+      HCTR_TRY(det_insert_verify(states, {Inserted{r.cls, kp, r.n, h->idx2}}, false, s));
+      rows_s = states->cls[r.cls].rows;
     }
-    if (opt == HCTR_OPT_FTRL) {  // the reference looks the weights up (inserting) for Ftrl
-      std::vector<Inserted> ins;
-      HCTR_TRY(class_lookup_insert(h, cw, r.cls, kp, r.n, h->idx, s, &ins));
-      HCTR_TRY(det_verify_inserts(h, ins, s));
-    } else
+    if (opt == HCTR_OPT_FTRL)  // the reference looks the weights up (inserting) for Ftrl
+      HCTR_TRY(det_insert_verify(h, {Inserted{r.cls, kp, r.n, h->idx}}, false, s));
+    else
       HCTR_TRY(cw.ht.get_mark(kp, r.n, nullptr, h->idx, s));
-    hipLaunchKernelGGL(det_update_kernel, dim3(grid_for(r.n * (size_t)cw.dim, kBlock, 4096)),
-                       dim3(kBlock), 0, s, o, r.n, cw.dim, h->idx, needs_state ? h->idx2 : nullptr,
-                       cw.rows, rows_s, ev_start_indices + r.off, wgrad);
+    const RowsByIndex rows = {h->idx, needs_state ? h->idx2 : nullptr, cw.rows, rows_s};
+    hipLaunchKernelGGL(det_update_kernel<RowsByIndex>,
+                       dim3(grid_for(r.n * (size_t)cw.dim, kBlock, 4096)), dim3(kBlock), 0, s, o,
+                       r.n, cw.dim, rows, ev_start_indices + r.off, wgrad);
     HCTR_LAUNCH_CHECK();
   }
   return HCTR_OK;

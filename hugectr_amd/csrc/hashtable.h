@@ -15,6 +15,84 @@ constexpr uint64_t kPendingBit = 1ull << 63;
 // kPendingBit, so later batches resolve it on the fast path (it reads as kInvalidIndex) instead
 // of re-entering the insert protocol and raising the overflow flag again
 constexpr uint64_t kNoRow = kPendingBit - 1;
+
+// a key as the table stores it: u32 keys are zero-extended
+template <typename K>
+__device__ __forceinline__ long long widen_key(K k) {
+  return (long long)k;
+}
+template <>
+__device__ __forceinline__ long long widen_key<uint32_t>(uint32_t k) {
+  return (long long)(unsigned long long)k;
+}
+
+// What an entry's value means to a reader.  row_of (the index's own get_insert / get_mark): a key
+// that met a full table owns no row and reads as a miss; a pending value passes through, for the
+// insert protocol to resolve.  live_row_of (the dynamic table's find-only passes, which run between
+// batches): everything from kNoRow up reads as a miss -- an erased key keeps its entry with the value
+// kInvalidIndex and owns no row, and a value a failed batch left pending is no row either.
+__device__ __forceinline__ uint64_t row_of(uint64_t v) { return v == kNoRow ? kInvalidIndex : v; }
+__device__ __forceinline__ uint64_t live_row_of(uint64_t v) { return v < kNoRow ? v : kInvalidIndex; }
+
+// ---- the linear-probe walk (the only two copies) --------------------------------------------------
+// From `slot` (the key's home, murmur3 % size, or wherever the caller stands) forward, wrapping at
+// `size`; `cur` = the key of tab[slot] as the caller has already loaded it.  The bound: a walk that
+// has looked at `size` slots has looked at all of them, so it ends there whatever the table holds.
+// In practice it ends at an empty slot long before: a table never fills (size = capacity / 0.75 and
+// at most `capacity` keys get a row; keys beyond that raise the overflow flag).
+constexpr uint64_t kHtAbsent = ~0ull;
+
+// find-only: the slot that holds k64, or kHtAbsent
+__device__ __forceinline__ uint64_t ht_walk_find(const HtEntry* __restrict__ tab, uint64_t size,
+                                                 long long k64, long long empty, uint64_t slot,
+                                                 long long cur) {
+  for (uint64_t probes = 0; probes < size; ++probes) {
+    if (cur == k64) return slot;
+    if (cur == empty) break;
+    slot = (slot + 1 == size) ? 0 : slot + 1;
+    cur = tab[slot].key;
+  }
+  return kHtAbsent;
+}
+__device__ __forceinline__ uint64_t ht_walk_find(const HtEntry* __restrict__ tab, uint64_t size,
+                                                 long long k64, long long empty, uint64_t slot) {
+  return ht_walk_find(tab, size, k64, empty, slot, tab[slot].key);
+}
+
+// claiming: the same walk, and an empty slot on the way is claimed for the key (CAS empty -> k64;
+// losing the CAS to another thread with the SAME key is as good as finding it).  (`found` is a
+// flag of its own, not a reserved slot number: the probe kernel sits at its 64-VGPR limit, and a
+// 64-bit select on the way out cost it two more spilled registers.)
+struct HtClaim {
+  uint64_t slot;
+  bool found;    // false: every slot holds another key
+  bool claimed;  // this thread put the key there
+};
+__device__ __forceinline__ HtClaim ht_walk_claim(HtEntry* __restrict__ tab, uint64_t size,
+                                                 long long k64, long long empty, uint64_t slot,
+                                                 long long cur) {
+  bool ok = false, claimed = false;
+  for (uint64_t probes = 0; probes < size; ++probes) {
+    if (cur == k64) {
+      ok = true;
+      break;
+    }
+    if (cur == empty) {
+      const unsigned long long old =
+          atomicCAS(reinterpret_cast<unsigned long long*>(&tab[slot].key),
+                    (unsigned long long)empty, (unsigned long long)k64);
+      if (old == (unsigned long long)empty || old == (unsigned long long)k64) {
+        ok = true;
+        claimed = old == (unsigned long long)empty;
+        break;
+      }
+    }
+    slot = (slot + 1 == size) ? 0 : slot + 1;
+    cur = tab[slot].key;
+  }
+  return {slot, ok, claimed};
+}
+
 constexpr int kHtTile = 1024;  // positions per compaction tile
 // workgroups of the cooperative finish kernel (co-resident; one per 4096 positions up to this cap).
 // 256: a batch of 1.7 M unseen keys 772 -> 647 us against 128 (512: no further gain), nothing

@@ -47,23 +47,11 @@ namespace {
 
 constexpr int kBlock = 256;
 
-template <typename K>
-__device__ __forceinline__ long long widen(K k) {
-  return (long long)k;
-}
-template <>
-__device__ __forceinline__ long long widen<uint32_t>(uint32_t k) {
-  return (long long)(unsigned long long)k;
-}
-
 __device__ __forceinline__ size_t live_count(const uint64_t* d_n, size_t n) {
   if (d_n == nullptr) return n;
   uint64_t v = *d_n;
   return v < n ? (size_t)v : n;
 }
-
-// a key that met a full table owns no row: it reads as a miss
-__device__ __forceinline__ uint64_t row_of(uint64_t v) { return v == kNoRow ? kInvalidIndex : v; }
 
 __global__ void ht_init_kernel(HtEntry* e, uint64_t size, long long empty) {
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < size;
@@ -96,31 +84,14 @@ __device__ __forceinline__ int ht_probe_insert_one(HtEntry* __restrict__ tab, ui
                                                    bool store_form) {
   // `cur` = the key of the home entry as the caller has just read it: an unseen key whose home slot
   // is empty goes straight to its claim.
-  const long long empty = KeyTraits<K>::empty;
-  const long long k64 = widen<K>(key);
-  bool ok = false, claimed = false;
-  for (uint64_t probes = 0; probes < size; ++probes) {
-    if (cur == k64) {
-      ok = true;
-      break;
-    }
-    if (cur == empty) {
-      unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&tab[slot].key),
-                                         (unsigned long long)empty, (unsigned long long)k64);
-      if (old == (unsigned long long)empty || old == (unsigned long long)k64) {
-        ok = true;
-        claimed = old == (unsigned long long)empty;
-        break;
-      }
-    }
-    slot = (slot + 1 == size) ? 0 : slot + 1;
-    cur = tab[slot].key;
-  }
-  if (!ok) {
+  const HtClaim w = ht_walk_claim(tab, size, widen_key<K>(key), KeyTraits<K>::empty, slot, cur);
+  if (!w.found) {
     atomicOr(d_error, 1u);
     out[i] = kInvalidIndex;
     return 0;
   }
+  slot = w.slot;
+  const bool claimed = w.claimed;
   out[i] = kPendingBit | slot;  // (overwritten below when the key turns out to own a row)
   if (store_form) {
     if (claimed) {
@@ -209,7 +180,7 @@ __global__ void __launch_bounds__(kBlock, 8)
       const size_t i = i0 + (size_t)u * nthreads;
       int pst = 0;
       if (i < nl) {
-        if ((long long)ent[u].x == widen<K>(key[u]) && ent[u].y < kPendingBit)
+        if ((long long)ent[u].x == widen_key<K>(key[u]) && ent[u].y < kPendingBit)
           out[i] = row_of(ent[u].y);
         else  // (issuing the four keys' claims together was measured: no gain with 4 % unseen
               //  keys, and the steady state lost 5 us to the extra registers)
@@ -740,21 +711,13 @@ __global__ void __launch_bounds__(kBlock)
     for (int u = 0; u < kHtUnroll; u++) {
       const size_t i = i0 + (size_t)u * nthreads;
       if (i >= nl) continue;
-      const long long k64 = widen<K>(key[u]);
+      const long long k64 = widen_key<K>(key[u]);
       uint64_t res = kInvalidIndex;
       if ((long long)ent[u].x == k64) {
         res = row_of(ent[u].y);
       } else if ((long long)ent[u].x != empty) {  // collision: walk on
-        uint64_t sl = (slot[u] + 1 == size) ? 0 : slot[u] + 1;
-        for (uint64_t probes = 1; probes <= size; ++probes) {
-          const long long cur = tab[sl].key;
-          if (cur == k64) {
-            res = row_of(tab[sl].val);
-            break;
-          }
-          if (cur == empty) break;
-          sl = (sl + 1 == size) ? 0 : sl + 1;
-        }
+        const uint64_t sl = ht_walk_find(tab, size, k64, empty, slot[u], (long long)ent[u].x);
+        if (sl != kHtAbsent) res = row_of(tab[sl].val);
       }
       out[i] = res;
     }
@@ -769,26 +732,9 @@ __global__ void __launch_bounds__(kBlock)
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
        i += (size_t)gridDim.x * kBlock) {
     const K key = keys[i];
-    const long long k64 = widen<K>(key);
-    uint64_t slot = (uint64_t)murmur3_key(key) % size;
-    bool ok = false;
-    for (uint64_t probes = 0; probes < size; ++probes) {
-      long long cur = tab[slot].key;
-      if (cur == k64) {
-        ok = true;
-        break;
-      }
-      if (cur == empty) {
-        unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&tab[slot].key),
-                                           (unsigned long long)empty, (unsigned long long)k64);
-        if (old == (unsigned long long)empty || old == (unsigned long long)k64) {
-          ok = true;
-          break;
-        }
-      }
-      slot = (slot + 1 == size) ? 0 : slot + 1;
-    }
-    if (ok) tab[slot].val = vals[i];
+    const uint64_t home = (uint64_t)murmur3_key(key) % size;
+    const HtClaim w = ht_walk_claim(tab, size, widen_key<K>(key), empty, home, tab[home].key);
+    if (w.found) tab[w.slot].val = vals[i];
     else atomicOr(d_error, 1u);
   }
 }
@@ -804,18 +750,11 @@ __global__ void __launch_bounds__(kBlock)
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n;
        i += (size_t)gridDim.x * kBlock) {
     const K key = keys[i];
-    const long long k64 = widen<K>(key);
-    uint64_t slot = (uint64_t)murmur3_key(key) % size;
-    for (uint64_t probes = 0; probes < size; ++probes) {
-      const long long cur = tab[slot].key;
-      if (cur == k64) {
-        const unsigned long long v = tab[slot].val;
-        if (v >= kPendingBit && v != kInvalidIndex) tab[slot].val = kInvalidIndex;  // (same value from every duplicate)
-        break;
-      }
-      if (cur == empty) break;
-      slot = (slot + 1 == size) ? 0 : slot + 1;
-    }
+    const uint64_t slot = ht_walk_find(tab, size, widen_key<K>(key), empty,
+                                       (uint64_t)murmur3_key(key) % size);
+    if (slot == kHtAbsent) continue;
+    const unsigned long long v = tab[slot].val;
+    if (v >= kPendingBit && v != kInvalidIndex) tab[slot].val = kInvalidIndex;  // (same value from every duplicate)
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAnd(d_error, ~4u);
 }
@@ -873,6 +812,16 @@ __global__ void hash_keys_kernel(const K* keys, size_t n, uint32_t* out) {
     out[i] = murmur3_key(keys[i]);
 }
 
+// the key that marks an unused slot of a table of this key type
+long long empty_key(int key_type) {
+  long long e = 0;
+  (void)with_key_type(key_type, [&](auto* k) -> int {
+    e = KeyTraits<std::remove_pointer_t<decltype(k)>>::empty;
+    return HCTR_OK;
+  });
+  return e;
+}
+
 }  // namespace
 
 int HashTable::create(size_t cap, int kt) {
@@ -919,8 +868,7 @@ int HashTable::destroy() {
 }
 
 int HashTable::clear(hipStream_t s) {
-  const long long empty =
-      key_type == HCTR_KEY_U32 ? KeyTraits<uint32_t>::empty : KeyTraits<long long>::empty;
+  const long long empty = empty_key(key_type);
   hipLaunchKernelGGL(ht_init_kernel, dim3(grid_for(size, 256, 8192)), dim3(256), 0, s, entries,
                      size, empty);
   HCTR_LAUNCH_CHECK();
@@ -958,28 +906,50 @@ int HashTable::reserve(size_t n) {
   return HCTR_OK;
 }
 
+namespace {
+
+// Workgroups of the finish kernel that the current device holds at once: a CPX partition or a
+// CU-masked device has far fewer than 256 CUs, and a grid that is not resident as a whole could only
+// time out at its barrier.  Asked once per device (a process may drive partitions / CU masks of
+// different sizes); kHtFinishBlocks when the runtime cannot say.
+size_t finish_resident_blocks() {
+  static std::mutex mu;
+  static std::map<int, size_t> per_device;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return (size_t)kHtFinishBlocks;
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = per_device.find(dev);
+  if (it == per_device.end()) {
+    int per_cu = 0, cus = 0;
+    size_t r = (size_t)kHtFinishBlocks;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ht_finish_kernel<0>, kFinBlock, 0) ==
+            hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        per_cu >= 1 && cus >= 1)
+      r = (size_t)per_cu * (size_t)cus;
+    else
+      (void)hipGetLastError();
+    it = per_device.emplace(dev, r).first;
+  }
+  return it->second;
+}
+
+}  // namespace
+
 int HashTable::get_insert(const void* keys, size_t n, const uint64_t* d_n, uint64_t* out,
                           hipStream_t s, const SlotSink* sink_in, const IndexExtras* ex) {
   if (n == 0) return HCTR_OK;
   HCTR_TRY(reserve(n));
-  SlotIdSink sink;
-  sink.slot_id = nullptr;
-  sink.row_offset = nullptr;
-  sink.key_is_u32 = key_type == HCTR_KEY_U32;
-  sink.buckets = 0;
-  sink.buckets_per_sample = 1;
-  sink.rank = 0;
-  sink.world = 1;
-  sink.localized = 0;
-  if (sink_in != nullptr) {
-    sink.slot_id = sink_in->slot_id;
-    sink.row_offset = sink_in->row_offset;
-    sink.buckets = sink_in->buckets;
-    sink.buckets_per_sample = sink_in->buckets_per_sample;
-    sink.rank = sink_in->rank;
-    sink.world = sink_in->world;
-    sink.localized = sink_in->localized;
-  }
+  const int u32 = key_type == HCTR_KEY_U32;
+  const SlotIdSink sink =
+      sink_in == nullptr
+          ? SlotIdSink{nullptr, nullptr, u32, 0, 1, 0, 1, 0}
+          : SlotIdSink{sink_in->slot_id, sink_in->row_offset,         u32,
+                       sink_in->buckets, sink_in->buckets_per_sample, sink_in->rank,
+                       sink_in->world,   sink_in->localized};
   IndexExtras none;
   const IndexExtras& x = ex ? *ex : none;
   // (bit 31 of a list entry is the "min deferred" flag)
@@ -989,74 +959,27 @@ int HashTable::get_insert(const void* keys, size_t n, const uint64_t* d_n, uint6
   // every key a workgroup may leave pending has a place in its segment of the list
   const size_t per_pass = (size_t)grid * kBlock * kHtUnroll;
   const uint32_t seg_cap = (uint32_t)(ceil_div<size_t>(n, per_pass) * kBlock * kHtUnroll);
-  if (key_type == HCTR_KEY_U32) {
-    hipLaunchKernelGGL(ht_probe_insert_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, entries,
-                       size, (const uint32_t*)keys, n, d_n, out, d_pending, pend_list, block_cnt,
-                       seg_cap, d_error, d_defer, d_new_count, (const uint32_t*)x.ro_src, (uint32_t*)x.ro_dst,
-                       x.n_offsets, x.one_hot);
-  } else {
-    hipLaunchKernelGGL(ht_probe_insert_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, entries,
-                       size, (const long long*)keys, n, d_n, out, d_pending, pend_list, block_cnt,
-                       seg_cap, d_error, d_defer, d_new_count, (const long long*)x.ro_src, (long long*)x.ro_dst,
-                       x.n_offsets, x.one_hot);
-  }
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(ht_probe_insert_kernel<K>, dim3(grid), dim3(kBlock), 0, s, entries, size,
+                       (const K*)keys, n, d_n, out, d_pending, pend_list, block_cnt, seg_cap,
+                       d_error, d_defer, d_new_count, (const K*)x.ro_src, (K*)x.ro_dst, x.n_offsets,
+                       x.one_hot);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
-  FinishCtl c;
-  c.pending = d_pending;
-  c.list = pend_list;
-  c.block_cnt = block_cnt;
-  c.probe_blocks = (uint32_t)grid;
-  c.seg_cap = seg_cap;
-  c.latched = d_latched;
-  c.error = d_error;
-  c.barrier = d_barrier;
-  c.defer = d_defer;
-  c.barrier_odd = d_barrier_odd;
-  c.counter = d_counter;
-  c.base = d_base;
-  c.new_count = d_new_count;
-  c.region_cnt = region_cnt;
-  c.masks2 = fin_masks;
-  c.parity = d_parity;
-  c.mask_words = mask_words;
-  c.one_hot_next = x.one_hot_next;
-  c.host_rows = x.host_rows;
-  c.host_seq = x.host_seq;
-  c.seq = x.seq;
-  c.host_error = x.host_error;
-  {  // (read per call: a test narrows it to force the give-up path)
-    const char* e = getenv("HCTR_HT_SPIN_LIMIT");
-    c.spin_limit = e ? (uint32_t)strtoul(e, nullptr, 10) : kSpinLimit;
-  }
+  // (HCTR_HT_SPIN_LIMIT is read per call: a test narrows it to force the give-up path)
+  const char* spin = getenv("HCTR_HT_SPIN_LIMIT");
+  const FinishCtl c = {
+      // (positional: the order of FinishCtl's members)
+      d_pending, d_latched, d_error, d_barrier, d_barrier_odd, d_defer, d_snap,
+      d_counter, d_base, d_new_count,
+      pend_list, block_cnt, (uint32_t)grid, seg_cap,
+      region_cnt, fin_masks, d_parity, mask_words,
+      x.one_hot_next, x.host_rows, x.host_seq, x.seq, x.host_error,
+      spin ? (uint32_t)strtoul(spin, nullptr, 10) : kSpinLimit};
   // few positions: fewer workgroups (every one of them takes part in the barrier), and never more
-  // than the device can hold at once (a CPX partition or a CU-masked device has far fewer than
-  // 256 CUs: a grid that is not resident as a whole could only time out at its barrier)
-  // (per device: a process may drive partitions / CU masks of different sizes)
-  size_t resident = (size_t)kHtFinishBlocks;
-  {
-    static std::mutex mu;
-    static std::map<int, size_t> per_device;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      std::lock_guard<std::mutex> lk(mu);
-      auto it = per_device.find(dev);
-      if (it == per_device.end()) {
-        int per_cu = 0, cus = 0;
-        size_t r = (size_t)kHtFinishBlocks;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ht_finish_kernel<0>, kFinBlock,
-                                                         0) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            per_cu >= 1 && cus >= 1)
-          r = (size_t)per_cu * (size_t)cus;
-        else
-          (void)hipGetLastError();
-        it = per_device.emplace(dev, r).first;
-      }
-      resident = it->second;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
+  // than the device can hold at once
   // (HCTR_HT_FINISH_BLOCKS: the cap, for measurements; at most kHtFinishBlocksMax)
   static const size_t cap = [] {
     const char* e = getenv("HCTR_HT_FINISH_BLOCKS");
@@ -1065,11 +988,11 @@ int HashTable::get_insert(const void* keys, size_t n, const uint64_t* d_n, uint6
     if (v > kHtFinishBlocksMax) v = kHtFinishBlocksMax;
     return (size_t)v;
   }();
+  const size_t resident = finish_resident_blocks();
   size_t fg = ceil_div<size_t>(n, (size_t)kFinBlock * 4);
   if (fg > cap) fg = cap;
   if (fg > resident) fg = resident;
   if (fg < 1) fg = 1;
-  c.snap = d_snap;
   if (x.two_launches) {
     hipLaunchKernelGGL(ht_finish_kernel<3>, dim3((int)fg), dim3(kFinBlock), 0, s, entries, out, n,
                        d_n, c, new_positions, sink, capacity);
@@ -1091,13 +1014,12 @@ int HashTable::get_mark(const void* keys, size_t n, const uint64_t* d_n, uint64_
                         hipStream_t s) {
   if (n == 0) return HCTR_OK;
   const int grid = grid_for(n, kBlock);
-  if (key_type == HCTR_KEY_U32) {
-    hipLaunchKernelGGL(ht_find_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, entries, size,
-                       (const uint32_t*)keys, n, d_n, out);
-  } else {
-    hipLaunchKernelGGL(ht_find_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, entries, size,
-                       (const long long*)keys, n, d_n, out);
-  }
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(ht_find_kernel<K>, dim3(grid), dim3(kBlock), 0, s, entries, size,
+                       (const K*)keys, n, d_n, out);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
@@ -1105,21 +1027,19 @@ int HashTable::get_mark(const void* keys, size_t n, const uint64_t* d_n, uint64_
 int HashTable::insert(const void* keys, const uint64_t* vals, size_t n, hipStream_t s) {
   if (n == 0) return HCTR_OK;
   const int grid = grid_for(n, kBlock);
-  if (key_type == HCTR_KEY_U32) {
-    hipLaunchKernelGGL(ht_insert_pairs_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, entries,
-                       size, (const uint32_t*)keys, vals, n, d_error);
-  } else {
-    hipLaunchKernelGGL(ht_insert_pairs_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, entries,
-                       size, (const long long*)keys, vals, n, d_error);
-  }
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(ht_insert_pairs_kernel<K>, dim3(grid), dim3(kBlock), 0, s, entries, size,
+                       (const K*)keys, vals, n, d_error);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
 
 int HashTable::count(hipStream_t s, size_t* out) {
   HCTR_TRY(reserve(max_n));
-  const long long empty =
-      key_type == HCTR_KEY_U32 ? KeyTraits<uint32_t>::empty : KeyTraits<long long>::empty;
+  const long long empty = empty_key(key_type);
   const size_t n_tiles = ceil_div<size_t>(size, kHtTile);
   const int tgrid = (int)(n_tiles < (size_t)kMaxGrid ? n_tiles : (size_t)kMaxGrid);
   hipLaunchKernelGGL(ht_occupied_count_kernel, dim3(tgrid), dim3(kBlock), 0, s, entries, size,
@@ -1153,8 +1073,7 @@ int HashTable::set_value_head(size_t v, hipStream_t s) {
 int HashTable::dump(int64_t* d_keys, uint64_t* d_vals, size_t* cnt, hipStream_t s) {
   size_t c = 0;
   HCTR_TRY(count(s, &c));  // leaves exclusive tile offsets in tile_sums
-  const long long empty =
-      key_type == HCTR_KEY_U32 ? KeyTraits<uint32_t>::empty : KeyTraits<long long>::empty;
+  const long long empty = empty_key(key_type);
   const size_t n_tiles = ceil_div<size_t>(size, kHtTile);
   const int tgrid = (int)(n_tiles < (size_t)kMaxGrid ? n_tiles : (size_t)kMaxGrid);
   hipLaunchKernelGGL(ht_dump_kernel, dim3(tgrid), dim3(kBlock), 0, s, entries, size, empty,
@@ -1168,12 +1087,12 @@ int HashTable::dump(int64_t* d_keys, uint64_t* d_vals, size_t* cnt, hipStream_t 
 int HashTable::recover(const void* keys, size_t n, hipStream_t s) {
   if (n > 0) {
     const int grid = grid_for(n, kBlock);
-    if (key_type == HCTR_KEY_U32)
-      hipLaunchKernelGGL(ht_unpend_kernel<uint32_t>, dim3(grid), dim3(kBlock), 0, s, entries, size,
-                         (const uint32_t*)keys, n, d_error);
-    else
-      hipLaunchKernelGGL(ht_unpend_kernel<long long>, dim3(grid), dim3(kBlock), 0, s, entries, size,
-                         (const long long*)keys, n, d_error);
+    HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+      using K = std::remove_pointer_t<decltype(k)>;
+      hipLaunchKernelGGL(ht_unpend_kernel<K>, dim3(grid), dim3(kBlock), 0, s, entries, size,
+                         (const K*)keys, n, d_error);
+      return HCTR_OK;
+    }));
     HCTR_LAUNCH_CHECK();
   }
   // the scalars of the insert protocol (not the row counter, not the error word): pending,
@@ -1208,15 +1127,12 @@ int hctr_hash_keys(const void* keys, int key_type, size_t n, uint32_t* out, hctr
   if (n == 0) return HCTR_OK;
   HCTR_REQUIRE(keys && out, "null pointer");
   hipStream_t s = as_stream(stream);
-  if (key_type == HCTR_KEY_U32) {
-    hipLaunchKernelGGL(hash_keys_kernel<uint32_t>, dim3(grid_for(n, 256)), dim3(256), 0, s,
-                       (const uint32_t*)keys, n, out);
-  } else if (key_type == HCTR_KEY_I64) {
-    hipLaunchKernelGGL(hash_keys_kernel<long long>, dim3(grid_for(n, 256)), dim3(256), 0, s,
-                       (const long long*)keys, n, out);
-  } else {
-    HCTR_REQUIRE(false, "key_type");
-  }
+  HCTR_TRY(with_key_type(key_type, [&](auto* k) -> int {
+    using K = std::remove_pointer_t<decltype(k)>;
+    hipLaunchKernelGGL(hash_keys_kernel<K>, dim3(grid_for(n, 256)), dim3(256), 0, s,
+                       (const K*)keys, n, out);
+    return HCTR_OK;
+  }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
