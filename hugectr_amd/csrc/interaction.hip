@@ -1146,3 +1146,11 @@ int hctr_interaction_bwd_indexed_scatter(size_t batch, int n_emb, int width, con
 }
 
 }  // extern "C"
+
+// attention.hip is a unit of its own (Makefile: SRCS).  The host interpreter's build (tests/emu)
+// lists its units by name and knows none called attention: so that its library still exports every
+// entry point of the C ABI, a non-hipcc build that does not announce the unit
+// (HCTR_EMU_ATTENTION_UNIT) takes the file in here, as sparse_update.hip does for su_segmented.hip.
+#if !defined(__HIPCC__) && !defined(HCTR_EMU_ATTENTION_UNIT)
+#include "attention.hip"
+#endif

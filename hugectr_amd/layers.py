@@ -187,6 +187,88 @@ class InteractionLayer(torch.nn.Module):
         return interaction(mlp, emb)
 
 
+class _MultiHeadAttentionFn(torch.autograd.Function):
+    """hctr_mha_fwd / hctr_mha_bwd (attention.hip): one wavefront per (sample, head); the backward
+    recomputes the probabilities from q, k and the mask, which are all that is saved"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, heads):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        B, m, hidden = q.shape
+        n = k.shape[1]
+        if k.shape != (B, n, hidden) or v.shape != k.shape or hidden % heads != 0:
+            raise ValueError(f"multi_head_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                             f"v {tuple(v.shape)}, {heads} heads")
+        if k.dtype != q.dtype or v.dtype != q.dtype:
+            raise ValueError("multi_head_attention: q, k and v of one dtype")
+        if mask is not None:
+            if mask.shape != (B, 1, m, n) or mask.dtype != q.dtype:
+                raise ValueError(f"multi_head_attention: mask {tuple(mask.shape)} {mask.dtype}, "
+                                 f"expected {(B, 1, m, n)} {q.dtype}")
+            mask = mask.contiguous()
+        out = torch.empty_like(q)
+        check(lib.hctr_mha_fwd(B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v), ptr(mask),
+                               ptr(out), _DT[q.dtype], stream_ptr()))
+        ctx.save_for_backward(q, k, v, mask)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, k, v, mask = ctx.saved_tensors
+        grad = grad.contiguous()
+        B, m, hidden = q.shape
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        check(lib.hctr_mha_bwd(B, ctx.heads, m, k.shape[1], hidden // ctx.heads, ptr(q), ptr(k),
+                               ptr(v), ptr(mask), ptr(grad), ptr(dq), ptr(dk), ptr(dv),
+                               _DT[q.dtype], stream_ptr()))
+        return dq, dk, dv, None, None
+
+
+def multi_head_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, heads: int):
+    """q [B, m, H d], k, v [B, n, H d], mask None or [B, 1, m, n] of 0 / 1 in q's dtype ->
+    [B, m, H d]: per head softmax(Q K^T / sqrt(d) - (1 - mask) 10000) V.  m, n <= 128, d a
+    multiple of 8 up to 64; fp32 / fp16 / bf16."""
+    return _MultiHeadAttentionFn.apply(q, k, v, mask, heads)
+
+
+class MultiHeadAttentionLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/multi_head_attention_layer.hpp (3-D inputs) with the masked
+    softmax folded in; no weights"""
+
+    def __init__(self, num_attention_heads: int = 1):
+        super().__init__()
+        self.num_attention_heads = num_attention_heads
+
+    def forward(self, q, k, v, mask=None):
+        return multi_head_attention(q, k, v, mask, self.num_attention_heads)
+
+
+def sequence_mask(len_from: torch.Tensor, len_to: torch.Tensor, max_from: int, max_to: int):
+    """len_from, len_to [B] (fp32 / fp16 / bf16, as the reference reads them from the dense input)
+    -> mask [B, 1, max_from, max_to] of that dtype: 1 where i < len_from[b] and j < len_to[b]"""
+    len_from, len_to = len_from.contiguous(), len_to.contiguous()
+    if len_from.dim() != 1 or len_to.shape != len_from.shape or len_to.dtype != len_from.dtype:
+        raise ValueError("sequence_mask: len_from and len_to are [B] vectors of one dtype")
+    B = len_from.shape[0]
+    mask = torch.empty((B, 1, max_from, max_to), dtype=len_from.dtype, device=len_from.device)
+    check(lib.hctr_sequence_mask(B, max_from, max_to, ptr(len_from), ptr(len_to), ptr(mask),
+                                 _DT[len_from.dtype], stream_ptr()))
+    return mask
+
+
+class SequenceMaskLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/sequence_mask_layer.hpp; no weights"""
+
+    def __init__(self, max_sequence_len_from: int, max_sequence_len_to: int):
+        super().__init__()
+        self.max_sequence_len_from = max_sequence_len_from
+        self.max_sequence_len_to = max_sequence_len_to
+
+    def forward(self, len_from, len_to):
+        return sequence_mask(len_from, len_to, self.max_sequence_len_from, self.max_sequence_len_to)
+
+
 class _CrossV1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, kernels, biases):

@@ -577,6 +577,29 @@ int hctr_emb_forward_interaction(hctr_embedding* e, int is_train, const void* ml
 int hctr_emb_backward_interaction(hctr_embedding* e, const void* mlp, const void* top_grad,
                                   void* mlp_grad, void* emb_grad, hctr_stream_t stream);
 
+/* MultiHeadAttentionLayer<T> + MaskedSoftmaxLayer<T>
+ * (R/HugeCTR/src/layers/multi_head_attention_layer.cu, masked_softmax_layer.cu) as one kernel each
+ * way, one wavefront per (sample, head).  q [B][seq_from][heads * size_per_head], k and v
+ * [B][seq_to][heads * size_per_head], mask NULL or [B][1][seq_from][seq_to] of 0 / 1 in the element
+ * type (shared by the heads) -> out [B][seq_from][heads * size_per_head]; per head
+ *   S = Q K^T / sqrt(size_per_head) - (1 - mask) 10000,  P = exp(S - rowmax) / (rowsum + 1e-6),
+ *   O = P V,  all in fp32 between the steps.
+ * The backward recomputes P from q, k and mask (the forward saves nothing); the mask gets no
+ * gradient.  dtype f32 / f16 / bf16; 1 <= seq_from, seq_to <= 128; size_per_head a multiple of 8,
+ * at most 64; heads >= 1; 16-byte aligned buffers.  Anything else is refused by name: there is no
+ * other kernel. */
+int hctr_mha_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                 const void* q, const void* k, const void* v, const void* mask, void* out,
+                 int dtype, hctr_stream_t stream);
+int hctr_mha_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                 const void* q, const void* k, const void* v, const void* mask,
+                 const void* top_grad, void* dq, void* dk, void* dv, int dtype,
+                 hctr_stream_t stream);
+/* SequenceMaskLayer<T> (R/HugeCTR/src/layers/sequence_mask_layer.cu): len_from, len_to [B] in the
+ * element type -> mask [B][1][max_from][max_to], 1 where i < len_from[b] and j < len_to[b]. */
+int hctr_sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,
+                       const void* len_to, void* mask, int dtype, hctr_stream_t stream);
+
 /* MultiCrossLayer<T> v1 (projection_dim = 0): x_{l+1} = x0 * (x_l . w_l) + b_l + x_l
  * (R/HugeCTR/src/layers/multi_cross_layer.cu:582-601,1023-1060).  kernels/biases [layers][w];
  * outputs [layers][B][w] (outputs[layers-1] is the layer output), hiddens [layers][B]. */

@@ -1,0 +1,86 @@
+"""Times hugectr_amd.multi_head_attention (attention.hip: one kernel each way) next to the same math
+through torch on the device -- the reference layer's recipe: transpose to [B, H, seq, d], bmm,
+scale, softmax with its 1e-6, bmm, transpose back -- forward and forward + backward, at BST's
+shape and at a heavy one.  Device events around batches of calls, medians over rounds, the two
+paths alternating inside a round.  One JSON line per (shape, dtype); `ratio_*` = torch / own.
+
+    python tools/mha_bench.py [--rounds 15] [--calls 20]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hugectr_amd as ha  # noqa: E402
+
+SHAPES = {"bst": (4096, 10, 32, 4), "heavy": (4096, 128, 256, 4)}  # B, seq, hidden, heads
+
+
+def torch_mha(q, k, v, heads):
+    B, m, hidden = q.shape
+    d = hidden // heads
+    qh, kh, vh = (x.view(B, -1, heads, d).transpose(1, 2).contiguous() for x in (q, k, v))
+    s = torch.matmul(qh, kh.transpose(2, 3)) / d ** 0.5
+    e = torch.exp(s - s.amax(-1, keepdim=True))
+    p = e / (e.sum(-1, keepdim=True) + 1e-6)
+    return torch.matmul(p, vh).transpose(1, 2).contiguous().view(B, m, hidden)
+
+
+def time_ms(fn, calls):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--calls", type=int, default=20)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "mha_bench needs the GPU"
+    for name, (B, seq, hidden, heads) in SHAPES.items():
+        for dt in (torch.float16, torch.bfloat16, torch.float32):
+            q, k, v, top = (torch.randn(B, seq, hidden, device="cuda").to(dt) for _ in range(4))
+            for t in (q, k, v):
+                t.requires_grad_(True)
+
+            def fwd(f):
+                with torch.no_grad():
+                    f()
+
+            def both(f):
+                f().backward(top)
+                q.grad = k.grad = v.grad = None
+
+            own = lambda: ha.multi_head_attention(q, k, v, None, heads)  # noqa: E731
+            ref = lambda: torch_mha(q, k, v, heads)  # noqa: E731
+            err = (own().float() - ref().float()).abs().max().item()
+            legs = {"own_fwd": lambda: fwd(own), "torch_fwd": lambda: fwd(ref),
+                    "own_fwd_bwd": lambda: both(own), "torch_fwd_bwd": lambda: both(ref)}
+            for f in legs.values():  # warm-up: code objects, library algorithm choices
+                for _ in range(3):
+                    f()
+            times = {n: [] for n in legs}
+            for _ in range(args.rounds):
+                for n, f in legs.items():
+                    times[n].append(time_ms(f, args.calls))
+            med = {n + "_ms": round(statistics.median(t), 4) for n, t in times.items()}
+            print(json.dumps({
+                "shape": name, "B": B, "seq": seq, "hidden": hidden, "heads": heads,
+                "dtype": str(dt).split(".")[1], **med,
+                "spread_own_fwd_ms": [round(min(times["own_fwd"]), 4), round(max(times["own_fwd"]), 4)],
+                "ratio_fwd": round(med["torch_fwd_ms"] / med["own_fwd_ms"], 3),
+                "ratio_fwd_bwd": round(med["torch_fwd_bwd_ms"] / med["own_fwd_bwd_ms"], 3),
+                "max_abs_diff_vs_torch": err}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
