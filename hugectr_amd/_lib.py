@@ -142,6 +142,10 @@ _SIGNATURES = {
     "hctr_mha_fwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
     "hctr_mha_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
                              c_int, _P]),
+    "hctr_mha_tiled_fwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int,
+                                   _P]),
+    "hctr_mha_tiled_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, c_int, _P]),
     "hctr_sequence_mask": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, c_int, _P]),
     "hctr_cross_v1_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -1,6 +1,13 @@
 // attention.hip -- multi-head attention (forward, backward) and the sequence mask:
 // kernels, host dispatch, hctr_mha_fwd / hctr_mha_bwd / hctr_sequence_mask.
 //
+// Two kernel families.  This file holds the first, for seq_from, seq_to <= 128 and size_per_head
+// <= 64: a whole (sample, head) in one wavefront's LDS, described below.  attention_tiled.hip, taken
+// in at the end, holds the second (hctr_mha_tiled_fwd / hctr_mha_tiled_bwd): blocks of 128 rows over
+// streamed 16-bit tiles, any shape up to 4096 x 4096 x 128.  The entry points do not choose: each
+// runs its own family and refuses what that family has no kernel for; the rule that picks is
+// hugectr_amd/layers.py's (the first family wherever it fits, the second for everything else).
+//
 // MultiHeadAttentionLayer<T> + MaskedSoftmaxLayer<T> + SequenceMaskLayer<T> of the reference
 // (R/HugeCTR/src/layers/multi_head_attention_layer.cu, masked_softmax_layer.cu,
 // sequence_mask_layer.cu: four transposes, two strided-batched GEMMs, a softmax launch, two
@@ -662,6 +669,9 @@ int sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,
   return HCTR_OK;
 }
 
+// the second kernel family: blocks of rows over streamed 16-bit tiles, any shape up to 4096 x 128
+#include "attention_tiled.hip"
+
 }  // namespace
 }  // namespace mha
 }  // namespace hctr
@@ -681,6 +691,21 @@ int hctr_mha_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per
                  hctr_stream_t stream) {
   return hctr::mha::bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, top_grad, dq,
                         dk, dv, dtype, stream);
+}
+
+int hctr_mha_tiled_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                       const void* q, const void* k, const void* v, const void* mask, void* out,
+                       void* stats, int dtype, hctr_stream_t stream) {
+  return hctr::mha::tiled_fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, out,
+                              stats, dtype, stream);
+}
+
+int hctr_mha_tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                       const void* q, const void* k, const void* v, const void* mask,
+                       const void* out, void* stats, const void* top_grad, void* dq, void* dk,
+                       void* dv, int dtype, hctr_stream_t stream) {
+  return hctr::mha::tiled_bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, out,
+                              stats, top_grad, dq, dk, dv, dtype, stream);
 }
 
 int hctr_sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,

@@ -188,8 +188,11 @@ class InteractionLayer(torch.nn.Module):
 
 
 class _MultiHeadAttentionFn(torch.autograd.Function):
-    """hctr_mha_fwd / hctr_mha_bwd (attention.hip): one wavefront per (sample, head); the backward
-    recomputes the probabilities from q, k and the mask, which are all that is saved"""
+    """attention.hip's two kernel families, chosen by shape alone.  m, n <= 128 and d <= 64:
+    hctr_mha_fwd / hctr_mha_bwd, one wavefront per (sample, head); the backward recomputes the
+    probabilities from q, k and the mask, which are all that is saved.  Everything else up to
+    4096 x 4096 x 128: hctr_mha_tiled_fwd / hctr_mha_tiled_bwd, which also keep the output and
+    four fp32 statistics per (head, query row)"""
 
     @staticmethod
     def forward(ctx, q, k, v, mask, heads):
@@ -207,18 +210,33 @@ class _MultiHeadAttentionFn(torch.autograd.Function):
                                  f"expected {(B, 1, m, n)} {q.dtype}")
             mask = mask.contiguous()
         out = torch.empty_like(q)
-        check(lib.hctr_mha_fwd(B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v), ptr(mask),
-                               ptr(out), _DT[q.dtype], stream_ptr()))
-        ctx.save_for_backward(q, k, v, mask)
         ctx.heads = heads
+        ctx.tiled = max(m, n) > 128 or hidden // heads > 64
+        if not ctx.tiled:
+            check(lib.hctr_mha_fwd(B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v),
+                                   ptr(mask), ptr(out), _DT[q.dtype], stream_ptr()))
+            ctx.save_for_backward(q, k, v, mask)
+            return out
+        stats = None
+        if any(ctx.needs_input_grad[:3]):
+            stats = torch.empty((B, heads, m, 4), dtype=torch.float32, device=q.device)
+        check(lib.hctr_mha_tiled_fwd(B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v),
+                                     ptr(mask), ptr(out), ptr(stats), _DT[q.dtype], stream_ptr()))
+        ctx.save_for_backward(q, k, v, mask, out, stats)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        q, k, v, mask = ctx.saved_tensors
+        q, k, v, mask = ctx.saved_tensors[:4]
         grad = grad.contiguous()
         B, m, hidden = q.shape
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        if ctx.tiled:
+            out, stats = ctx.saved_tensors[4:]
+            check(lib.hctr_mha_tiled_bwd(B, ctx.heads, m, k.shape[1], hidden // ctx.heads, ptr(q),
+                                         ptr(k), ptr(v), ptr(mask), ptr(out), ptr(stats), ptr(grad),
+                                         ptr(dq), ptr(dk), ptr(dv), _DT[q.dtype], stream_ptr()))
+            return dq, dk, dv, None, None
         check(lib.hctr_mha_bwd(B, ctx.heads, m, k.shape[1], hidden // ctx.heads, ptr(q), ptr(k),
                                ptr(v), ptr(mask), ptr(grad), ptr(dq), ptr(dk), ptr(dv),
                                _DT[q.dtype], stream_ptr()))
@@ -227,8 +245,10 @@ class _MultiHeadAttentionFn(torch.autograd.Function):
 
 def multi_head_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, heads: int):
     """q [B, m, H d], k, v [B, n, H d], mask None or [B, 1, m, n] of 0 / 1 in q's dtype ->
-    [B, m, H d]: per head softmax(Q K^T / sqrt(d) - (1 - mask) 10000) V.  m, n <= 128, d a
-    multiple of 8 up to 64; fp32 / fp16 / bf16."""
+    [B, m, H d]: per head softmax(Q K^T / sqrt(d) - (1 - mask) 10000) V.  m, n <= 4096, d a
+    multiple of 8 up to 128; fp32 / fp16 / bf16.  m, n <= 128 with d <= 64 run on the kernels that
+    hold a whole head in one wavefront, every other shape on the tiled kernels; the shape alone
+    decides."""
     return _MultiHeadAttentionFn.apply(q, k, v, mask, heads)
 
 

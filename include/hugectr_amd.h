@@ -586,8 +586,8 @@ int hctr_emb_backward_interaction(hctr_embedding* e, const void* mlp, const void
  *   O = P V,  all in fp32 between the steps.
  * The backward recomputes P from q, k and mask (the forward saves nothing); the mask gets no
  * gradient.  dtype f32 / f16 / bf16; 1 <= seq_from, seq_to <= 128; size_per_head a multiple of 8,
- * at most 64; heads >= 1; 16-byte aligned buffers.  Anything else is refused by name: there is no
- * other kernel. */
+ * at most 64; heads >= 1; 16-byte aligned buffers.  Anything else is refused by name: these two
+ * entry points have no other kernel (hctr_mha_tiled_fwd / hctr_mha_tiled_bwd below do). */
 int hctr_mha_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
                  const void* q, const void* k, const void* v, const void* mask, void* out,
                  int dtype, hctr_stream_t stream);
@@ -595,6 +595,21 @@ int hctr_mha_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per
                  const void* q, const void* k, const void* v, const void* mask,
                  const void* top_grad, void* dq, void* dk, void* dv, int dtype,
                  hctr_stream_t stream);
+/* The same layer for every other shape, a second kernel family (attention_tiled.hip): a workgroup
+ * of four wavefronts per (sample, head, block of 128 rows), the other side streamed through LDS in
+ * 16-bit tiles, online softmax.  Same tensors, formulas and dtypes as hctr_mha_fwd / hctr_mha_bwd;
+ * 1 <= seq_from, seq_to <= 4096; size_per_head a multiple of 8, at most 128 (small shapes are served
+ * too).  stats: NULL, or fp32 [B][heads][seq_from][4] that the forward fills with each row's max,
+ * 1 / (sum + 1e-6) and smallest penalty; the backward needs it and the forward's out, and uses the
+ * fourth slot as its own scratch (rowsum(dO o O)).  The backward is two launches without atomics:
+ * two runs give the same bits. */
+int hctr_mha_tiled_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                       const void* q, const void* k, const void* v, const void* mask, void* out,
+                       void* stats, int dtype, hctr_stream_t stream);
+int hctr_mha_tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                       const void* q, const void* k, const void* v, const void* mask,
+                       const void* out, void* stats, const void* top_grad, void* dq, void* dk,
+                       void* dv, int dtype, hctr_stream_t stream);
 /* SequenceMaskLayer<T> (R/HugeCTR/src/layers/sequence_mask_layer.cu): len_from, len_to [B] in the
  * element type -> mask [B][1][max_from][max_to], 1 where i < len_from[b] and j < len_to[b]. */
 int hctr_sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,

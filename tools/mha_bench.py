@@ -1,8 +1,11 @@
-"""Times hugectr_amd.multi_head_attention (attention.hip: one kernel each way) next to the same math
-through torch on the device -- the reference layer's recipe: transpose to [B, H, seq, d], bmm,
-scale, softmax with its 1e-6, bmm, transpose back -- forward and forward + backward, at BST's
-shape and at a heavy one.  Device events around batches of calls, medians over rounds, the two
-paths alternating inside a round.  One JSON line per (shape, dtype); `ratio_*` = torch / own.
+"""Times hugectr_amd.multi_head_attention (attention.hip: two kernel families, chosen by shape) next
+to the same math through torch on the device -- the reference layer's recipe: transpose to
+[B, H, seq, d], bmm, scale, softmax with its 1e-6, bmm, transpose back -- forward and forward +
+backward: at BST's shape and a heavy one (the kernels that hold a head in one wavefront), at a long
+and a wide one (the tiled kernels).  At the heavy shape the tiled entry points are also called
+directly (`tiled_*`), next to the kernels the layer picks there.  Device events around batches of
+calls, medians over rounds, the paths alternating inside a round.  One JSON line per (shape,
+dtype); `ratio_*` = torch / own, `ratio_tiled_*` = torch / tiled.
 
     python tools/mha_bench.py [--rounds 15] [--calls 20]
 """
@@ -16,8 +19,29 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hugectr_amd as ha  # noqa: E402
+from hugectr_amd._lib import check, lib, ptr, stream_ptr  # noqa: E402
+from hugectr_amd.layers import _DT  # noqa: E402
 
-SHAPES = {"bst": (4096, 10, 32, 4), "heavy": (4096, 128, 256, 4)}  # B, seq, hidden, heads
+SHAPES = {"bst": (4096, 10, 32, 4), "heavy": (4096, 128, 256, 4),  # B, seq, hidden, heads
+          "long": (1024, 512, 256, 4), "wide": (4096, 128, 512, 4)}
+
+
+def tiled_direct(q, k, v, top, heads):
+    """hctr_mha_tiled_fwd / _bwd on preallocated buffers -> (forward, forward + backward, out)"""
+    B, m, hidden = q.shape
+    out, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
+    stats = torch.empty((B, heads, m, 4), dtype=torch.float32, device=q.device)
+    shape = (B, heads, m, k.shape[1], hidden // heads)
+    io = (ptr(q), ptr(k), ptr(v), None)
+
+    def fwd():
+        check(lib.hctr_mha_tiled_fwd(*shape, *io, ptr(out), ptr(stats), _DT[q.dtype], stream_ptr()))
+
+    def both():
+        fwd()
+        check(lib.hctr_mha_tiled_bwd(*shape, *io, ptr(out), ptr(stats), ptr(top), ptr(dq), ptr(dk),
+                                     ptr(dv), _DT[q.dtype], stream_ptr()))
+    return fwd, both, out
 
 
 def torch_mha(q, k, v, heads):
@@ -65,6 +89,9 @@ def main():
             err = (own().float() - ref().float()).abs().max().item()
             legs = {"own_fwd": lambda: fwd(own), "torch_fwd": lambda: fwd(ref),
                     "own_fwd_bwd": lambda: both(own), "torch_fwd_bwd": lambda: both(ref)}
+            if name == "heavy":
+                legs["tiled_fwd"], legs["tiled_fwd_bwd"], t_out = tiled_direct(
+                    q.detach(), k.detach(), v.detach(), top, heads)
             for f in legs.values():  # warm-up: code objects, library algorithm choices
                 for _ in range(3):
                     f()
@@ -79,6 +106,10 @@ def main():
                 "spread_own_fwd_ms": [round(min(times["own_fwd"]), 4), round(max(times["own_fwd"]), 4)],
                 "ratio_fwd": round(med["torch_fwd_ms"] / med["own_fwd_ms"], 3),
                 "ratio_fwd_bwd": round(med["torch_fwd_bwd_ms"] / med["own_fwd_bwd_ms"], 3),
+                **({"ratio_tiled_fwd": round(med["torch_fwd_ms"] / med["tiled_fwd_ms"], 3),
+                    "ratio_tiled_fwd_bwd": round(med["torch_fwd_bwd_ms"] / med["tiled_fwd_bwd_ms"], 3),
+                    "max_abs_diff_tiled_vs_torch": (t_out.float() - ref().float()).abs().max().item()}
+                   if name == "heavy" else {}),
                 "max_abs_diff_vs_torch": err}), flush=True)
 
 
