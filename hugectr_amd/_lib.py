@@ -147,6 +147,9 @@ _SIGNATURES = {
     "hctr_mha_tiled_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P, c_int, _P]),
     "hctr_sequence_mask": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, c_int, _P]),
+    "hctr_layer_norm_fwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, c_float, _P, _P, c_int, _P]),
+    "hctr_layer_norm_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "hctr_layer_norm_bwd_scratch_bytes": (c_size_t, [c_size_t, c_int]),
     "hctr_cross_v1_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd_workspace_bytes": (c_size_t, [c_size_t, c_int, c_int]),

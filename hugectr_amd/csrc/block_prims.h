@@ -24,6 +24,15 @@ __device__ __forceinline__ T wave_reduce_sum(T v) {
   return v;
 }
 
+// sum over each aligned group of G consecutive lanes (G a power of two, 1 .. 64), as a butterfly:
+// every lane of a group ends with the same bits, and lanes of other groups are never read
+template <int G, typename T>
+__device__ __forceinline__ T group_reduce_sum(T v) {
+#pragma unroll
+  for (int d = G / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
 // exclusive scan over a workgroup of BLOCK threads (BLOCK multiple of 64, <= 1024).
 // Returns the exclusive prefix of `v` for this thread; *total receives the block sum.
 // smem must hold BLOCK/64 + 1 elements of T.

@@ -1154,3 +1154,9 @@ int hctr_interaction_bwd_indexed_scatter(size_t batch, int n_emb, int width, con
 #if !defined(__HIPCC__) && !defined(HCTR_EMU_ATTENTION_UNIT)
 #include "attention.hip"
 #endif
+
+// layer_norm.hip likewise: a unit of its own under hipcc, taken in here by a build that knows no unit
+// of that name and does not announce one (HCTR_EMU_LAYER_NORM_UNIT).
+#if !defined(__HIPCC__) && !defined(HCTR_EMU_LAYER_NORM_UNIT)
+#include "layer_norm.hip"
+#endif

@@ -289,6 +289,71 @@ class SequenceMaskLayer(torch.nn.Module):
         return sequence_mask(len_from, len_to, self.max_sequence_len_from, self.max_sequence_len_to)
 
 
+class _LayerNormFn(torch.autograd.Function):
+    """layer_norm.hip: hctr_layer_norm_fwd / hctr_layer_norm_bwd.  Saved for the backward: x, residual,
+    gamma and two fp32 statistics per row (mean, 1 / std), which exist only when some input wants a
+    gradient; the normalised rows are recomputed.  x and residual share one gradient tensor"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, residual):
+        hidden = gamma.numel()
+        if x.dim() < 1 or x.shape[-1] != hidden or gamma.shape != (hidden,) or beta.shape != gamma.shape:
+            raise ValueError(f"layer_norm: x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, "
+                             f"beta {tuple(beta.shape)}")
+        if x.dtype not in _DT or gamma.dtype != torch.float32 or beta.dtype != torch.float32:
+            raise ValueError("layer_norm: x of fp32 / fp16 / bf16, gamma and beta of fp32")
+        if residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype):
+            raise ValueError(f"layer_norm: residual {tuple(residual.shape)} {residual.dtype}, "
+                             f"expected {tuple(x.shape)} {x.dtype}")
+        x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
+        residual = None if residual is None else residual.contiguous()
+        rows = x.numel() // max(hidden, 1)
+        y = torch.empty_like(x)
+        stats = None
+        if any(ctx.needs_input_grad):
+            stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        check(lib.hctr_layer_norm_fwd(rows, hidden, ptr(x), ptr(residual), ptr(gamma), ptr(beta), eps,
+                                      ptr(y), ptr(stats), _DT[x.dtype], stream_ptr()))
+        ctx.save_for_backward(x, residual, gamma, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, residual, gamma, stats = ctx.saved_tensors
+        grad = grad.contiguous()
+        hidden = gamma.numel()
+        rows = x.numel() // hidden
+        dz, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
+        scratch = torch.empty(lib.hctr_layer_norm_bwd_scratch_bytes(rows, hidden) // 4,
+                              dtype=torch.float32, device=x.device)
+        check(lib.hctr_layer_norm_bwd(rows, hidden, ptr(x), ptr(residual), ptr(gamma), ptr(stats),
+                                      ptr(grad), ptr(dz), ptr(dgamma), ptr(dbeta), ptr(scratch),
+                                      _DT[x.dtype], stream_ptr()))
+        return dz, dgamma, dbeta, None, None if residual is None else dz
+
+
+def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5,
+               residual=None):
+    """x [..., hidden] (fp32 / fp16 / bf16), gamma and beta [hidden] fp32, residual None or like x ->
+    like x: per row of z = x (+ residual), (z - mean) / sqrt(var + eps) * gamma + beta with the biased
+    variance, in fp32.  hidden 1 .. 8192, any value; x and residual receive the same gradient"""
+    return _LayerNormFn.apply(x, gamma, beta, eps, residual)
+
+
+class LayerNormLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/layer_norm_layer.hpp over the last dimension, with the Add that
+    precedes it in a transformer block as an optional second input; fp32 gamma = 1, beta = 0"""
+
+    def __init__(self, hidden: int, eps: float = 1e-5):
+        super().__init__()
+        self.eps = eps
+        self.gamma = torch.nn.Parameter(torch.ones(hidden, dtype=torch.float32))
+        self.beta = torch.nn.Parameter(torch.zeros(hidden, dtype=torch.float32))
+
+    def forward(self, x, residual=None):
+        return layer_norm(x, self.gamma, self.beta, self.eps, residual)
+
+
 class _CrossV1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, kernels, biases):

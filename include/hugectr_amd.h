@@ -615,6 +615,28 @@ int hctr_mha_tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int si
 int hctr_sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,
                        const void* len_to, void* mask, int dtype, hctr_stream_t stream);
 
+/* LayerNormLayer<T> (R/HugeCTR/src/layers/layer_norm_layer.cu) with the Add in front of it folded
+ * in (layer_norm.hip).  x, residual (or NULL), y, dy, dz [rows][hidden] in the element type (f32 /
+ * f16 / bf16); gamma, beta, dgamma, dbeta [hidden] always fp32; all arithmetic fp32.  Per row, with
+ * z = x (+ residual):  mean = sum(z) / hidden,  var = sum((z - mean)^2) / hidden (biased, two passes
+ * around the mean),  rstd = 1 / sqrt(var + eps),  y = (z - mean) rstd gamma + beta.
+ * stats: NULL (nothing but y is written), or fp32 [rows][2] that receives (mean, rstd) for the
+ * backward.  The backward reads x, residual, dy and stats, writes dz -- the gradient of x and of
+ * residual, one tensor -- and dgamma / dbeta through `scratch`
+ * (hctr_layer_norm_bwd_scratch_bytes(rows, hidden) bytes, 16-byte aligned): one fp32 [2][hidden]
+ * partial per workgroup, added in workgroup order by a second launch.  No atomics: two runs give
+ * the same bits.  1 <= hidden <= 8192 (any value; 16-byte accesses when hidden is a multiple of
+ * 16 bytes' worth of elements and the buffers are 16-byte aligned), rows * hidden < 2^31, eps > 0;
+ * anything else is refused by name.  rows = 0 is served (dgamma and dbeta, when given, become zeros). */
+int hctr_layer_norm_fwd(size_t rows, int hidden, const void* x, const void* residual,
+                        const float* gamma, const float* beta, float eps, void* y, float* stats,
+                        int dtype, hctr_stream_t stream);
+int hctr_layer_norm_bwd(size_t rows, int hidden, const void* x, const void* residual,
+                        const float* gamma, const float* stats, const void* dy, void* dz,
+                        float* dgamma, float* dbeta, void* scratch, int dtype,
+                        hctr_stream_t stream);
+size_t hctr_layer_norm_bwd_scratch_bytes(size_t rows, int hidden);
+
 /* MultiCrossLayer<T> v1 (projection_dim = 0): x_{l+1} = x0 * (x_l . w_l) + b_l + x_l
  * (R/HugeCTR/src/layers/multi_cross_layer.cu:582-601,1023-1060).  kernels/biases [layers][w];
  * outputs [layers][B][w] (outputs[layers-1] is the layer output), hiddens [layers][B]. */
