@@ -150,6 +150,12 @@ _SIGNATURES = {
     "hctr_layer_norm_fwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, c_float, _P, _P, c_int, _P]),
     "hctr_layer_norm_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "hctr_layer_norm_bwd_scratch_bytes": (c_size_t, [c_size_t, c_int]),
+    "hctr_col_stats_scratch_bytes": (c_size_t, [c_size_t, c_int]),
+    "hctr_batch_norm_fwd": (c_int, [c_size_t, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P, _P, _P,
+                                    c_int, c_int, _P]),
+    "hctr_batch_norm_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "hctr_prelu_dice_fwd": (c_int, [c_size_t, c_int, _P, c_float, c_float, _P, _P, _P, c_int, _P]),
+    "hctr_prelu_dice_bwd": (c_int, [c_size_t, c_int, _P, _P, c_float, c_float, _P, _P, c_int, _P]),
     "hctr_cross_v1_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd_workspace_bytes": (c_size_t, [c_size_t, c_int, c_int]),

@@ -1160,3 +1160,8 @@ int hctr_interaction_bwd_indexed_scatter(size_t batch, int n_emb, int width, con
 #if !defined(__HIPCC__) && !defined(HCTR_EMU_LAYER_NORM_UNIT)
 #include "layer_norm.hip"
 #endif
+
+// batch_norm.hip likewise (HCTR_EMU_BATCH_NORM_UNIT).
+#if !defined(__HIPCC__) && !defined(HCTR_EMU_BATCH_NORM_UNIT)
+#include "batch_norm.hip"
+#endif

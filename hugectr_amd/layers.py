@@ -354,6 +354,140 @@ class LayerNormLayer(torch.nn.Module):
         return layer_norm(x, self.gamma, self.beta, self.eps, residual)
 
 
+def _columns(op, x):
+    """(rows, n) of the reference's rule: rows = shape[0], every other dimension is a column"""
+    if x.dim() < 1 or x.dtype not in _DT:
+        raise ValueError(f"{op}: x of fp32 / fp16 / bf16 with at least one dimension, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    n = 1
+    for d in x.shape[1:]:
+        n *= d
+    return x.shape[0], n
+
+
+def _col_scratch(rows, n, device):
+    return torch.empty(lib.hctr_col_stats_scratch_bytes(rows, n) // 4, dtype=torch.float32,
+                       device=device)
+
+
+class _BatchNormFn(torch.autograd.Function):
+    """batch_norm.hip: hctr_batch_norm_fwd / hctr_batch_norm_bwd.  Saved for the backward: x, gamma and
+    the fp32 [2][n] (mean, 1 / std) of the batch, which exist only when some input wants a gradient;
+    the normalised values are recomputed.  The running statistics are updated in place"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, factor, eps):
+        rows, n = _columns("batch_norm", x)
+        per_col = (gamma, beta, running_mean, running_var)
+        if any(t.shape != (n,) or t.dtype != torch.float32 for t in per_col):
+            raise ValueError(f"batch_norm: gamma, beta, running_mean, running_var of fp32 [{n}] for x "
+                             f"{tuple(x.shape)}, got {[tuple(t.shape) for t in per_col]}")
+        if any(not t.is_contiguous() for t in (running_mean, running_var)):
+            raise ValueError("batch_norm: running_mean and running_var contiguous (updated in place)")
+        x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
+        y = torch.empty_like(x)
+        save = None
+        if training and any(ctx.needs_input_grad):
+            save = torch.empty((2, n), dtype=torch.float32, device=x.device)
+        scratch = _col_scratch(rows, n, x.device) if training else None
+        check(lib.hctr_batch_norm_fwd(rows, n, ptr(x), ptr(gamma), ptr(beta), factor, eps,
+                                      ptr(running_mean), ptr(running_var), ptr(y), ptr(save),
+                                      ptr(scratch), int(training), _DT[x.dtype], stream_ptr()))
+        ctx.save_for_backward(x, gamma, save)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, gamma, save = ctx.saved_tensors
+        if save is None:
+            raise ValueError("batch_norm: the backward needs the batch statistics of a training forward")
+        grad = grad.contiguous()
+        rows, n = x.shape[0], gamma.numel()
+        dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
+        scratch = _col_scratch(rows, n, x.device)
+        check(lib.hctr_batch_norm_bwd(rows, n, ptr(x), ptr(gamma), ptr(save), ptr(grad), ptr(dx),
+                                      ptr(dgamma), ptr(dbeta), ptr(scratch), _DT[x.dtype],
+                                      stream_ptr()))
+        return dx, dgamma, dbeta, None, None, None, None, None
+
+
+def batch_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+               running_var: torch.Tensor, training: bool, factor: float = 1.0, eps: float = 1e-5):
+    """x [rows, ...] (fp32 / fp16 / bf16), everything after the first dimension a column (n of them,
+    1 .. 65536); gamma, beta, running_mean, running_var [n] fp32 -> like x.  training: the batch's
+    mean and biased variance per column, (x - mean) / sqrt(var + eps) * gamma + beta, and
+    running = (1 - factor) running + factor (mean, unbiased var) in place; else the running
+    statistics in the same formula, one launch"""
+    return _BatchNormFn.apply(x, gamma, beta, running_mean, running_var, training, factor, eps)
+
+
+class BatchNormLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/batch_norm_layer.hpp; fp32 gamma = 1, beta = 0, buffers
+    running_mean = 0, running_var = 1; self.training picks the path.  With the reference's default
+    factor = 1 the running statistics are those of the last training batch, so the buffers' initial
+    values no longer matter after one step"""
+
+    def __init__(self, num_features: int, factor: float = 1.0, eps: float = 1e-5):
+        super().__init__()
+        self.factor, self.eps = factor, eps
+        self.gamma = torch.nn.Parameter(torch.ones(num_features, dtype=torch.float32))
+        self.beta = torch.nn.Parameter(torch.zeros(num_features, dtype=torch.float32))
+        self.register_buffer("running_mean", torch.zeros(num_features, dtype=torch.float32))
+        self.register_buffer("running_var", torch.ones(num_features, dtype=torch.float32))
+
+    def forward(self, x):
+        return batch_norm(x, self.gamma, self.beta, self.running_mean, self.running_var,
+                          self.training, self.factor, self.eps)
+
+
+class _PReLUDiceFn(torch.autograd.Function):
+    """batch_norm.hip: hctr_prelu_dice_fwd / hctr_prelu_dice_bwd.  Saved for the backward: x and the
+    fp32 [2][n] (mean, var) of the batch, which exist only when x wants a gradient"""
+
+    @staticmethod
+    def forward(ctx, x, alpha, eps):
+        rows, n = _columns("prelu_dice", x)
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        stats = None
+        if ctx.needs_input_grad[0]:
+            stats = torch.empty((2, n), dtype=torch.float32, device=x.device)
+        scratch = _col_scratch(rows, n, x.device)
+        check(lib.hctr_prelu_dice_fwd(rows, n, ptr(x), alpha, eps, ptr(y), ptr(stats), ptr(scratch),
+                                      _DT[x.dtype], stream_ptr()))
+        ctx.save_for_backward(x, stats)
+        ctx.alpha, ctx.eps = alpha, eps
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, stats = ctx.saved_tensors
+        grad = grad.contiguous()
+        dx = torch.empty_like(x)
+        check(lib.hctr_prelu_dice_bwd(x.shape[0], stats.shape[1], ptr(x), ptr(stats), ctx.alpha,
+                                      ctx.eps, ptr(grad), ptr(dx), _DT[x.dtype], stream_ptr()))
+        return dx, None, None
+
+
+def prelu_dice(x: torch.Tensor, alpha: float, eps: float):
+    """x [rows, ...] (fp32 / fp16 / bf16) -> like x: p x + (1 - p) alpha x with
+    p = sigmoid((x - mean) / sqrt(var + eps)) of the batch's mean and biased variance per column, in
+    training and evaluation alike.  The gradient is the reference's: every element sees only its own
+    1 / rows share of mean and variance"""
+    return _PReLUDiceFn.apply(x, alpha, eps)
+
+
+class PReLUDiceLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/prelu_dice_layer.hpp; no weights"""
+
+    def __init__(self, alpha: float, eps: float):
+        super().__init__()
+        self.alpha, self.eps = alpha, eps
+
+    def forward(self, x):
+        return prelu_dice(x, self.alpha, self.eps)
+
+
 class _CrossV1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, kernels, biases):

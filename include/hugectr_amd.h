@@ -637,6 +637,45 @@ int hctr_layer_norm_bwd(size_t rows, int hidden, const void* x, const void* resi
                         hctr_stream_t stream);
 size_t hctr_layer_norm_bwd_scratch_bytes(size_t rows, int hidden);
 
+/* BatchNormLayer<T> (R/HugeCTR/src/layers/batch_norm_layer.cu, cuDNN's per-activation mode) and
+ * PRelu_Dice_Layer<T> (R/HugeCTR/src/layers/prelu_dice_layer.cu): statistics of every COLUMN of a
+ * row-major [rows][n] tensor over its rows (batch_norm.hip).  x, y, dy, dx [rows][n] in the element
+ * type (f32 / f16 / bf16); gamma, beta, dgamma, dbeta, running_mean, running_var [n] and save, stats
+ * [2][n] always fp32; all arithmetic fp32.  With m = rows:  mean = sum_r x / m,
+ * var = sum_r (x - mean)^2 / m (biased, around the mean: per row slab (count, mean, M2), slabs merged
+ * in ascending order by the pairwise update).
+ * BatchNorm, training != 0:  rstd = 1 / sqrt(var + eps),  y = (x - mean) rstd gamma + beta;
+ * running_mean = (1 - factor) running_mean + factor mean, running_var likewise with the unbiased
+ * var m / max(m - 1, 1) (both NULL: not kept); save: NULL or [2][n] that receives (mean, rstd).
+ * training == 0:  y = (x - running_mean) / sqrt(running_var + eps) gamma + beta in one launch,
+ * nothing but y is written, scratch may be NULL.  Backward (xh = (x - mean) rstd from x and save):
+ * dbeta = sum_r dy, dgamma = sum_r dy xh, dx = gamma rstd (dy - dbeta / m - xh dgamma / m).
+ * PReLU_Dice, the same in training and evaluation:  p = 1 / (1 + exp((mean - x) / sqrt(var + eps))),
+ * y = p x + (1 - p) alpha x;  stats: NULL or [2][n] that receives (mean, var).  Its backward is the
+ * reference's, the diagonal of the Jacobian (not the full batch gradient), one launch:
+ * r1 = r3 = 0 when var + eps < 1e-8 else r1 = 1 / sqrt(var + eps), r3 = r1^3;  ys = (mean - x) r1,
+ * ys_x = (1 / m - 1) r1 + (mean - x)^2 r3 / m,  p_x = -p (1 - p) ys_x,
+ * dx = ((p_x x + p)(1 - alpha) + alpha) dy.
+ * scratch: hctr_col_stats_scratch_bytes(rows, n) bytes (enough for every element type), one fp32
+ * pair per column and row slab; the slab count depends on (rows, n, dtype) only and nothing is
+ * atomic: two runs give the same bits.  1 <= n <= 65536 (any value; 16-byte accesses when n is a
+ * multiple of 16 bytes' worth of elements and the buffers are 16-byte aligned), rows * n < 2^31,
+ * eps > 0 (Dice: eps >= 0), 0 <= factor <= 1; anything else is refused by name.  rows = 0 is served:
+ * no output is touched, except that dgamma and dbeta, when given, become zeros. */
+size_t hctr_col_stats_scratch_bytes(size_t rows, int n);
+int hctr_batch_norm_fwd(size_t rows, int n, const void* x, const float* gamma, const float* beta,
+                        float factor, float eps, float* running_mean, float* running_var,
+                        void* y, float* save /* [2][n] or NULL */, void* scratch,
+                        int training, int dtype, hctr_stream_t stream);
+int hctr_batch_norm_bwd(size_t rows, int n, const void* x, const float* gamma, const float* save,
+                        const void* dy, void* dx, float* dgamma, float* dbeta, void* scratch,
+                        int dtype, hctr_stream_t stream);
+int hctr_prelu_dice_fwd(size_t rows, int n, const void* x, float alpha, float eps, void* y,
+                        float* stats /* [2][n] mean, var */, void* scratch, int dtype,
+                        hctr_stream_t stream);
+int hctr_prelu_dice_bwd(size_t rows, int n, const void* x, const float* stats, float alpha,
+                        float eps, const void* dy, void* dx, int dtype, hctr_stream_t stream);
+
 /* MultiCrossLayer<T> v1 (projection_dim = 0): x_{l+1} = x0 * (x_l . w_l) + b_l + x_l
  * (R/HugeCTR/src/layers/multi_cross_layer.cu:582-601,1023-1060).  kernels/biases [layers][w];
  * outputs [layers][B][w] (outputs[layers-1] is the layer output), hiddens [layers][B]. */
