@@ -156,6 +156,12 @@ _SIGNATURES = {
     "hctr_batch_norm_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "hctr_prelu_dice_fwd": (c_int, [c_size_t, c_int, _P, c_float, c_float, _P, _P, _P, c_int, _P]),
     "hctr_prelu_dice_bwd": (c_int, [c_size_t, c_int, _P, _P, c_float, c_float, _P, _P, c_int, _P]),
+    "hctr_matmul_fwd": (c_int, [c_size_t, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
+    "hctr_matmul_bwd": (c_int, [c_size_t, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+    "hctr_reduce_mean_fwd": (c_int, [c_size_t, c_size_t, c_size_t, _P, _P, c_int, _P]),
+    "hctr_reduce_mean_bwd": (c_int, [c_size_t, c_size_t, c_size_t, _P, _P, c_int, _P]),
+    "hctr_fused_reshape_concat_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
+    "hctr_fused_reshape_concat_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
     "hctr_cross_v1_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd_workspace_bytes": (c_size_t, [c_size_t, c_int, c_int]),

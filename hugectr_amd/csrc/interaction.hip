@@ -1165,3 +1165,8 @@ int hctr_interaction_bwd_indexed_scatter(size_t batch, int n_emb, int width, con
 #if !defined(__HIPCC__) && !defined(HCTR_EMU_BATCH_NORM_UNIT)
 #include "batch_norm.hip"
 #endif
+
+// sequence_ops.hip likewise (HCTR_EMU_SEQUENCE_OPS_UNIT).
+#if !defined(__HIPCC__) && !defined(HCTR_EMU_SEQUENCE_OPS_UNIT)
+#include "sequence_ops.hip"
+#endif

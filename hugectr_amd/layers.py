@@ -5,6 +5,7 @@ MultiCrossLayer:  R/HugeCTR/include/layers/multi_cross_layer.hpp:104-177
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -486,6 +487,168 @@ class PReLUDiceLayer(torch.nn.Module):
 
     def forward(self, x):
         return prelu_dice(x, self.alpha, self.eps)
+
+
+def _matmul_shape(a, b):
+    """(batch, m, n, k, output shape) of the reference's four input forms"""
+    da, db = a.dim(), b.dim()
+    if a.dtype not in _DT or b.dtype != a.dtype:
+        raise ValueError(f"matrix_multiply: a and b of one dtype, fp32 / fp16 / bf16, got {a.dtype}, "
+                         f"{b.dtype}")
+    if (da, db) == (2, 3):  # [m, n] x [n, g, h] -> [m, g, h]
+        ok, batch, k, out = a.shape[1] == b.shape[0], 1, b.shape[1] * b.shape[2], (a.shape[0], *b.shape[1:])
+    else:
+        ok = da == db and da in (2, 3, 4) and a.shape[:-2] == b.shape[:-2] and a.shape[-1] == b.shape[-2]
+        batch = 1
+        for d in a.shape[:-2]:
+            batch *= d
+        k, out = b.shape[-1], (*a.shape[:-1], b.shape[-1])
+    if not ok:
+        raise ValueError(f"matrix_multiply: [m, n] x [n, k] with zero, one or two equal leading "
+                         f"dimensions, or [m, n] x [n, g, h]; got {tuple(a.shape)} x {tuple(b.shape)}")
+    return batch, a.shape[-2], a.shape[-1], k, out
+
+
+class _MatrixMultiplyFn(torch.autograd.Function):
+    """sequence_ops.hip: hctr_matmul_fwd / hctr_matmul_bwd.  Saved for the backward: a and b
+    themselves (no copy); an input that wants no gradient gets none computed"""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        batch, m, n, k, out = _matmul_shape(a, b)
+        a, b = a.contiguous(), b.contiguous()
+        c = torch.empty(out, dtype=a.dtype, device=a.device)
+        check(lib.hctr_matmul_fwd(batch, m, n, k, ptr(a), ptr(b), ptr(c), _DT[a.dtype], stream_ptr()))
+        ctx.save_for_backward(a, b)
+        ctx.dims = (batch, m, n, k)
+        return c
+
+    @staticmethod
+    def backward(ctx, grad):
+        a, b = ctx.saved_tensors
+        grad = grad.contiguous()
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        check(lib.hctr_matmul_bwd(*ctx.dims, ptr(a), ptr(b), ptr(grad), ptr(da), ptr(db),
+                                  _DT[a.dtype], stream_ptr()))
+        return da, db
+
+
+def matrix_multiply(a: torch.Tensor, b: torch.Tensor):
+    """a [..., m, n] x b [..., n, k] -> [..., m, k] per item, for 2-D x 2-D, 3-D x 3-D, 4-D x 4-D
+    (equal leading sizes) and [m, n] x [n, g, h] -> [m, g, h]; fp32 / fp16 / bf16, m, n, k 1 .. 4096,
+    fp32 sums rounded once.  Small items (m n + n k + m k <= 1024) run packed, the rest on MFMA tiles"""
+    return _MatrixMultiplyFn.apply(a, b)
+
+
+class MatrixMultiplyLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/matrix_multiply_layer.hpp; no weights"""
+
+    def forward(self, a, b):
+        return matrix_multiply(a, b)
+
+
+class _ReduceMeanFn(torch.autograd.Function):
+    """sequence_ops.hip: hctr_reduce_mean_fwd / hctr_reduce_mean_bwd.  Nothing is saved"""
+
+    @staticmethod
+    def forward(ctx, x, axis):
+        if x.dtype not in _DT or not 1 <= x.dim() <= 3:
+            raise ValueError(f"reduce_mean: x of fp32 / fp16 / bf16 with 1 to 3 dimensions, got "
+                             f"{tuple(x.shape)} {x.dtype}")
+        if not 0 <= axis < x.dim():
+            raise ValueError(f"reduce_mean: axis 0 .. {x.dim() - 1} for x {tuple(x.shape)}, got {axis}")
+        x = x.contiguous()
+        outer, inner = 1, 1
+        for d in x.shape[:axis]:
+            outer *= d
+        for d in x.shape[axis + 1:]:
+            inner *= d
+        ctx.dims, ctx.shape = (outer, x.shape[axis], inner), x.shape
+        y = torch.empty((*x.shape[:axis], 1, *x.shape[axis + 1:]), dtype=x.dtype, device=x.device)
+        check(lib.hctr_reduce_mean_fwd(*ctx.dims, ptr(x), ptr(y), _DT[x.dtype], stream_ptr()))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        grad = grad.contiguous()
+        dx = torch.empty(ctx.shape, dtype=grad.dtype, device=grad.device)
+        check(lib.hctr_reduce_mean_bwd(*ctx.dims, ptr(grad), ptr(dx), _DT[grad.dtype], stream_ptr()))
+        return dx, None
+
+
+def reduce_mean(x: torch.Tensor, axis: int):
+    """x of 1 to 3 dimensions (fp32 / fp16 / bf16) -> its mean over `axis`, which stays with size 1;
+    fp32 sums in a fixed order, rounded once"""
+    return _ReduceMeanFn.apply(x, axis)
+
+
+class ReduceMeanLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/reduce_mean_layer.hpp; no weights"""
+
+    def __init__(self, axis: int):
+        super().__init__()
+        self.axis = axis
+
+    def forward(self, x):
+        return reduce_mean(x, self.axis)
+
+
+def _frc_call(entry, tensors, widths, batch, slots, item, ad, dtype):
+    """the host-side arrays of device pointers and widths the entry points take by value"""
+    num = len(tensors)
+    ptrs = (ctypes.c_void_p * num)(*[t.data_ptr() for t in tensors])
+    check(entry(batch, slots, num, ptrs, (ctypes.c_int * num)(*widths), ptr(item), ptr(ad),
+                _DT[dtype], stream_ptr()))
+
+
+class _FusedReshapeConcatFn(torch.autograd.Function):
+    """sequence_ops.hip: hctr_fused_reshape_concat_fwd / _bwd.  Nothing is saved but the shapes"""
+
+    @staticmethod
+    def forward(ctx, *inputs):
+        if not 1 <= len(inputs) <= 8:
+            raise ValueError(f"fused_reshape_concat: 1 .. 8 inputs, got {len(inputs)}")
+        first = inputs[0]
+        for t in inputs:
+            if t.dim() != 3 or t.dtype not in _DT or t.dtype != first.dtype or t.shape[:2] != first.shape[:2]:
+                raise ValueError("fused_reshape_concat: inputs [B, S, w_i] of one dtype (fp32 / fp16 / "
+                                 f"bf16) with equal B and S, got {[tuple(t.shape) for t in inputs]}")
+        if first.shape[1] < 1 or any(t.shape[2] < 1 for t in inputs):
+            raise ValueError(f"fused_reshape_concat: S >= 1 and every width >= 1, got "
+                             f"{[tuple(t.shape) for t in inputs]}")
+        inputs = [t.contiguous() for t in inputs]
+        batch, slots = first.shape[:2]
+        ctx.widths = [t.shape[2] for t in inputs]
+        ctx.dims = (batch, slots)
+        W = sum(ctx.widths)
+        item = torch.empty((batch * (slots - 1), W), dtype=first.dtype, device=first.device)
+        ad = torch.empty((batch, W), dtype=first.dtype, device=first.device)
+        _frc_call(lib.hctr_fused_reshape_concat_fwd, inputs, ctx.widths, batch, slots, item, ad,
+                  first.dtype)
+        return item, ad
+
+    @staticmethod
+    def backward(ctx, ditem, dad):
+        ditem, dad = ditem.contiguous(), dad.contiguous()
+        batch, slots = ctx.dims
+        grads = [torch.empty((batch, slots, w), dtype=dad.dtype, device=dad.device) for w in ctx.widths]
+        _frc_call(lib.hctr_fused_reshape_concat_bwd, grads, ctx.widths, batch, slots, ditem, dad,
+                  dad.dtype)
+        return tuple(grads)
+
+
+def fused_reshape_concat(inputs):
+    """inputs: 1 .. 8 tensors [B, S, w_i] of one dtype -> (item [B (S - 1), W], ad [B, W]) with
+    W = sum w_i: the inputs side by side, slots 0 .. S - 2 of every sample in item, the last in ad"""
+    return _FusedReshapeConcatFn.apply(*inputs)
+
+
+class FusedReshapeConcatLayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/fused_reshape_concat_layer.hpp; no weights"""
+
+    def forward(self, inputs):
+        return fused_reshape_concat(inputs)
 
 
 class _CrossV1Fn(torch.autograd.Function):

@@ -676,6 +676,44 @@ int hctr_prelu_dice_fwd(size_t rows, int n, const void* x, float alpha, float ep
 int hctr_prelu_dice_bwd(size_t rows, int n, const void* x, const float* stats, float alpha,
                         float eps, const void* dy, void* dx, int dtype, hctr_stream_t stream);
 
+/* MatrixMultiplyLayer<T> (R/HugeCTR/src/layers/matrix_multiply_layer.cu:103-107, its letters): for
+ * each of `batch` items, A [m][n] . B [n][k] -> C [m][k], n the inner dimension; the backward reads
+ * A, B and dC and writes dA = dC . B^T and dB = A^T . dC, either of which may be NULL (that product is
+ * skipped; the operand only it reads may then be NULL too).  Elements f32 / f16 / bf16, row-major
+ * and dense; products summed in fp32 (fp32 inputs multiplied as fp32, CUBLAS_COMPUTE_32F on
+ * CUDA_R_32F) and rounded once on the store.  Two kernel bodies in sequence_ops.hip, picked by
+ * (m, n, k) alone: m n + n k + m k <= 1024 runs the packed VALU body (slabs of consecutive items
+ * through LDS), everything else 64 x 64 MFMA tiles; no transposed copy is written.  No atomics: two
+ * runs give the same bits.  1 <= m, n, k <= 4096, batch * (m n, n k, m k) < 2^31; anything else is
+ * refused by name.  batch = 0 is served. */
+int hctr_matmul_fwd(size_t batch, int m, int n, int k, const void* a, const void* b, void* c,
+                    int dtype, hctr_stream_t stream);
+int hctr_matmul_bwd(size_t batch, int m, int n, int k, const void* a, const void* b, const void* dc,
+                    void* da /* or NULL */, void* db /* or NULL */, int dtype, hctr_stream_t stream);
+
+/* ReduceMeanLayer<T> (R/HugeCTR/src/layers/reduce_mean_layer.cu:141-148): x [outer][len][inner] ->
+ * y [outer][1][inner], fp32 sums in a fixed order divided by len and rounded once; the backward
+ * writes dy / len into every one of the len rows of dx.  len >= 1, outer * len * inner < 2^31;
+ * outer = 0 or inner = 0 is served. */
+int hctr_reduce_mean_fwd(size_t outer, size_t len, size_t inner, const void* x, void* y, int dtype,
+                         hctr_stream_t stream);
+int hctr_reduce_mean_bwd(size_t outer, size_t len, size_t inner, const void* dy, void* dx, int dtype,
+                         hctr_stream_t stream);
+
+/* FusedReshapeConcatLayer<T> (R/HugeCTR/src/layers/fused_reshape_concat_layer.cu:29-62): `num`
+ * inputs [batch][slots][widths[i]] side by side into rows of W = sum widths: slots 0 .. slots - 2 of
+ * every sample, in order, -> item [batch (slots - 1)][W]; the last slot -> ad [batch][W].  `inputs`
+ * and `widths` are HOST arrays of `num` device pointers and widths; they travel to the kernel by
+ * value, no device-side table exists.  The backward copies ditem / dad back into dinputs, every
+ * element written once.  A pure copy: bit-exact.  1 <= num <= 8, slots >= 1 (slots = 1: item is
+ * empty and may be NULL), widths >= 1, rows = batch * slots with rows * W < 2^31; batch = 0 is served. */
+int hctr_fused_reshape_concat_fwd(size_t batch, int slots, int num, const void* const* inputs,
+                                  const int* widths, void* item, void* ad, int dtype,
+                                  hctr_stream_t stream);
+int hctr_fused_reshape_concat_bwd(size_t batch, int slots, int num, void* const* dinputs,
+                                  const int* widths, const void* ditem, const void* dad, int dtype,
+                                  hctr_stream_t stream);
+
 /* MultiCrossLayer<T> v1 (projection_dim = 0): x_{l+1} = x0 * (x_l . w_l) + b_l + x_l
  * (R/HugeCTR/src/layers/multi_cross_layer.cu:582-601,1023-1060).  kernels/biases [layers][w];
  * outputs [layers][B][w] (outputs[layers-1] is the layer output), hiddens [layers][B]. */
