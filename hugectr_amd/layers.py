@@ -245,8 +245,11 @@ class _MultiHeadAttentionFn(torch.autograd.Function):
 
 
 def multi_head_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, heads: int):
-    """q [B, m, H d], k, v [B, n, H d], mask None or [B, 1, m, n] of 0 / 1 in q's dtype ->
-    [B, m, H d]: per head softmax(Q K^T / sqrt(d) - (1 - mask) 10000) V.  m, n <= 4096, d a
+    """q [B, m, H d], k, v [B, n, H d], mask None or [B, 1, m, n] in q's dtype ->
+    [B, m, H d]: per head softmax(Q K^T / sqrt(d) - (1 - mask) 10000) V, the softmax's sum taken
+    with + 1e-6.  The mask is read as a value, not as a flag: 1 keeps a key, 0 puts it 10000 below,
+    anything between puts it (1 - mask) 10000 below; what a whole row has in common cancels, so a
+    fully masked row attends as if it had no mask.  m, n <= 4096, d a
     multiple of 8 up to 128; fp32 / fp16 / bf16.  m, n <= 128 with d <= 64 run on the kernels that
     hold a whole head in one wavefront, every other shape on the tiled kernels; the shape alone
     decides."""
