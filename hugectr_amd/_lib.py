@@ -146,6 +146,14 @@ _SIGNATURES = {
                                    _P]),
     "hctr_mha_tiled_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P, c_int, _P]),
+    "hctr_mha_len_fwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int,
+                                 _P]),
+    "hctr_mha_len_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
+                                 _P, _P, c_int, _P]),
+    "hctr_mha_tiled_len_fwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
+                                       _P, c_int, _P]),
+    "hctr_mha_tiled_len_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
+                                       _P, _P, _P, _P, _P, c_int, _P]),
     "hctr_sequence_mask": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, c_int, _P]),
     "hctr_layer_norm_fwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, c_float, _P, _P, c_int, _P]),
     "hctr_layer_norm_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),

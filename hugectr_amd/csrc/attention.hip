@@ -1,5 +1,8 @@
 // attention.hip -- multi-head attention (forward, backward) and the sequence mask:
-// kernels, host dispatch, hctr_mha_fwd / hctr_mha_bwd / hctr_sequence_mask.
+// kernels, host dispatch, hctr_mha_fwd / hctr_mha_bwd / hctr_sequence_mask, and the *_len_* entries
+// of both families, which take the two length vectors in the place of the mask and run the same
+// kernel bodies (template parameter LEN: the 0 / 1 decision is formed in registers from the
+// sample's two floats -- LenBounds below -- and no mask tensor is read).
 //
 // Two kernel families.  This file holds the first, for seq_from, seq_to <= 128 and size_per_head
 // <= 64: a whole (sample, head) in one wavefront's LDS, described below.  attention_tiled.hip, taken
@@ -289,6 +292,30 @@ __device__ __forceinline__ float logit(float qk, float scale, const T* mrow, flo
   if (key >= n) return -INFINITY;
   return qk * scale - (penalty(mrow, key) - pmin);
 }
+// ---- the mask as two lengths (the *_len_* entries) ---------------------------------------------------
+// valid(b, i, j) = (float)i < len_from[b] && (float)j < len_to[b], sequence_mask_kernel's comparison,
+// formed from the two floats of a sample; no mask tensor is read.
+// how many of the integers 0 .. hi - 1 lie, as floats, below len: clamp(ceil(len), 0, hi), 0 for NaN
+__device__ __forceinline__ int count_below(float len, int hi) {
+  return len > 0.f ? (len < (float)hi ? (int)ceilf(len) : hi) : 0;
+}
+// one sample: keys 0 .. nv - 1 are valid; rows from first_plain on (and every row when no key is
+// valid) are plain: their penalty is common to the row and cancels, so they attend to all n keys.
+// Every other row treats a key >= nv like a key >= n: logit -inf, weight exactly 0
+struct LenBounds {
+  int nv, first_plain, n;
+  __device__ __forceinline__ LenBounds(const float* len_from, const float* len_to, size_t b, int m,
+                                       int n_)
+      : nv(count_below(len_to[b], n_)), first_plain(nv == 0 ? 0 : count_below(len_from[b], m)),
+        n(n_) {}
+  // where the keys of `row` end (>= 1)
+  __device__ __forceinline__ int key_end(int row) const { return row < first_plain ? nv : n; }
+  // the largest key_end among the rows below row_end (<= m)
+  __device__ __forceinline__ int key_end_upto(int row_end) const {
+    return row_end > first_plain ? n : nv;
+  }
+};
+
 // acc: raw q.k -> P; returns the row's max and 1 / (sum + eps) through rmax / rinv
 template <typename T>
 __device__ __forceinline__ void softmax_rows(f32x16 (&acc)[kSeqTiles], int nt, int n, float scale,
@@ -353,11 +380,15 @@ __device__ __forceinline__ size_t head_offset(const MhaShape& s, size_t b, int h
 // ================================================================================================
 // Forward
 // ================================================================================================
-template <typename T>
+// LEN: the mask comes from len_from / len_to (fp32 [B]) and `dense` is not read; otherwise from
+// `dense` (or no mask) and the lengths are not read
+template <typename T, bool LEN>
 __global__ void __launch_bounds__(64)
     mha_fwd_kernel(size_t n_heads_total, MhaShape s, const T* __restrict__ q,
-                   const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ mask,
+                   const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dense,
+                   const float* __restrict__ len_from, const float* __restrict__ len_to,
                    T* __restrict__ out, float scale) {
+  const T* mask = LEN ? nullptr : dense;
   HCTR_DYN_LDS16(float, smem);
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
   float* qt = smem;
@@ -373,6 +404,11 @@ __global__ void __launch_bounds__(64)
   for (size_t p = blockIdx.x; p < n_heads_total; p += gridDim.x) {
     const size_t b = p / s.heads;
     const int hd = (int)(p % s.heads);
+    int nv = s.n, first_plain = s.m;  // (no lengths: every row's keys end at n)
+    if (LEN) {
+      const LenBounds lb(len_from, len_to, b, s.m, s.n);
+      nv = lb.nv, first_plain = lb.first_plain;
+    }
     load_rows(qt, s.ld, q + head_offset(s, b, hd, s.m), stride, s.m, s.d, lane);
     load_rows(kt, s.ld, k + head_offset(s, b, hd, s.n), stride, s.n, s.d, lane);
     load_rows(vt, s.ld, v + head_offset(s, b, hd, s.n), stride, s.n, s.d, lane);
@@ -386,7 +422,9 @@ __global__ void __launch_bounds__(64)
       float pmin = mask ? row_min_penalty(mrow, nt, s.n, h) : 0.f;
       if (mask) pmin = fminf(pmin, __shfl_xor(pmin, 32));
       float rmax, rinv;
-      softmax_rows(acc, nt, s.n, scale, mrow, pmin, h, rmax, rinv);
+      // lengths: the minimum is known to be 0; a key past the row's end is a key past n
+      softmax_rows(acc, nt, LEN && q0 + r < first_plain ? nv : s.n, scale, mrow, pmin, h, rmax,
+                   rinv);
       put_block(pb, s.sld, acc, nt, lane);
       __syncthreads();
       // O block = P V: lane = column c of O_h, registers = query rows
@@ -413,12 +451,14 @@ __global__ void __launch_bounds__(64)
 // ================================================================================================
 // Backward
 // ================================================================================================
-template <typename T>
+template <typename T, bool LEN>
 __global__ void __launch_bounds__(64)
     mha_bwd_kernel(size_t n_heads_total, MhaShape s, const T* __restrict__ q,
-                   const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ mask,
+                   const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dense,
+                   const float* __restrict__ len_from, const float* __restrict__ len_to,
                    const T* __restrict__ top, T* __restrict__ dq, T* __restrict__ dk,
                    T* __restrict__ dv, float scale) {
+  const T* mask = LEN ? nullptr : dense;
   HCTR_DYN_LDS16(float, smem);
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
   float* qt = smem;
@@ -436,6 +476,11 @@ __global__ void __launch_bounds__(64)
     const size_t b = p / s.heads;
     const int hd = (int)(p % s.heads);
     const size_t off_m = head_offset(s, b, hd, s.m), off_n = head_offset(s, b, hd, s.n);
+    int nv = s.n, first_plain = s.m;
+    if (LEN) {
+      const LenBounds lb(len_from, len_to, b, s.m, s.n);
+      nv = lb.nv, first_plain = lb.first_plain;
+    }
     load_rows(qt, s.ld, q + off_m, stride, s.m, s.d, lane);
     load_rows(gt, s.ld, top + off_m, stride, s.m, s.d, lane);
     load_rows(kt, s.ld, k + off_n, stride, s.n, s.d, lane);
@@ -452,7 +497,9 @@ __global__ void __launch_bounds__(64)
       float pmin = mask ? row_min_penalty(mrow, nt, s.n, h) : 0.f;
       if (mask) pmin = fminf(pmin, __shfl_xor(pmin, 32));
       float rmax, rinv;
-      softmax_rows(acc, nt, s.n, scale, mrow, pmin, h, rmax, rinv);
+      // lengths: the minimum is known to be 0; a key past the row's end is a key past n
+      softmax_rows(acc, nt, LEN && q0 + r < first_plain ? nv : s.n, scale, mrow, pmin, h, rmax,
+                   rinv);
       // dP = dO V^T in the same layout, delta = rowsum(dP o P), acc <- dS = P o (dP - delta)
       f32x16 dp[kSeqTiles];
       float delta = 0.f;
@@ -508,12 +555,13 @@ __global__ void __launch_bounds__(64)
         const T* mrow = (mask && qi < s.m) ? mask + (b * s.m + qi) * (size_t)s.n : nullptr;
         const float rmax = st[qi], rinv = st[s.mp + qi], delta = st[2 * s.mp + qi],
                     pmin = st[3 * s.mp + qi];
+        const int kend = LEN && qi < first_plain ? nv : s.n;
         const f32x16 sc = tile_rr<T>(kt, s.ld, k0, qt, s.ld, q0, ksd, lane);
         const f32x16 dp = tile_rr<T>(vt, s.ld, k0, gt, s.ld, q0, ksd, lane);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
           const int kl = tile_row(reg, h);
-          const float pr = __expf(logit(sc[reg], scale, mrow, pmin, k0 + kl, s.n) - rmax) * rinv;
+          const float pr = __expf(logit(sc[reg], scale, mrow, pmin, k0 + kl, kend) - rmax) * rinv;
           ptt[kl * kTileLd + r] = pr;
           dst[kl * kTileLd + r] = pr * (dp[reg] - delta);
         }
@@ -604,46 +652,67 @@ int allow_dyn_lds(K kernel, size_t lds) {
 }
 
 
+// where a call's mask comes from: a dense tensor (NULL: no mask), or the two fp32 [B] length vectors
+// of the *_len_* entries (no alignment asked of them: they are read a float at a time)
+struct MaskSrc {
+  const void* dense;
+  const float *len_from, *len_to;
+  bool lengths;
+  bool complete() const { return !lengths || (len_from && len_to); }  // for a batch that is not empty
+};
+// f(std::true_type) for lengths, f(std::false_type) for a dense mask: the kernels' LEN
+template <typename F>
+int with_mask_src(const MaskSrc& ms, F&& f) {
+  return ms.lengths ? f(std::true_type{}) : f(std::false_type{});
+}
+
 int fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head, const void* q,
-        const void* k, const void* v, const void* mask, void* out, int dtype,
+        const void* k, const void* v, const MaskSrc& ms, void* out, int dtype,
         hctr_stream_t stream) {
   HCTR_TRY(mha_check(heads, seq_from, seq_to, size_per_head, dtype));
-  HCTR_REQUIRE(aligned16(q, k, v, mask, out), "mha: 16-byte aligned buffers");
+  HCTR_REQUIRE(aligned16(q, k, v, ms.dense, out), "mha: 16-byte aligned buffers");
   if (batch == 0) return HCTR_OK;
-  HCTR_REQUIRE(q && k && v && out, "null pointer");
+  HCTR_REQUIRE(q && k && v && out && ms.complete(), "null pointer");
   const MhaShape sh(heads, seq_from, seq_to, size_per_head);
   const size_t lds = (size_t)sh.fwd_floats() * 4, total = batch * (size_t)heads;
   const float scale = 1.f / sqrtf((float)size_per_head);
   hipStream_t s = as_stream(stream);
   HCTR_TRY(with_dtype(dtype, [&](auto* t) -> int {
     using T = std::remove_pointer_t<decltype(t)>;
-    HCTR_TRY(allow_dyn_lds(mha_fwd_kernel<T>, lds));
-    hipLaunchKernelGGL(mha_fwd_kernel<T>, dim3(mha_grid(total)), dim3(64), lds, s, total, sh,
-                       (const T*)q, (const T*)k, (const T*)v, (const T*)mask, (T*)out, scale);
-    return HCTR_OK;
+    return with_mask_src(ms, [&](auto len) -> int {
+      auto kernel = mha_fwd_kernel<T, decltype(len)::value>;
+      HCTR_TRY(allow_dyn_lds(kernel, lds));
+      hipLaunchKernelGGL(kernel, dim3(mha_grid(total)), dim3(64), lds, s, total, sh, (const T*)q,
+                         (const T*)k, (const T*)v, (const T*)ms.dense, ms.len_from, ms.len_to,
+                         (T*)out, scale);
+      return HCTR_OK;
+    });
   }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
 
 int bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head, const void* q,
-        const void* k, const void* v, const void* mask, const void* top_grad, void* dq, void* dk,
+        const void* k, const void* v, const MaskSrc& ms, const void* top_grad, void* dq, void* dk,
         void* dv, int dtype, hctr_stream_t stream) {
   HCTR_TRY(mha_check(heads, seq_from, seq_to, size_per_head, dtype));
-  HCTR_REQUIRE(aligned16(q, k, v, mask, top_grad, dq, dk, dv), "mha: 16-byte aligned buffers");
+  HCTR_REQUIRE(aligned16(q, k, v, ms.dense, top_grad, dq, dk, dv), "mha: 16-byte aligned buffers");
   if (batch == 0) return HCTR_OK;
-  HCTR_REQUIRE(q && k && v && top_grad && dq && dk && dv, "null pointer");
+  HCTR_REQUIRE(q && k && v && top_grad && dq && dk && dv && ms.complete(), "null pointer");
   const MhaShape sh(heads, seq_from, seq_to, size_per_head);
   const size_t lds = (size_t)sh.bwd_floats() * 4, total = batch * (size_t)heads;
   const float scale = 1.f / sqrtf((float)size_per_head);
   hipStream_t s = as_stream(stream);
   HCTR_TRY(with_dtype(dtype, [&](auto* t) -> int {
     using T = std::remove_pointer_t<decltype(t)>;
-    HCTR_TRY(allow_dyn_lds(mha_bwd_kernel<T>, lds));
-    hipLaunchKernelGGL(mha_bwd_kernel<T>, dim3(mha_grid(total)), dim3(64), lds, s, total, sh,
-                       (const T*)q, (const T*)k, (const T*)v, (const T*)mask, (const T*)top_grad,
-                       (T*)dq, (T*)dk, (T*)dv, scale);
-    return HCTR_OK;
+    return with_mask_src(ms, [&](auto len) -> int {
+      auto kernel = mha_bwd_kernel<T, decltype(len)::value>;
+      HCTR_TRY(allow_dyn_lds(kernel, lds));
+      hipLaunchKernelGGL(kernel, dim3(mha_grid(total)), dim3(64), lds, s, total, sh, (const T*)q,
+                         (const T*)k, (const T*)v, (const T*)ms.dense, ms.len_from, ms.len_to,
+                         (const T*)top_grad, (T*)dq, (T*)dk, (T*)dv, scale);
+      return HCTR_OK;
+    });
   }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
@@ -681,31 +750,65 @@ extern "C" {
 int hctr_mha_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
                  const void* q, const void* k, const void* v, const void* mask, void* out,
                  int dtype, hctr_stream_t stream) {
-  return hctr::mha::fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, out, dtype,
-                        stream);
+  return hctr::mha::fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                        {mask, nullptr, nullptr, false}, out, dtype, stream);
+}
+
+int hctr_mha_len_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                     const void* q, const void* k, const void* v, const float* len_from,
+                     const float* len_to, void* out, int dtype, hctr_stream_t stream) {
+  return hctr::mha::fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                        {nullptr, len_from, len_to, true}, out, dtype, stream);
 }
 
 int hctr_mha_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
                  const void* q, const void* k, const void* v, const void* mask,
                  const void* top_grad, void* dq, void* dk, void* dv, int dtype,
                  hctr_stream_t stream) {
-  return hctr::mha::bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, top_grad, dq,
-                        dk, dv, dtype, stream);
+  return hctr::mha::bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                        {mask, nullptr, nullptr, false}, top_grad, dq, dk, dv, dtype, stream);
+}
+
+int hctr_mha_len_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                     const void* q, const void* k, const void* v, const float* len_from,
+                     const float* len_to, const void* top_grad, void* dq, void* dk, void* dv,
+                     int dtype, hctr_stream_t stream) {
+  return hctr::mha::bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                        {nullptr, len_from, len_to, true}, top_grad, dq, dk, dv, dtype, stream);
 }
 
 int hctr_mha_tiled_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
                        const void* q, const void* k, const void* v, const void* mask, void* out,
                        void* stats, int dtype, hctr_stream_t stream) {
-  return hctr::mha::tiled_fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, out,
-                              stats, dtype, stream);
+  return hctr::mha::tiled_fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                              {mask, nullptr, nullptr, false}, out, stats, dtype, stream);
+}
+
+int hctr_mha_tiled_len_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                           const void* q, const void* k, const void* v, const float* len_from,
+                           const float* len_to, void* out, void* stats, int dtype,
+                           hctr_stream_t stream) {
+  return hctr::mha::tiled_fwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                              {nullptr, len_from, len_to, true}, out, stats, dtype, stream);
 }
 
 int hctr_mha_tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
                        const void* q, const void* k, const void* v, const void* mask,
                        const void* out, void* stats, const void* top_grad, void* dq, void* dk,
                        void* dv, int dtype, hctr_stream_t stream) {
-  return hctr::mha::tiled_bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v, mask, out,
-                              stats, top_grad, dq, dk, dv, dtype, stream);
+  return hctr::mha::tiled_bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                              {mask, nullptr, nullptr, false}, out, stats, top_grad, dq, dk, dv,
+                              dtype, stream);
+}
+
+int hctr_mha_tiled_len_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                           const void* q, const void* k, const void* v, const float* len_from,
+                           const float* len_to, const void* out, void* stats,
+                           const void* top_grad, void* dq, void* dk, void* dv, int dtype,
+                           hctr_stream_t stream) {
+  return hctr::mha::tiled_bwd(batch, heads, seq_from, seq_to, size_per_head, q, k, v,
+                              {nullptr, len_from, len_to, true}, out, stats, top_grad, dq, dk, dv,
+                              dtype, stream);
 }
 
 int hctr_sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,

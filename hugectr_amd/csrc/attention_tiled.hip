@@ -37,6 +37,18 @@
 //     dQ += dS K (K tile read transposed);
 //   dkv sweep, per block of 128 keys over Q / dO tiles (+ their statistics): K and V rows in
 //     registers, dV += P^T dO and dK += dS^T Q with the dO / Q tiles read transposed.
+//
+// The mask as two lengths (LEN; hctr_mha_tiled_len_fwd / _bwd): the same three bodies.  A workgroup
+// reads its sample's two floats (LenBounds: nv valid keys, rows from first_plain on are plain).  A
+// row's keys end at nv or, for a plain row, at n; past that end a key is what a key >= n is, and
+// the smallest penalty is 0, so nothing is carried for it.  What is skipped:
+//   forward, dq sweep: a block streams tiles only up to the largest end among its live rows
+//     (ceil(nv / 64) tiles when all of them are valid), a wavefront leaves a tile's 32-key sub-tile
+//     that lies past every one of its own rows (KeyEnds);
+//   dkv sweep: a block of keys at or past nv is reached by plain rows only and starts at the query
+//     tile that holds first_plain; without a plain row it stores zeros and streams nothing.
+// Trip counts and barriers depend on the lengths, blockIdx and the shape only; the wavefront's
+// skip holds no barrier and no LDS store.
 
 constexpr int kTiledMaxSeq = 4096;
 constexpr int kTiledMaxHead = 128;
@@ -285,15 +297,41 @@ __device__ __forceinline__ f32x16 zero_tile() {
   return (f32x16){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 }
 
+// Where the keys end in a block of query rows (forward, dq sweep).  A dense mask: at n, for all.
+// LEN: `row` for this lane's own row (LenBounds::key_end), `wave` the largest among the live rows of
+// its wavefront, `block` the largest among the block's.  block depends on the sample's two lengths,
+// blockIdx and the shape only, so every trip count and barrier taken from it is the same for the
+// whole workgroup; wave is the same for the 64 lanes of a wavefront (tid >> 6) and bounds only
+// code without a barrier or an LDS store.
+template <bool LEN>
+struct KeyEnds {
+  int row, wave, block;
+  __device__ __forceinline__ KeyEnds(const float* len_from, const float* len_to,
+                                     const TiledBlock& blk, int m, int n, int tid) {
+    row = wave = block = n;
+    if (LEN) {
+      const LenBounds lb(len_from, len_to, blk.b, m, n);
+      const int w0 = blk.row0 + (tid >> 6) * 32;
+      row = lb.key_end(w0 + (tid & 31));
+      wave = lb.key_end_upto(w0 + 32 < m ? w0 + 32 : m);
+      block = lb.key_end_upto(blk.row0 + kBlockRows < m ? blk.row0 + kBlockRows : m);
+    }
+  }
+};
+
 // ================================================================================================
 // Forward
 // ================================================================================================
-template <typename T, int DT>
+// LEN (all three kernels): the mask comes from len_from / len_to (fp32 [B]) and `dense` is not read;
+// otherwise from `dense` (or no mask) and the lengths are not read
+template <typename T, int DT, bool LEN>
 __global__ void __launch_bounds__(kTiledThreads)
     mha_tiled_fwd_kernel(int heads, int m, int n, int d, const T* __restrict__ q,
                          const T* __restrict__ k, const T* __restrict__ v,
-                         const T* __restrict__ mask, T* __restrict__ out, float* __restrict__ stats,
-                         float scale) {
+                         const T* __restrict__ dense, const float* __restrict__ len_from,
+                         const float* __restrict__ len_to, T* __restrict__ out,
+                         float* __restrict__ stats, float scale) {
+  const T* mask = LEN ? nullptr : dense;
   using G = TileGeo<T, DT>;
   HCTR_DYN_LDS16(u16, tsmem);
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -306,6 +344,7 @@ __global__ void __launch_bounds__(kTiledThreads)
   const T* kg = k + tiled_head_offset(blk.b, blk.hd, n, heads, d);
   const T* vg = v + tiled_head_offset(blk.b, blk.hd, n, heads, d);
   const T* mrow = (mask && live) ? mask + (blk.b * m + qrow) * (size_t)n : nullptr;
+  const KeyEnds<LEN> ke(len_from, len_to, blk, m, n, tid);
 
   typename Tl<T>::frag qf[2 * DT];
   load_frags<T, DT>(qf, live ? q + off_m : nullptr, d, h);
@@ -315,17 +354,18 @@ __global__ void __launch_bounds__(kTiledThreads)
   float rmax = -INFINITY, rsum = 0.f, rmin = mask ? INFINITY : 0.f;  // (rsum: this lane's half)
 
   Stage<T, DT> st;
-  const int nt = (n + kTileRows - 1) / kTileRows;
-  st.load(kg, vg, stride, 0, n, d, tid);
+  // tiles up to the block's last key (workgroup-uniform: KeyEnds), keys past it are not loaded
+  const int nt = (ke.block + kTileRows - 1) / kTileRows;
+  st.load(kg, vg, stride, 0, ke.block, d, tid);
   st.store(tsmem, tid);
   __syncthreads();
   for (int it = 0; it < nt; it++) {
     const u16* kt = tsmem + (it & 1) * G::stage;
     const u16* vt = kt + G::tile;
-    if (it + 1 < nt) st.load(kg, vg, stride, (it + 1) * kTileRows, n, d, tid);
+    if (it + 1 < nt) st.load(kg, vg, stride, (it + 1) * kTileRows, ke.block, d, tid);
     for (int sub = 0; sub < kTileRows; sub += 32) {
       const int key0 = it * kTileRows + sub;
-      if (key0 >= n) break;
+      if (key0 >= ke.wave) break;  // past every row of this wavefront (the first sub-tile never is)
       f32x16 s = mma_rows<T, DT>(kt, sub, qf, ksd, lane);
       float pen[16];
 #pragma unroll
@@ -350,11 +390,11 @@ __global__ void __launch_bounds__(kTiledThreads)
 #pragma unroll
       for (int reg = 0; reg < 16; reg++) {
         const int key = key0 + tile_row(reg, h);
-        s[reg] = key < n ? s[reg] * scale - (pen[reg] - rmin) : -INFINITY;
+        s[reg] = key < ke.row ? s[reg] * scale - (pen[reg] - rmin) : -INFINITY;
         mx = fmaxf(mx, s[reg]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mnew = fmaxf(rmax, mx);  // finite: key0 < n
+      const float mnew = fmaxf(rmax, mx);  // finite: key 0 < ke.row
       const float alpha = __expf(rmax - mnew);
       float sum = 0.f;
 #pragma unroll
@@ -384,13 +424,15 @@ __global__ void __launch_bounds__(kTiledThreads)
 // ================================================================================================
 // Backward: the dq sweep
 // ================================================================================================
-template <typename T, int DT>
+template <typename T, int DT, bool LEN>
 __global__ void __launch_bounds__(kTiledThreads)
     mha_tiled_dq_kernel(int heads, int m, int n, int d, const T* __restrict__ q,
                         const T* __restrict__ k, const T* __restrict__ v,
-                        const T* __restrict__ mask, const T* __restrict__ out,
+                        const T* __restrict__ dense, const float* __restrict__ len_from,
+                        const float* __restrict__ len_to, const T* __restrict__ out,
                         const T* __restrict__ top, float* __restrict__ stats, T* __restrict__ dq,
                         float scale) {
+  const T* mask = LEN ? nullptr : dense;
   using G = TileGeo<T, DT>;
   HCTR_DYN_LDS16(u16, tsmem);
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -403,6 +445,7 @@ __global__ void __launch_bounds__(kTiledThreads)
   const T* kg = k + tiled_head_offset(blk.b, blk.hd, n, heads, d);
   const T* vg = v + tiled_head_offset(blk.b, blk.hd, n, heads, d);
   const T* mrow = (mask && live) ? mask + (blk.b * m + qrow) * (size_t)n : nullptr;
+  const KeyEnds<LEN> ke(len_from, len_to, blk, m, n, tid);
 
   typename Tl<T>::frag qf[2 * DT], gf[2 * DT];  // the lane's rows of Q and dO
   load_frags<T, DT>(qf, live ? q + off_m : nullptr, d, h);
@@ -431,23 +474,24 @@ __global__ void __launch_bounds__(kTiledThreads)
   for (int ct = 0; ct < DT; ct++) g[ct] = zero_tile();
 
   Stage<T, DT> st;
-  const int nt = (n + kTileRows - 1) / kTileRows;
-  st.load(kg, vg, stride, 0, n, d, tid);
+  // tiles up to the block's last key (workgroup-uniform: KeyEnds), keys past it are not loaded
+  const int nt = (ke.block + kTileRows - 1) / kTileRows;
+  st.load(kg, vg, stride, 0, ke.block, d, tid);
   st.store(tsmem, tid);
   __syncthreads();
   for (int it = 0; it < nt; it++) {
     const u16* kt = tsmem + (it & 1) * G::stage;
     const u16* vt = kt + G::tile;
-    if (it + 1 < nt) st.load(kg, vg, stride, (it + 1) * kTileRows, n, d, tid);
+    if (it + 1 < nt) st.load(kg, vg, stride, (it + 1) * kTileRows, ke.block, d, tid);
     for (int sub = 0; sub < kTileRows; sub += 32) {
       const int key0 = it * kTileRows + sub;
-      if (key0 >= n) break;
+      if (key0 >= ke.wave) break;  // past every row of this wavefront (the first sub-tile never is)
       f32x16 s = mma_rows<T, DT>(kt, sub, qf, ksd, lane);
       const f32x16 dp = mma_rows<T, DT>(vt, sub, gf, ksd, lane);
 #pragma unroll
       for (int reg = 0; reg < 16; reg++) {
         const int key = key0 + tile_row(reg, h);
-        const float p = __expf(logit(s[reg], scale, mrow, rmin, key, n) - rmax) * rinv;
+        const float p = __expf(logit(s[reg], scale, mrow, rmin, key, ke.row) - rmax) * rinv;
         s[reg] = p * (dp[reg] - delta);
       }
       mma_tr<T, DT>(g, kt, sub, s, lane);
@@ -461,13 +505,15 @@ __global__ void __launch_bounds__(kTiledThreads)
 // ================================================================================================
 // Backward: the dkv sweep
 // ================================================================================================
-template <typename T, int DT>
+template <typename T, int DT, bool LEN>
 __global__ void __launch_bounds__(kTiledThreads)
     mha_tiled_dkv_kernel(int heads, int m, int n, int d, const T* __restrict__ q,
                          const T* __restrict__ k, const T* __restrict__ v,
-                         const T* __restrict__ mask, const T* __restrict__ top,
+                         const T* __restrict__ dense, const float* __restrict__ len_from,
+                         const float* __restrict__ len_to, const T* __restrict__ top,
                          const float* __restrict__ stats, T* __restrict__ dk, T* __restrict__ dv,
                          float scale) {
+  const T* mask = LEN ? nullptr : dense;
   using G = TileGeo<T, DT>;
   HCTR_DYN_LDS16(u16, tsmem);
   // the statistics of a tile's 64 query rows, double buffered like the tiles, in front of them
@@ -500,12 +546,25 @@ __global__ void __launch_bounds__(kTiledThreads)
       sst = row0 + tid < m ? *reinterpret_cast<const f32x4*>(sg + (size_t)(row0 + tid) * 4)
                            : (f32x4){0.f, 0.f, 0.f, 0.f};  // 1 / (sum + eps) = 0: P = dS = 0
   };
-  st.load(qg, gg, stride, 0, m, d, tid);
-  load_stats(0);
-  st.store(tiles, tid);
-  if (tid < kTileRows) stt[tid] = sst;
+  // LEN: a row below first_plain reaches the keys below nv only, every other row all of them.  A
+  // block whose keys all lie at or past nv is reached by the plain rows alone: it starts at the
+  // tile that holds first_plain, and with no plain row (first_plain == m) streams nothing and
+  // stores the zeros.  it0 depends on the sample's two lengths, blockIdx and the shape only, so the
+  // trip count and the barriers are the same for the whole workgroup
+  int it0 = 0, first_plain = 0;
+  bool key_valid = true;
+  if (LEN) {
+    const LenBounds lb(len_from, len_to, blk.b, m, n);
+    first_plain = lb.first_plain;
+    key_valid = key < lb.nv;
+    if (blk.row0 >= lb.nv) it0 = first_plain == m ? nt : first_plain / kTileRows;
+  }
+  st.load(qg, gg, stride, it0 * kTileRows, m, d, tid);  // (rows past m: zeros, nothing is read)
+  load_stats(it0 * kTileRows);
+  st.store(tiles + (it0 & 1) * G::stage, tid);
+  if (tid < kTileRows) stt[(it0 & 1) * kTileRows + tid] = sst;
   __syncthreads();
-  for (int it = 0; it < nt; it++) {
+  for (int it = it0; it < nt; it++) {
     const u16* qt = tiles + (it & 1) * G::stage;
     const u16* gt = qt + G::tile;
     const f32x4* sv = stt + (it & 1) * kTileRows;
@@ -523,7 +582,8 @@ __global__ void __launch_bounds__(kTiledThreads)
         const int ql = sub + tile_row(reg, h), qi = it * kTileRows + ql;
         const f32x4 row = sv[ql];  // max, 1 / (sum + eps), smallest penalty, delta
         const T* mrow = (mcol && qi < m) ? mcol + (size_t)qi * n : nullptr;
-        const float lg = live ? p[reg] * scale - (penalty(mrow, 0) - row[2]) : -INFINITY;
+        const bool reached = live && (!LEN || key_valid || qi >= first_plain);
+        const float lg = reached ? p[reg] * scale - (penalty(mrow, 0) - row[2]) : -INFINITY;
         p[reg] = __expf(lg - row[0]) * row[1];
         ds[reg] = p[reg] * (ds[reg] - row[3]);
       }
@@ -575,12 +635,12 @@ int with_tiled_types(int dtype, int size_per_head, F&& f) {
 }
 
 int tiled_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head, const void* q,
-              const void* k, const void* v, const void* mask, void* out, void* stats, int dtype,
+              const void* k, const void* v, const MaskSrc& ms, void* out, void* stats, int dtype,
               hctr_stream_t stream) {
   HCTR_TRY(tiled_check(heads, seq_from, seq_to, size_per_head, dtype));
-  HCTR_REQUIRE(aligned16(q, k, v, mask, out, stats), "mha_tiled: 16-byte aligned buffers");
+  HCTR_REQUIRE(aligned16(q, k, v, ms.dense, out, stats), "mha_tiled: 16-byte aligned buffers");
   if (batch == 0) return HCTR_OK;
-  HCTR_REQUIRE(q && k && v && out, "null pointer");
+  HCTR_REQUIRE(q && k && v && out && ms.complete(), "null pointer");
   unsigned grid;
   HCTR_TRY(tiled_grid(batch, heads, seq_from, &grid));
   const float scale = 1.f / sqrtf((float)size_per_head);
@@ -588,26 +648,28 @@ int tiled_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_he
   HCTR_TRY(with_tiled_types(dtype, size_per_head, [&](auto* t, auto dt) -> int {
     using T = std::remove_pointer_t<decltype(t)>;
     constexpr int DT = decltype(dt)::value;
-    auto kernel = mha_tiled_fwd_kernel<T, DT>;
-    const size_t lds = TileGeo<T, DT>::lds_bytes;
-    HCTR_TRY(allow_dyn_lds(kernel, lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTiledThreads), lds, s, heads, seq_from, seq_to,
-                       size_per_head, (const T*)q, (const T*)k, (const T*)v, (const T*)mask, (T*)out,
-                       (float*)stats, scale);
-    return HCTR_OK;
+    return with_mask_src(ms, [&](auto len) -> int {
+      auto kernel = mha_tiled_fwd_kernel<T, DT, decltype(len)::value>;
+      const size_t lds = TileGeo<T, DT>::lds_bytes;
+      HCTR_TRY(allow_dyn_lds(kernel, lds));
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTiledThreads), lds, s, heads, seq_from, seq_to,
+                         size_per_head, (const T*)q, (const T*)k, (const T*)v, (const T*)ms.dense,
+                         ms.len_from, ms.len_to, (T*)out, (float*)stats, scale);
+      return HCTR_OK;
+    });
   }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;
 }
 
 int tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head, const void* q,
-              const void* k, const void* v, const void* mask, const void* out, void* stats,
+              const void* k, const void* v, const MaskSrc& ms, const void* out, void* stats,
               const void* top_grad, void* dq, void* dk, void* dv, int dtype, hctr_stream_t stream) {
   HCTR_TRY(tiled_check(heads, seq_from, seq_to, size_per_head, dtype));
-  HCTR_REQUIRE(aligned16(q, k, v, mask, out, stats, top_grad, dq, dk, dv),
+  HCTR_REQUIRE(aligned16(q, k, v, ms.dense, out, stats, top_grad, dq, dk, dv),
                "mha_tiled: 16-byte aligned buffers");
   if (batch == 0) return HCTR_OK;
-  HCTR_REQUIRE(q && k && v && top_grad && dq && dk && dv, "null pointer");
+  HCTR_REQUIRE(q && k && v && top_grad && dq && dk && dv && ms.complete(), "null pointer");
   HCTR_REQUIRE(out && stats, "mha_tiled_bwd: out and stats of the forward");
   unsigned grid_q, grid_k;
   HCTR_TRY(tiled_grid(batch, heads, seq_from, &grid_q));
@@ -617,19 +679,23 @@ int tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_he
   HCTR_TRY(with_tiled_types(dtype, size_per_head, [&](auto* t, auto dt) -> int {
     using T = std::remove_pointer_t<decltype(t)>;
     constexpr int DT = decltype(dt)::value;
-    auto dq_kernel = mha_tiled_dq_kernel<T, DT>;
-    auto dkv_kernel = mha_tiled_dkv_kernel<T, DT>;
-    const size_t lds = TileGeo<T, DT>::lds_bytes;
-    const size_t lds_kv = lds + 2 * kTileRows * sizeof(f32x4);
-    HCTR_TRY(allow_dyn_lds(dq_kernel, lds));
-    HCTR_TRY(allow_dyn_lds(dkv_kernel, lds_kv));
-    hipLaunchKernelGGL(dq_kernel, dim3(grid_q), dim3(kTiledThreads), lds, s, heads, seq_from,
-                       seq_to, size_per_head, (const T*)q, (const T*)k, (const T*)v, (const T*)mask,
-                       (const T*)out, (const T*)top_grad, (float*)stats, (T*)dq, scale);
-    hipLaunchKernelGGL(dkv_kernel, dim3(grid_k), dim3(kTiledThreads), lds_kv, s, heads, seq_from,
-                       seq_to, size_per_head, (const T*)q, (const T*)k, (const T*)v, (const T*)mask,
-                       (const T*)top_grad, (const float*)stats, (T*)dk, (T*)dv, scale);
-    return HCTR_OK;
+    return with_mask_src(ms, [&](auto len) -> int {
+      auto dq_kernel = mha_tiled_dq_kernel<T, DT, decltype(len)::value>;
+      auto dkv_kernel = mha_tiled_dkv_kernel<T, DT, decltype(len)::value>;
+      const size_t lds = TileGeo<T, DT>::lds_bytes;
+      const size_t lds_kv = lds + 2 * kTileRows * sizeof(f32x4);
+      HCTR_TRY(allow_dyn_lds(dq_kernel, lds));
+      HCTR_TRY(allow_dyn_lds(dkv_kernel, lds_kv));
+      hipLaunchKernelGGL(dq_kernel, dim3(grid_q), dim3(kTiledThreads), lds, s, heads, seq_from,
+                         seq_to, size_per_head, (const T*)q, (const T*)k, (const T*)v,
+                         (const T*)ms.dense, ms.len_from, ms.len_to, (const T*)out,
+                         (const T*)top_grad, (float*)stats, (T*)dq, scale);
+      hipLaunchKernelGGL(dkv_kernel, dim3(grid_k), dim3(kTiledThreads), lds_kv, s, heads, seq_from,
+                         seq_to, size_per_head, (const T*)q, (const T*)k, (const T*)v,
+                         (const T*)ms.dense, ms.len_from, ms.len_to, (const T*)top_grad,
+                         (const float*)stats, (T*)dk, (T*)dv, scale);
+      return HCTR_OK;
+    });
   }));
   HCTR_LAUNCH_CHECK();
   return HCTR_OK;

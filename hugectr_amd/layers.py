@@ -193,10 +193,11 @@ class _MultiHeadAttentionFn(torch.autograd.Function):
     hctr_mha_fwd / hctr_mha_bwd, one wavefront per (sample, head); the backward recomputes the
     probabilities from q, k and the mask, which are all that is saved.  Everything else up to
     4096 x 4096 x 128: hctr_mha_tiled_fwd / hctr_mha_tiled_bwd, which also keep the output and
-    four fp32 statistics per (head, query row)"""
+    four fp32 statistics per (head, query row).  With the two fp32 length vectors in the place of
+    the mask: the *_len_* entry of the same family, and the lengths are what is saved"""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, heads):
+    def forward(ctx, q, k, v, mask, heads, len_from, len_to):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, m, hidden = q.shape
         n = k.shape[1]
@@ -210,41 +211,50 @@ class _MultiHeadAttentionFn(torch.autograd.Function):
                 raise ValueError(f"multi_head_attention: mask {tuple(mask.shape)} {mask.dtype}, "
                                  f"expected {(B, 1, m, n)} {q.dtype}")
             mask = mask.contiguous()
+        for x in (len_from, len_to):
+            if x is not None and (x.shape != (B,) or x.device != q.device):
+                raise ValueError(f"multi_head_attention: lengths {tuple(x.shape)} on {x.device}, "
+                                 f"expected {(B,)} on {q.device}")
         out = torch.empty_like(q)
-        ctx.heads = heads
+        ctx.heads, ctx.lengths = heads, len_from is not None
         ctx.tiled = max(m, n) > 128 or hidden // heads > 64
+        # the mask's place in the argument list: one pointer, or the two length vectors
+        src = (ptr(len_from), ptr(len_to)) if ctx.lengths else (ptr(mask),)
+        shape = (B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v), *src)
         if not ctx.tiled:
-            check(lib.hctr_mha_fwd(B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v),
-                                   ptr(mask), ptr(out), _DT[q.dtype], stream_ptr()))
-            ctx.save_for_backward(q, k, v, mask)
+            fn = lib.hctr_mha_len_fwd if ctx.lengths else lib.hctr_mha_fwd
+            check(fn(*shape, ptr(out), _DT[q.dtype], stream_ptr()))
+            ctx.save_for_backward(q, k, v, mask, len_from, len_to)
             return out
         stats = None
         if any(ctx.needs_input_grad[:3]):
             stats = torch.empty((B, heads, m, 4), dtype=torch.float32, device=q.device)
-        check(lib.hctr_mha_tiled_fwd(B, heads, m, n, hidden // heads, ptr(q), ptr(k), ptr(v),
-                                     ptr(mask), ptr(out), ptr(stats), _DT[q.dtype], stream_ptr()))
-        ctx.save_for_backward(q, k, v, mask, out, stats)
+        fn = lib.hctr_mha_tiled_len_fwd if ctx.lengths else lib.hctr_mha_tiled_fwd
+        check(fn(*shape, ptr(out), ptr(stats), _DT[q.dtype], stream_ptr()))
+        ctx.save_for_backward(q, k, v, mask, len_from, len_to, out, stats)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        q, k, v, mask = ctx.saved_tensors[:4]
+        q, k, v, mask, len_from, len_to = ctx.saved_tensors[:6]
         grad = grad.contiguous()
         B, m, hidden = q.shape
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        src = (ptr(len_from), ptr(len_to)) if ctx.lengths else (ptr(mask),)
+        shape = (B, ctx.heads, m, k.shape[1], hidden // ctx.heads, ptr(q), ptr(k), ptr(v), *src)
+        grads = (ptr(grad), ptr(dq), ptr(dk), ptr(dv), _DT[q.dtype], stream_ptr())
         if ctx.tiled:
-            out, stats = ctx.saved_tensors[4:]
-            check(lib.hctr_mha_tiled_bwd(B, ctx.heads, m, k.shape[1], hidden // ctx.heads, ptr(q),
-                                         ptr(k), ptr(v), ptr(mask), ptr(out), ptr(stats), ptr(grad),
-                                         ptr(dq), ptr(dk), ptr(dv), _DT[q.dtype], stream_ptr()))
-            return dq, dk, dv, None, None
-        check(lib.hctr_mha_bwd(B, ctx.heads, m, k.shape[1], hidden // ctx.heads, ptr(q), ptr(k),
-                               ptr(v), ptr(mask), ptr(grad), ptr(dq), ptr(dk), ptr(dv),
-                               _DT[q.dtype], stream_ptr()))
-        return dq, dk, dv, None, None
+            out, stats = ctx.saved_tensors[6:]
+            fn = lib.hctr_mha_tiled_len_bwd if ctx.lengths else lib.hctr_mha_tiled_bwd
+            check(fn(*shape, ptr(out), ptr(stats), *grads))
+        else:
+            fn = lib.hctr_mha_len_bwd if ctx.lengths else lib.hctr_mha_bwd
+            check(fn(*shape, *grads))
+        return dq, dk, dv, None, None, None, None
 
 
-def multi_head_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, heads: int):
+def multi_head_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, heads: int,
+                         lengths=None):
     """q [B, m, H d], k, v [B, n, H d], mask None or [B, 1, m, n] in q's dtype ->
     [B, m, H d]: per head softmax(Q K^T / sqrt(d) - (1 - mask) 10000) V, the softmax's sum taken
     with + 1e-6.  The mask is read as a value, not as a flag: 1 keeps a key, 0 puts it 10000 below,
@@ -252,20 +262,34 @@ def multi_head_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask
     fully masked row attends as if it had no mask.  m, n <= 4096, d a
     multiple of 8 up to 128; fp32 / fp16 / bf16.  m, n <= 128 with d <= 64 run on the kernels that
     hold a whole head in one wavefront, every other shape on the tiled kernels; the shape alone
-    decides."""
-    return _MultiHeadAttentionFn.apply(q, k, v, mask, heads)
+    decides.
+
+    lengths = (len_from, len_to), two [B] tensors of fp32 / fp16 / bf16 (what sequence_mask
+    accepts; widened to fp32 here, which is exact; no gradient), in the place of mask: the result
+    of mask = sequence_mask(len_from, len_to, m, n) without that tensor being written or read, and
+    without the work on keys past len_to.  A masked key's weight is exactly 0 where the dense mask
+    gives exp(-10000 + the row's spread of scores), which is 0 in fp32 below a spread of about
+    9 890 (include/hugectr_amd.h, hctr_mha_len_fwd)."""
+    len_from = len_to = None
+    if lengths is not None:
+        if mask is not None:
+            raise ValueError("multi_head_attention: mask or lengths, not both")
+        if len(lengths) != 2 or any(not torch.is_tensor(x) or x.dtype not in _DT for x in lengths):
+            raise ValueError("multi_head_attention: lengths = (len_from, len_to), fp32 / fp16 / bf16")
+        len_from, len_to = (x.detach().float().contiguous() for x in lengths)
+    return _MultiHeadAttentionFn.apply(q, k, v, mask, heads, len_from, len_to)
 
 
 class MultiHeadAttentionLayer(torch.nn.Module):
     """R/HugeCTR/include/layers/multi_head_attention_layer.hpp (3-D inputs) with the masked
-    softmax folded in; no weights"""
+    softmax folded in -- and, given lengths, the sequence mask too; no weights"""
 
     def __init__(self, num_attention_heads: int = 1):
         super().__init__()
         self.num_attention_heads = num_attention_heads
 
-    def forward(self, q, k, v, mask=None):
-        return multi_head_attention(q, k, v, mask, self.num_attention_heads)
+    def forward(self, q, k, v, mask=None, lengths=None):
+        return multi_head_attention(q, k, v, mask, self.num_attention_heads, lengths)
 
 
 def sequence_mask(len_from: torch.Tensor, len_to: torch.Tensor, max_from: int, max_to: int):

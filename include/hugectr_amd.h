@@ -610,6 +610,38 @@ int hctr_mha_tiled_bwd(size_t batch, int heads, int seq_from, int seq_to, int si
                        const void* q, const void* k, const void* v, const void* mask,
                        const void* out, void* stats, const void* top_grad, void* dq, void* dk,
                        void* dv, int dtype, hctr_stream_t stream);
+/* The four entries above with the mask given as the two length vectors SequenceMaskLayer would
+ * expand: len_from, len_to fp32 [B] (any alignment, non-NULL for batch > 0) in the place of `mask`,
+ * everything else -- tensors, dtypes, shape limits, what is refused and by which name, stats -- as
+ * the sibling's.  No mask tensor exists: valid(b, i, j) = (float)i < len_from[b] && (float)j <
+ * len_to[b], sequence_mask's comparison, is formed in registers.  With nv(b) = the number of keys
+ * j < seq_to with (float)j < len_to[b] (clamp(ceil(len_to), 0, seq_to); 0 for NaN or negative; 2.5
+ * keeps keys 0, 1, 2): a row i with !((float)i < len_from[b]), and every row when nv(b) = 0, is
+ * plain and attends to all seq_to keys without a penalty (what the dense formula gives a fully
+ * masked row: the common -10000 cancels); every other row treats a key >= nv(b) like a key >=
+ * seq_to: logit -inf, weight exactly 0, nothing to dq from it and nothing from that row to its dk,
+ * dv.  That equals softmax(q.k / sqrt(d) - (1 - mask) 10000) with mask = hctr_sequence_mask of the
+ * same lengths whenever the scores of a row spread over less than about 9 890 (exp(-87.3) is the
+ * smallest fp32 weight that is not 0 beside the row's maximum).  The tiled entries also skip the
+ * key tiles past nv(b) for blocks of valid rows, and in the dkv sweep the query tiles that cannot
+ * reach a block of keys >= nv(b); every row of dq, dk, dv is written, skipped ones with zeros.
+ * stats' third slot (the smallest penalty) is 0. */
+int hctr_mha_len_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                     const void* q, const void* k, const void* v, const float* len_from,
+                     const float* len_to, void* out, int dtype, hctr_stream_t stream);
+int hctr_mha_len_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                     const void* q, const void* k, const void* v, const float* len_from,
+                     const float* len_to, const void* top_grad, void* dq, void* dk, void* dv,
+                     int dtype, hctr_stream_t stream);
+int hctr_mha_tiled_len_fwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                           const void* q, const void* k, const void* v, const float* len_from,
+                           const float* len_to, void* out, void* stats, int dtype,
+                           hctr_stream_t stream);
+int hctr_mha_tiled_len_bwd(size_t batch, int heads, int seq_from, int seq_to, int size_per_head,
+                           const void* q, const void* k, const void* v, const float* len_from,
+                           const float* len_to, const void* out, void* stats,
+                           const void* top_grad, void* dq, void* dk, void* dv, int dtype,
+                           hctr_stream_t stream);
 /* SequenceMaskLayer<T> (R/HugeCTR/src/layers/sequence_mask_layer.cu): len_from, len_to [B] in the
  * element type -> mask [B][1][max_from][max_to], 1 where i < len_from[b] and j < len_to[b]. */
 int hctr_sequence_mask(size_t batch, int max_from, int max_to, const void* len_from,

@@ -7,6 +7,14 @@ directly (`tiled_*`), next to the kernels the layer picks there.  Device events 
 calls, medians over rounds, the paths alternating inside a round.  One JSON line per (shape,
 dtype); `ratio_*` = torch / own, `ratio_tiled_*` = torch / tiled.
 
+Three more legs per (shape, dtype), forward and forward + backward, the mask from lengths:
+`mask` (sequence_mask, then attention with that mask: both launches, what a BST graph runs every
+step; every length = seq), `lengths_full` (the same lengths handed to the kernels, no mask tensor)
+and `lengths_ragged` (integer lengths uniform in [1, seq] from a fixed seed, len_from = len_to).
+At the heavy shape the three go to the tiled entries directly.  `spread_*`: (min, max) over the
+rounds; `work_frac`: the share of (32-row, 32-key) sub-tiles the ragged lengths leave the forward
+and the dq sweep, `work_frac_dkv` the dkv sweep, both computed here from the lengths.
+
     python tools/mha_bench.py [--rounds 15] [--calls 20]
 """
 import argparse
@@ -26,22 +34,46 @@ SHAPES = {"bst": (4096, 10, 32, 4), "heavy": (4096, 128, 256, 4),  # B, seq, hid
           "long": (1024, 512, 256, 4), "wide": (4096, 128, 512, 4)}
 
 
-def tiled_direct(q, k, v, top, heads):
-    """hctr_mha_tiled_fwd / _bwd on preallocated buffers -> (forward, forward + backward, out)"""
+def tiled_direct(q, k, v, top, heads, mask_lens=None, lengths=None):
+    """hctr_mha_tiled_fwd / _bwd on preallocated buffers -> (forward, forward + backward, out).
+    mask_lens: each forward builds the mask from these lengths first; lengths: the *_len_* entries"""
     B, m, hidden = q.shape
     out, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
     stats = torch.empty((B, heads, m, 4), dtype=torch.float32, device=q.device)
     shape = (B, heads, m, k.shape[1], hidden // heads)
-    io = (ptr(q), ptr(k), ptr(v), None)
+    io = [ptr(q), ptr(k), ptr(v), None]
+    f, b = lib.hctr_mha_tiled_fwd, lib.hctr_mha_tiled_bwd
+    if lengths is not None:
+        f, b = lib.hctr_mha_tiled_len_fwd, lib.hctr_mha_tiled_len_bwd
+        io[3:] = [ptr(lengths[0]), ptr(lengths[1])]
+
+    held = {}  # the mask of the last forward, for its backward
 
     def fwd():
-        check(lib.hctr_mha_tiled_fwd(*shape, *io, ptr(out), ptr(stats), _DT[q.dtype], stream_ptr()))
+        if mask_lens is not None:
+            held["mask"] = ha.sequence_mask(*mask_lens, m, k.shape[1])
+            io[3] = ptr(held["mask"])
+        check(f(*shape, *io, ptr(out), ptr(stats), _DT[q.dtype], stream_ptr()))
 
     def both():
         fwd()
-        check(lib.hctr_mha_tiled_bwd(*shape, *io, ptr(out), ptr(stats), ptr(top), ptr(dq), ptr(dk),
-                                     ptr(dv), _DT[q.dtype], stream_ptr()))
+        check(b(*shape, *io, ptr(out), ptr(stats), ptr(top), ptr(dq), ptr(dk), ptr(dv),
+                _DT[q.dtype], stream_ptr()))
     return fwd, both, out
+
+
+def work_fracs(lens, seq):
+    """lens: integer lengths in [1, seq], len_from = len_to -> the share of 32 x 32 sub-tiles
+    attention_tiled.hip's rules keep: (forward and dq sweep, dkv sweep)"""
+    sub = -(-seq // 32)
+    kept_q = kept_k = 0
+    for L in lens.tolist():  # nv = first_plain = L
+        for w0 in range(0, seq, 32):  # a wavefront's 32 query rows: all keys if one of them is plain
+            kept_q += sub if min(w0 + 32, seq) > L else -(-L // 32)
+        for k0 in range(0, seq, 128):  # a block of 128 keys: past nv, from first_plain's tile on
+            waves = -(-(min(k0 + 128, seq) - k0) // 32)
+            kept_k += waves * (sub if k0 < L else sub - 2 * (L // 64))
+    return kept_q / (len(lens) * sub * sub), kept_k / (len(lens) * sub * sub)
 
 
 def torch_mha(q, k, v, heads):
@@ -92,6 +124,26 @@ def main():
             if name == "heavy":
                 legs["tiled_fwd"], legs["tiled_fwd_bwd"], t_out = tiled_direct(
                     q.detach(), k.detach(), v.detach(), top, heads)
+            full = torch.full((B,), float(seq), device="cuda")
+            ragged = torch.randint(1, seq + 1, (B,), generator=torch.Generator().manual_seed(seq))
+            wf, wf_dkv = work_fracs(ragged, seq)
+            ragged = ragged.float().cuda()
+            full_dt = full.to(dt)  # (10, 128 and 512 are exact in bf16)
+            for leg, kw in (("mask", {"mask_lens": (full_dt, full_dt)}),
+                            ("lengths_full", {"lengths": (full, full)}),
+                            ("lengths_ragged", {"lengths": (ragged, ragged)})):
+                if name == "heavy":
+                    legs[leg + "_fwd"], legs[leg + "_fwd_bwd"], _ = tiled_direct(
+                        q.detach(), k.detach(), v.detach(), top, heads, **kw)
+                    continue
+                if leg == "mask":
+                    layer = lambda ml=kw["mask_lens"]: ha.multi_head_attention(  # noqa: E731
+                        q, k, v, ha.sequence_mask(*ml, seq, seq), heads)
+                else:
+                    layer = lambda ln=kw["lengths"]: ha.multi_head_attention(  # noqa: E731
+                        q, k, v, None, heads, lengths=ln)
+                legs[leg + "_fwd"] = lambda f=layer: fwd(f)
+                legs[leg + "_fwd_bwd"] = lambda f=layer: both(f)
             for f in legs.values():  # warm-up: code objects, library algorithm choices
                 for _ in range(3):
                     f()
@@ -104,6 +156,9 @@ def main():
                 "shape": name, "B": B, "seq": seq, "hidden": hidden, "heads": heads,
                 "dtype": str(dt).split(".")[1], **med,
                 "spread_own_fwd_ms": [round(min(times["own_fwd"]), 4), round(max(times["own_fwd"]), 4)],
+                **{f"spread_{n}_ms": [round(min(t), 4), round(max(t), 4)] for n, t in times.items()
+                   if n.startswith(("mask", "lengths"))},
+                "work_frac": round(wf, 4), "work_frac_dkv": round(wf_dkv, 4),
                 "ratio_fwd": round(med["torch_fwd_ms"] / med["own_fwd_ms"], 3),
                 "ratio_fwd_bwd": round(med["torch_fwd_bwd_ms"] / med["own_fwd_bwd_ms"], 3),
                 **({"ratio_tiled_fwd": round(med["torch_fwd_ms"] / med["tiled_fwd_ms"], 3),
