@@ -6,10 +6,10 @@ is missing.  See DESIGN.md / INTEGRATION.md.
 from . import _lib  # noqa: F401  (loads the HIP library or raises)
 from ._lib import HugeCTRAmdError  # noqa: F401
 from .embedding import OptParams, SparseEmbeddingHash, backward_reorder, forward_reorder  # noqa: F401
-from .layers import (BatchNormLayer, FusedReshapeConcatLayer, InteractionLayer,  # noqa: F401
+from .layers import (BatchNormLayer, FusedReshapeConcatLayer, GRULayer, InteractionLayer,  # noqa: F401
                      LayerNormLayer, MatrixMultiplyLayer, MultiCrossLayer, MultiHeadAttentionLayer,
                      PReLUDiceLayer, ReduceMeanLayer, SequenceMaskLayer, batch_norm,
-                     fused_reshape_concat, interaction, interaction_gather, interaction_indexed,
+                     fused_reshape_concat, gru, interaction, interaction_gather, interaction_indexed,
                      layer_norm, matrix_multiply, multi_head_attention, prelu_dice, reduce_mean,
                      sequence_mask)
 

@@ -170,6 +170,10 @@ _SIGNATURES = {
     "hctr_reduce_mean_bwd": (c_int, [c_size_t, c_size_t, c_size_t, _P, _P, c_int, _P]),
     "hctr_fused_reshape_concat_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
     "hctr_fused_reshape_concat_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
+    "hctr_gru_workspace": (c_int, [c_size_t, c_int, c_int, c_int, _SZP, _SZP]),
+    "hctr_gru_fwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P]),
+    "hctr_gru_bwd": (c_int, [c_size_t, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                             c_int, _P]),
     "hctr_cross_v1_fwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd": (c_int, [c_size_t, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hctr_cross_v1_bwd_workspace_bytes": (c_size_t, [c_size_t, c_int, c_int]),

@@ -1170,3 +1170,8 @@ int hctr_interaction_bwd_indexed_scatter(size_t batch, int n_emb, int width, con
 #if !defined(__HIPCC__) && !defined(HCTR_EMU_SEQUENCE_OPS_UNIT)
 #include "sequence_ops.hip"
 #endif
+
+// gru.hip likewise (HCTR_EMU_GRU_UNIT).
+#if !defined(__HIPCC__) && !defined(HCTR_EMU_GRU_UNIT)
+#include "gru.hip"
+#endif

@@ -678,6 +678,88 @@ class FusedReshapeConcatLayer(torch.nn.Module):
         return fused_reshape_concat(inputs)
 
 
+def _gru_dims(x, weight, hidden, batch_first):
+    """(batch, seq, vec, hidden, batch_first) of the C entry points"""
+    if x.dim() != 3 or x.dtype not in _DT:
+        raise ValueError(f"gru: x of three dimensions, [S, B, V] or (batch_first) [B, S, V], fp32 / "
+                         f"fp16 / bf16; got {tuple(x.shape)} {x.dtype}")
+    if not isinstance(hidden, int) or hidden < 1:
+        raise ValueError(f"gru: hidden >= 1, got {hidden!r}")
+    vec = x.shape[2]
+    if hidden > 256 or not 1 <= vec <= 1024:
+        raise ValueError(f"gru: hidden 1 .. 256 and x's last dimension (the vector size) 1 .. 1024, "
+                         f"got hidden = {hidden}, x {tuple(x.shape)}")
+    if weight.device != x.device:
+        raise ValueError(f"gru: weight on x's device, got {weight.device} and {x.device}")
+    if weight.dim() != 1 or weight.numel() != 3 * hidden * (vec + hidden + 1) or weight.dtype != x.dtype:
+        raise ValueError(f"gru: weight is one flat vector of 3 H V + 3 H H + 3 H = "
+                         f"{3 * hidden * (vec + hidden + 1)} elements of x's dtype (H = {hidden}, V = "
+                         f"{vec}); got {tuple(weight.shape)} {weight.dtype}")
+    batch, seq = (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
+    return batch, seq, vec, hidden, int(bool(batch_first))
+
+
+class _GRUFn(torch.autograd.Function):
+    """gru.hip: hctr_gru_fwd / hctr_gru_bwd.  Saved for the backward: x, weight, y and the fp32
+    reserve [S][B][4][H] (r, z, n, Rn h), which a forward without gradient does not write"""
+
+    @staticmethod
+    def forward(ctx, x, weight, hidden, batch_first):
+        dims = _gru_dims(x, weight, hidden, batch_first)
+        x, weight = x.contiguous(), weight.contiguous()
+        y = torch.empty((*x.shape[:2], hidden), dtype=x.dtype, device=x.device)
+        train = any(ctx.needs_input_grad[:2])
+        sizes = (ctypes.c_size_t(), ctypes.c_size_t())
+        check(lib.hctr_gru_workspace(*dims[:4], ctypes.byref(sizes[0]), ctypes.byref(sizes[1])))
+        reserve = torch.empty(sizes[0].value // 4, dtype=torch.float32, device=x.device) if train else None
+        check(lib.hctr_gru_fwd(*dims, ptr(x), ptr(weight), ptr(y), ptr(reserve), _DT[x.dtype],
+                               stream_ptr()))
+        if train:
+            ctx.save_for_backward(x, weight, y, reserve)
+            ctx.dims, ctx.scratch = dims, sizes[1].value // 4
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, weight, y, reserve = ctx.saved_tensors
+        grad = grad.contiguous()
+        dx, dw = torch.empty_like(x), torch.empty_like(weight)
+        scratch = torch.empty(ctx.scratch, dtype=torch.float32, device=x.device)
+        check(lib.hctr_gru_bwd(*ctx.dims, ptr(x), ptr(weight), ptr(y), ptr(reserve), ptr(grad), ptr(dx),
+                               ptr(dw), ptr(scratch), _DT[x.dtype], stream_ptr()))
+        return dx, dw, None, None
+
+
+def gru(x: torch.Tensor, weight: torch.Tensor, hidden: int, batch_first: bool = False):
+    """x [S, B, V] (batch_first: [B, S, V]) -> y [S, B, H] ([B, S, H]): a one-layer GRU with initial
+    state zero.  weight: flat, Wr Wz Wn [H][V], Rr Rz Rn [H][H], br bz bn [H] (z the update gate);
+    n = tanh(Wn x + r o (Rn h) + bn), h_t = (1 - z) o n + z o h_{t-1}.  fp32 / fp16 / bf16, H 1 .. 256,
+    V 1 .. 1024; fp32 sums and gates, the 16-bit state rounded once a step"""
+    return _GRUFn.apply(x, weight, hidden, batch_first)
+
+
+class GRULayer(torch.nn.Module):
+    """R/HugeCTR/include/layers/gru_layer.hpp.  weight: the reference's flat layout, uniform in
+    +-1 / sqrt(hidden)"""
+
+    def __init__(self, hidden: int, vector_size: int, batch_first: bool = False):
+        super().__init__()
+        if not (isinstance(hidden, int) and hidden >= 1):
+            raise ValueError(f"GRULayer: hidden >= 1, got {hidden!r}")
+        if not (isinstance(vector_size, int) and vector_size >= 1):
+            raise ValueError(f"GRULayer: vector_size >= 1, got {vector_size!r}")
+        self.hidden, self.vector_size, self.batch_first = hidden, vector_size, batch_first
+        bound = hidden ** -0.5
+        self.weight = torch.nn.Parameter(
+            torch.empty(3 * hidden * (vector_size + hidden + 1)).uniform_(-bound, bound))
+
+    def forward(self, x):
+        if x.dim() == 3 and x.shape[2] != self.vector_size:
+            raise ValueError(f"GRULayer: x's last dimension is vector_size = {self.vector_size}, got "
+                             f"{tuple(x.shape)}")
+        return gru(x, self.weight, self.hidden, self.batch_first)
+
+
 class _CrossV1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, kernels, biases):

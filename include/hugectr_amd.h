@@ -746,6 +746,28 @@ int hctr_fused_reshape_concat_bwd(size_t batch, int slots, int num, void* const*
                                   const int* widths, const void* ditem, const void* dad, int dtype,
                                   hctr_stream_t stream);
 
+/* GRULayer<T> (R/HugeCTR/src/layers/gru_layer.cu: a cuDNN GRU, unidirectional, one layer, single
+ * input bias, linear input, initial state zero), gru.hip.  x [seq][batch][vec] -> y [seq][batch][hidden]
+ * (batch_first != 0: x [batch][seq][vec], y [batch][seq][hidden], read and written in place).  `weight`
+ * is one flat vector of 3 H V + 3 H H + 3 H elements: Wr Wz Wn [H][V], Rr Rz Rn [H][H], br bz bn [H];
+ *   r = sig(Wr x + Rr h + br), z = sig(Wz x + Rz h + bz), n = tanh(Wn x + r o (Rn h) + bn),
+ *   h_t = (1 - z) o n + z o h_{t-1}, y_t = h_t.
+ * Elements f32 / f16 / bf16 for x, y and the weights alike; products summed in fp32, gates in fp32;
+ * the state that enters step t + 1 is y_t as stored (16-bit types: rounded once a step).  `reserve`
+ * (fp32 [seq][batch][4][hidden]: r, z, n, Rn h_{t-1}) is written when not NULL and read by the
+ * backward, which from dy writes dx (x's layout) and dweight (weight's layout) and needs `scratch`;
+ * hctr_gru_workspace gives both sizes in bytes.  No gradient flows into the initial state.  No
+ * atomics: two runs give the same bits.  1 <= hidden <= 256, 1 <= vec <= 1024, seq >= 1,
+ * seq * batch * max(vec, hidden) < 2^31; anything else is refused by name.  batch = 0 is served. */
+int hctr_gru_workspace(size_t batch, int seq, int vec, int hidden, size_t* reserve_bytes,
+                       size_t* scratch_bytes);
+int hctr_gru_fwd(size_t batch, int seq, int vec, int hidden, int batch_first, const void* x,
+                 const void* weight, void* y, void* reserve /* or NULL */, int dtype,
+                 hctr_stream_t stream);
+int hctr_gru_bwd(size_t batch, int seq, int vec, int hidden, int batch_first, const void* x,
+                 const void* weight, const void* y, const void* reserve, const void* dy, void* dx,
+                 void* dweight, void* scratch, int dtype, hctr_stream_t stream);
+
 /* MultiCrossLayer<T> v1 (projection_dim = 0): x_{l+1} = x0 * (x_l . w_l) + b_l + x_l
  * (R/HugeCTR/src/layers/multi_cross_layer.cu:582-601,1023-1060).  kernels/biases [layers][w];
  * outputs [layers][B][w] (outputs[layers-1] is the layer output), hiddens [layers][B]. */
